@@ -6,12 +6,14 @@ A step = one pass of the hot path as the reference's front end runs it on a ster
 wireframe_matcher, stage 1 and the line filter, junctions + descriptors on the left one (feature_detector.cc:94-104) — and one LightGlue
 match, at the reference's 512x512 internal resolution (src/plnet.cpp:17-21), over one batch of `--pairs` synthetic stereo pairs that
 are already resident in HBM.  `--detector superpoint` is the point-only step (2x SuperPoint-VGG detect + LightGlue: what
-`Detect(left, right, features)` runs with use_superpoint = 1); it is also timed in the default run and reported beside the headline.
+`Detect(left, right, features)` runs with use_superpoint = 1); `--full` also times it beside the headline.
 One process per GPU; ranks shard pairs (weak scaling) and gather their matches to rank 0 every step.
 This file is the command line; the workloads live in benchlib/ (stereo.py = the headline + track + frontend, seq.py = BASELINE configs[3], b1.py = batch-1 latency,
 side.py = SuperGlue / loop closure / host API) and share one line builder (benchlib/common.py: `line`).
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3                 # the headline alone
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full          # + CPU baseline, roofline, per-stage table, point-only step, host to host
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs bench_outputs    # + the last timed step's outputs as .npy files
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -41,7 +43,14 @@ def main():
                     help="detector (encoder) storage type; fp16 = the reference's kFP16 engines and the type that meets the parity gates")
     ap.add_argument("--matcher-dtype", default="fp16", choices=["bf16", "fp16"],
                     help="matcher storage type (fp16 = the reference's kFP16 engines, light_glue.cpp:115)")
-    ap.add_argument("--cpu-pairs", type=int, default=20, help="CPU-baseline sample size (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline, the dominant kernel's events in the timed steps (roofline), the "
+                         "per-stage table, and beside the stereo step the point-only step and the host-to-host pass.  Without it a run sets up, warms up, "
+                         "times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64; a fixed sample of the "
+                         "pairs when the whole batch would pass 64 MB): stereo, track and frontend workloads")
+    ap.add_argument("--cpu-pairs", type=int, default=None, help="CPU-baseline sample size (0 = skip; default 20 with --full, else 0)")
     ap.add_argument("--matcher", default="lightglue", choices=["lightglue", "superglue"],
                     help="superglue: 18-layer GNN + 100 Sinkhorn iterations (BASELINE configs[4]: --width 1280 --height 720 --max-keypoints 1024)")
     ap.add_argument("--detector", default=None, choices=["superpoint", "plnet"],
@@ -70,7 +79,8 @@ def main():
     ap.add_argument("--io", default="resident", choices=["resident", "host"],
                     help="stereo workload: `value` = the step with inputs resident in HBM (the contract's default) or host to host — pinned host images in, features / "
                          "lines / junctions / matches back in pinned host memory, PCIe on copy streams beside the compute stream (the resident rate rides along as value_resident)")
-    ap.add_argument("--io-steps", type=int, default=20, help="steps of the host-to-host pass the default line reports beside the resident rate (0 = skip)")
+    ap.add_argument("--io-steps", type=int, default=None, help="steps of the host-to-host pass the default line reports beside the resident rate (0 = skip; "
+                                                                "default 20 with --full or --io host, else 0)")
     ap.add_argument("--inflight", type=int, default=1, choices=[1, 2],
                     help="stereo workload: steps in flight on the device — 2 = consecutive steps alternate between two contexts (own arena and stream), so that the matcher of "
                          "step i runs beside the encoder of step i + 1")
@@ -79,9 +89,20 @@ def main():
     ap.add_argument("--groups", type=int, default=0, help="--workload seq, native driver: groups of sequences half a step apart (0 = 2 from 4 sequences on, else 1)")
     ap.add_argument("--no-affinity", action="store_true", help="do not give each local rank its own share of the host cores (os.sched_setaffinity)")
     ap.add_argument("--tuning", default="", help="airfe_tuning overrides for A/B runs, e.g. assign_fused=0,overlap_lines=0 (include/airfe.h)")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--stage-steps", type=int, default=3, help="extra untimed steps for the per-stage table")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: no HIP events (no roofline, no per-stage table); implied without --full")
+    ap.add_argument("--stage-steps", type=int, default=None, help="extra untimed steps for the per-stage table (default 3 with --full, else 0)")
     args = ap.parse_args()
+    # a plain run measures the headline only; --full adds the rest (an explicit --cpu-pairs / --io-steps sizes that part either way)
+    if args.cpu_pairs is None:
+        args.cpu_pairs = 20 if args.full else 0
+    if args.io_steps is None:
+        args.io_steps = 20 if args.full or args.io == "host" else 0
+    if args.stage_steps is None:
+        args.stage_steps = 3 if args.full else 0
+    if not args.full:
+        args.no_profile = True
+    if args.dump_outputs and (args.workload in ("b1", "seq", "loop") or args.plnet_host or args.matcher == "superglue"):
+        raise SystemExit("--dump-outputs: the stereo, track and frontend workloads write their outputs")
     args.tuning = {kv.split("=")[0]: int(kv.split("=")[1]) for kv in args.tuning.split(",") if kv} or None
     args.steps_given = args.steps
     if args.steps is None:

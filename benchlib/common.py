@@ -73,6 +73,32 @@ def line(args, *, metric, value, unit, world, steps, warmup, ms_per_step, config
     return out
 
 
+DUMP_BYTES = 64 * 10**6      # --dump-outputs: at most this many bytes in all
+
+
+def dump_outputs(out_dir, arrays, pairs, seed=0):
+    """--dump-outputs: arrays = {name: (tensor, valid rows per item or None)}, every tensor's leading dimension k x pairs (item j * pairs + b
+    belongs to pair b).  Rows past an item's count are zeroed (the entries leave them unspecified).  float32 / float64 stay, integers become
+    float64 (exact).  When the whole batch would pass DUMP_BYTES, a fixed sample of the pairs (seeded) is written, all of each pair's items;
+    pair_index.npy names the pairs written."""
+    import numpy as np
+    host = {k: (t.cpu().numpy(), None if c is None else c.cpu().numpy()) for k, (t, c) in arrays.items()}
+    size = lambda a: a.size * (4 if a.dtype == np.float32 else 8)
+    per_pair = sum(size(a) for a, _ in host.values()) // pairs
+    n = min(pairs, (DUMP_BYTES - 256 * (len(host) + 1)) // (per_pair + 8))        # (256: room for each file's .npy header)
+    if n < 1:
+        raise SystemExit(f"--dump-outputs: one pair's outputs ({per_pair} bytes) pass the {DUMP_BYTES}-byte limit")
+    sel = np.arange(pairs) if n == pairs else np.sort(np.random.default_rng(seed).choice(pairs, n, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "pair_index.npy"), sel.astype(np.float64))
+    for name, (a, cnt) in host.items():
+        rows = np.concatenate([j * pairs + sel for j in range(a.shape[0] // pairs)])
+        a = a[rows].astype(np.float32 if a.dtype == np.float32 else np.float64)
+        if cnt is not None:
+            a[np.arange(a.shape[1])[None, :] >= cnt[rows][:, None]] = 0
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def stage_table(stages, n_steps):
     """ctx.profile_read() of n_steps bracketed steps -> ({stage: {ms_per_step, share, tflops, algo_gbs, bound, frac}}, algorithmic FLOPs per step):
     each stage against its own roof (algorithmic FLOPs or bytes of the stage / its event time / the peak)."""

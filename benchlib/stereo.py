@@ -234,6 +234,29 @@ def run(args, rank, world, local, dev):
         if world > 1:          # the step's match lists to rank 0: copied on the compute stream, gathered on a SIDE stream behind an event;
             gatherer.add(idx, sc, nm, stream=stream)      # barrier() drains it (torch.cuda.synchronize)
 
+    def outputs(slot):
+        """what one step handed its caller, for --dump-outputs: {name: (tensor, valid rows per item or None)}"""
+        o = second if slot else dict(fl=fl, fr=fr, nl=nl, nr=nr, idx=idx, sc=sc, nm=nm)
+        if plnet and not slot:
+            o.update(lines=lines, nlines=nlines, junc=junc, njunc=njunc, found=found)
+        if track:                # the new frames (the right images) against the last keyframe
+            d = dict(features=(fr, nr), n_features=(nr, None))
+            if plnet:
+                d.update(lines=(lines[B:], nlines[B:]), n_lines=(nlines[B:], None))
+        else:
+            d = dict(features_left=(o["fl"], o["nl"]), features_right=(o["fr"], o["nr"]), n_left=(o["nl"], None), n_right=(o["nr"], None))
+            if plnet:
+                d.update(lines=(o["lines"], o["nlines"]), n_lines=(o["nlines"], None), junctions_left=(o["junc"], o["njunc"]),
+                         n_junctions_left=(o["njunc"], None), found=(o["found"], None))
+        d.update(match_index=(o["idx"], o["nm"]), match_score=(o["sc"], o["nm"]), n_matches=(o["nm"], None))
+        if frontend:
+            for side, r in enumerate(rel):
+                nli = nlines[side * B:(side + 1) * B]
+                d.update({f"point_line_rowptr_{side}": (r["rp"], nli + 1), f"point_line_index_{side}": (r["pi"], r["tot"]),
+                          f"point_line_distance_{side}": (r["pd"], r["tot"]), f"point_line_total_{side}": (r["tot"], None)})
+            d.update(line_matches=(line_matches, nlines[:B]), bow_words=(words, nl), bow_weights=(wweights, nl))
+        return d
+
     torch.cuda.synchronize(dev)
     for i in range(args.warmup * len(ctxs)):
         step(i % len(ctxs))
@@ -250,6 +273,8 @@ def run(args, rank, world, local, dev):
             step(i % len(ctxs))
     cm.barrier(dev, world)
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        cm.dump_outputs(args.dump_outputs, outputs((args.steps - 1) % len(ctxs)), B)
     dom = None
     if not args.no_profile:
         doms = [c_.profile_read()[cm.DOMINANT_STAGE] for c_ in ctxs]
@@ -272,7 +297,7 @@ def run(args, rank, world, local, dev):
     cm.barrier(dev, world)
     headline = plnet and not track and not frontend
     points_only = None
-    if headline:            # the point-only step (Detect(left, right, features) with use_superpoint = 1) on the same context and inputs
+    if headline and args.full:            # the point-only step (Detect(left, right, features) with use_superpoint = 1) on the same context and inputs
         for _ in range(args.warmup):
             points_step()
         cm.barrier(dev, world)
@@ -360,7 +385,7 @@ def run(args, rank, world, local, dev):
             out["config"]["workload"] += "; + rectification of both raw images, point-line association, stereo line matching, BoW quantisation (synthetic vocabulary, 10^4 words)"
             out["config"]["points_on_lines_mean_left"] = float(rel[0]["tot"].float().mean())
             out["config"]["stereo_line_matches_mean"] = float(np.mean([(lm[b, :nlh[b]] >= 0).sum() for b in range(B)]))
-        if headline:
+        if points_only is not None:
             out["config"]["points_only_pairs_per_s"] = points_only
             out["config"]["points_only_note"] = ("the point-only step (2x detect + LightGlue, airfe_stereo_batch_dev: `--detector superpoint`) timed on the "
                                                  "same context and inputs over the same number of steps")

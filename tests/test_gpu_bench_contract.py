@@ -1,11 +1,13 @@
 """bench.py prints ONE JSON line with the driver's contract (metric / value / unit / n_gpus / steps / warmup / ms_per_step / dtype / config /
 roofline / cpu_baseline): a small run of every workload switch, so that a change to the engine cannot silently break the line the
-driver parses."""
+driver parses.  A plain run measures the headline only; --full adds the CPU baseline, the roofline, the stage table, the point-only step
+and the host-to-host pass."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -13,6 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _run(*args):
+    """one bench.py run -> its JSON line (a test that needs more than the headline passes --full)"""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
@@ -21,7 +24,7 @@ def _run(*args):
 
 
 def test_default_workload_line():
-    d = _run("--pairs", "8", "--steps", "3", "--warmup", "1", "--cpu-pairs", "2")
+    d = _run("--pairs", "8", "--steps", "3", "--warmup", "1", "--cpu-pairs", "2", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -62,9 +65,32 @@ def test_default_workload_line():
     assert d["host"]["cores_per_rank"] == [None]       # one rank: nothing to share
 
 
+def test_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline alone; --dump-outputs writes what the last timed step computed, the same on every run with
+    the same arguments, and what a --full run's timed steps computed too"""
+    args = ("--pairs", "8", "--steps", "3", "--warmup", "1")
+    d = _run(*args, "--dump-outputs", str(tmp_path / "a"))
+    assert d["unit"] == "pairs/s" and d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "fp16" and d["higher_is_better"] is True
+    assert abs(d["value"] - 8 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"] and d["config"]["matches_mean"] > 50
+    assert d["roofline"] is None and d["cpu_baseline"] is None and "stages" not in d and "host_to_host" not in d
+    assert "points_only_pairs_per_s" not in d["config"]
+    _run(*args, "--dump-outputs", str(tmp_path / "b"))
+    _run(*args, "--dump-outputs", str(tmp_path / "c"), "--full", "--cpu-pairs", "0", "--io-steps", "0")
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert "features_left.npy" in names and "match_index.npy" in names and "lines.npy" in names and "junctions_left.npy" in names
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64 * 10**6
+    for f in names:
+        a = np.load(tmp_path / "a" / f)
+        assert a.dtype in (np.float32, np.float64), f
+        assert np.array_equal(a, np.load(tmp_path / "b" / f)) and np.array_equal(a, np.load(tmp_path / "c" / f)), f
+    n = np.load(tmp_path / "a" / "n_matches.npy")
+    assert n.shape == (8,) and abs(n.mean() - d["config"]["matches_mean"]) < 1e-6
+    assert np.array_equal(np.load(tmp_path / "a" / "pair_index.npy"), np.arange(8))
+
+
 def test_two_steps_in_flight_line():
     """--inflight 2: consecutive steps alternate between two contexts; the line says so, and the run itself checks that both contexts return the same matches"""
-    d = _run("--pairs", "8", "--steps", "4", "--warmup", "1", "--cpu-pairs", "0", "--io-steps", "0", "--inflight", "2")
+    d = _run("--pairs", "8", "--steps", "4", "--warmup", "1", "--cpu-pairs", "0", "--io-steps", "0", "--inflight", "2", "--full")
     assert d["config"]["steps_in_flight"] == 2 and "steps_in_flight_note" in d["config"] and d["steps"] == 4
     assert abs(d["value"] - 8 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"] and d["config"]["matches_mean"] > 50
     assert d["roofline"]["launches"] == 4 and 0.0 < d["roofline"]["frac"] < 1.0
@@ -104,7 +130,8 @@ def test_track_workload_line():
 def test_seq_workload_line():
     """--workload seq (BASELINE configs[3]): S sequences driven as map_builder.cc:83-141 drives the front end — a short run of the batched driver and of the
     one-call driver; the schedule contains keyframes, normal frames and (scenes of 10 frames) promotions"""
-    d = _run("--workload", "seq", "--sequences", "3", "--frames", "34", "--warmup", "2", "--scene-len", "10", "--cpu-pairs", "3", "--min-num-match", "100")
+    d = _run("--workload", "seq", "--sequences", "3", "--frames", "34", "--warmup", "2", "--scene-len", "10", "--cpu-pairs", "3", "--min-num-match", "100",
+             "--full")
     assert d["unit"] == "frames/s" and d["steps"] == 32 and d["warmup"] == 2 and d["n_gpus"] == 1 and d["value"] > 0
     assert abs(d["value"] - 3 * 32 / (d["ms_per_step"] * 32 * 1e-3)) <= 1e-6 * d["value"]
     sch = d["config"]["schedule"]
@@ -167,7 +194,7 @@ def test_two_ranks_report_their_host_time_on_their_own_cores(monkeypatch):
 
 def test_frontend_workload_line():
     """the whole per-keyframe front end, device-resident: rectify -> PLNet x2 -> LightGlue -> AssignPointsToLines x2 -> MatchLines -> BoW"""
-    d = _run("--workload", "frontend", "--pairs", "8", "--steps", "3", "--warmup", "1")
+    d = _run("--workload", "frontend", "--pairs", "8", "--steps", "3", "--warmup", "1", "--full")
     assert d["unit"] == "stereo keyframes/s" and d["n_gpus"] == 1 and d["value"] > 0 and "AssignPointsToLines" in d["metric"]
     assert d["config"]["matches_mean"] > 30 and d["config"]["lines_mean"] >= 30
     assert d["config"]["points_on_lines_mean_left"] > 50 and d["config"]["stereo_line_matches_mean"] >= 3

@@ -1,6 +1,6 @@
-"""The reference's OWN façade — /root/reference/src/feature_detector.cc and src/point_matcher.cc, compiled unchanged (shim/Makefile) — running
+"""The reference's OWN façade — the reference's src/feature_detector.cc and src/point_matcher.cc, compiled unchanged (shim/Makefile) — running
 on the GPU through the TensorRT-free wrappers and libairfe.so (missing #2: INTEGRATION.md's "compile untouched" as a tested
-statement).  shim/_build/facade_gpu is built where the reference tree is (this container; __graft_entry__.build()) and travels to the GPU box.
+statement).  oracle/_ref/facade_gpu is built where the reference tree is (oracle/Makefile, __graft_entry__.build()) and is used as it is elsewhere.
 Configuration goes through the reference's own include/read_configs.h (a YAML file in its format); every output of all six Detect overloads
 (src/feature_detector.cc:36,52,62,71,83,97) and of MatchingPoints (src/point_matcher.cc:50-107) must equal, byte for byte, what the ctypes path
 returns through the same C ABI with the same packs."""
@@ -15,7 +15,7 @@ from airslam_amd import api, synth, weights
 from conftest import GOLDEN, ROOT
 
 pytestmark = pytest.mark.gpu
-EXE = os.path.join(ROOT, "shim", "_build", "facade_gpu")
+EXE = os.path.join(ROOT, "oracle", "_ref", "facade_gpu")
 
 YAML = """plnet:
   use_superpoint: {sp}
@@ -75,10 +75,7 @@ ros_publisher:
 @pytest.fixture(scope="module")
 def models(tmp_path_factory):
     if not os.path.exists(EXE):
-        if os.path.isdir("/root/reference/src"):
-            subprocess.run(["make", "-C", os.path.join(ROOT, "shim")], check=True)
-        else:
-            pytest.skip("shim/_build/facade_gpu was not built (no reference tree here and no prebuilt binary)")
+        pytest.skip("oracle/_ref/facade_gpu was not built (no reference tree where the tree was built and no prebuilt binary)")
     md = tmp_path_factory.mktemp("models")
     w = dict(sp=weights.synthetic_superpoint(1234), s0=weights.synthetic_plnet_s0(1234), lg=weights.synthetic_lightglue(1234),
              sg=weights.synthetic_superglue(1234))

@@ -6,10 +6,10 @@ TAG=${1:-r02}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="python bench.py --steps 5 --warmup 2 --cpu-pairs 0 --no-profile ${BENCH_ARGS:-}"
+CMD="python bench.py --steps 5 --warmup 2 --cpu-pairs 0 --no-profile --full ${BENCH_ARGS:-}"
 rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -- $CMD > $OUT/bench_under_rocprof.json 2> $OUT/kt.err
 python tools/rocpd_summary.py $OUT/kt/kt_results.db $OUT/kernel_stats.csv
-PC="python bench.py --steps 2 --warmup 1 --cpu-pairs 0 --no-profile ${BENCH_ARGS:-}"
+PC="python bench.py --steps 2 --warmup 1 --cpu-pairs 0 --no-profile --full ${BENCH_ARGS:-}"
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA GRBM_GUI_ACTIVE --kernel-trace -d $OUT/pa -o a -- $PC > /dev/null 2> $OUT/pa.err
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU_TRANS_F32 --kernel-trace -d $OUT/pb -o b -- $PC > /dev/null 2> $OUT/pb.err
 python tools/pmc_summary.py $OUT/pmc_summary.json $OUT/pa/a_results.db $OUT/pb/b_results.db > $OUT/pmc_summary.txt 2>&1

@@ -5,7 +5,7 @@
 #
 # steps
 #   tests [pytest args]                 -m gpu suite (default: all of tests/, not -x)                  -> pytest[_N].log
-#   bench <name> [bench.py args]        one bench line                                                  -> bench_<name>.json (+ .err)
+#   bench <name> [bench.py args]        one bench line (--full)                                         -> bench_<name>.json (+ .err)
 #   kstats <name> [bench.py args]       rocprofv3 --kernel-trace --stats of a short bench run           -> kstats_<name>.csv + the kernels matching $KFILTER
 #   ab <name> <label[=tuning]>...       kernel-level A/B: kstats per label, `--tuning` from the label    -> ab_<name>.txt   (extra bench args: $AB_ARGS)
 #   pmc [bench.py args]                 tools/gpu_profile.sh (kernel stats + PMC passes in their own runs + HBM traffic)
@@ -47,7 +47,7 @@ step() {
       timeout ${PYTEST_TIMEOUT:-1800} python -m pytest "$@" -q -m gpu > "$log" 2>&1; echo "pytest rc=$? ($log)"; tail -${PYTEST_TAIL:-15} "$log" | cut -c1-300 ;;
     bench)
       local name=$1; shift
-      timeout ${BENCH_TIMEOUT:-600} python bench.py "$@" > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err"; echo "bench $name rc=$?"
+      timeout ${BENCH_TIMEOUT:-600} python bench.py --full "$@" > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err"; echo "bench $name rc=$?"
       python tools/bench_brief.py "$OUT/bench_$name.json" ;;
     kstats) kstats "$@" ;;
     ab)

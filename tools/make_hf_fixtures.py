@@ -2,6 +2,8 @@
 """tests/golden/hf_pin.npz: outputs of Hugging Face transformers' SuperPoint / LightGlue / SuperGlue ports on the seeded inputs of
 tests/hf_cases.py with the seeded weights of airslam_amd.weights (oracle/hf_pin.py).  Run in the build container (transformers is
 installed there); the GPU twin tests/test_gpu_hf_pin.py compares the HIP library with this file where transformers is missing.
+Also tests/golden/hf_pin_portable.npz: the first LightGlue and SuperGlue case on portable CPU kernels (hf_cases.PORTABLE_CPU_ENV), stored as
+float16 differences to hf_pin.npz's scores of the same case; tests/test_oracle_hf_pin_cpu.py recomputes them on the same kernels.
 
     python tools/make_hf_fixtures.py
 """
@@ -39,6 +41,11 @@ def main():
     path = os.path.join(ROOT, "tests", "golden", "hf_pin.npz")
     np.savez_compressed(path, **out)
     print(path, os.path.getsize(path), "bytes;", {k: v.shape for k, v in out.items()})
+    portable = hf_cases.matcher_scores(hf_cases.PORTABLE_KEYS)
+    delta = {k: (portable[k].astype(np.float64) - out[k]).astype(np.float16) for k in hf_cases.PORTABLE_KEYS}
+    path = os.path.join(ROOT, "tests", "golden", "hf_pin_portable.npz")
+    np.savez_compressed(path, **delta)
+    print(path, os.path.getsize(path), "bytes; largest difference", {k: float(np.abs(v).max()) for k, v in delta.items()})
 
 
 if __name__ == "__main__":
