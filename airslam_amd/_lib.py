@@ -63,6 +63,7 @@ SIGNATURES = {
     "airfe_seq_end": (C.c_int, [C.c_void_p, C.POINTER(SeqFrame)]),
     "airfe_seq_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(SeqFrame)]),
     "airfe_seq_stream": (C.c_void_p, [C.c_void_p]),
+    "airfe_seq_set_outlier_rejection": (C.c_int, [C.c_void_p, C.c_int]),
     "airfe_seq_wall_split": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "airfe_default_cfg": (None, [C.POINTER(Cfg)]),
     "airfe_default_tuning": (None, [C.POINTER(Tuning)]),
@@ -126,6 +127,10 @@ SIGNATURES = {
                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "airfe_match_lines_batch_dev": (C.c_int, [C.c_void_p] + [C.c_void_p] * 8 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "airfe_fundamental_ransac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "airfe_fundamental_ransac_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "airfe_set_outlier_rejection": (C.c_int, [C.c_void_p, C.c_int]),
     "airfe_sync": (C.c_int, [C.c_void_p]),
     "airfe_superglue_status": (C.c_int, [C.c_void_p, C.c_void_p]),
     "airfe_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),

@@ -199,11 +199,14 @@ class Context:
         return feat[:n.value].copy(), lines[:nl.value].copy(), junc[:nj.value].copy()
 
     def stereo_keyframe(self, left: np.ndarray, right: np.ndarray, match: bool = True, want_junctions: bool = True, cap_lines: int = 4096,
-                        cap_junc: int = 2048, track: bool = False, ref_feat=None):
+                        cap_junc: int = 2048, track: bool = False, ref_feat=None, outlier_rejection: bool = False):
         """ONE stereo keyframe in one call (airfe_stereo_keyframe ≙ map_builder.cc:85-86): -> dict(featL, featR [n,259], linesL, linesR [L,4] float64,
         juncL [K,259], idx [m,2] int32, score [m]) — idx / score absent with match=False.  track=True (airfe_stereo_keyframe_tracked): also the temporal
         match of map_builder.cc:96 against the last keyframe's features (`ref_feat` [n,259]: uploaded when given, else the ones on the device) in the SAME
-        LightGlue forward -> track_idx [t,2] (reference, left), track_score [t]."""
+        LightGlue forward -> track_idx [t,2] (reference, left), track_score [t].  outlier_rejection=True: the temporal list passes the F-matrix RANSAC
+        on the device (map_builder.cc:96 passes `true`; the stereo list, :86, never does)."""
+        if outlier_rejection and not track:
+            raise AirfeError("stereo_keyframe: outlier_rejection applies to the temporal match: pass track=True")
         if ref_feat is not None and not track:
             raise AirfeError("stereo_keyframe: ref_feat is the temporal match's reference: pass track=True")
         if track and not match:
@@ -232,8 +235,12 @@ class Context:
         if track:
             ref = None if ref_feat is None else np.ascontiguousarray(ref_feat, dtype=np.float32).reshape(-1, FEAT)
             tidx, tsc, nt = np.empty((cap, 2), np.int32), np.empty((cap,), np.float32), C.c_int(0)
-            self._chk(self._l.airfe_stereo_keyframe_tracked(*args, None if ref is None else ref.ctypes.data, 0 if ref is None else len(ref), tidx.ctypes.data,
-                                                            tsc.ctypes.data, C.byref(nt)), "airfe_stereo_keyframe_tracked")
+            self._chk(self._l.airfe_set_outlier_rejection(self._h, int(outlier_rejection)), "airfe_set_outlier_rejection")
+            try:
+                self._chk(self._l.airfe_stereo_keyframe_tracked(*args, None if ref is None else ref.ctypes.data, 0 if ref is None else len(ref),
+                                                                tidx.ctypes.data, tsc.ctypes.data, C.byref(nt)), "airfe_stereo_keyframe_tracked")
+            finally:
+                self._l.airfe_set_outlier_rejection(self._h, 0)
         else:
             self._chk(self._l.airfe_stereo_keyframe(*args), "airfe_stereo_keyframe")
         out = dict(featL=fl[:n[0]], featR=fr[:n[1]], linesL=ll[:n[2]], linesR=lr[:n[3]], juncL=jl[:n[4]])
@@ -243,9 +250,10 @@ class Context:
             out["track_idx"], out["track_score"] = tidx[:nt.value], tsc[:nt.value]
         return out
 
-    def track_frame(self, gray: np.ndarray, ref_feat=None):
+    def track_frame(self, gray: np.ndarray, ref_feat=None, outlier_rejection: bool = False):
         """ONE tracked frame in one call (airfe_track_frame ≙ map_builder.cc:94-101): points of `gray` + LightGlue against the last keyframe's features
-        (`ref_feat` [n,259]: uploaded when given, kept on the device when None) -> (feat [n,259], idx [m,2] (reference, new), score [m])."""
+        (`ref_feat` [n,259]: uploaded when given, kept on the device when None) -> (feat [n,259], idx [m,2] (reference, new), score [m]).
+        outlier_rejection=True: the list passes the F-matrix RANSAC on the device before it comes back (:101 passes `true`)."""
         gray = np.asarray(gray)
         if gray.ndim != 2 or gray.dtype != np.uint8 or gray.size == 0:
             raise AirfeError("empty image")
@@ -255,9 +263,13 @@ class Context:
         feat, idx, sc = np.empty((cap, FEAT), np.float32), np.empty((cap, 2), np.int32), np.empty((cap,), np.float32)
         n, nm = C.c_int(0), C.c_int(0)
         ref = None if ref_feat is None else np.ascontiguousarray(ref_feat, dtype=np.float32).reshape(-1, FEAT)
-        self._chk(self._l.airfe_track_frame(self._h, gray.ctypes.data, gray.shape[0], gray.shape[1], gray.strides[0],
-                                            None if ref is None else ref.ctypes.data, 0 if ref is None else len(ref), feat.ctypes.data, cap, C.byref(n),
-                                            idx.ctypes.data, sc.ctypes.data, cap, C.byref(nm)), "airfe_track_frame")
+        self._chk(self._l.airfe_set_outlier_rejection(self._h, int(outlier_rejection)), "airfe_set_outlier_rejection")
+        try:
+            self._chk(self._l.airfe_track_frame(self._h, gray.ctypes.data, gray.shape[0], gray.shape[1], gray.strides[0],
+                                                None if ref is None else ref.ctypes.data, 0 if ref is None else len(ref), feat.ctypes.data, cap, C.byref(n),
+                                                idx.ctypes.data, sc.ctypes.data, cap, C.byref(nm)), "airfe_track_frame")
+        finally:
+            self._l.airfe_set_outlier_rejection(self._h, 0)
         return feat[:n.value], idx[:nm.value], sc[:nm.value]
 
     def promote_frame(self, right: np.ndarray):
@@ -441,6 +453,27 @@ class Context:
         self._chk(self._l.airfe_detect_points_batch_dev(self._h, gray_t.data_ptr(), b, h, w, gray_t.stride(1),
                                                         gray_t.stride(0), feat_t.data_ptr(), feat_t.shape[1],
                                                         n_t.data_ptr(), self._stream(stream)), "airfe_detect_points_batch_dev")
+
+    def fundamental_ransac(self, f0: np.ndarray, f1: np.ndarray, idx: np.ndarray, score: np.ndarray):
+        """F-matrix RANSAC on ONE match list (airfe_fundamental_ransac ≙ point_matcher.cc:95-104; contract: include/airfe.h): f0 [n0,259], f1 [n1,259]
+        rows in original pixels, idx [m,2] (index into f0, into f1), score [m] -> (idx [k,2], score [k]): the kept matches in their order."""
+        f0 = np.ascontiguousarray(f0, dtype=np.float32).reshape(-1, FEAT)
+        f1 = np.ascontiguousarray(f1, dtype=np.float32).reshape(-1, FEAT)
+        idx = np.array(idx, dtype=np.int32, copy=True).reshape(-1, 2)
+        score = np.array(score, dtype=np.float32, copy=True).reshape(-1)
+        if len(score) != len(idx):
+            raise AirfeError("fundamental_ransac: idx and score differ in length")
+        k = C.c_int(0)
+        self._chk(self._l.airfe_fundamental_ransac(self._h, f0.ctypes.data, len(f0), f1.ctypes.data, len(f1), idx.ctypes.data, score.ctypes.data, len(idx),
+                                                   C.byref(k)), "airfe_fundamental_ransac")
+        return idx[:k.value], score[:k.value]
+
+    def fundamental_ransac_batch_dev(self, f0_t, f1_t, idx_t, score_t, nm_t, F_t=None, stream=None):
+        """airfe_fundamental_ransac_batch_dev: f0_t / f1_t [B,cap,259], idx_t [B,mcap,2], score_t [B,mcap], nm_t [B] (filtered in place), F_t [B,9] float64."""
+        self._chk(self._l.airfe_fundamental_ransac_batch_dev(self._h, f0_t.data_ptr(), None, f1_t.data_ptr(), None, f0_t.shape[0], f0_t.shape[1],
+                                                             idx_t.data_ptr(), score_t.data_ptr(), idx_t.shape[1], nm_t.data_ptr(),
+                                                             None if F_t is None else F_t.data_ptr(), self._stream(stream)),
+                  "airfe_fundamental_ransac_batch_dev")
 
     def match_lightglue_batch_dev(self, f0_t, n0_t, f1_t, n1_t, idx_t, score_t, nm_t, stream=None):
         self._chk(self._l.airfe_match_lightglue_batch_dev(self._h, f0_t.data_ptr(), n0_t.data_ptr(), f1_t.data_ptr(),
@@ -654,8 +687,8 @@ class FeatureDetector:
 
 
 class PointMatcher:
-    """Mirror of PointMatcher (include/point_matcher.h:8-24, src/point_matcher.cc).  The F-matrix RANSAC of
-    MatchingPoints (cv::findFundamentalMat, :95-104) stays in the reference's own code and is not part of this path."""
+    """Mirror of PointMatcher (include/point_matcher.h:8-24, src/point_matcher.cc).  MatchingPoints' outlier_rejection runs the F-matrix RANSAC
+    of :95-104 (cv::findFundamentalMat there) on the device, by the project's contract (include/airfe.h, "F-matrix RANSAC"; not OpenCV's numerics)."""
 
     def __init__(self, ctx: Context, image_width: int, image_height: int, matcher: int = 0):
         self._ctx = ctx
@@ -670,8 +703,8 @@ class PointMatcher:
         out[2] = (features[2] - np.float32(height // 2)) * l_inv
         return out
 
-    def MatchingPoints(self, features0: np.ndarray, features1: np.ndarray):
-        """-> (count, matches) with matches = list of (queryIdx, trainIdx, distance) ≙ cv::DMatch."""
+    def MatchingPoints(self, features0: np.ndarray, features1: np.ndarray, outlier_rejection: bool = False):
+        """-> (count, matches) with matches = list of (queryIdx, trainIdx, distance) ≙ cv::DMatch.  outlier_rejection: the reference's fourth argument."""
         if features0.shape[1] < 1 or features1.shape[1] < 1:
             return 0, []                                          # point_matcher.cc:53-55
         scale = 0.7 if self.matcher else 0.5
@@ -686,4 +719,11 @@ class PointMatcher:
             for i in range(len(i0)):                              # point_matcher.cc:82-91
                 if 0 <= i0[i] < len(i1) and i1[i0[i]] == i:
                     matches.append((i, int(i0[i]), float(np.float32(1.0 - (m0[i] + m1[i0[i]]) / 2.0))))
+        if outlier_rejection and len(matches) > 8:                # point_matcher.cc:95-104
+            f0 = np.ascontiguousarray(np.asarray(features0, np.float32).T)
+            f1 = np.ascontiguousarray(np.asarray(features1, np.float32).T)
+            idx = np.array([(q, t) for q, t, _ in matches], np.int32)
+            dist = np.array([d for _, _, d in matches], np.float32)           # carried as the "score": the kernel moves it with its pair, untouched
+            kidx, kd = self._ctx.fundamental_ransac(f0, f1, idx, dist)
+            matches = [(int(q), int(t), float(d)) for (q, t), d in zip(kidx, kd)]
         return len(matches), matches

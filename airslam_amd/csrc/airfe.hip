@@ -1,6 +1,7 @@
 // airfe — context life cycle, host staging and the C ABI of libairfe.so (include/airfe.h, include/airfe_debug.h); the pipelines behind it live in
 // airfe_load.hip / airfe_detect.hip / airfe_match.hip (see airfe_host.h).
 #include "airfe_host.h"
+#include "fransac_core.h"
 
 namespace airfe_host {
 thread_local std::string g_err;
@@ -801,6 +802,74 @@ int airfe_match_lines_batch_dev(airfe_ctx* c, const int32_t* d_row_ptr0, const i
   return 0;
 } AIRFE_CATCH(c)
 
+// F-matrix RANSAC (src/point_matcher.cc:95-104) over B device match lists, in place, on `st` (kernels_fransac.hip).  Its scratch grows only behind
+// a synchronisation of the stream it was last used on (one stream at a time per context: the contract of every *_dev entry).
+static int fransac_queue(airfe_ctx* c, const float* d_f0, const float* d_f1, int B, int cap, int32_t* d_idx, float* d_score, int mcap, int* d_nmatch,
+                         double* d_F, hipStream_t st) {
+  const size_t score_bytes = (size_t)B * FR_RANSAC_ITERS * 3 * 4;
+  if (ensure_block(c, c->fr_scratch, c->fr_scratch_bytes, score_bytes + (size_t)B * 16, c->fr_scratch_stream)) return 1;
+  c->fr_scratch_stream = st;
+  FransacArgs a;
+  a.f0 = d_f0; a.f1 = d_f1; a.cap = cap; a.mcap = mcap; a.idx = d_idx; a.score = d_score; a.nmatch = d_nmatch; a.F = d_F;
+  a.scores = reinterpret_cast<int*>(c->fr_scratch);
+  a.state = reinterpret_cast<int*>(c->fr_scratch + score_bytes);
+  launch_fransac(a, B, st);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+int airfe_fundamental_ransac_batch_dev(airfe_ctx* c, const float* d_f0, const int* d_n0, const float* d_f1, const int* d_n1, int B, int cap, int32_t* d_idx,
+                                       float* d_score, int mcap, int* d_nmatch, double* d_F, void* stream) try {
+  AIRFE_ENTER(c);
+  (void)d_n0; (void)d_n1;
+  if (B < 1 || cap < 1 || mcap < 1 || !d_f0 || !d_f1 || !d_idx || !d_score || !d_nmatch) return fail(c, "fundamental_ransac_batch_dev: bad argument");
+  if (mcap > FR_MAX_MATCHES) return fail(c, "fundamental_ransac_batch_dev: mcap > 1024");
+  return fransac_queue(c, d_f0, d_f1, B, cap, d_idx, d_score, mcap, d_nmatch, d_F, stream ? (hipStream_t)stream : c->stream);
+} AIRFE_CATCH(c)
+
+int airfe_fundamental_ransac(airfe_ctx* c, const float* f0, int n0, const float* f1, int n1, int32_t* idx, float* score, int m, int* kept) try {
+  AIRFE_ENTER(c);
+  if (!kept || m < 0 || n0 < 0 || n1 < 0 || (m > 0 && (!idx || !score || !f0 || !f1))) return fail(c, "fundamental_ransac: bad argument");
+  if (m > FR_MAX_MATCHES) return fail(c, "fundamental_ransac: more than 1024 matches");
+  for (int i = 0; i < m; ++i)                                        // the reference indexes the feature matrices with these
+    if (idx[2 * i] < 0 || idx[2 * i] >= n0 || idx[2 * i + 1] < 0 || idx[2 * i + 1] >= n1) return fail(c, "fundamental_ransac: match index out of range");
+  *kept = m;
+  if (m < 9) return 0;                                               // point_matcher.cc:95: the list as it is (the kernels' gate says the same)
+  const int cap = std::max(n0, n1);
+  const size_t fb = (size_t)cap * AIRFE_FEAT_DIM * 4, mb = (size_t)m * 12;
+  if (ensure_block(c, c->fr_stage, c->fr_stage_bytes, 64 + 2 * fb + mb)) return 1;
+  int* d_nm = reinterpret_cast<int*>(c->fr_stage);
+  float* d_f0 = reinterpret_cast<float*>(c->fr_stage + 64);
+  float* d_f1 = reinterpret_cast<float*>(c->fr_stage + 64 + fb);
+  int32_t* d_idx = reinterpret_cast<int32_t*>(c->fr_stage + 64 + 2 * fb);
+  float* d_sc = reinterpret_cast<float*>(c->fr_stage + 64 + 2 * fb + (size_t)m * 8);
+  hipStream_t st = c->stream;
+  DrainOnError drain{c, true};
+  HIPCHK(c, hipMemcpyAsync(d_nm, &m, 4, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_f0, f0, (size_t)n0 * AIRFE_FEAT_DIM * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_f1, f1, (size_t)n1 * AIRFE_FEAT_DIM * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_idx, idx, (size_t)m * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_sc, score, (size_t)m * 4, hipMemcpyHostToDevice, st));
+  if (fransac_queue(c, d_f0, d_f1, 1, cap, d_idx, d_sc, m, d_nm, nullptr, st)) return 1;
+  int nk = 0;
+  HIPCHK(c, hipMemcpyAsync(&nk, d_nm, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (nk > 0) {
+    HIPCHK(c, hipMemcpyAsync(idx, d_idx, (size_t)nk * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(score, d_sc, (size_t)nk * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+  }
+  drain.armed = false;
+  *kept = nk;
+  return 0;
+} AIRFE_CATCH(c)
+
+int airfe_set_outlier_rejection(airfe_ctx* c, int on) try {
+  AIRFE_ENTER(c);
+  c->outlier_rejection = on != 0;
+  return 0;
+} AIRFE_CATCH(c)
+
 int airfe_has_line_branch(const airfe_ctx* c) { return c && c->has_s0 && c->has_s1; }
 
 // caller-supplied stage-0 tensors (golden / known-answer tests of everything downstream) -> stage slot 0 + the CHW LOI block
@@ -1110,6 +1179,10 @@ static int stereo_keyframe_impl(airfe_ctx* c, const uint8_t* left, const uint8_t
                          want_j ? d_jn : nullptr, capJd, want_j ? cnt + 5 : nullptr, cnt + 6, match ? d_idx : nullptr, d_sc, Np, cnt + 10, st, &early_copy, &rows_copy,
                          track ? &x2 : nullptr))
       return 1;
+    // the temporal list only (map_builder.cc:96 passes true, :86 false): F-RANSAC on the device before it is copied back
+    if (track && c->outlier_rejection &&
+        fransac_queue(c, x2.f0, d_fL, 1, Np, d_idx + (size_t)Np * 2, d_sc + Np, Np, cnt + 11, nullptr, st))
+      return 1;
     HIPCHK(c, hipMemcpyAsync(c->pin + early, cnt, 64, hipMemcpyDeviceToHost, st));
     if (match) HIPCHK(c, hipMemcpyAsync(c->pin + late, d_idx, (size_t)Np * (track ? 24 : 16) , hipMemcpyDeviceToHost, st));
     if (match && !track) HIPCHK(c, hipMemcpyAsync(c->pin + late + (size_t)Np * 16, d_sc, (size_t)Np * 4, hipMemcpyDeviceToHost, st));
@@ -1264,6 +1337,7 @@ int airfe_track_frame(airfe_ctx* c, const uint8_t* gray, int h, int w, int strid
   HIPCHK(c, hipMemcpyAsync(c->pin, c->tk_blk, early, hipMemcpyDeviceToHost, c->stream2));
   HIPCHK(c, hipEventRecord(c->ev_feat, c->stream2));
   if (lightglue_dev(c, d_ref, d_nref, d_new, cnt, 1, Np, AIRFE_FEAT_DIM, 1, 1, d_idx, d_sc, Np, cnt + 2, nullptr, st)) return 1;
+  if (c->outlier_rejection && fransac_queue(c, d_ref, d_new, 1, Np, d_idx, d_sc, Np, cnt + 2, nullptr, st)) return 1;   // point_matcher.cc:95-104
   HIPCHK(c, hipMemcpyAsync(c->pin + early, cnt, 64, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipMemcpyAsync(c->pin + late, d_idx, (size_t)Np * 12, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipEventSynchronize(c->ev_feat));

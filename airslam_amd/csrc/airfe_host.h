@@ -115,6 +115,10 @@ struct airfe_ctx {
   uint8_t *pl_scratch = nullptr, *ml_scratch = nullptr;   // scratch of airfe_assign_points_to_lines_batch_dev (counts) / airfe_match_lines_batch_dev (bit rows, row maxima): one each
   size_t pl_scratch_bytes = 0, ml_scratch_bytes = 0;
   hipStream_t pl_scratch_stream = nullptr, ml_scratch_stream = nullptr;   // the stream each was last used on (synchronised before the block is replaced)
+  uint8_t* fr_scratch = nullptr; size_t fr_scratch_bytes = 0;           // airfe_fundamental_ransac_batch_dev: per-model scores [B][1000][3] + state [B][4]
+  hipStream_t fr_scratch_stream = nullptr;
+  uint8_t* fr_stage = nullptr; size_t fr_stage_bytes = 0;               // airfe_fundamental_ransac: the one pair's rows and list on the device
+  bool outlier_rejection = false;                                       // airfe_set_outlier_rejection: F-RANSAC behind the temporal match of track_frame / stereo_keyframe_tracked
   bool nms_map_valid = true;     // heat_nms holds the last batch's NMS'd maps (large batches skip writing them)
   bool force_nms_map = false;    // the batched PLNet path reads junction scores from them: written at every batch size while set
   int Lmax = 1;                  // images the line-path arena holds (= Dmax)

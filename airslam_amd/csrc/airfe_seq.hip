@@ -134,6 +134,7 @@ struct airfe_seq {
   std::vector<SeqJob> jl;
   // the time-step in flight
   bool in_flight = false;
+  bool outlier_rejection = false;   // airfe_seq_set_outlier_rejection: F-RANSAC behind the temporal LightGlue batch (map_builder.cc:101 passes true)
   std::vector<int> kset, nset, tset, pset, newkf, kpos, tpos;
   std::vector<CurRows> cur;
   const uint8_t* R_step = nullptr;
@@ -409,6 +410,12 @@ int airfe_seq_create(airfe_ctx* kf, airfe_ctx* nf, int S, const airfe_seq_policy
 
 void* airfe_seq_stream(airfe_seq* s) { return s ? (void*)s->stream : nullptr; }
 
+int airfe_seq_set_outlier_rejection(airfe_seq* s, int on) try {
+  if (!s) return 1;
+  s->outlier_rejection = on != 0;
+  return 0;
+} SEQ_CATCH(s)
+
 int airfe_seq_wall_split(airfe_seq* s, double* queue_s, double* wait_s, double* host_s, int* host_syncs, int* steps) try {
   if (!s) return 1;
   if (queue_s) *queue_s = s->t_queue;
@@ -480,6 +487,8 @@ int airfe_seq_begin(airfe_seq* s, const uint8_t* d_left, const uint8_t* d_right,
     }
     if (launch_jobs(s, s->stream)) return 1;
     SEQ_CTX(s, s->nf, airfe_match_lightglue_batch_dev(s->nf, s->tref, s->tref_n, s->tcur, s->tcur_n, nt, K, s->tidx, s->tsc, K, s->tnm, s->stream));
+    if (s->outlier_rejection)   // point_matcher.cc:95-104 on the device, in place, before the pack: AddKeyframeCheck counts the filtered lists
+      SEQ_CTX(s, s->nf, airfe_fundamental_ransac_batch_dev(s->nf, s->tref, s->tref_n, s->tcur, s->tcur_n, nt, K, s->tidx, s->tsc, K, s->tnm, nullptr, s->stream));
   }
   // everything the host side of the loop reads -> the pinned staging set, valid rows only: one launch
   int* C = G.counts;

@@ -327,4 +327,18 @@ struct MlArgs {
 };
 void launch_match_lines(const MlArgs& a, int B, hipStream_t st);
 
+// F-matrix RANSAC (src/point_matcher.cc:95-104) over B device match lists, compacted in place (kernels_fransac.hip; contract: include/airfe.h)
+#define FR_MAX_MATCHES 1024           // matches per pair the kernels hold in LDS (max_keypoints <= 1024)
+struct FransacArgs {
+  const float *f0 = nullptr, *f1 = nullptr;   // [B][cap][259], original pixel coordinates
+  int cap = 0, mcap = 0;                      // mcap <= FR_MAX_MATCHES
+  int32_t* idx = nullptr;                     // [B][mcap][2]   in / out
+  float* score = nullptr;                     // [B][mcap]      in / out
+  int* nmatch = nullptr;                      // [B]            in / out
+  double* F = nullptr;                        // [B][9] the selected model (zeros: none / list below the gate), or nullptr
+  int* scores = nullptr;                      // scratch [B][1000][3]: per model inlier count (RANSAC) / median error bits (LMedS), -1 = no model
+  int* state = nullptr;                       // scratch [B][4]: niters bound, decided, selected model (3 s + root; -1 none, -2 gate)
+};
+void launch_fransac(const FransacArgs& a, int B, hipStream_t st);
+
 }  // namespace airfe

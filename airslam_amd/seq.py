@@ -28,8 +28,9 @@ Three drivers of the same loop, with identical per-frame outputs (tests/test_gpu
     while the host decides for the other.
 
 The keyframe POLICY (AddKeyframeCheck, Frame::AddRightFeatures' stereo count) is the caller's, not the path's: it is restated here (file:line on every
-function) only so that the loop can run without the SLAM back end.  Not restated: the F-matrix RANSAC behind MatchingPoints(..., true)
-(src/point_matcher.cc:95-104, cv::findFundamentalMat) — the temporal matches are the matcher's own list; IMU branches (UseIMU() is false in the VO configs).
+function) only so that the loop can run without the SLAM back end.  The F-matrix RANSAC behind MatchingPoints(..., true) (src/point_matcher.cc:95-104,
+cv::findFundamentalMat there) runs on the device with outlier_rejection=True (every driver takes it; default False: the temporal matches are the matcher's own
+list) by the project's contract (include/airfe.h, "F-matrix RANSAC").  Not restated: IMU branches (UseIMU() is false in the VO configs).
 
 Two contexts, like the reference's two detector objects: `kf` = PLNet (+ stage 1) + LightGlue, `nf` = SuperPoint + LightGlue.
 """
@@ -165,8 +166,10 @@ class _LoopState:
 class SequenceFrontEnd:
     """ONE sequence, one frame per call, batch-1 host entries (the module docstring has the map)."""
 
-    def __init__(self, kf: api.Context, nf: api.Context, cfg: Optional[KeyframeConfig] = None):
+    def __init__(self, kf: api.Context, nf: api.Context, cfg: Optional[KeyframeConfig] = None, outlier_rejection: bool = False):
         self.kf, self.nf, self.cfg = kf, nf, cfg or KeyframeConfig()
+        self.outlier_rejection = outlier_rejection
+        self._rej = dict(outlier_rejection=True) if outlier_rejection else {}     # (only when asked: the oracle's contexts take the calls without it)
         self.state = _LoopState()
         self._ref_on = {id(kf): False, id(nf): False}     # which context holds the current reference rows on its device block
         self._nf_has_frame = False
@@ -183,7 +186,7 @@ class SequenceFrontEnd:
         r = FrameResult(candidate=st.candidate())
         if r.candidate:
             if st.init:        # keyframe + its temporal match in one call (map_builder.cc:85-86 and :100-101)
-                k = self.kf.stereo_keyframe(left, right, track=True, ref_feat=self._ref_arg(self.kf))
+                k = self.kf.stereo_keyframe(left, right, track=True, ref_feat=self._ref_arg(self.kf), **self._rej)
                 r.matches_idx, r.matches_score = k["track_idx"], k["track_score"]
             else:
                 k = self.kf.stereo_keyframe(left, right)
@@ -193,7 +196,7 @@ class SequenceFrontEnd:
             r.good_stereo_point = good_stereo_points(cfg, r.features_left, r.features_right, r.stereo_idx)
             self._nf_has_frame = False
         else:
-            r.features_left, r.matches_idx, r.matches_score = self.nf.track_frame(left, ref_feat=self._ref_arg(self.nf))
+            r.features_left, r.matches_idx, r.matches_score = self.nf.track_frame(left, ref_feat=self._ref_arg(self.nf), **self._rej)
             self._nf_has_frame = True
 
         def promote():
@@ -214,12 +217,13 @@ class BatchedSequences:
     tensors [S, h, w] uint8 and returns S FrameResults whose arrays are the bytes SequenceFrontEnd returns for each sequence on its own."""
 
     def __init__(self, kf: api.Context, nf: api.Context, S: int, cfg: Optional[KeyframeConfig] = None, cap_lines: int = 1024, cap_junc: int = 1024,
-                 device=None, copy_results: bool = True):
+                 device=None, copy_results: bool = True, outlier_rejection: bool = False):
         """copy_results = False: the arrays of a step's FrameResults are VIEWS of pinned staging memory, valid until the end of the NEXT step (two staging sets
         alternate) — a consumer that hands them on within a frame time saves S x 0.4 MB of host copies per step (1.6 ms at S = 16)."""
         import torch
         self.t = torch
         self.kf, self.nf, self.S, self.cfg = kf, nf, S, cfg or KeyframeConfig()
+        self.outlier_rejection = outlier_rejection
         self.states = [_LoopState() for _ in range(S)]
         K = nf.max_keypoints
         assert kf.max_keypoints == K, "both contexts must be created with the same max_keypoints"
@@ -308,6 +312,8 @@ class BatchedSequences:
                 self.tcur[:nt] = self.cur.index_select(0, ts); self.tcur_n[:nt] = self.cur_n.index_select(0, ts)
                 self.nf.match_lightglue_batch_dev(self.tref[:nt], self.tref_n[:nt], self.tcur[:nt], self.tcur_n[:nt], self.tidx[:nt], self.tsc[:nt], self.tnm[:nt],
                                                   stream=sh)
+                if self.outlier_rejection:   # point_matcher.cc:95-104, in place, where the native driver queues it (airfe_seq.hip)
+                    self.nf.fundamental_ransac_batch_dev(self.tref[:nt], self.tcur[:nt], self.tidx[:nt], self.tsc[:nt], self.tnm[:nt], stream=sh)
             # everything the host side of the loop reads, in one wait
             h_cur, h_cur_n = self._home("cur", S), self._home("cur_n", S)
             if kset:
@@ -398,7 +404,7 @@ class NativeSequences:
     `raw` the ctypes array of airfe_seq_frame records of the last step (what a C++ caller would read)."""
 
     def __init__(self, kf: api.Context, nf: api.Context, S: int, cfg: Optional[KeyframeConfig] = None, cap_lines: int = 1024, cap_junc: int = 1024,
-                 device=None, copy_results: bool = True, temporal_buffers: bool = False):
+                 device=None, copy_results: bool = True, temporal_buffers: bool = False, outlier_rejection: bool = False):
         import ctypes as C
         from . import _lib
         self._C, self._l = C, _lib.lib()
@@ -420,6 +426,8 @@ class NativeSequences:
         if self._l.airfe_seq_create(kf._h, nf._h, S, C.byref(pol), cap_lines, cap_junc, ptrs[0], ptrs[1], ptrs[2], C.byref(h)):
             raise api.AirfeError("airfe_seq_create: " + (self._l.airfe_seq_last_error(None) or b"").decode())
         self._h = h
+        if outlier_rejection and self._l.airfe_seq_set_outlier_rejection(self._h, 1):
+            raise api.AirfeError("airfe_seq_set_outlier_rejection failed")
         self.raw = (_lib.SeqFrame * S)()
         self.copy_results = copy_results
         self.stream_ptr = self._l.airfe_seq_stream(self._h)

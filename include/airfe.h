@@ -159,14 +159,15 @@ int airfe_stereo_keyframe(airfe_ctx* ctx, const uint8_t* left, const uint8_t* ri
  * matches, true) — which every keyframe candidate runs as well.  The two LightGlue calls are independent, so they ride in ONE forward as a batch of two pairs
  * (at this size a forward costs the same for one pair as for two).  ref_feat [n_ref][259] = the last keyframe's features (NULL: the ones already on the device,
  * shared with airfe_track_frame); track_idx [mcap][2] = (reference index, left index), track_score, *ntrack.  Everything else as airfe_stereo_keyframe; per
- * pair the bits of two separate airfe_match_lightglue calls.  Needs cfg.max_batch >= 2. */
+ * pair the bits of two separate airfe_match_lightglue calls.  Needs cfg.max_batch >= 2.  airfe_set_outlier_rejection(ctx, 1): the track_* list (:96, `true`)
+ * passes the F-matrix RANSAC on the device; the stereo list (:86, `false`) never does. */
 int airfe_stereo_keyframe_tracked(airfe_ctx* ctx, const uint8_t* left, const uint8_t* right, int h, int w, int stride, float* featL, float* featR, int cap,
                                   int* nL, int* nR, double* linesL, double* linesR, int capL, int* nlinesL, int* nlinesR, float* juncL, int capJ,
                                   int* njuncL, int32_t* match_idx, float* match_score, int mcap, int* nmatch, const float* ref_feat, int n_ref,
                                   int32_t* track_idx, float* track_score, int* ntrack);
 /* ONE tracked (non-keyframe) frame through host buffers — src/map_builder.cc:94-101: Detect(image_left_rect, left_features) followed by
- * MatchingPoints(features_last_keyframe, left_features, matches, true) (the F-matrix RANSAC behind the matcher, point_matcher.cc:95-104, stays the
- * reference's).  ref_feat [n_ref][259] = the last keyframe's features: uploaded when given, KEPT on the device when NULL (pass them once per keyframe);
+ * MatchingPoints(features_last_keyframe, left_features, matches, true) (the F-matrix RANSAC behind the matcher, point_matcher.cc:95-104, runs on the
+ * device before the list is copied back when airfe_set_outlier_rejection(ctx, 1) asks for it; default: the matcher's list).  ref_feat [n_ref][259] = the last keyframe's features: uploaded when given, KEPT on the device when NULL (pass them once per keyframe);
  * feat / *n = the new frame's features; match_idx [mcap][2] = (reference index, new index), match_score, *nmatch.  Same bits as airfe_detect_points +
  * airfe_match_lightglue on NormalizeKeypoints'ed rows.  Needs the detector and LightGlue packs in one context, fp16 / bf16. */
 int airfe_track_frame(airfe_ctx* ctx, const uint8_t* gray, int h, int w, int stride, const float* ref_feat, int n_ref, float* feat, int cap, int* n,
@@ -192,6 +193,50 @@ int airfe_match_lightglue(airfe_ctx* ctx, const float* f0, int n0, const float* 
  *   idx0 [n0], idx1 [n1] (-1 = unmatched), ms0 [n0], ms1 [n1] doubles (decode, src/super_glue.cpp:339-367). */
 int airfe_match_superglue(airfe_ctx* ctx, const float* f0, int n0, const float* f1, int n1, int32_t* idx0, int32_t* idx1,
                           double* ms0, double* ms1);
+
+/* ---- F-matrix RANSAC: the outlier rejection of MatchingPoints(..., outlier_rejection = true) (src/point_matcher.cc:95-104) ---------------
+ * The reference calls cv::findFundamentalMat(points0, points1, cv::FM_RANSAC, 20, 0.99, inliers) when more than 8 matches are left and keeps the inliers
+ * in order (matches[j++] = matches[i]).  The contract below restates the PUBLIC behaviour of OpenCV's legacy (non-USAC) FM_RANSAC path; OpenCV is not part
+ * of this project's build or tests, so nothing here is checked against OpenCV and nothing claims bit-equality with it.  Its numerics are ours, on every
+ * side: the HIP kernels (airslam_amd/csrc/kernels_fransac.hip), the C++ stand-in of cv::findFundamentalMat the tests run the reference's own
+ * MatchingPoints against (shim/stubs/mini_support.cpp; both share airslam_amd/csrc/fransac_core.h) and the numpy restatement (tests/fransac_ref.py).
+ *   input    the matched keypoints in ORIGINAL pixels, converted as the reference converts them: cv::Point is Point_<int> built from the floats, so x, y
+ *            are truncated toward zero, then used as doubles.  LightGlue: the pairs in list order; SuperGlue: the mutual pairs in i order (:65-92).
+ *   gate     fewer than 9 matches: the list comes back unchanged, bit for bit.
+ *   samples  sample s (0, 1, ...) draws attempt a = 0, 1, ... < 64: slot k (0..6) is match floor(hi32(h) * m / 2^32) with
+ *            h = splitmix64(0x2545F4914F6CDD1D ^ (s << 32 | a << 8 | k)) (splitmix64: z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *            z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31).  An attempt is rejected when two slots repeat an index or any 3 of its points are
+ *            collinear in either image (OpenCV's test: |dx2 dy1 - dy2 dx1| <= FLT_EPSILON (|dx1| + |dy1| + |dx2| + |dy2|)); a sample whose 64 attempts are
+ *            all rejected yields no model.  The draws depend on (s, a, k, m) only: not on a pair's position in a batch or the batch size.
+ *   solver   the 7-point algorithm in fp64: rows [x1 x0, x1 y0, x1, y1 x0, y1 y0, y1, x0, y0, 1]; Gaussian elimination with partial pivoting (first
+ *            largest |pivot|) over columns 0..6 (a pivot <= 1e-12 max|A| = no model), null vectors F1 = (.., 1, 0), F2 = (.., 0, 1) by back substitution;
+ *            det(a F1 + (1 - a) F2) = 0 as a cubic solved in closed form (trigonometric for three real roots, Cardano for one; quadratic / linear when
+ *            the leading coefficients are exactly 0), 1 or 3 models per sample in root order; F scaled so that F(2,2) = 1 where |F(2,2)| > DBL_EPSILON;
+ *            models with a non-finite entry are dropped.  F is row-major with x1^T F x0 = 0.
+ *   error    per match, in double: d = x1^T F x0, (a, b, .) = F x0, (a', b', .) = F^T x1, err = max(d^2 / (a'^2 + b'^2), d^2 / (a^2 + b^2)) (NaN = +inf),
+ *            rounded to float.
+ *   RANSAC   (15 and more matches) inlier: err <= 400.0f (20 px).  Sequentially, in sample order and root order: a model replaces the best only with
+ *            STRICTLY more inliers than max(best, 6) (the first one wins ties); each replacement sets niters = RANSACUpdateNumIters(0.99, outliers / m,
+ *            7, 1000); the search stops at the first sample index >= niters (at most 1000 samples).  The device scores samples in parallel; a scan over
+ *            the scores in sample order selects exactly the model this sequential rule selects.
+ *   LMedS    (9 to 14 matches: OpenCV's FM_RANSAC runs LMedS there) the same solver over samples 0..299 (round(log(0.01) / log(1 - 0.55^7))); the model
+ *            with the smallest median error (the element of rank m / 2, float) wins, first on ties; inliers: err <= (float)sigma^2 with
+ *            sigma = max(2.5 * 1.4826 * (1 + 5 / (m - 7)) * sqrt(median), 0.001); fewer than 7 inliers = no model.
+ *   no model (every sample degenerate, no model above 6 inliers, LMedS below 7): nothing is kept, the count is 0.
+ *   output   the kept matches in their original order, each index pair with its own score (DMatch::distance = 1 - score survives); F (optional) = the
+ *            selected model, 9 doubles, zeros when there is none or the gate returned the list as it was.
+ * Per pair the batch and the one-call entries give the same bytes. */
+/* ≙ point_matcher.cc:95-104 on ONE pair through host buffers: f0 [n0][259], f1 [n1][259] rows (original pixels), the list idx [m][2] (index into f0, into f1)
+ * + score [m], filtered in place; *kept = the new length.  m <= 1024. */
+int airfe_fundamental_ransac(airfe_ctx* ctx, const float* f0, int n0, const float* f1, int n1, int32_t* idx, float* score, int m, int* kept);
+/* the same over B device-resident pairs, in place and asynchronous on `stream`: d_f0 / d_f1 [B][cap][259], the match lists airfe_match_lightglue_batch_dev
+ * writes (d_idx [B][mcap][2], d_score [B][mcap], d_nmatch [B]; mcap <= 1024), d_F [B][9] or NULL.  d_n0 / d_n1 are the feature counts (not read: the
+ * indices come from the matcher). */
+int airfe_fundamental_ransac_batch_dev(airfe_ctx* ctx, const float* d_f0, const int* d_n0, const float* d_f1, const int* d_n1, int B, int cap,
+                                       int32_t* d_idx, float* d_score, int mcap, int* d_nmatch, double* d_F, void* stream);
+/* ≙ the `outlier_rejection` argument at the reference's call sites that pass `true` (map_builder.cc:101 and :96): on = 1 filters the temporal list of
+ * airfe_track_frame and the track_* list of airfe_stereo_keyframe_tracked on the device before they are copied back.  Default 0. */
+int airfe_set_outlier_rejection(airfe_ctx* ctx, int on);
 
 /* ---- next row after the path ---------------------------------------------------- */
 /* ≙ AssignPointsToLines (src/line_processor.cc:68-120), called on the path's own outputs (frame.cc:125,177,184).

@@ -14,8 +14,10 @@
  * writes only the valid rows into pinned memory.
  *
  * The keyframe POLICY (AddKeyframeCheck, the stereo count of Frame::AddRightFeatures, src/frame.cc:141-172) is the caller's in the reference; it is restated
- * in the driver (file:line at each function) because the loop cannot run without it.  Not restated: the F-matrix RANSAC behind MatchingPoints(..., true)
- * (src/point_matcher.cc:95-104) and the IMU branches (UseIMU() is false in the VO configurations).
+ * in the driver (file:line at each function) because the loop cannot run without it.  The F-matrix RANSAC behind MatchingPoints(..., true)
+ * (src/point_matcher.cc:95-104) runs on the device when airfe_seq_set_outlier_rejection(s, 1) asks for it (default off: the lists as the matcher left them);
+ * its numerics are the project's contract (include/airfe.h, "F-matrix RANSAC"), not OpenCV's.  Not restated: the IMU branches (UseIMU() is false in the VO
+ * configurations).
  *
  * Per (sequence, frame) the results are the bytes airslam_amd.seq.SequenceFrontEnd returns through the one-call host entries (tests/test_gpu_seq.py).
  * Same conventions as include/airfe.h: 0 = ok, non-zero = failure with airfe_seq_last_error(); never throws; reads no environment.
@@ -75,7 +77,8 @@ typedef struct airfe_seq_frame {
  * The contexts stay the caller's (destroy them after the driver) and must not be used by anyone else while the driver lives (one stream, one calling thread).
  * cap_lines / cap_junc: rows kept per image; more lines / junctions than that is an error of the step (the reference has no limits).
  * d_tidx [S][max_keypoints][2], d_tscore [S][max_keypoints], d_tn [S] (device, may all be NULL): where the temporal match lists of a time-step are left on the
- * device — row j = the j-th initialised sequence in ascending order — for a caller that forwards them (the K-frame gather of BASELINE configs[3]). */
+ * device — row j = the j-th initialised sequence in ascending order — for a caller that forwards them (the K-frame gather of BASELINE configs[3]); with outlier
+ * rejection on they hold the lists after the F-matrix RANSAC, the lists AddKeyframeCheck decided on. */
 int airfe_seq_create(airfe_ctx* kf, airfe_ctx* nf, int S, const airfe_seq_policy* policy, int cap_lines, int cap_junc, int32_t* d_tidx, float* d_tscore,
                      int* d_tn, airfe_seq** out);
 void airfe_seq_destroy(airfe_seq* s);
@@ -90,6 +93,9 @@ const char* airfe_seq_last_error(const airfe_seq* s); /* s may be NULL (creation
 int airfe_seq_begin(airfe_seq* s, const uint8_t* d_left, const uint8_t* d_right, int h, int w, int stride, size_t img_stride);
 int airfe_seq_end(airfe_seq* s, airfe_seq_frame* out);
 int airfe_seq_step(airfe_seq* s, const uint8_t* d_left, const uint8_t* d_right, int h, int w, int stride, size_t img_stride, airfe_seq_frame* out);
+/* ≙ the `true` of MatchingPoints(..., matches, true) at src/map_builder.cc:101: on = 1 queues airfe_fundamental_ransac_batch_dev on the temporal lists right
+ * behind the temporal LightGlue batch of every later time-step (before the results are packed), so the keyframe decisions see the filtered lists.  Default 0. */
+int airfe_seq_set_outlier_rejection(airfe_seq* s, int on);
 /* the stream the temporal match lists are complete on (for a caller that forwards d_tidx / d_tscore / d_tn: order behind it) */
 void* airfe_seq_stream(airfe_seq* s);
 /* where a time-step's wall time went since the last call (seconds, summed; host_syncs counted): queueing device work, waiting for the device, the host side of

@@ -1,7 +1,7 @@
 // mini-OpenCV: a stand-in for <opencv2/opencv.hpp> — OpenCV is not installed in the build container.
 // Only what AirSLAM's front-end sources touch (see shim/stubs/Eigen/Core for why this exists): cv::Mat as a strided 8-bit
 // image, Size, Point_, Vec, DMatch, KeyPoint, Scalar, cv::resize for CV_8UC1 / INTER_LINEAR, and a declared
-// cv::findFundamentalMat (defined in shim/stubs/mini_opencv.cpp to fail loudly: F-RANSAC stays OpenCV's).
+// cv::findFundamentalMat (defined in shim/stubs/mini_support.cpp: the project's restatement of FM_RANSAC, include/airfe.h "F-matrix RANSAC").
 //
 // cv::resize here is OUR restatement of OpenCV 4.x's 8-bit bilinear path (imgproc/src/resize.cpp: 11-bit horizontal
 // coefficients with cvRound, vertical `(((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2`) — the same
@@ -168,8 +168,8 @@ inline FileStorage& operator<<(FileStorage& fs, const T&) { return fs; }
 template <class M>
 inline void eigen2cv(const M&, Mat& dst) { dst = Mat(); }     // FSuperpoint::toMat32F (k-means training helper): float matrices are not modelled
 
-// declared like OpenCV's; the definition (shim/stubs/mini_opencv.cpp) aborts with a message — the F-RANSAC of
-// PointMatcher::MatchingPoints(outlier_rejection = true) is OpenCV's and out of scope
+// declared like OpenCV's; the definition (shim/stubs/mini_support.cpp) restates the legacy FM_RANSAC path as the project's contract states it
+// (include/airfe.h, "F-matrix RANSAC"; not OpenCV's numerics) for the one call the reference makes: PointMatcher::MatchingPoints(outlier_rejection = true)
 Mat findFundamentalMat(const std::vector<Point>& points1, const std::vector<Point>& points2, int method, double ransacReprojThreshold,
                        double confidence, std::vector<uchar>& mask);
 }  // namespace cv
