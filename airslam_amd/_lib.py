@@ -131,6 +131,14 @@ SIGNATURES = {
     "airfe_fundamental_ransac_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "airfe_set_outlier_rejection": (C.c_int, [C.c_void_p, C.c_int]),
+    "airfe_pnp_ransac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "airfe_pnp_ransac_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "airfe_stereo_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.POINTER(C.c_int)]),
+    "airfe_stereo_points_batch_dev": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5),
+    "airfe_track_pose_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "airfe_sync": (C.c_int, [C.c_void_p]),
     "airfe_superglue_status": (C.c_int, [C.c_void_p, C.c_void_p]),
     "airfe_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),

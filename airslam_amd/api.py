@@ -475,6 +475,62 @@ class Context:
                                                              None if F_t is None else F_t.data_ptr(), self._stream(stream)),
                   "airfe_fundamental_ransac_batch_dev")
 
+    def pnp_ransac(self, obj: np.ndarray, img: np.ndarray, K):
+        """PnP RANSAC on ONE problem (airfe_pnp_ransac ≙ cv::solvePnPRansac in SolvePnPWithCV, g2o_optimization.cc:1085-1134; contract: include/airfe.h):
+        obj [n,3], img [n,2] (doubles; rounded to float as cv::Point3f / Point2f), K = (fx, fy, cx, cy) -> dict(Twc [4,4], Rt [12] (Rcw row-major, tcw),
+        inlier [n] uint8, count)."""
+        obj = np.ascontiguousarray(obj, np.float64).reshape(-1, 3)
+        img = np.ascontiguousarray(img, np.float64).reshape(-1, 2)
+        if len(obj) != len(img):
+            raise AirfeError("pnp_ransac: obj and img differ in length")
+        k = np.ascontiguousarray(K, np.float64).reshape(4)
+        Twc, Rt = np.zeros(16), np.zeros(12)
+        mask = np.zeros(max(len(obj), 1), np.uint8)
+        cnt = C.c_int(0)
+        self._chk(self._l.airfe_pnp_ransac(self._h, obj.ctypes.data, img.ctypes.data, len(obj), k.ctypes.data, Twc.ctypes.data, Rt.ctypes.data,
+                                           mask.ctypes.data, C.byref(cnt)), "airfe_pnp_ransac")
+        return dict(Twc=Twc.reshape(4, 4), Rt=Rt, inlier=mask[:len(obj)], count=cnt.value)
+
+    def pnp_ransac_batch_dev(self, obj_t, img_t, n_t, K, Twc_t, inlier_t, count_t, Rt_t=None, stream=None):
+        """airfe_pnp_ransac_batch_dev: obj_t [B,ncap,3] / img_t [B,ncap,2] float32, n_t [B] int32 -> Twc_t [B,16] float64, inlier_t [B,ncap] uint8,
+        count_t [B] int32, Rt_t [B,12] float64 (optional)."""
+        k = np.ascontiguousarray(K, np.float64).reshape(4)
+        self._chk(self._l.airfe_pnp_ransac_batch_dev(self._h, obj_t.data_ptr(), img_t.data_ptr(), n_t.data_ptr(), obj_t.shape[0], obj_t.shape[1],
+                                                     k.ctypes.data, Twc_t.data_ptr(), None if Rt_t is None else Rt_t.data_ptr(), inlier_t.data_ptr(),
+                                                     count_t.data_ptr(), self._stream(stream)), "airfe_pnp_ransac_batch_dev")
+
+    def stereo_points(self, cam, featL: np.ndarray, featR: np.ndarray, idx: np.ndarray):
+        """Frame::AddRightFeatures + BackProjectPoint on ONE stereo list (airfe_stereo_points): cam = (min_x_diff, max_x_diff, max_y_diff, bf, fx, fy, cx, cy),
+        featL [nL,259], featR [nR,259], idx [m,2] (left, right) -> dict(u_right [nL], depth [nL] (-1 unset), xyz [nL,3] (NaN unset), good)."""
+        cam = np.ascontiguousarray(cam, np.float64).reshape(8)
+        featL = np.ascontiguousarray(featL, np.float32).reshape(-1, FEAT)
+        featR = np.ascontiguousarray(featR, np.float32).reshape(-1, FEAT)
+        idx = np.ascontiguousarray(idx, np.int32).reshape(-1, 2)
+        nL = len(featL)
+        u, d, xyz = np.empty(max(nL, 1)), np.empty(max(nL, 1)), np.empty((max(nL, 1), 3))
+        good = C.c_int(0)
+        self._chk(self._l.airfe_stereo_points(self._h, cam.ctypes.data, featL.ctypes.data, nL, featR.ctypes.data, len(featR), idx.ctypes.data, len(idx),
+                                              u.ctypes.data, d.ctypes.data, xyz.ctypes.data, C.byref(good)), "airfe_stereo_points")
+        return dict(u_right=u[:nL], depth=d[:nL], xyz=xyz[:nL], good=good.value)
+
+    def stereo_points_batch_dev(self, cam, featL_t, nL_t, featR_t, nR_t, idx_t, nm_t, u_right_t, depth_t, xyz_t, good_t, stream=None):
+        """airfe_stereo_points_batch_dev: feat [B,cap,259], n [B], idx_t [B,mcap,2], nm_t [B] -> u_right_t / depth_t [B,cap], xyz_t [B,cap,3] float64,
+        good_t [B] int32."""
+        cam = np.ascontiguousarray(cam, np.float64).reshape(8)
+        self._chk(self._l.airfe_stereo_points_batch_dev(self._h, cam.ctypes.data, featL_t.data_ptr(), nL_t.data_ptr(), featR_t.data_ptr(), nR_t.data_ptr(),
+                                                        featL_t.shape[0], featL_t.shape[1], idx_t.data_ptr(), nm_t.data_ptr(), idx_t.shape[1],
+                                                        u_right_t.data_ptr(), depth_t.data_ptr(), xyz_t.data_ptr(), good_t.data_ptr(), self._stream(stream)),
+                  "airfe_stereo_points_batch_dev")
+
+    def track_pose_batch_dev(self, K, xyz_t, feat_t, tidx_t, ntrack_t, Twc_t, mask_t, count_t, Rt_t=None, stream=None):
+        """airfe_track_pose_batch_dev: keyframe points xyz_t [B,capK,3] float64, current rows feat_t [B,cap,259], temporal lists tidx_t [B,mcap,2]
+        (keyframe, current) + ntrack_t [B] -> Twc_t [B,16], mask_t [B,mcap] uint8 (per list entry), count_t [B], Rt_t [B,12] (optional)."""
+        k = np.ascontiguousarray(K, np.float64).reshape(4)
+        self._chk(self._l.airfe_track_pose_batch_dev(self._h, k.ctypes.data, xyz_t.data_ptr(), xyz_t.shape[1], feat_t.data_ptr(), feat_t.shape[1],
+                                                     tidx_t.data_ptr(), ntrack_t.data_ptr(), tidx_t.shape[1], tidx_t.shape[0], Twc_t.data_ptr(),
+                                                     None if Rt_t is None else Rt_t.data_ptr(), mask_t.data_ptr(), count_t.data_ptr(),
+                                                     self._stream(stream)), "airfe_track_pose_batch_dev")
+
     def match_lightglue_batch_dev(self, f0_t, n0_t, f1_t, n1_t, idx_t, score_t, nm_t, stream=None):
         self._chk(self._l.airfe_match_lightglue_batch_dev(self._h, f0_t.data_ptr(), n0_t.data_ptr(), f1_t.data_ptr(),
                                                           n1_t.data_ptr(), f0_t.shape[0], f0_t.shape[1], idx_t.data_ptr(),

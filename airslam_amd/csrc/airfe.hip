@@ -2,6 +2,7 @@
 // airfe_load.hip / airfe_detect.hip / airfe_match.hip (see airfe_host.h).
 #include "airfe_host.h"
 #include "fransac_core.h"
+#include "pnp_core.h"
 
 namespace airfe_host {
 thread_local std::string g_err;
@@ -868,6 +869,116 @@ int airfe_set_outlier_rejection(airfe_ctx* c, int on) try {
   AIRFE_ENTER(c);
   c->outlier_rejection = on != 0;
   return 0;
+} AIRFE_CATCH(c)
+
+// PnP RANSAC (g2o_optimization.cc:1085-1134) over B device problems on `st` (kernels_pnp.hip): scores + models of the 100 samples in the context's
+// scratch (grown only behind a synchronisation of the stream it was last used on, as fransac_queue's).
+static int pnp_queue(airfe_ctx* c, const float* d_obj, const float* d_img, const int* d_n, int B, int ncap, const double* K, double* d_Twc, double* d_Rt,
+                     uint8_t* d_mask, int mcap, const int* d_map, int* d_count, hipStream_t st) {
+  const size_t score_bytes = ((size_t)B * PNP_MAX_ITERS * 4 + 255) / 256 * 256;
+  if (ensure_block(c, c->pn_scratch, c->pn_scratch_bytes, score_bytes + (size_t)B * PNP_MAX_ITERS * 12 * 8, c->pn_scratch_stream)) return 1;
+  c->pn_scratch_stream = st;
+  PnpArgs a;
+  a.obj = d_obj; a.img = d_img; a.n = d_n; a.ncap = ncap;
+  a.fx = K[0]; a.fy = K[1]; a.cx = K[2]; a.cy = K[3];
+  a.scores = reinterpret_cast<int*>(c->pn_scratch);
+  a.models = reinterpret_cast<double*>(c->pn_scratch + score_bytes);
+  a.Twc = d_Twc; a.Rt = d_Rt; a.mask = d_mask; a.mcap = mcap; a.map = d_map; a.count = d_count;
+  launch_pnp(a, B, st);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+int airfe_pnp_ransac_batch_dev(airfe_ctx* c, const float* d_obj, const float* d_img, const int* d_n, int B, int ncap, const double* K, double* d_Twc,
+                               double* d_Rt, uint8_t* d_inlier, int* d_count, void* stream) try {
+  AIRFE_ENTER(c);
+  if (B < 1 || ncap < 1 || !d_obj || !d_img || !d_n || !K || !d_Twc || !d_inlier || !d_count) return fail(c, "pnp_ransac_batch_dev: bad argument");
+  if (ncap > PNP_MAX_POINTS) return fail(c, "pnp_ransac_batch_dev: ncap > 1024");
+  return pnp_queue(c, d_obj, d_img, d_n, B, ncap, K, d_Twc, d_Rt, d_inlier, ncap, nullptr, d_count, stream ? (hipStream_t)stream : c->stream);
+} AIRFE_CATCH(c)
+
+int airfe_pnp_ransac(airfe_ctx* c, const double* obj, const double* img, int n, const double* K, double* Twc, double* Rt, uint8_t* inlier, int* count) try {
+  AIRFE_ENTER(c);
+  if (n < 0 || !K || !Twc || !count || (n > 0 && (!obj || !img || !inlier))) return fail(c, "pnp_ransac: bad argument");
+  if (n > PNP_MAX_POINTS) return fail(c, "pnp_ransac: more than 1024 correspondences");
+  const int ncap = std::max(n, 1);
+  // one block: n | Twc [16] | Rt [12] | count | obj [ncap][3] f32 | img [ncap][2] f32 | mask [ncap]
+  const size_t o_obj = 256, o_img = o_obj + (size_t)ncap * 12, o_mask = o_img + (size_t)ncap * 8;
+  if (ensure_block(c, c->pn_stage, c->pn_stage_bytes, o_mask + ncap)) return 1;
+  std::vector<float> h((size_t)ncap * 5, 0.f);
+  for (int i = 0; i < n; ++i) {                                      // cv::Point3f / cv::Point2f: the doubles rounded to float
+    for (int k = 0; k < 3; ++k) h[3 * i + k] = (float)obj[3 * i + k];
+    for (int k = 0; k < 2; ++k) h[(size_t)ncap * 3 + 2 * i + k] = (float)img[2 * i + k];
+  }
+  uint8_t* d = c->pn_stage;
+  int* d_n = reinterpret_cast<int*>(d);
+  double* d_Twc = reinterpret_cast<double*>(d + 8);
+  double* d_Rt = reinterpret_cast<double*>(d + 8 + 128);
+  int* d_count = reinterpret_cast<int*>(d + 8 + 128 + 96);
+  hipStream_t st = c->stream;
+  DrainOnError drain{c, true};
+  HIPCHK(c, hipMemcpyAsync(d_n, &n, 4, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d + o_obj, h.data(), (size_t)ncap * 20, hipMemcpyHostToDevice, st));
+  if (pnp_queue(c, reinterpret_cast<float*>(d + o_obj), reinterpret_cast<float*>(d + o_img), d_n, 1, ncap, K, d_Twc, d_Rt, d + o_mask, ncap, nullptr,
+                d_count, st)) return 1;
+  double rt[12];
+  HIPCHK(c, hipMemcpyAsync(Twc, d_Twc, 128, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(rt, d_Rt, 96, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(count, d_count, 4, hipMemcpyDeviceToHost, st));
+  if (n > 0) HIPCHK(c, hipMemcpyAsync(inlier, d + o_mask, n, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  drain.armed = false;
+  if (Rt) memcpy(Rt, rt, 96);
+  return 0;
+} AIRFE_CATCH(c)
+
+int airfe_stereo_points(airfe_ctx* c, const double* cam, const float* featL, int nL, const float* featR, int nR, const int32_t* idx, int m, double* u_right,
+                        double* depth, double* xyz, int* good) try {
+  if (!c) return 1;
+  if (!cam || !good || nL < 0 || nR < 0 || m < 0 || (nL > 0 && (!featL || !u_right || !depth || !xyz)) || (m > 0 && (!idx || !featR)))
+    return fail(c, "stereo_points: bad argument");
+  for (int j = 0; j < m; ++j)                                        // Frame::AddRightFeatures indexes both feature matrices with these
+    if (idx[2 * j] < 0 || idx[2 * j] >= nL || idx[2 * j + 1] < 0 || idx[2 * j + 1] >= nR) return fail(c, "stereo_points: match index out of range");
+  *good = pnp_stereo_host(featL, nL, featR, idx, m, cam, u_right, depth, xyz);
+  return 0;
+} AIRFE_CATCH(c)
+
+int airfe_stereo_points_batch_dev(airfe_ctx* c, const double* cam, const float* d_featL, const int* d_nL, const float* d_featR, const int* d_nR, int B,
+                                  int cap, const int32_t* d_idx, const int* d_nmatch, int mcap, double* d_u_right, double* d_depth, double* d_xyz,
+                                  int* d_good, void* stream) try {
+  AIRFE_ENTER(c);
+  if (B < 1 || cap < 1 || mcap < 1 || !cam || !d_featL || !d_nL || !d_featR || !d_nR || !d_idx || !d_nmatch || !d_u_right || !d_depth || !d_xyz || !d_good)
+    return fail(c, "stereo_points_batch_dev: bad argument");
+  if (cap > PNP_STEREO_CAP) return fail(c, "stereo_points_batch_dev: cap > 4096");
+  StereoArgs s;
+  s.fl = d_featL; s.fr = d_featR; s.nl = d_nL; s.nr = d_nR; s.cap = cap; s.idx = d_idx; s.nmatch = d_nmatch; s.mcap = mcap;
+  s.min_x_diff = cam[0]; s.max_x_diff = cam[1]; s.max_y_diff = cam[2]; s.bf = cam[3]; s.fx = cam[4]; s.fy = cam[5]; s.cx = cam[6]; s.cy = cam[7];
+  s.u_right = d_u_right; s.depth = d_depth; s.xyz = d_xyz; s.good = d_good;
+  launch_stereo_points(s, B, stream ? (hipStream_t)stream : c->stream);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+} AIRFE_CATCH(c)
+
+int airfe_track_pose_batch_dev(airfe_ctx* c, const double* K, const double* d_xyz, int capK, const float* d_feat, int cap, const int32_t* d_tidx,
+                               const int* d_ntrack, int mcap, int B, double* d_Twc, double* d_Rt, uint8_t* d_mask, int* d_count, void* stream) try {
+  AIRFE_ENTER(c);
+  if (B < 1 || capK < 1 || cap < 1 || mcap < 1 || !K || !d_xyz || !d_feat || !d_tidx || !d_ntrack || !d_Twc || !d_mask || !d_count)
+    return fail(c, "track_pose_batch_dev: bad argument");
+  if (mcap > PNP_MAX_POINTS) return fail(c, "track_pose_batch_dev: mcap > 1024");
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  // the gathered problems: obj [B][mcap][3] | img [B][mcap][2] f32 | map [B][mcap] | n [B]
+  const size_t per = (size_t)mcap * 24;
+  if (ensure_block(c, c->pn_gather, c->pn_gather_bytes, (size_t)B * per + (size_t)B * 4, c->pn_gather_stream)) return 1;
+  c->pn_gather_stream = st;
+  PnpGatherArgs g;
+  g.xyz = d_xyz; g.capK = capK; g.feat = d_feat; g.cap = cap; g.tidx = d_tidx; g.ntrack = d_ntrack; g.mcap = mcap; g.ncap = mcap;
+  g.obj = reinterpret_cast<float*>(c->pn_gather);
+  g.img = reinterpret_cast<float*>(c->pn_gather + (size_t)B * mcap * 12);
+  g.map = reinterpret_cast<int*>(c->pn_gather + (size_t)B * mcap * 20);
+  g.n = reinterpret_cast<int*>(c->pn_gather + (size_t)B * per);
+  launch_pnp_gather(g, B, st);
+  HIPCHK(c, hipGetLastError());
+  return pnp_queue(c, g.obj, g.img, g.n, B, mcap, K, d_Twc, d_Rt, d_mask, mcap, g.map, d_count, st);
 } AIRFE_CATCH(c)
 
 int airfe_has_line_branch(const airfe_ctx* c) { return c && c->has_s0 && c->has_s1; }

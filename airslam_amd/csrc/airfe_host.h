@@ -118,6 +118,11 @@ struct airfe_ctx {
   uint8_t* fr_scratch = nullptr; size_t fr_scratch_bytes = 0;           // airfe_fundamental_ransac_batch_dev: per-model scores [B][1000][3] + state [B][4]
   hipStream_t fr_scratch_stream = nullptr;
   uint8_t* fr_stage = nullptr; size_t fr_stage_bytes = 0;               // airfe_fundamental_ransac: the one pair's rows and list on the device
+  uint8_t* pn_scratch = nullptr; size_t pn_scratch_bytes = 0;           // airfe_pnp_ransac_batch_dev: per-sample scores [B][100] + models [B][100][12]
+  hipStream_t pn_scratch_stream = nullptr;
+  uint8_t* pn_gather = nullptr; size_t pn_gather_bytes = 0;             // airfe_track_pose_batch_dev: the gathered correspondences
+  hipStream_t pn_gather_stream = nullptr;
+  uint8_t* pn_stage = nullptr; size_t pn_stage_bytes = 0;               // airfe_pnp_ransac: the one problem on the device
   bool outlier_rejection = false;                                       // airfe_set_outlier_rejection: F-RANSAC behind the temporal match of track_frame / stereo_keyframe_tracked
   bool nms_map_valid = true;     // heat_nms holds the last batch's NMS'd maps (large batches skip writing them)
   bool force_nms_map = false;    // the batched PLNet path reads junction scores from them: written at every batch size while set

@@ -341,4 +341,38 @@ struct FransacArgs {
 };
 void launch_fransac(const FransacArgs& a, int B, hipStream_t st);
 
+// PnP RANSAC of SolvePnPWithCV (src/g2o_optimization/g2o_optimization.cc:1085-1134) over B device problems (kernels_pnp.hip; contract: include/airfe.h)
+struct PnpArgs {
+  const float *obj = nullptr, *img = nullptr;   // [B][ncap][3], [B][ncap][2]
+  const int* n = nullptr;                       // [B] correspondences
+  int ncap = 0;                                 // <= PNP_MAX_POINTS
+  double fx = 0, fy = 0, cx = 0, cy = 0;
+  int* scores = nullptr;                        // scratch [B][100]: inliers per sample, -1 = no model
+  double* models = nullptr;                     // scratch [B][100][12]
+  double *Twc = nullptr, *Rt = nullptr;         // [B][16], [B][12] or nullptr
+  uint8_t* mask = nullptr;                      // [B][mcap]: every entry written (0 beyond the problem's points)
+  int mcap = 0;
+  const int* map = nullptr;                     // [B][ncap] or nullptr: mask slot of correspondence i (the composite: its list entry)
+  int* count = nullptr;                         // [B]
+};
+void launch_pnp(const PnpArgs& a, int B, hipStream_t st);
+struct PnpGatherArgs {                          // the tracking composite: list entries whose keyframe point exists -> correspondences
+  const double* xyz = nullptr; int capK = 0;    // [B][capK][3] keyframe points (NaN: none)
+  const float* feat = nullptr; int cap = 0;     // [B][cap][259] current rows
+  const int32_t* tidx = nullptr; const int* ntrack = nullptr; int mcap = 0;   // [B][mcap][2] (ref, cur), [B]
+  float *obj = nullptr, *img = nullptr; int* map = nullptr; int* n = nullptr; int ncap = 0;
+};
+void launch_pnp_gather(const PnpGatherArgs& g, int B, hipStream_t st);
+#define PNP_STEREO_CAP 4096           // keypoints per frame the stereo kernel holds in LDS
+struct StereoArgs {
+  const float *fl = nullptr, *fr = nullptr;     // [B][cap][259]
+  const int *nl = nullptr, *nr = nullptr;       // [B]
+  int cap = 0;
+  const int32_t* idx = nullptr; const int* nmatch = nullptr; int mcap = 0;    // [B][mcap][2] (left, right), [B]
+  double min_x_diff = 0, max_x_diff = 0, max_y_diff = 0, bf = 0, fx = 0, fy = 0, cx = 0, cy = 0;
+  double *u_right = nullptr, *depth = nullptr, *xyz = nullptr;                // [B][cap], [B][cap], [B][cap][3]
+  int* good = nullptr;                          // [B]
+};
+void launch_stereo_points(const StereoArgs& s, int B, hipStream_t st);
+
 }  // namespace airfe

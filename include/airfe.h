@@ -238,6 +238,92 @@ int airfe_fundamental_ransac_batch_dev(airfe_ctx* ctx, const float* d_f0, const 
  * airfe_track_frame and the track_* list of airfe_stereo_keyframe_tracked on the device before they are copied back.  Default 0. */
 int airfe_set_outlier_rejection(airfe_ctx* ctx, int on);
 
+/* ---- PnP RANSAC: SolvePnPWithCV (src/g2o_optimization/g2o_optimization.cc:1085-1134) ----------------------------------------------------------------
+ * The reference seeds every tracked frame's pose (src/map_builder.cc:307-315, on every frame while the IMU is not initialised) and relocalization's best
+ * candidate (src/map_user.cc:386-390) with cv::solvePnPRansac(object_points, image_points, K, dist, rvec, tvec, false, 100, 20.0, 0.99, inliers) and the
+ * default SOLVEPNP_ITERATIVE.  The contract below restates the PUBLIC behaviour of that call; OpenCV is not part of this project's build or tests, so
+ * nothing here is checked against OpenCV and nothing claims bit-equality with it: the numerics are the project's own, on every side — the HIP kernels
+ * (airslam_amd/csrc/kernels_pnp.hip), the host core (pnp_solve_host in airslam_amd/csrc/pnp_core.h, which the kernels share) and the numpy restatement
+ * (tests/pnp_ref.py).  fp64 unless said otherwise, no fused multiply-adds, sums in the order written; the only non-rational function is sqrt.
+ *   input    object points as cv::Point3f (the doubles rounded to float), image points as cv::Point2f, K = (fx, fy, cx, cy) in double, no distortion
+ *            (Camera::GetDistCoeffs is all zeros, src/camera.cc:264-266).  Every float is used as a double.
+ *   gate     fewer than 8 correspondences (g2o_optimization.cc:1108): count 0, no model.
+ *   samples  sample s (0..99) draws attempt a = 0, 1, ... < 64: slot k (0..4) is point floor(hi32(h) * n / 2^32) with
+ *            h = splitmix64(0x6A09E667F3BCC909 ^ (s << 32 | a << 8 | k)) (splitmix64 as in "F-matrix RANSAC").  An attempt that repeats an index is
+ *            rejected; a sample whose 64 attempts are all rejected yields no model.  No other degeneracy test (OpenCV's PnP callback has no checkSubset).
+ *            The draws depend on (s, a, k, n) only.
+ *   Jacobi   (used three times below) cyclic Jacobi on a symmetric n x n matrix A, V = I: before each sweep (at most 30) stop when
+ *            sum_{p<q} A_pq^2 <= 1e-30 sum_p A_pp^2 (both sums row-major); a sweep visits (p, q) for p = 0..n-2, q = p+1..n-1, skips A_pq == 0, else
+ *            th = (A_qq - A_pp) / (2 A_pq), t = sign(th) / (|th| + sqrt(th^2 + 1)) (sign(0) = +1), c = 1 / sqrt(t^2 + 1), s = t c;
+ *            A_pp -= t A_pq, A_qq += t A_pq, A_pq = A_qp = 0, for k != p, q: A_kp = A_pk = c A_kp - s A_kq, A_kq = A_qk = s A_kp + c A_kq (old values),
+ *            for every k: V_kp = c V_kp - s V_kq, V_kq = s V_kp + c V_kq.  Eigenvalue i = A_ii, eigenvector = column i of V; eigenvalues are ranked by
+ *            value, ties by index.
+ *   EPnP     (Lepetit, Moreno-Noguer & Fua 2009) on the sample's 5 points:
+ *            control points: c0 = the centroid (sum / 5); the 3 x 3 scatter S = sum (X - c0)(X - c0)^T by Jacobi; axis j = 0, 1, 2 = eigenvectors u_j in
+ *            descending eigenvalue order, s_j = sqrt(max(lambda_j, 0) / 5), c_{j+1} = c0 + s_j u_j.
+ *            alphas: the pseudo-inverse of [s_j u_j]: alpha_{j+1} = u_j . (X - c0) / s_j where s_j > 1e-10 s_0, else 0; alpha_0 = 1 - a1 - a2 - a3.
+ *            So PLANAR and COLLINEAR samples are defined (their short axes get weight 0); they give a finite model or none.
+ *            M^T M (12 x 12) summed over the points of the rows [a_j fx, 0, a_j (cx - u)] and [0, a_j fy, a_j (cy - v)] (j = 0..3), upper triangle, then
+ *            mirrored; its null space = the eigenvectors v_0..v_3 of the 4 smallest eigenvalues (Jacobi), v_0 the smallest.
+ *            L (6 x 10) and rho (6) over the control-point pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), d_k = v_k[a] - v_k[b]:
+ *            [d0.d0, 2 d0.d1, d1.d1, 2 d0.d2, 2 d1.d2, d2.d2, 2 d0.d3, 2 d1.d3, 2 d2.d3, d3.d3], rho = |c_a - c_b|^2.
+ *            betas N = 1: columns (0, 1, 3, 6) of L, least squares -> x; b0 = sqrt(|x0|), b_k = sign(x0) x_k / b0.  N = 2: columns 0..2;
+ *            b0 = sqrt(|x0|), b1 = sqrt(|x2|) where x2 has x0's sign (else 0), b0 negated where x1 < 0, b2 = b3 = 0.  N = 3: columns 0..4, as N = 2 and
+ *            b2 = x3 / b0.  Each then 5 Gauss-Newton steps on the 4 betas (rows [2 l0 b0 + l1 b1 + l3 b2 + l6 b3, l1 b0 + 2 l2 b1 + l4 b2 + l7 b3,
+ *            l3 b0 + l4 b1 + 2 l5 b2 + l8 b3, l6 b0 + l7 b1 + l8 b2 + 2 l9 b3], residual rho - L . b~); a failed solve ends them.  Least squares = the
+ *            normal equations by Gaussian elimination with partial pivoting (first largest |pivot|; a pivot not > 0 fails the solve: that N is skipped).
+ *            R, t: control points in the camera frame c~_j = sum_k b_k v_k[j], points p_i = sum_j alpha_ij c~_j, all negated when p_0.z < 0; Horn's
+ *            quaternion: S = sum (X - X0)(p - p0)^T, the 4 x 4 matrix N(S) of Horn (1987), its eigenvector of the largest eigenvalue (Jacobi)
+ *            normalised = q -> R, t = p0 - R X0.  The solution with the smallest summed reprojection distance over the 5 points wins (N = 1 first on
+ *            ties); a non-finite model counts as no model.
+ *   error    per correspondence: Xc = R X + t; 1/z = 1 where z == 0 (as cvProjectPoints2); u = x / z * fx + cx rounded to float; err = dx^2 + dy^2 in
+ *            float without FMA.  Inlier: err <= 400.0f (20 px).
+ *   RANSAC   sequentially in sample order: a model replaces the best only with STRICTLY more inliers than max(best, 4); the first wins ties; each
+ *            replacement sets niters = RANSACUpdateNumIters(0.99, (n - good) / n, 5, niters) ((1 - ep)^5 as repeated products; log; rint); the search
+ *            stops at the first sample index >= niters, 100 samples at most.  The device scores the samples in parallel; one lane then walks the
+ *            scores in this order and selects exactly the model the rule selects.
+ *   refine   Levenberg-Marquardt on the winner's inliers from the winner (cvFindExtrinsicCameraParams2's 20 iterations, FLT_EPSILON): the update
+ *            (w, tau) maps R, t to Cay(w) R, t + tau, Cay(w) = I + 2 / (1 + w.w) ([w]x + [w]x^2) (rational: no trigonometry).  Residuals in double
+ *            (u - u_obs); J^T J, J^T r and r^T r are summed as 64 partials (partial l over the points l, l + 64, ... in order) added in lane order.
+ *            lambda = 1e-3; each iteration solves (A + lambda diag(A)) delta = -g (Gaussian elimination; a failed solve stops); a trial with a smaller
+ *            cost is taken (lambda / 10; stop when max |delta| < FLT_EPSILON), otherwise lambda * 10.  No refinement when the start cost is not finite
+ *            and > 0; a non-finite result keeps the RANSAC model.  The inlier mask and count are the RANSAC winner's, as OpenCV reports them.
+ *   output   Twc (16 doubles, row-major) as SolvePnPWithCV converts the pose: Rwc = Rcw^T, twc = Rwc (-tcw); Rt (optional) = Rcw row-major, tcw;
+ *            inlier [n] (uint8), count.  No model: count 0, identity pose, every mask entry 0.
+ * Per problem the batch, the one-call and the host core give the same bytes, whatever the batch size and the problem's position in it. */
+/* ≙ cv::solvePnPRansac inside SolvePnPWithCV on ONE problem through host buffers: obj [n][3], img [n][2] doubles, K = (fx, fy, cx, cy); n <= 1024.
+ * Twc [16], Rt [12] (may be NULL), inlier [n], *count. */
+int airfe_pnp_ransac(airfe_ctx* ctx, const double* obj, const double* img, int n, const double* K, double* Twc, double* Rt, uint8_t* inlier, int* count);
+/* the same over B device-resident problems, asynchronous on `stream`: d_obj [B][ncap][3], d_img [B][ncap][2] floats, d_n [B] (clamped to 0..ncap),
+ * ncap <= 1024; K is a HOST array read at the call; d_Twc [B][16], d_Rt [B][12] or NULL, d_inlier [B][ncap] (every entry written), d_count [B]. */
+int airfe_pnp_ransac_batch_dev(airfe_ctx* ctx, const float* d_obj, const float* d_img, const int* d_n, int B, int ncap, const double* K, double* d_Twc,
+                               double* d_Rt, uint8_t* d_inlier, int* d_count, void* stream);
+
+/* ---- Stereo points: Frame::AddRightFeatures (src/frame.cc:141-172) + Frame::BackProjectPoint / Camera::BackProjectStereo (src/frame.cc:299-305,
+ * src/camera.cc:275-280) on the stereo match list ----------------------------------------------------------------------------------------------------
+ *   cam [8] = min_x_diff, max_x_diff, max_y_diff, bf, fx, fy, cx, cy (HOST array).  Per list entry (left i, right r), in list order: dx = |xl - xr|,
+ *   dy = |yl - yr| (float differences, then double); kept when dx > min_x_diff, dx < max_x_diff, dy <= max_y_diff (:147-157); then
+ *   parallax = (double)(xl - xr) (a FLOAT difference) must lie in (min_x_diff, max_x_diff) (:161-172); such an entry counts as good and sets
+ *   u_right[i] = xr, depth[i] = bf / parallax — a later entry overwrites an earlier one.  The point of a left keypoint with a u_right:
+ *   ((xl - cx) / fx', (yl - cy) / fy', 1) * d with 1 / fx' = 1.0 / fx (Camera's _fx_inv) and d = bf / (xl - u_right) in DOUBLE (camera.cc:277): the
+ *   two roundings can differ in the last bits, as the reference's do.  Unset keypoints: u_right = depth = -1, point NaN.
+ *   *good / d_good = the number of good entries (= airfe_seq_good_stereo_points on the same input). */
+int airfe_stereo_points(airfe_ctx* ctx, const double* cam, const float* featL, int nL, const float* featR, int nR, const int32_t* idx, int m, double* u_right,
+                        double* depth, double* xyz, int* good);
+/* over B device frames: d_featL / d_featR [B][cap][259] (cap <= 4096), d_nL / d_nR [B], d_idx [B][mcap][2] (left, right) + d_nmatch [B] (the stereo
+ * matcher's lists); d_u_right / d_depth [B][cap], d_xyz [B][cap][3] (every slot written), d_good [B].  Asynchronous on `stream`. */
+int airfe_stereo_points_batch_dev(airfe_ctx* ctx, const double* cam, const float* d_featL, const int* d_nL, const float* d_featR, const int* d_nR, int B,
+                                  int cap, const int32_t* d_idx, const int* d_nmatch, int mcap, double* d_u_right, double* d_depth, double* d_xyz,
+                                  int* d_good, void* stream);
+/* Tracking composite: SolvePnPWithCV as tracking feeds it right after a keyframe (map_builder.cc:307-315), all on the device.  Per problem: the
+ * keyframe's points d_xyz [B][capK][3] (airfe_stereo_points_batch_dev), the current rows d_feat [B][cap][259], the temporal list d_tidx [B][mcap][2]
+ * = (keyframe index, current index) + d_ntrack [B] (airfe_track_frame / the batch matcher; mcap <= 1024).  Correspondences = the list entries whose
+ * keyframe point exists, in list order (as SolvePnPWithCV skips null mappoints): object point = the keyframe point rounded to float, image point = the
+ * current row's (x, y).  Result: the current frame's pose in the keyframe's camera frame (d_Twc [B][16], d_Rt [B][12] or NULL), d_mask [B][mcap]
+ * indexed by LIST ENTRY (0 for entries without a point), d_count [B]. */
+int airfe_track_pose_batch_dev(airfe_ctx* ctx, const double* K, const double* d_xyz, int capK, const float* d_feat, int cap, const int32_t* d_tidx,
+                               const int* d_ntrack, int mcap, int B, double* d_Twc, double* d_Rt, uint8_t* d_mask, int* d_count, void* stream);
+
 /* ---- next row after the path ---------------------------------------------------- */
 /* ≙ AssignPointsToLines (src/line_processor.cc:68-120), called on the path's own outputs (frame.cc:125,177,184).
  *   lines [L][4] doubles (x1,y1,x2,y2) = the std::vector<Eigen::Vector4d> storage; feat [N][259] rows (x,y = floats 1,2).
