@@ -49,6 +49,22 @@ class SeqFrame(C.Structure):
                                              "matches_score")])
 
 
+class DebugLinearArgs(C.Structure):
+    """airfe_debug_linear_args (include/airfe_debug.h)"""
+    _fields_ = ([(n, C.c_int) for n in ("prec", "M", "K", "K1", "N")] + [(n, C.c_void_p) for n in ("x1", "x2", "w", "b")]
+                + [("epi", C.c_int), ("act", C.c_int), ("rowidx", C.c_void_p), ("src_rows", C.c_int), ("rot_cos", C.c_void_p), ("rot_sin", C.c_void_p),
+                   ("Np", C.c_int), ("H", C.c_int), ("x32", C.c_void_p), ("d2s_hc", C.c_int), ("d2s_wc", C.c_int), ("flag", C.c_void_p),
+                   ("kernel", C.c_int), ("gr_wgs", C.c_int), ("out", C.c_void_p), ("out2", C.c_void_p)])
+
+
+class DebugLgBlockArgs(C.Structure):
+    """airfe_debug_lg_block_args (include/airfe_debug.h)"""
+    _fields_ = ([("prec", C.c_int), ("M", C.c_int)] + [(n, C.c_void_p) for n in ("attn", "x32", "xb", "wo", "bo", "w1", "b1", "gamma", "beta", "w2", "b2")]
+                + [(n, C.c_int) for n in ("relu", "tokens_per_wg", "mixed", "nqk_n")]
+                + [(n, C.c_void_p) for n in ("nqk_w", "nqk_b", "nv_w", "nv_b", "rot_cos", "rot_sin")]
+                + [("Np", C.c_int)] + [(n, C.c_void_p) for n in ("q", "k", "vt")] + [("rows_past", C.c_int * 5)])
+
+
 # name -> (restype, argtypes); every symbol include/*.h declares
 SIGNATURES = {
     "airfe_copy_rows_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -164,6 +180,10 @@ SIGNATURES = {
     "airfe_debug_trace_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "airfe_debug_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                    C.c_void_p]),
+    "airfe_debug_linear": (C.c_int, [C.c_void_p, C.POINTER(DebugLinearArgs)]),
+    "airfe_debug_qkv": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p] * 3),
+    "airfe_debug_lg_block": (C.c_int, [C.c_void_p, C.POINTER(DebugLgBlockArgs)]),
+    "airfe_debug_ln_gelu": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "airfe_debug_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
 

@@ -436,6 +436,105 @@ class Context:
                                            y.ctypes.data), "airfe_debug_gemm")
         return y
 
+    # kernel names of airfe_debug_linear's `kernel` (include/airfe_debug.h)
+    DEBUG_KERNELS = {"dispatch": 0, "small": 1, "tiled": 2, "gemm8": 3, "gemmr": 4, "gemmr_gather": 5, "gemmr_gather128": 6}
+
+    def debug_linear(self, x1, w, b, prec, epi=0, act=0, x2=None, rowidx=None, rot=None, Np=0, x32=None, d2s=None, kernel="dispatch", gr_wgs=0):
+        """One form of the GEMM family (include/airfe_debug.h, airfe_debug_linear) on host fp32 tensors: x1 [M, K1] ([src_rows, K1] with rowidx [M]),
+        x2 [M, K - K1], w [N, K], b [N]; rot = (cos, sin) [M, 32]; x32 [M, N] (EPI_RESID); d2s = (hc, wc) (EPI_SOFTMAX_D2S).  Returns out in the
+        kernel's own layout, and for EPI_HEADS with N = 512 (q, k), for EPI_RESID (xb, x32), for EPI_SOFTMAX_D2S (heat, flag)."""
+        f32 = lambda t: None if t is None else np.ascontiguousarray(t, np.float32)
+        x1, w, b, x2, x32 = f32(x1), f32(w), f32(b), f32(x2), (None if x32 is None else np.array(x32, np.float32, copy=True))
+        n, k = w.shape
+        m = len(rowidx) if rowidx is not None else x1.shape[0]
+        a = _lib.DebugLinearArgs(prec=prec, M=m, K=k, K1=x1.shape[1], N=n, x1=x1.ctypes.data, w=w.ctypes.data, b=b.ctypes.data, epi=epi, act=act, Np=Np, H=4,
+                                 kernel=self.DEBUG_KERNELS[kernel], gr_wgs=gr_wgs)
+        keep = []
+        if x2 is not None:
+            a.x2 = x2.ctypes.data
+        if rowidx is not None:
+            ri = np.ascontiguousarray(rowidx, np.int32)
+            keep.append(ri)
+            a.rowidx, a.src_rows = ri.ctypes.data, x1.shape[0]
+        if rot is not None:
+            rc, rs = f32(rot[0]), f32(rot[1])
+            keep += [rc, rs]
+            a.rot_cos, a.rot_sin = rc.ctypes.data, rs.ctypes.data
+        if x32 is not None:
+            a.x32 = x32.ctypes.data
+        flag = np.zeros(1, np.int32)
+        out2 = None
+        if epi == 5:
+            hc, wc = d2s
+            a.d2s_hc, a.d2s_wc, a.flag = hc, wc, flag.ctypes.data
+            out = np.empty((m // (hc * wc), 8 * hc, 8 * wc), np.float32)
+        elif epi in (3, 4):
+            s = m // Np
+            out = np.empty((s, 4, Np, 64) if epi == 3 else (s, 4, 64, Np), np.float32)
+            if epi == 3 and n == 512:
+                out2 = np.empty_like(out)
+                a.out2 = out2.ctypes.data
+        else:
+            out = np.empty((m, n), np.float32)
+        a.out = out.ctypes.data
+        self._chk(self._l.airfe_debug_linear(self._h, C.byref(a)), "airfe_debug_linear")
+        if epi == 5:
+            return out, int(flag[0])
+        if epi == 2:
+            return out, x32
+        return (out, out2) if out2 is not None else out
+
+    def debug_qkv(self, x, wqk, bqk, wv, bv, prec, Np, rot=None, pair=True, gr_wgs=0):
+        """airfe_debug_qkv: x [M, 256] -> (q, k or None, vt): q / k [S, 4, Np, 64], vt [S, 4, 64, Np]; pair: one gemmr_pair launch"""
+        f32 = lambda t: np.ascontiguousarray(t, np.float32)
+        x, wqk, bqk, wv, bv = f32(x), f32(wqk), f32(bqk), f32(wv), f32(bv)
+        m, nqk, s = x.shape[0], wqk.shape[0], x.shape[0] // Np
+        q = np.empty((s, 4, Np, 64), np.float32)
+        k = np.empty_like(q) if nqk == 512 else None
+        vt = np.empty((s, 4, 64, Np), np.float32)
+        rc, rs = (f32(rot[0]), f32(rot[1])) if rot is not None else (None, None)
+        ptr = lambda t: None if t is None else t.ctypes.data
+        self._chk(self._l.airfe_debug_qkv(self._h, prec, m, Np, ptr(x), ptr(wqk), ptr(bqk), nqk, ptr(wv), ptr(bv), ptr(rc), ptr(rs), int(pair), gr_wgs, ptr(q),
+                                          ptr(k), ptr(vt)), "airfe_debug_qkv")
+        return q, k, vt
+
+    def debug_lg_block(self, attn, x32, w1, b1, w2, b2, prec, gamma=None, beta=None, wo=None, bo=None, relu=False, tokens_per_wg=128, mixed=False,
+                       nqk=None, nv=None, rot=None, Np=0):
+        """airfe_debug_lg_block: the fused post-attention block on host tensors.  nqk = (w [n, 256], b), nv = (w [256, 256], b): the next layer's
+        projections.  Returns dict x32, xb, q, k, vt (None where absent) and rows_past (rows past M written in x32, xb, q, k, vt)."""
+        f32 = lambda t: None if t is None else np.ascontiguousarray(t, np.float32)
+        m = attn.shape[0]
+        attn, w1, b1, w2, b2, gamma, beta, wo, bo = map(f32, (attn, w1, b1, w2, b2, gamma, beta, wo, bo))
+        x32 = np.array(x32, np.float32, copy=True)
+        xb = np.empty_like(x32)
+        ptr = lambda t: None if t is None else t.ctypes.data
+        a = _lib.DebugLgBlockArgs(prec=prec, M=m, attn=ptr(attn), x32=ptr(x32), xb=ptr(xb), wo=ptr(wo), bo=ptr(bo), w1=ptr(w1), b1=ptr(b1), gamma=ptr(gamma),
+                                  beta=ptr(beta), w2=ptr(w2), b2=ptr(b2), relu=int(relu), tokens_per_wg=tokens_per_wg, mixed=int(mixed), Np=Np)
+        q = k = vt = None
+        keep = []
+        if nqk is not None:
+            (qw, qb), (vw, vb) = map(lambda p: (f32(p[0]), f32(p[1])), (nqk, nv))
+            keep += [qw, qb, vw, vb]
+            s = m // Np
+            q, vt = np.empty((s, 4, Np, 64), np.float32), np.empty((s, 4, 64, Np), np.float32)
+            a.nqk_n, a.nqk_w, a.nqk_b, a.nv_w, a.nv_b, a.q, a.vt = qw.shape[0], ptr(qw), ptr(qb), ptr(vw), ptr(vb), ptr(q), ptr(vt)
+            if qw.shape[0] == 512:
+                k = np.empty_like(q)
+                a.k = ptr(k)
+        if rot is not None:
+            rc, rs = f32(rot[0]), f32(rot[1])
+            keep += [rc, rs]
+            a.rot_cos, a.rot_sin = ptr(rc), ptr(rs)
+        self._chk(self._l.airfe_debug_lg_block(self._h, C.byref(a)), "airfe_debug_lg_block")
+        return {"x32": x32, "xb": xb, "q": q, "k": k, "vt": vt, "rows_past": list(a.rows_past)}
+
+    def debug_ln_gelu(self, h, gamma, beta, prec):
+        """airfe_debug_ln_gelu: launch_ln_gelu in place on h [M, 512] (rounded to the 2-byte type on the way in) -> the kernel's result"""
+        h = np.array(h, np.float32, copy=True)
+        gamma, beta = np.ascontiguousarray(gamma, np.float32), np.ascontiguousarray(beta, np.float32)
+        self._chk(self._l.airfe_debug_ln_gelu(self._h, prec, h.ctypes.data, gamma.ctypes.data, beta.ctypes.data, h.shape[0]), "airfe_debug_ln_gelu")
+        return h
+
     def debug_attention(self, q, k, v, lens, cross=False):
         """The matcher's flash attention alone (include/airfe_debug.h): q, k, v [S, H, n, 64] fp32 (scale and log2 e already inside q / k), lens [S] -> out [S, n, H * 64]."""
         q = np.ascontiguousarray(q, np.float32); k = np.ascontiguousarray(k, np.float32); v = np.ascontiguousarray(v, np.float32)

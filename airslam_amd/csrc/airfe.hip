@@ -1791,6 +1791,307 @@ int airfe_debug_gemm(airfe_ctx* c, const float* x, int M, int K, const float* w,
   return rc;
 } AIRFE_CATCH(c)
 
+}  // extern "C"
+
+// ---- the GEMM family one form at a time (include/airfe_debug.h): host tensors -> the production launchers -> host tensors
+static std::vector<uint16_t> dbg_rows2(const float* x, int rows, int cols, int rows_cap, int prec) {
+  std::vector<uint16_t> v((size_t)rows_cap * cols, 0);
+  if (x)
+    for (size_t i = 0; i < (size_t)rows * cols; ++i) v[i] = cvt2(x[i], prec);
+  return v;
+}
+static std::vector<float> dbg_rows4(const float* x, int rows, int cols, int rows_cap) {
+  std::vector<float> v((size_t)rows_cap * cols, 0.f);
+  if (x) memcpy(v.data(), x, (size_t)rows * cols * sizeof(float));
+  return v;
+}
+template <class T>
+static T* dbg_canary(airfe_ctx* tmp, size_t n) {       // an output buffer whose every byte starts as 0xFF (NaN in fp32, fp16 and bf16)
+  T* p = dalloc<T>(tmp, n, false);
+  if (p) (void)hipMemset(p, 0xFF, std::max<size_t>(n, 1) * sizeof(T));
+  return p;
+}
+static void dbg_back2(const std::vector<uint16_t>& v, size_t n, int prec, float* out) {
+  for (size_t i = 0; i < n; ++i) out[i] = back2(v[i], prec);
+}
+
+extern "C" {
+
+int airfe_debug_linear(airfe_ctx* c, const airfe_debug_linear_args* a) try {
+  AIRFE_ENTER(c);
+  if (!a || !a->x1 || !a->w || !a->b || !a->out) return fail(c, "debug_linear: null argument");
+  const int prec = a->prec, M = a->M, K = a->K, N = a->N, epi = a->epi, kern = a->kernel, K1 = a->x2 ? a->K1 : K;
+  if ((prec != 0 && prec != 1) || M < 1 || N < 1 || (K != 128 && K != 256 && K != 512) || K1 < 32 || K1 % 32 || K1 > K || (a->x2 && K1 == K) ||
+      epi < EPI_STORE || epi > EPI_SOFTMAX_D2S || kern < AIRFE_DEBUG_KERNEL_DISPATCH || kern > AIRFE_DEBUG_KERNEL_GEMMR_GATHER128 || (a->act != ACT_NONE && a->act != ACT_RELU))
+    return fail(c, "debug_linear: bad argument");
+  const bool trans = epi == EPI_HEADS_T, heads = epi == EPI_HEADS || trans, d2s = epi == EPI_SOFTMAX_D2S;
+  if (heads && ((a->H != 4 && a->H != 0) || a->Np < 16 || a->Np % 16 || M % a->Np || (epi == EPI_HEADS ? (N != 256 && N != 512) || (N == 512 && !a->out2) : N != 256)))
+    return fail(c, "debug_linear: head layouts need H = 4, M = S * Np with Np a multiple of 16, N = 256 (or 512 with out2 for EPI_HEADS)");
+  if ((a->rot_cos || a->rot_sin) && (epi != EPI_HEADS || !a->rot_cos || !a->rot_sin)) return fail(c, "debug_linear: rotary is an EPI_HEADS form");
+  if (epi == EPI_RESID && (!a->x32 || N % 64)) return fail(c, "debug_linear: EPI_RESID needs x32 and N a multiple of 64");
+  if (d2s && (K != 256 || N != 65 || a->x2 || a->rowidx || a->act || a->d2s_hc < 1 || a->d2s_wc < 1 || M % (a->d2s_hc * a->d2s_wc) || M % 16 ||
+              (kern != AIRFE_DEBUG_KERNEL_DISPATCH && kern != AIRFE_DEBUG_KERNEL_GEMM8)))
+    return fail(c, "debug_linear: EPI_SOFTMAX_D2S is launch_gemm8's head kernel: K = 256, N = 65, dense rows, M = B * hc * wc, M % 16 == 0");
+  if (a->rowidx) {
+    if (kern != AIRFE_DEBUG_KERNEL_GEMM8 && kern != AIRFE_DEBUG_KERNEL_GEMMR_GATHER && kern != AIRFE_DEBUG_KERNEL_GEMMR_GATHER128)
+      return fail(c, "debug_linear: a row gather runs in gemm8, gemmr_gather or gemmr_gather128 only");
+    if (a->src_rows < 1) return fail(c, "debug_linear: rowidx needs src_rows");
+    for (int r = 0; r < M; ++r)
+      if (a->rowidx[r] < 0 || a->rowidx[r] >= a->src_rows) return fail(c, "debug_linear: rowidx entry outside 0 .. src_rows - 1");
+  }
+  static const int row_tile[7] = {128, 32, 128, 256, 32, 32, 64};
+  const int Mp = d2s ? M : (M + row_tile[kern] - 1) / row_tile[kern] * row_tile[kern];
+  const int xrows = a->rowidx ? a->src_rows : Mp;
+  const int ldo = (epi == EPI_STORE || epi == EPI_STORE_F32) ? (N + 7) / 8 * 8 : N;
+  const int Sg = heads ? (Mp + a->Np - 1) / a->Np : 0, S = heads ? M / a->Np : 0;
+  airfe_ctx tmp;   // only as an allocation list holder
+  tmp.prec = prec;
+  tmp.pack_prec = prec;
+  LinW lw;
+  if (!make_linear(&tmp, a->w, a->b, K, N, lw)) { for (void* p : tmp.allocs) (void)hipFree(p); return fail(c, "debug_linear: allocation failed"); }
+  GemmArgs g;
+  g.X1 = dupload(&tmp, dbg_rows2(a->x1, a->rowidx ? a->src_rows : M, K1, xrows, prec)); g.ld1 = K1; g.K1 = K1;
+  if (a->x2) { g.X2 = dupload(&tmp, dbg_rows2(a->x2, M, K - K1, Mp, prec)); g.ld2 = K - K1; }
+  g.Wp = lw.w; g.bias = lw.b; g.M = Mp; g.N = N; g.cb_total = lw.cbt; g.epi = epi; g.act = a->act; g.ldo = ldo; g.Np = a->Np; g.H = 4;
+  g.small_max = c->gemm_small_max; g.g8_min = c->gemm8_min; g.gr_min = c->gemmr_min; g.gr_wgs = a->gr_wgs > 0 ? a->gr_wgs : c->gemmr_wgs;
+  if (a->rot_cos) { g.rot_cos = dupload(&tmp, dbg_rows4(a->rot_cos, M, 32, Mp)); g.rot_sin = dupload(&tmp, dbg_rows4(a->rot_sin, M, 32, Mp)); }
+  if (a->rowidx) { std::vector<int> ri(Mp, 0); memcpy(ri.data(), a->rowidx, (size_t)M * sizeof(int)); g.rowidx = dupload(&tmp, ri); }
+  size_t out_elems = 0;
+  if (epi == EPI_STORE || epi == EPI_RESID) out_elems = (size_t)Mp * ldo;
+  else if (heads) out_elems = (size_t)Sg * 4 * a->Np * 64;
+  if (epi == EPI_STORE_F32) g.out = dbg_canary<float>(&tmp, (size_t)Mp * ldo);
+  else if (d2s) g.out = dbg_canary<float>(&tmp, (size_t)M * 64);
+  else g.out = dbg_canary<uint16_t>(&tmp, out_elems);
+  if (epi == EPI_HEADS && N == 512) g.out2 = dbg_canary<uint16_t>(&tmp, out_elems);
+  if (epi == EPI_RESID) g.x32 = dupload(&tmp, dbg_rows4(a->x32, M, N, Mp));
+  if (d2s) { g.d2s_hc = a->d2s_hc; g.d2s_wc = a->d2s_wc; g.flag = dalloc<int>(&tmp, 1); }
+  bool ok = g.X1 && (!a->x2 || g.X2) && g.out && (!(epi == EPI_HEADS && N == 512) || g.out2) && (epi != EPI_RESID || g.x32) && (!a->rot_cos || (g.rot_cos && g.rot_sin)) &&
+            (!a->rowidx || g.rowidx) && (!d2s || g.flag);
+  int rc = ok ? 0 : fail(c, "debug_linear: allocation failed");
+  // a forced kernel runs only where its own applicability test says yes: never a silent fall-back to another kernel
+  const char* refused = nullptr;
+  if (!rc) switch (kern) {
+    case AIRFE_DEBUG_KERNEL_DISPATCH:
+      if (d2s) launch_gemm8(prec, K, false, g, c->stream);
+      else launch_gemm(prec, K, trans, g, c->stream);
+      break;
+    case AIRFE_DEBUG_KERNEL_SMALL:                       // launch_gemm's own row test with every other path moved out of reach
+      if (d2s || a->rowidx) refused = "gemm_small";
+      else { g.small_max = 1 << 30; g.g8_min = 1 << 30; g.gr_min = 1 << 30; launch_gemm(prec, K, trans, g, c->stream); }
+      break;
+    case AIRFE_DEBUG_KERNEL_TILED:
+      if (d2s || a->rowidx || K1 % 64) refused = "gemm_kernel";
+      else { g.small_max = -1; g.g8_min = 1 << 30; g.gr_min = 1 << 30; launch_gemm(prec, K, trans, g, c->stream); }
+      break;
+    case AIRFE_DEBUG_KERNEL_GEMM8:
+      if (K1 % 64) refused = "gemm8";
+      else launch_gemm8(prec, K, trans, g, c->stream);
+      break;
+    case AIRFE_DEBUG_KERNEL_GEMMR:
+      if (a->rowidx || !gemmr_applicable(K, trans, g)) refused = "gemmr";
+      else launch_gemmr(prec, trans, g, c->stream);
+      break;
+    case AIRFE_DEBUG_KERNEL_GEMMR_GATHER:
+      if (!gemmr_gather_applicable(K, g)) refused = "gemmr_gather";
+      else launch_gemmr_gather(prec, g, c->stream);
+      break;
+    default:
+      if (!gemmr_gather128_applicable(g)) refused = "gemmr_gather128";
+      else launch_gemmr_gather128(prec, g, c->stream);
+      break;
+  }
+  if (refused) rc = fail(c, std::string("debug_linear: ") + refused + " does not apply to this form");
+  if (!rc && (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c))) rc = fail(c, "debug_linear: kernel failed");
+  if (!rc) {
+    if (epi == EPI_STORE_F32 || d2s) {
+      std::vector<float> ho(d2s ? (size_t)M * 64 : (size_t)Mp * ldo);
+      (void)hipMemcpy(ho.data(), g.out, ho.size() * 4, hipMemcpyDeviceToHost);
+      if (d2s) memcpy(a->out, ho.data(), ho.size() * 4);
+      else
+        for (int m = 0; m < M; ++m) memcpy(a->out + (size_t)m * N, ho.data() + (size_t)m * ldo, (size_t)N * 4);
+      if (d2s && a->flag) (void)hipMemcpy(a->flag, g.flag, sizeof(int), hipMemcpyDeviceToHost);
+    } else if (heads) {
+      std::vector<uint16_t> ho(out_elems);
+      const size_t n = (size_t)S * 4 * a->Np * 64;
+      (void)hipMemcpy(ho.data(), g.out, ho.size() * 2, hipMemcpyDeviceToHost);
+      dbg_back2(ho, n, prec, a->out);
+      if (g.out2) {
+        (void)hipMemcpy(ho.data(), g.out2, ho.size() * 2, hipMemcpyDeviceToHost);
+        dbg_back2(ho, n, prec, a->out2);
+      }
+    } else {
+      std::vector<uint16_t> ho(out_elems);
+      (void)hipMemcpy(ho.data(), g.out, ho.size() * 2, hipMemcpyDeviceToHost);
+      for (int m = 0; m < M; ++m)
+        for (int n = 0; n < N; ++n) a->out[(size_t)m * N + n] = back2(ho[(size_t)m * ldo + n], prec);
+      if (epi == EPI_RESID) (void)hipMemcpy(a->x32, g.x32, (size_t)M * N * 4, hipMemcpyDeviceToHost);
+    }
+  }
+  for (void* p : tmp.allocs) (void)hipFree(p);
+  return rc;
+} AIRFE_CATCH(c)
+
+int airfe_debug_qkv(airfe_ctx* c, int prec, int M, int Np, const float* x, const float* wqk, const float* bqk, int nqk, const float* wv, const float* bv,
+                    const float* rot_cos, const float* rot_sin, int pair, int gr_wgs, float* q, float* k, float* vt) try {
+  AIRFE_ENTER(c);
+  if ((prec != 0 && prec != 1) || M < 1 || Np < 16 || Np % 16 || M % Np || (nqk != 256 && nqk != 512) || !x || !wqk || !bqk || !wv || !bv || !q || !vt ||
+      (nqk == 512 && !k) || (!rot_cos) != (!rot_sin))
+    return fail(c, "debug_qkv: bad argument");
+  const int Mp = (M + 127) / 128 * 128, Sg = (Mp + Np - 1) / Np, S = M / Np;
+  const size_t elems = (size_t)Sg * 4 * Np * 64, n = (size_t)S * 4 * Np * 64;
+  airfe_ctx tmp;
+  tmp.prec = prec;
+  tmp.pack_prec = prec;
+  LinW lqk, lv;
+  const bool packed = make_linear(&tmp, wqk, bqk, 256, nqk, lqk) && make_linear(&tmp, wv, bv, 256, 256, lv);
+  GemmArgs ga, gb;
+  const uint16_t* dx = dupload(&tmp, dbg_rows2(x, M, 256, Mp, prec));
+  ga.X1 = gb.X1 = dx; ga.ld1 = gb.ld1 = 256; ga.K1 = gb.K1 = 256; ga.M = gb.M = Mp; ga.Np = gb.Np = Np; ga.H = gb.H = 4;
+  ga.Wp = lqk.w; ga.bias = lqk.b; ga.N = nqk; ga.cb_total = lqk.cbt; ga.epi = EPI_HEADS; ga.ldo = nqk;
+  gb.Wp = lv.w; gb.bias = lv.b; gb.N = 256; gb.cb_total = lv.cbt; gb.epi = EPI_HEADS_T; gb.ldo = 256;
+  ga.out = dbg_canary<uint16_t>(&tmp, elems);
+  if (nqk == 512) ga.out2 = dbg_canary<uint16_t>(&tmp, elems);
+  gb.out = dbg_canary<uint16_t>(&tmp, elems);
+  if (rot_cos) { ga.rot_cos = dupload(&tmp, dbg_rows4(rot_cos, M, 32, Mp)); ga.rot_sin = dupload(&tmp, dbg_rows4(rot_sin, M, 32, Mp)); }
+  for (GemmArgs* g : {&ga, &gb}) {
+    g->small_max = c->gemm_small_max; g->g8_min = c->gemm8_min; g->gr_min = c->gemmr_min; g->gr_wgs = gr_wgs > 0 ? gr_wgs : c->gemmr_wgs;
+  }
+  int rc = (packed && dx && ga.out && gb.out && (nqk != 512 || ga.out2) && (!rot_cos || (ga.rot_cos && ga.rot_sin))) ? 0 : fail(c, "debug_qkv: allocation failed");
+  if (!rc) {
+    if (pair) {
+      if (!gemmr_pair_applicable(ga, gb)) rc = fail(c, "debug_qkv: gemmr_pair does not apply to this form");
+      else launch_gemmr_pair(prec, ga, gb, c->stream);
+    } else {
+      launch_gemm(prec, 256, false, ga, c->stream);
+      launch_gemm(prec, 256, true, gb, c->stream);
+    }
+  }
+  if (!rc && (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c))) rc = fail(c, "debug_qkv: kernel failed");
+  if (!rc) {
+    std::vector<uint16_t> ho(elems);
+    (void)hipMemcpy(ho.data(), ga.out, elems * 2, hipMemcpyDeviceToHost);
+    dbg_back2(ho, n, prec, q);
+    if (nqk == 512) {
+      (void)hipMemcpy(ho.data(), ga.out2, elems * 2, hipMemcpyDeviceToHost);
+      dbg_back2(ho, n, prec, k);
+    }
+    (void)hipMemcpy(ho.data(), gb.out, elems * 2, hipMemcpyDeviceToHost);
+    dbg_back2(ho, n, prec, vt);
+  }
+  for (void* p : tmp.allocs) (void)hipFree(p);
+  return rc;
+} AIRFE_CATCH(c)
+
+int airfe_debug_lg_block(airfe_ctx* c, airfe_debug_lg_block_args* a) try {
+  AIRFE_ENTER(c);
+  if (!a || !a->attn || !a->x32 || !a->xb || !a->w1 || !a->b1 || !a->w2 || !a->b2 || (!a->relu && (!a->gamma || !a->beta)) || (!a->wo) != (!a->bo))
+    return fail(c, "debug_lg_block: null argument");
+  const int prec = a->prec, M = a->M, T = a->tokens_per_wg, nq = a->nqk_n, Np = a->Np;
+  if ((prec != 0 && prec != 1) || M < 1 || (T != 32 && T != 64 && T != 112 && T != 128) || (nq != 0 && nq != 256 && nq != 512) || (a->relu && nq))
+    return fail(c, "debug_lg_block: bad argument");
+  if (a->mixed) {                                        // the two-round split or nothing: launch_lg_blockf would quietly run uniform passes
+    const int tiles = (M + 15) / 16, W = c->n_cu;
+    if (a->wo || T != 112 || W <= 0 || tiles <= 7 * W || tiles > 13 * W) return fail(c, "debug_lg_block: the mixed split does not apply to this form");
+  }
+  if (nq && (!a->nqk_w || !a->nqk_b || !a->nv_w || !a->nv_b || !a->q || !a->vt || (nq == 512) != (a->rot_cos && a->rot_sin) || (nq == 512 && !a->k) || Np < 16 ||
+             Np % 16 || M % Np))
+    return fail(c, "debug_lg_block: the next projection needs its weights and outputs, rotary exactly when nqk_n = 512, and M = S * Np (Np a multiple of 16)");
+  const int cap = M + 256;                               // every pass form stays below M + 127 rows
+  const int Sg = nq ? (cap + Np - 1) / Np : 0, S = nq ? M / Np : 0;
+  const size_t helems = (size_t)Sg * 4 * Np * 64;
+  airfe_ctx tmp;
+  tmp.prec = prec;
+  tmp.pack_prec = prec;
+  LinW lo, l1, l2, lq, lv;
+  bool ok = (!a->wo || make_linear(&tmp, a->wo, a->bo, 256, 256, lo)) && make_linear(&tmp, a->w1, a->b1, 512, 512, l1) && make_linear(&tmp, a->w2, a->b2, 512, 256, l2) &&
+            (!nq || (make_linear(&tmp, a->nqk_w, a->nqk_b, 256, nq, lq) && make_linear(&tmp, a->nv_w, a->nv_b, 256, 256, lv)));
+  const bool fr = lg_blockf_frag_weights();
+  std::vector<float> x32h = dbg_rows4(a->x32, M, 256, cap);
+  std::vector<uint16_t> xbh((size_t)cap * 256);
+  for (size_t i = 0; i < xbh.size(); ++i) xbh[i] = cvt2(x32h[i], prec);
+  std::vector<float> gb(1024, 0.f);
+  if (!a->relu) { memcpy(gb.data(), a->gamma, 512 * 4); memcpy(gb.data() + 512, a->beta, 512 * 4); }
+  LgBlockFArgs g;
+  g.attn = dupload(&tmp, dbg_rows2(a->attn, M, 256, cap, prec));
+  g.xb = dupload(&tmp, xbh);
+  g.x32 = dupload(&tmp, x32h);
+  const float* dgb = dupload(&tmp, gb);
+  g.wo = a->wo ? (fr ? lo.wf : lo.w) : nullptr; g.bo = a->wo ? lo.b : nullptr;
+  g.w1 = fr ? l1.wf : l1.w; g.b1 = l1.b; g.w2 = fr ? l2.wf : l2.w; g.b2 = l2.b;
+  g.gamma = dgb; g.beta = dgb ? dgb + 512 : nullptr;
+  g.M = M; g.tokens_per_wg = T; g.mixed = a->mixed; g.n_cu = c->n_cu; g.relu = a->relu;
+  if (nq) {
+    g.nqk_w = fr ? lq.wf : lq.w; g.nqk_b = lq.b; g.nqk_n = nq; g.nv_w = fr ? lv.wf : lv.w; g.nv_b = lv.b; g.Np = Np; g.H = 4;
+    if (nq == 512) { g.rot_cos = dupload(&tmp, dbg_rows4(a->rot_cos, M, 32, cap)); g.rot_sin = dupload(&tmp, dbg_rows4(a->rot_sin, M, 32, cap)); }
+    g.q_out = dbg_canary<uint16_t>(&tmp, helems);
+    if (nq == 512) g.k_out = dbg_canary<uint16_t>(&tmp, helems);
+    g.vt_out = dbg_canary<uint16_t>(&tmp, helems);
+  }
+  ok = ok && g.attn && g.xb && g.x32 && dgb && (!nq || (g.q_out && g.vt_out && (nq != 512 || (g.k_out && g.rot_cos && g.rot_sin))));
+  int rc = ok ? 0 : fail(c, "debug_lg_block: allocation failed");
+  if (!rc) {
+    launch_lg_blockf(prec, g, c->stream);
+    if (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c)) rc = fail(c, "debug_lg_block: kernel failed");
+  }
+  if (!rc) {
+    // rows past M that the launch changed: x32 / xb against their initial (zero) rows, q / k / v^T against the 0xFFFF fill
+    std::vector<float> x32o((size_t)cap * 256);
+    std::vector<uint16_t> xbo((size_t)cap * 256);
+    (void)hipMemcpy(x32o.data(), g.x32, x32o.size() * 4, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(xbo.data(), g.xb, xbo.size() * 2, hipMemcpyDeviceToHost);
+    memcpy(a->x32, x32o.data(), (size_t)M * 256 * 4);
+    dbg_back2(xbo, (size_t)M * 256, prec, a->xb);
+    for (int i = 0; i < 5; ++i) a->rows_past[i] = 0;
+    for (int r = M; r < cap; ++r)
+      for (int f = 0; f < 256; ++f) {
+        const size_t e = (size_t)r * 256 + f;
+        if (memcmp(&x32o[e], &x32h[e], 4)) a->rows_past[0] = r - M + 1;
+        if (xbo[e] != xbh[e]) a->rows_past[1] = r - M + 1;
+      }
+    if (nq) {
+      uint16_t* dev[3] = {g.q_out, g.k_out, g.vt_out};
+      float* host[3] = {a->q, a->k, a->vt};
+      std::vector<uint16_t> ho(helems);
+      for (int j = 0; j < 3; ++j) {
+        if (!dev[j]) continue;
+        (void)hipMemcpy(ho.data(), dev[j], helems * 2, hipMemcpyDeviceToHost);
+        dbg_back2(ho, (size_t)S * 4 * Np * 64, prec, host[j]);
+        for (size_t e = (size_t)S * 4 * Np * 64; e < helems; ++e) {
+          if (ho[e] == 0xFFFF) continue;
+          const size_t s = e / ((size_t)4 * Np * 64), w = e % ((size_t)Np * 64);
+          const int row = (int)(s * Np + (j == 2 ? w % Np : w / 64));          // q / k [s][h][n][64], v^T [s][h][d][n]
+          a->rows_past[2 + j] = std::max(a->rows_past[2 + j], row - M + 1);
+        }
+      }
+    }
+  }
+  for (void* p : tmp.allocs) (void)hipFree(p);
+  return rc;
+} AIRFE_CATCH(c)
+
+int airfe_debug_ln_gelu(airfe_ctx* c, int prec, float* h, const float* gamma, const float* beta, int M) try {
+  AIRFE_ENTER(c);
+  if ((prec != 0 && prec != 1) || M < 1 || !h || !gamma || !beta) return fail(c, "debug_ln_gelu: bad argument");
+  airfe_ctx tmp;
+  std::vector<float> gb(1024);
+  memcpy(gb.data(), gamma, 512 * 4);
+  memcpy(gb.data() + 512, beta, 512 * 4);
+  uint16_t* dh = dupload(&tmp, dbg_rows2(h, M, 512, M, prec));
+  float* dgb = dupload(&tmp, gb);
+  int rc = dh && dgb ? 0 : fail(c, "debug_ln_gelu: allocation failed");
+  if (!rc) {
+    launch_ln_gelu(prec, dh, dgb, dgb + 512, M, c->stream);
+    if (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c)) rc = fail(c, "debug_ln_gelu: kernel failed");
+  }
+  if (!rc) {
+    std::vector<uint16_t> ho((size_t)M * 512);
+    (void)hipMemcpy(ho.data(), dh, ho.size() * 2, hipMemcpyDeviceToHost);
+    dbg_back2(ho, ho.size(), prec, h);
+  }
+  for (void* p : tmp.allocs) (void)hipFree(p);
+  return rc;
+} AIRFE_CATCH(c)
+
 int airfe_debug_attention(airfe_ctx* c, const float* q, const float* k, const float* v, const int* lens, int S, int H, int n, int cross, float* out) try {
   AIRFE_ENTER(c);
   if (c->mprec == 2) return fail(c, "debug_attention drives the 2-byte kernel (matcher_precision fp16 / bf16)");

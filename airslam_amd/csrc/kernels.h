@@ -74,7 +74,8 @@ struct LgBlockFArgs {
   int relu = 0;              // 1: ReLU instead of LayerNorm + GELU (the SuperGlue block; gamma / beta unused)
   // the NEXT attention layer's projections, computed from the block's result (nqk_w == nullptr: none).  nqk_n = 512: q | k with rotary
   // (rows 0..255 -> q_out, 256..511 -> k_out), 256: the cross block's shared projection (-> q_out); nv: V, stored transposed.
-  // Layouts as EPI_HEADS / EPI_HEADS_T; a ragged last pass stores its surplus rows too (arena slack).
+  // Layouts as EPI_HEADS / EPI_HEADS_T; a ragged last pass stores its surplus rows too (arena slack: up to the pass's extent past M, which
+  // tests/test_gpu_lg_block.py reads back through airfe_debug_lg_block's rows_past).
   const uint16_t *nqk_w = nullptr, *nv_w = nullptr;
   const float *nqk_b = nullptr, *nv_b = nullptr, *rot_cos = nullptr, *rot_sin = nullptr;
   int nqk_n = 0, Np = 0, H = 4;

@@ -466,8 +466,10 @@ __device__ __forceinline__ void lf_pass(const LgBlockFArgs& a, char* smem, const
         bet[q][u] = *reinterpret_cast<const f32x4*>(a.beta + wf * 64 + q * 32 + g * 8 + u * 4);
       }
   }
-  // ---- LayerNorm(512): per-wave partial sums over its 64 features, exchanged through ST (indexed by feature block, so the
-  // summation order does not depend on which wave owned it)
+  // ---- LayerNorm(512): per-wave partials over its 64 features — the sum and the sum of squares about the WAVE's own mean (Chan's form) —
+  // exchanged through ST (indexed by feature block, so the summation order does not depend on which wave owned it).  A one-pass sum of
+  // squares cancels in fp32 for rows whose |mean| is large against their spread (tests/test_gpu_lg_block.py, the LayerNorm edge rows:
+  // 4x the derived bound at |mean| / std ~ 300); deviations from a local mean do not.
   if constexpr (!RELU) {
     float2* st = reinterpret_cast<float2*>(smem + LF_ST);
 #pragma unroll
@@ -476,11 +478,16 @@ __device__ __forceinline__ void lf_pass(const LgBlockFArgs& a, char* smem, const
 #pragma unroll
       for (int t = 0; t < 4; ++t)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          s1 += h[t][m][e];
-          s2 = fmaf(h[t][m][e], h[t][m][e], s2);
-        }
+        for (int e = 0; e < 4; ++e) s1 += h[t][m][e];
       s1 = rows_sum(s1);
+      const float mw = s1 * (1.0f / 64.0f);
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float d = h[t][m][e] - mw;
+          s2 = fmaf(d, d, s2);
+        }
       s2 = rows_sum(s2);
       if (g == 0) st[wf * 128 + m * 16 + l15] = make_float2(s1, s2);
     }
@@ -505,13 +512,15 @@ __device__ __forceinline__ void lf_pass(const LgBlockFArgs& a, char* smem, const
     for (int m = 0; m < (RELU ? 0 : NMT); ++m) {
       float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-      for (int w = 0; w < 8; ++w) {
-        const float2 p = st[w * 128 + m * 16 + l15];
-        s1 += p.x;
-        s2 += p.y;
-      }
+      for (int w = 0; w < 8; ++w) s1 += st[w * 128 + m * 16 + l15].x;
       const float mean = s1 * (1.0f / 512.0f);
-      const float var = fmaxf(s2 * (1.0f / 512.0f) - mean * mean, 0.f);
+#pragma unroll
+      for (int w = 0; w < 8; ++w) {                                 // M2 = sum over waves of M2_w + 64 (mean_w - mean)^2
+        const float2 p = st[w * 128 + m * 16 + l15];
+        const float dm = p.x * (1.0f / 64.0f) - mean;
+        s2 += fmaf(64.0f * dm, dm, p.y);
+      }
+      const float var = s2 * (1.0f / 512.0f);
       rstd[m] = 1.0f / sqrtf(var + 1e-5f);
       nmr[m] = -mean * rstd[m];
     }

@@ -43,6 +43,71 @@ int airfe_debug_preprocess(airfe_ctx* ctx, const uint8_t* gray, int h, int w, in
 int airfe_debug_conv3x3(airfe_ctx* ctx, const float* x, int B, int cin, int H, int W, const float* w, const float* b,
                         int cout, int pool, float* y);
 int airfe_debug_gemm(airfe_ctx* ctx, const float* x, int M, int K, const float* w, const float* b, int N, int relu, float* y);
+/* ---- the matcher's / detector's GEMM family one form at a time (tests/test_gpu_linear_kernels.py, tests/test_gpu_lg_block.py).  HOST fp32 tensors in, rounded to the
+ * 2-byte type `prec` (0 = bf16, 1 = fp16) on the way in; weights packed as the pipelines pack them (scale 1); HOST fp32 out in the kernel's own layout.  The kernels
+ * are the production ones: nothing here has a kernel of its own. */
+enum {
+  AIRFE_DEBUG_KERNEL_DISPATCH = 0,        /* launch_gemm's own choice by the context's row thresholds (EPI_SOFTMAX_D2S: launch_gemm8's head kernel) */
+  AIRFE_DEBUG_KERNEL_SMALL = 1,           /* gemm_small_kernel */
+  AIRFE_DEBUG_KERNEL_TILED = 2,           /* gemm_kernel */
+  AIRFE_DEBUG_KERNEL_GEMM8 = 3,           /* gemm8_kernel (head_softmax_d2s_kernel for EPI_SOFTMAX_D2S) */
+  AIRFE_DEBUG_KERNEL_GEMMR = 4,           /* gemmr_kernel */
+  AIRFE_DEBUG_KERNEL_GEMMR_GATHER = 5,    /* gemmr_gather_kernel */
+  AIRFE_DEBUG_KERNEL_GEMMR_GATHER128 = 6  /* gemmr_gather128_kernel */
+};
+/* One linear y = W cat(x1, x2) + b through epilogue `epi` (airfe::Epi: 0 store, 1 store fp32, 2 residual, 3 heads, 4 heads transposed, 5 soft-max + depth-to-space).
+ * The rows are padded with zero rows to the forced kernel's row tile (DISPATCH: 128, as the matcher pads its token count); only the first M come back.  A forced
+ * kernel that does not apply to the form is an ERROR, never a fall-back to another kernel. */
+typedef struct airfe_debug_linear_args {
+  int prec, M, K, K1, N;          /* K in {128, 256, 512}; K1 = K without x2 */
+  const float* x1;                /* [M][K1] ([src_rows][K1] with rowidx) */
+  const float* x2;                /* [M][K - K1] or NULL */
+  const float* w;                 /* [N][K] */
+  const float* b;                 /* [N] */
+  int epi, act;                   /* act: 1 = ReLU */
+  const int* rowidx;              /* [M] source rows of x1 (gather) or NULL */
+  int src_rows;
+  const float* rot_cos;           /* [M][32] (EPI_HEADS rotary) or NULL */
+  const float* rot_sin;
+  int Np, H;                      /* head layouts: M = S * Np, H heads of 64 */
+  float* x32;                     /* EPI_RESID: [M][N] residual in, x32 + W x + b out */
+  int d2s_hc, d2s_wc;             /* EPI_SOFTMAX_D2S: M = B * hc * wc cells, N = 65 */
+  int* flag;                      /* EPI_SOFTMAX_D2S: 1 when a cell's logits were not finite */
+  int kernel;                     /* AIRFE_DEBUG_KERNEL_* */
+  int gr_wgs;                     /* streaming kernels' workgroups (<= 0: the context's) */
+  float* out;                     /* [M][N] | heads [S][H][Np][64] (N = 512: q) | transposed [S][H][64][Np] | heat [B][8 hc][8 wc] */
+  float* out2;                    /* EPI_HEADS with N = 512: k [S][H][Np][64] */
+} airfe_debug_linear_args;
+int airfe_debug_linear(airfe_ctx* ctx, const airfe_debug_linear_args* a);
+/* one layer's attention inputs over rows x [M][256]: head-major q|k (wqk [nqk][256], nqk = 512 with rotary (q -> q, k -> k) or 256 (-> q)) and transposed V
+ * (wv [256][256] -> vt [S][4][64][Np]); pair = 1: ONE gemmr_pair launch (an error where it does not apply), 0: the two linears through launch_gemm's dispatch */
+int airfe_debug_qkv(airfe_ctx* ctx, int prec, int M, int Np, const float* x, const float* wqk, const float* bqk, int nqk, const float* wv, const float* bv,
+                    const float* rot_cos, const float* rot_sin, int pair, int gr_wgs, float* q, float* k, float* vt);
+/* the fused post-attention block (launch_lg_blockf) on HOST tensors.  xb is built as the 2-byte copy of x32 (the pipeline's invariant).  Every buffer has
+ * rows_cap >= M + 256 rows (input rows past M are zero); output rows past M start as a canary, and rows_past[0..4] = rows past M that the launch wrote in
+ * x32, xb, q, k, vt (0: none). */
+typedef struct airfe_debug_lg_block_args {
+  int prec, M;
+  const float* attn;              /* [M][256] */
+  float* x32;                     /* [M][256] in / out */
+  float* xb;                      /* [M][256] out */
+  const float *wo, *bo;           /* [256][256], [256]; NULL: w1's message half is already folded (the kernel's ffn.0 reads cat(x, attn)) */
+  const float *w1, *b1;           /* [512][512], [512] */
+  const float *gamma, *beta;      /* [512] */
+  const float *w2, *b2;           /* [256][512], [256] */
+  int relu;                       /* 1: ReLU instead of LayerNorm + GELU */
+  int tokens_per_wg, mixed;       /* 32, 64, 112, 128; mixed: the two-round split (folded, 112) on the device's CUs */
+  int nqk_n;                      /* 0: no next projection; 512: q | k with rotary; 256: shared */
+  const float *nqk_w, *nqk_b;     /* [nqk_n][256], [nqk_n] */
+  const float *nv_w, *nv_b;       /* [256][256], [256] */
+  const float *rot_cos, *rot_sin; /* [M][32] (nqk_n = 512) */
+  int Np;                         /* head layouts: M = S * Np */
+  float *q, *k, *vt;              /* [S][4][Np][64] x 2, [S][4][64][Np] */
+  int rows_past[5];
+} airfe_debug_lg_block_args;
+int airfe_debug_lg_block(airfe_ctx* ctx, airfe_debug_lg_block_args* a);
+/* launch_ln_gelu in place on h [M][512] (rounded to the 2-byte type on the way in) */
+int airfe_debug_ln_gelu(airfe_ctx* ctx, int prec, float* h, const float* gamma, const float* beta, int M);
 /* the matcher's flash attention alone (kernels_attn.hip) on HOST fp32 tensors, rounded to the matcher's 2-byte type on the way in: q, k [S][H][n][64] with the
  * soft-max scale and log2 e ALREADY inside (the kernel computes p = 2^(q.k - shift)), v [S][H][n][64], lens [S] (keys / queries beyond lens[s] are padding), cross:
  * sequence s attends to sequence s ^ 1.  out [S][n][H*64] fp32.  n <= max_keypoints (rounded up to 16 inside); S * H a multiple of 8.  The way to drive the kernel's

@@ -1,5 +1,7 @@
-"""Kernel-level parity on the GPU: the MFMA conv / GEMM kernels behind the C ABI vs fp32 references on inputs
-pre-rounded to the storage type (so only accumulation order and the output rounding differ)."""
+"""Kernel-level parity on the GPU: the MFMA conv / GEMM kernels behind the C ABI vs torch / float64 references on inputs
+pre-rounded to the storage type (so only accumulation order and the output rounding differ), with blanket tolerances.
+The GEMM family's epilogues, gathers and kernels one by one, and the fused LightGlue block, are checked against fp64
+references with derived per-element bounds in test_gpu_linear_kernels.py and test_gpu_lg_block.py (tests/kernel_ref.py)."""
 import numpy as np
 import pytest
 import torch
