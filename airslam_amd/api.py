@@ -630,6 +630,62 @@ class Context:
                                                      None if Rt_t is None else Rt_t.data_ptr(), mask_t.data_ptr(), count_t.data_ptr(),
                                                      self._stream(stream)), "airfe_track_pose_batch_dev")
 
+    @staticmethod
+    def _tcb(Tcb):
+        """(keep-alive array, pointer or None) of Tcb = (Rcb row-major, tcb) [12], a 4x4 Tcb, or None (identity)"""
+        if Tcb is None:
+            return None, None
+        t = np.ascontiguousarray(Tcb, np.float64)
+        if t.size == 16:
+            t = np.ascontiguousarray(np.concatenate([t.reshape(4, 4)[:3, :3].reshape(9), t.reshape(4, 4)[:3, 3]]))
+        t = t.reshape(12)
+        return t, t.ctypes.data
+
+    def frame_optimize(self, X: np.ndarray, obs: np.ndarray, cam, thr, Twc0, Tcb=None):
+        """Pose-only frame optimisation on ONE problem (airfe_frame_optimize ≙ the vision-only, points-only FrameOptimization of tracking,
+        g2o_optimization.cc:446-898; contract: include/airfe.h "Frame optimisation"): X [n,3] map points, obs [n,3] = (x, y, u_right; stereo iff
+        u_right > 0), cam = (fx, fy, cx, cy, bf), thr = (mono, stereo) chi-square thresholds, Twc0 [4,4] the start pose, Tcb (optional)
+        -> dict(Twc [4,4], Rt [12] (Rcw row-major, tcw), inlier [n] uint8, num_inliers)."""
+        X = np.ascontiguousarray(X, np.float64).reshape(-1, 3)
+        obs = np.ascontiguousarray(obs, np.float64).reshape(-1, 3)
+        if len(X) != len(obs):
+            raise AirfeError("frame_optimize: X and obs differ in length")
+        cam = np.ascontiguousarray(cam, np.float64).reshape(5)
+        thr = np.ascontiguousarray(thr, np.float64).reshape(2)
+        T0 = np.ascontiguousarray(Twc0, np.float64).reshape(16)
+        keep, tcb = self._tcb(Tcb)
+        Twc, Rt = np.zeros(16), np.zeros(12)
+        mask = np.zeros(max(len(X), 1), np.uint8)
+        num = C.c_int(0)
+        self._chk(self._l.airfe_frame_optimize(self._h, X.ctypes.data, obs.ctypes.data, len(X), cam.ctypes.data, tcb, thr.ctypes.data, T0.ctypes.data,
+                                               Twc.ctypes.data, Rt.ctypes.data, mask.ctypes.data, C.byref(num)), "airfe_frame_optimize")
+        return dict(Twc=Twc.reshape(4, 4), Rt=Rt, inlier=mask[:len(X)], num_inliers=num.value)
+
+    def frame_optimize_batch_dev(self, X_t, obs_t, n_t, Twc0_t, cam, thr, Twc_t, inlier_t, num_t, Rt_t=None, Tcb=None, stream=None):
+        """airfe_frame_optimize_batch_dev: X_t / obs_t [B,ncap,3] float64, n_t [B] int32, Twc0_t [B,16] float64 -> Twc_t [B,16] float64,
+        inlier_t [B,ncap] uint8, num_t [B] int32, Rt_t [B,12] float64 (optional).  Asynchronous on `stream`."""
+        cam = np.ascontiguousarray(cam, np.float64).reshape(5)
+        thr = np.ascontiguousarray(thr, np.float64).reshape(2)
+        keep, tcb = self._tcb(Tcb)
+        self._chk(self._l.airfe_frame_optimize_batch_dev(self._h, X_t.data_ptr(), obs_t.data_ptr(), n_t.data_ptr(), X_t.shape[0], X_t.shape[1],
+                                                         Twc0_t.data_ptr(), cam.ctypes.data, tcb, thr.ctypes.data, Twc_t.data_ptr(),
+                                                         None if Rt_t is None else Rt_t.data_ptr(), inlier_t.data_ptr(), num_t.data_ptr(),
+                                                         self._stream(stream)), "airfe_frame_optimize_batch_dev")
+
+    def track_pose_opt_batch_dev(self, cam, thr, lost_num_match, xyz_t, feat_t, tidx_t, ntrack_t, Twc_t, mask_t, num_t, ok_t, u_right_t=None,
+                                 Twc_last_t=None, Rt_t=None, pnp_count_t=None, stream=None):
+        """airfe_track_pose_opt_batch_dev (FramePoseOptimization without IMU, map_builder.cc:307-317, 353-417): the inputs of track_pose_batch_dev plus
+        u_right_t [B,cap] float64 of the current frame (None: all mono), Twc_last_t [B,16] (None: identity), lost_num_match, cam = (fx, fy, cx, cy, bf),
+        thr -> Twc_t [B,16], mask_t [B,mcap] uint8 (per list entry), num_t [B], ok_t [B] int32, Rt_t [B,12], pnp_count_t [B] (optional)."""
+        cam = np.ascontiguousarray(cam, np.float64).reshape(5)
+        thr = np.ascontiguousarray(thr, np.float64).reshape(2)
+        opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self._chk(self._l.airfe_track_pose_opt_batch_dev(self._h, cam.ctypes.data, thr.ctypes.data, int(lost_num_match), xyz_t.data_ptr(), xyz_t.shape[1],
+                                                         feat_t.data_ptr(), feat_t.shape[1], tidx_t.data_ptr(), ntrack_t.data_ptr(), tidx_t.shape[1],
+                                                         tidx_t.shape[0], opt(u_right_t), opt(Twc_last_t), Twc_t.data_ptr(), opt(Rt_t), mask_t.data_ptr(),
+                                                         num_t.data_ptr(), ok_t.data_ptr(), opt(pnp_count_t), self._stream(stream)),
+                  "airfe_track_pose_opt_batch_dev")
+
     def match_lightglue_batch_dev(self, f0_t, n0_t, f1_t, n1_t, idx_t, score_t, nm_t, stream=None):
         self._chk(self._l.airfe_match_lightglue_batch_dev(self._h, f0_t.data_ptr(), n0_t.data_ptr(), f1_t.data_ptr(),
                                                           n1_t.data_ptr(), f0_t.shape[0], f0_t.shape[1], idx_t.data_ptr(),

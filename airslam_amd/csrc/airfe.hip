@@ -3,6 +3,7 @@
 #include "airfe_host.h"
 #include "fransac_core.h"
 #include "pnp_core.h"
+#include "poseopt_core.h"
 
 namespace airfe_host {
 thread_local std::string g_err;
@@ -979,6 +980,111 @@ int airfe_track_pose_batch_dev(airfe_ctx* c, const double* K, const double* d_xy
   launch_pnp_gather(g, B, st);
   HIPCHK(c, hipGetLastError());
   return pnp_queue(c, g.obj, g.img, g.n, B, mcap, K, d_Twc, d_Rt, d_mask, mcap, g.map, d_count, st);
+} AIRFE_CATCH(c)
+
+// Pose-only frame optimisation (g2o_optimization.cc:446-898, one free pose, point edges) over B device problems on `st` (kernels_poseopt.hip)
+static int poseopt_queue(airfe_ctx* c, const double* d_X, const double* d_obs, const int* d_n, int B, int ncap, const double* d_Twc0, const double* cam,
+                         const double* Tcb, const double* thr, double* d_Twc, double* d_Rt, uint8_t* d_inlier, int mcap, const int* d_map, int* d_num,
+                         int lost, int* d_ok, hipStream_t st) {
+  PoseoptArgs a;
+  a.X = d_X; a.obs = d_obs; a.n = d_n; a.ncap = ncap; a.Twc0 = d_Twc0;
+  for (int k = 0; k < 5; ++k) a.cam[k] = cam[k];
+  for (int k = 0; k < 2; ++k) a.thr[k] = thr[k];
+  if (Tcb) {
+    for (int k = 0; k < 12; ++k) a.Tcb[k] = Tcb[k];
+    a.has_tcb = 1;
+  }
+  a.Twc = d_Twc; a.Rt = d_Rt; a.inlier = d_inlier; a.mcap = mcap; a.map = d_map; a.num = d_num; a.lost = lost; a.ok = d_ok;
+  launch_poseopt(a, B, st);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+int airfe_frame_optimize_batch_dev(airfe_ctx* c, const double* d_X, const double* d_obs, const int* d_n, int B, int ncap, const double* d_Twc0,
+                                   const double* cam, const double* Tcb, const double* thr, double* d_Twc, double* d_Rt, uint8_t* d_inlier, int* d_num,
+                                   void* stream) try {
+  AIRFE_ENTER(c);
+  if (B < 1 || ncap < 1 || !d_X || !d_obs || !d_n || !d_Twc0 || !cam || !thr || !d_Twc || !d_inlier || !d_num)
+    return fail(c, "frame_optimize_batch_dev: bad argument");
+  if (ncap > PO_MAX_POINTS) return fail(c, "frame_optimize_batch_dev: ncap > 1024");
+  return poseopt_queue(c, d_X, d_obs, d_n, B, ncap, d_Twc0, cam, Tcb, thr, d_Twc, d_Rt, d_inlier, ncap, nullptr, d_num, -1, nullptr,
+                       stream ? (hipStream_t)stream : c->stream);
+} AIRFE_CATCH(c)
+
+int airfe_frame_optimize(airfe_ctx* c, const double* X, const double* obs, int n, const double* cam, const double* Tcb, const double* thr,
+                         const double* Twc0, double* Twc, double* Rt, uint8_t* inlier, int* num_inliers) try {
+  AIRFE_ENTER(c);
+  if (n < 0 || !cam || !thr || !Twc0 || !Twc || !num_inliers || (n > 0 && (!X || !obs || !inlier))) return fail(c, "frame_optimize: bad argument");
+  if (n > PO_MAX_POINTS) return fail(c, "frame_optimize: more than 1024 constraints");
+  const int ncap = std::max(n, 1);
+  // one block: n | Twc0 [16] | Twc [16] | Rt [12] | num | X [ncap][3] | obs [ncap][3] | inlier [ncap]
+  const size_t o_X = 512, o_obs = o_X + (size_t)ncap * 24, o_mask = o_obs + (size_t)ncap * 24;
+  if (ensure_block(c, c->po_stage, c->po_stage_bytes, o_mask + ncap)) return 1;
+  uint8_t* d = c->po_stage;
+  int* d_n = reinterpret_cast<int*>(d);
+  double* d_Twc0 = reinterpret_cast<double*>(d + 8);
+  double* d_Twc = reinterpret_cast<double*>(d + 8 + 128);
+  double* d_Rt = reinterpret_cast<double*>(d + 8 + 256);
+  int* d_num = reinterpret_cast<int*>(d + 8 + 256 + 96);
+  hipStream_t st = c->stream;
+  DrainOnError drain{c, true};
+  HIPCHK(c, hipMemcpyAsync(d_n, &n, 4, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_Twc0, Twc0, 128, hipMemcpyHostToDevice, st));
+  if (n > 0) {
+    HIPCHK(c, hipMemcpyAsync(d + o_X, X, (size_t)n * 24, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d + o_obs, obs, (size_t)n * 24, hipMemcpyHostToDevice, st));
+  }
+  if (poseopt_queue(c, reinterpret_cast<double*>(d + o_X), reinterpret_cast<double*>(d + o_obs), d_n, 1, ncap, d_Twc0, cam, Tcb, thr, d_Twc, d_Rt,
+                    d + o_mask, ncap, nullptr, d_num, -1, nullptr, st)) return 1;
+  double rt[12];
+  HIPCHK(c, hipMemcpyAsync(Twc, d_Twc, 128, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(rt, d_Rt, 96, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(num_inliers, d_num, 4, hipMemcpyDeviceToHost, st));
+  if (n > 0) HIPCHK(c, hipMemcpyAsync(inlier, d + o_mask, n, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  drain.armed = false;
+  if (Rt) memcpy(Rt, rt, 96);
+  return 0;
+} AIRFE_CATCH(c)
+
+int airfe_track_pose_opt_batch_dev(airfe_ctx* c, const double* cam, const double* thr, int lost_num_match, const double* d_xyz, int capK,
+                                   const float* d_feat, int cap, const int32_t* d_tidx, const int* d_ntrack, int mcap, int B, const double* d_u_right,
+                                   const double* d_Twc_last, double* d_Twc, double* d_Rt, uint8_t* d_mask, int* d_num, int* d_ok, int* d_pnp_count,
+                                   void* stream) try {
+  AIRFE_ENTER(c);
+  if (B < 1 || capK < 1 || cap < 1 || mcap < 1 || lost_num_match < 0 || !cam || !thr || !d_xyz || !d_feat || !d_tidx || !d_ntrack || !d_Twc || !d_mask ||
+      !d_num || !d_ok)
+    return fail(c, "track_pose_opt_batch_dev: bad argument");
+  if (mcap > PNP_MAX_POINTS) return fail(c, "track_pose_opt_batch_dev: mcap > 1024");
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  // the PnP gather's block (as airfe_track_pose_batch_dev): obj [B][mcap][3] | img [B][mcap][2] f32 | map [B][mcap] | n [B]
+  const size_t per = (size_t)mcap * 24;
+  if (ensure_block(c, c->pn_gather, c->pn_gather_bytes, (size_t)B * per + (size_t)B * 4, c->pn_gather_stream)) return 1;
+  c->pn_gather_stream = st;
+  // this entry's block: X [B][mcap][3] | obs [B][mcap][3] | Twc_pnp [B][16] | Twc0 [B][16] f64 | pnp count [B] | pnp mask [B][mcap]
+  const size_t o_obs = (size_t)B * per, o_pnp = 2 * o_obs, o_seed = o_pnp + (size_t)B * 128, o_cnt = o_seed + (size_t)B * 128;
+  const size_t o_msk = o_cnt + ((size_t)B * 4 + 7) / 8 * 8;
+  if (ensure_block(c, c->po_gather, c->po_gather_bytes, o_msk + (size_t)B * mcap, c->po_gather_stream)) return 1;
+  c->po_gather_stream = st;
+  PnpGatherArgs g;
+  g.xyz = d_xyz; g.capK = capK; g.feat = d_feat; g.cap = cap; g.tidx = d_tidx; g.ntrack = d_ntrack; g.mcap = mcap; g.ncap = mcap;
+  g.obj = reinterpret_cast<float*>(c->pn_gather);
+  g.img = reinterpret_cast<float*>(c->pn_gather + (size_t)B * mcap * 12);
+  g.map = reinterpret_cast<int*>(c->pn_gather + (size_t)B * mcap * 20);
+  g.n = reinterpret_cast<int*>(c->pn_gather + (size_t)B * per);
+  launch_pnp_gather(g, B, st);
+  HIPCHK(c, hipGetLastError());
+  double* d_pnp = reinterpret_cast<double*>(c->po_gather + o_pnp);
+  int* d_cnt = d_pnp_count ? d_pnp_count : reinterpret_cast<int*>(c->po_gather + o_cnt);
+  if (pnp_queue(c, g.obj, g.img, g.n, B, mcap, cam, d_pnp, nullptr, c->po_gather + o_msk, mcap, g.map, d_cnt, st)) return 1;
+  PoseoptGatherArgs q;
+  q.xyz = d_xyz; q.capK = capK; q.feat = d_feat; q.cap = cap; q.tidx = d_tidx; q.mcap = mcap; q.map = g.map; q.n = g.n; q.ncap = mcap;
+  q.u_right = d_u_right; q.Twc_pnp = d_pnp; q.Twc_last = d_Twc_last; q.pnp_count = d_cnt; q.lost = lost_num_match;
+  q.X = reinterpret_cast<double*>(c->po_gather); q.obs = reinterpret_cast<double*>(c->po_gather + o_obs);
+  q.Twc0 = reinterpret_cast<double*>(c->po_gather + o_seed);
+  launch_poseopt_gather(q, B, st);
+  HIPCHK(c, hipGetLastError());
+  return poseopt_queue(c, q.X, q.obs, g.n, B, mcap, q.Twc0, cam, nullptr, thr, d_Twc, d_Rt, d_mask, mcap, g.map, d_num, lost_num_match, d_ok, st);
 } AIRFE_CATCH(c)
 
 int airfe_has_line_branch(const airfe_ctx* c) { return c && c->has_s0 && c->has_s1; }

@@ -123,6 +123,9 @@ struct airfe_ctx {
   uint8_t* pn_gather = nullptr; size_t pn_gather_bytes = 0;             // airfe_track_pose_batch_dev: the gathered correspondences
   hipStream_t pn_gather_stream = nullptr;
   uint8_t* pn_stage = nullptr; size_t pn_stage_bytes = 0;               // airfe_pnp_ransac: the one problem on the device
+  uint8_t* po_stage = nullptr; size_t po_stage_bytes = 0;               // airfe_frame_optimize: the one problem on the device
+  uint8_t* po_gather = nullptr; size_t po_gather_bytes = 0;             // airfe_track_pose_opt_batch_dev: PnP results, seeds and gathered constraints
+  hipStream_t po_gather_stream = nullptr;
   bool outlier_rejection = false;                                       // airfe_set_outlier_rejection: F-RANSAC behind the temporal match of track_frame / stereo_keyframe_tracked
   bool nms_map_valid = true;     // heat_nms holds the last batch's NMS'd maps (large batches skip writing them)
   bool force_nms_map = false;    // the batched PLNet path reads junction scores from them: written at every batch size while set

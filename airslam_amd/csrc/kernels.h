@@ -376,4 +376,32 @@ struct StereoArgs {
 };
 void launch_stereo_points(const StereoArgs& s, int B, hipStream_t st);
 
+// Pose-only frame optimisation (FrameOptimization of tracking, g2o_optimization.cc:446-898) over B device problems (kernels_poseopt.hip; contract: include/airfe.h)
+struct PoseoptArgs {
+  const double *X = nullptr, *obs = nullptr;    // [B][ncap][3] map points, [B][ncap][3] observations (x, y, u_right)
+  const int* n = nullptr;                       // [B] constraints
+  int ncap = 0;                                 // <= PO_MAX_POINTS
+  const double* Twc0 = nullptr;                 // [B][16] start poses
+  double cam[5] = {0, 0, 0, 0, 0}, thr[2] = {0, 0}, Tcb[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+  int has_tcb = 0;
+  double *Twc = nullptr, *Rt = nullptr;         // [B][16], [B][12] or nullptr
+  uint8_t* inlier = nullptr;                    // [B][mcap]: every entry written
+  int mcap = 0;
+  const int* map = nullptr;                     // [B][ncap] or nullptr: flag slot of constraint i (the composite: its list entry)
+  int* num = nullptr;                           // [B]
+  int lost = -1;                                // the composite: the start pose is kept unless num > lost (-1: the optimised pose always)
+  int* ok = nullptr;                            // [B] or nullptr: num > lost
+};
+void launch_poseopt(const PoseoptArgs& a, int B, hipStream_t st);
+struct PoseoptGatherArgs {                      // the composite's glue: seed + constraints of the list entries the PnP gather kept
+  const double* xyz = nullptr; int capK = 0;
+  const float* feat = nullptr; int cap = 0;
+  const int32_t* tidx = nullptr; int mcap = 0;
+  const int *map = nullptr, *n = nullptr; int ncap = 0;         // the PnP gather's output
+  const double* u_right = nullptr;              // [B][cap] or nullptr (all mono)
+  const double *Twc_pnp = nullptr, *Twc_last = nullptr; const int* pnp_count = nullptr; int lost = 0;
+  double *X = nullptr, *obs = nullptr, *Twc0 = nullptr;
+};
+void launch_poseopt_gather(const PoseoptGatherArgs& g, int B, hipStream_t st);
+
 }  // namespace airfe

@@ -449,6 +449,13 @@ FR_HD void pnp_lm_start(double* S, const double* Rt, const double* tot) {
   S[PL_LAM] = 1e-3;
   S[PL_STOP] = (isfinite(tot[27]) && tot[27] > 0.0) ? 0.0 : 1.0;
 }
+// Cay(w) = I + 2 / (1 + w.w) ([w]x + [w]x^2), row-major in C [9] (shared with poseopt_core.h)
+FR_HD void pnp_cayley(double w0, double w1, double w2, double* C) {
+  const double nn = (w0 * w0 + w1 * w1) + w2 * w2, k = 2.0 / (1.0 + nn);
+  C[0] = 1.0 + k * (w0 * w0 - nn); C[1] = k * (-w2 + w0 * w1);      C[2] = k * (w1 + w0 * w2);
+  C[3] = k * (w2 + w1 * w0);       C[4] = 1.0 + k * (w1 * w1 - nn); C[5] = k * (-w0 + w1 * w2);
+  C[6] = k * (-w1 + w2 * w0);      C[7] = k * (w0 + w2 * w1);       C[8] = 1.0 + k * (w2 * w2 - nn);
+}
 FR_HD int pnp_uidx(int r, int c) { return r * 6 - (r * (r - 1)) / 2 + (c - r); }
 // (A + lambda diag(A)) delta = -g; the trial pose.  A singular system stops the refinement.
 FR_HD void pnp_lm_propose(double* S) {
@@ -463,12 +470,8 @@ FR_HD void pnp_lm_propose(double* S) {
   }
   double* d = S + PL_DEL;
   if (!pnp_gauss(N, 6, d)) { S[PL_STOP] = 1.0; return; }
-  const double w0 = d[0], w1 = d[1], w2 = d[2];
-  const double nn = (w0 * w0 + w1 * w1) + w2 * w2, k = 2.0 / (1.0 + nn);
   double* C = N;
-  C[0] = 1.0 + k * (w0 * w0 - nn); C[1] = k * (-w2 + w0 * w1);      C[2] = k * (w1 + w0 * w2);
-  C[3] = k * (w2 + w1 * w0);       C[4] = 1.0 + k * (w1 * w1 - nn); C[5] = k * (-w0 + w1 * w2);
-  C[6] = k * (-w1 + w2 * w0);      C[7] = k * (w0 + w2 * w1);       C[8] = 1.0 + k * (w2 * w2 - nn);
+  pnp_cayley(d[0], d[1], d[2], C);
   const double* R = S + PL_CUR;
   for (int r = 0; r < 3; ++r)
     for (int c = 0; c < 3; ++c) S[PL_TRY + 3 * r + c] = (C[3 * r] * R[c] + C[3 * r + 1] * R[3 + c]) + C[3 * r + 2] * R[6 + c];

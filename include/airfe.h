@@ -324,6 +324,69 @@ int airfe_stereo_points_batch_dev(airfe_ctx* ctx, const double* cam, const float
 int airfe_track_pose_batch_dev(airfe_ctx* ctx, const double* K, const double* d_xyz, int capK, const float* d_feat, int cap, const int32_t* d_tidx,
                                const int* d_ntrack, int mcap, int B, double* d_Twc, double* d_Rt, uint8_t* d_mask, int* d_count, void* stream);
 
+/* ---- Frame optimisation: the vision-only, points-only FrameOptimization of tracking (src/map_builder.cc:353-417 ->
+ * src/g2o_optimization/g2o_optimization.cc:446-898) ----------------------------------------------------------------------------------------------------
+ * In TrackFrame the line constraint vectors stay empty and, while the IMU is not initialised, there is one free pose and no IMU edge: the call is a
+ * pose-only Levenberg-Marquardt over <= 1024 mono / stereo reprojection edges with Huber kernels, three rounds of optimize(10), and a chi-square
+ * classification after each round.  The contract below restates the PUBLIC behaviour of that call; g2o is not part of this project's build or tests, so
+ * nothing here is checked against g2o and nothing claims equality with it: the numerics are the project's own, on every side — the HIP kernel
+ * (airslam_amd/csrc/kernels_poseopt.hip), the host core (poseopt_solve_host in airslam_amd/csrc/poseopt_core.h, which the kernel shares) and the Python
+ * restatement (tests/poseopt_ref.py).  fp64, no fused multiply-adds, sums in the order written; the only non-rational function is sqrt.
+ *   input    n <= 1024 constraints in list order: map point X (3 doubles, in the frame the start pose is expressed in), observation (x, y, u_right);
+ *            STEREO iff u_right > 0 (map_builder.cc:370).  cam = (fx, fy, cx, cy, bf).  Tcb = Rcb (row-major), tcb; NULL = identity.
+ *            thr = (mono_point, stereo_point): the chi-square values of `optimization.tracking`; Huber delta = sqrt(threshold)
+ *            (g2o_optimization.cc:572-573); information = identity.  Start pose Twc0 (16 doubles, row-major).
+ *   state    as VIPose: Rwb = Rwc Rcb, twb = Rwc tcb + twc; Rcw = Rcb Rwb^T, tcw = tcb - Rcw twb; tbc = -(Rcb^T tcb).
+ *   edge     Xc = Rcw X + tcw; iz = 1.0 / Xc.z; u = Xc.x iz fx + cx, v = Xc.y iz fy + cy; e = (x - u, y - v) and, stereo, u_right - (u - bf iz)
+ *            (edge_project_point.cc:23-44, 100-122); a mono edge's third component is +0.  chi2 = (e0 e0 + e1 e1) + e2 e2.
+ *   Jacobian analytic — the one the reference carries in comments (edge_project_point.cc:57-83, 135-166): J = P Rcb D, P = [fx iz, 0, -(fx (Xc.x iz) iz);
+ *            0, fy iz, -(fy (Xc.y iz) iz)], stereo third row = the first with (2,2) + bf (iz iz); Xb = Rcb^T Xc + tbc; D = [ -[Xb]x | I ].  A mono
+ *            edge's third row is zero.  STATED DIFFERENCE: the reference leaves linearizeOplus to g2o's numeric differentiation.
+ *   robust   g2o's Huber: chi2 <= delta^2: rho = chi2, w = 1; else s = sqrt(chi2), rho = 2 s delta - delta^2, w = delta / s.  Per edge of level 0:
+ *            H += w J^T J (21 upper entries), g += w J^T e (b = -g), chi += rho.
+ *   sums     H, g and chi are summed as 64 partials (partial l over the constraints l, l + 64, ... in order, from +0) added in lane order from +0 —
+ *            the rule of the PnP refinement.  The partial count is part of the contract.
+ *   optimize g2o's OptimizationAlgorithmLevenberg::solve as published, 10 iterations.  Iteration 0: lambda = 1e-5 max_j |H_jj|, ni = 2.  Each
+ *            iteration: H, g, chi at the current pose; then trials: solve (H + lambda I) dx = b by Gaussian elimination with partial pivoting (the
+ *            one of "PnP RANSAC"; a failed solve: dx = 0, chi_new = +inf); trial Rwb' = Rwb Cay(dr / 2), twb' = twb + Rwb dt (dr = dx[0..2],
+ *            dt = dx[3..5]; Cay as in "PnP RANSAC" — STATED DIFFERENCE: VIPose::Update uses SO3Exp, with which Cay(dr / 2) agrees to second order; no
+ *            NormalizeRotation); chi_new = the robust chi at the trial; rho = (chi - chi_new) / (sum_j dx_j (lambda dx_j + b_j) + 1e-3).
+ *            rho > 0 and chi_new finite: the trial is taken, lambda *= max(1/3, min(1 - (2 rho - 1)^3, 2/3)), ni = 2; else lambda *= ni, ni *= 2
+ *            (lambda not finite ends the trials at once).  Trials repeat while rho < 0 and fewer than 10 were made in this iteration.  The round's
+ *            optimisation ends early when an iteration made 10 trials, when rho == 0, or when lambda is not finite.
+ *   rounds   three times (g2o_optimization.cc:726-814): reset the pose to the START pose, optimize over the level-0 edges, then for EVERY edge
+ *            chi2 at the round's final pose, rounded to float: outlier (level 1) iff (double)(float)chi2 > threshold, inlier (level 0) otherwise
+ *            — an edge can come back.  n < 10 stops after the first round.  STATED DIFFERENCE: g2o leaves stale errors on inlier edges when the
+ *            last trial was rejected; here every edge is evaluated at the accepted pose.
+ *   output   Twc = Twb Tcb^-1 (16 doubles), Rt (optional) = Rcw row-major, tcw; inlier [n] (the last round's flags), num_inliers = n - outliers of
+ *            the last round (:897).  n == 0, or a final pose that is not finite: Twc = the start pose's 16 doubles, Rt = the start pose's, every
+ *            flag 0, num_inliers 0.  A NaN in Rt is written as the canonical quiet NaN (0x7ff8000000000000).
+ * Per problem the batch, the one-call and the host core give the same bytes, whatever the batch size and the problem's position in it. */
+/* ONE problem through host buffers: X [n][3], obs [n][3] doubles, cam [5], Tcb [12] or NULL, thr [2], Twc0 [16]; n <= 1024.
+ * Twc [16], Rt [12] (may be NULL), inlier [n], *num_inliers. */
+int airfe_frame_optimize(airfe_ctx* ctx, const double* X, const double* obs, int n, const double* cam, const double* Tcb, const double* thr,
+                         const double* Twc0, double* Twc, double* Rt, uint8_t* inlier, int* num_inliers);
+/* the same over B device-resident problems, asynchronous on `stream`, no host synchronisation: d_X [B][ncap][3], d_obs [B][ncap][3] doubles, d_n [B]
+ * (clamped to 0..ncap), ncap <= 1024, d_Twc0 [B][16]; cam, Tcb (or NULL), thr are HOST arrays read at the call; d_Twc [B][16], d_Rt [B][12] or NULL,
+ * d_inlier [B][ncap] (every entry written), d_num [B]. */
+int airfe_frame_optimize_batch_dev(airfe_ctx* ctx, const double* d_X, const double* d_obs, const int* d_n, int B, int ncap, const double* d_Twc0,
+                                   const double* cam, const double* Tcb, const double* thr, double* d_Twc, double* d_Rt, uint8_t* d_inlier, int* d_num,
+                                   void* stream);
+/* Tracking composite: FramePoseOptimization without IMU (map_builder.cc:307-317, 353-417) on the inputs of airfe_track_pose_batch_dev, all on the
+ * device, nothing copied to the host in between.  Additional inputs: d_u_right [B][cap] of the CURRENT frame (NULL = every constraint mono, the
+ * normal-frame case; for a keyframe it is airfe_stereo_points_batch_dev's output), d_Twc_last [B][16] (the last tracked pose; NULL = identity),
+ * lost_num_match, cam = (fx, fy, cx, cy, bf), thr.  Per problem: (1) the gather and PnP RANSAC of airfe_track_pose_batch_dev; (2) the seed is the PnP
+ * pose, or Twc_last when |t_pnp - t_last| > 1.0 or the PnP count < lost_num_match; (3) constraints = the list entries whose keyframe point exists, in
+ * list order: X = the keyframe point in double, (x, y) = the current row's, u_right = d_u_right[current index] (the matcher's lists are one-to-one; a
+ * repeated current index is NOT deduplicated: each entry is a constraint of its own); (4) the frame optimisation from the seed, Tcb = identity.
+ * d_Twc [B][16] = the optimised pose when num_inliers > lost_num_match, else the seed; d_Rt [B][12] or NULL likewise; d_mask [B][mcap] by LIST ENTRY =
+ * the optimisation's inlier flags (0 for entries without a point; the reference applies them only when d_ok is set); d_num [B] = num_inliers;
+ * d_ok [B] = num_inliers > lost_num_match; d_pnp_count [B] or NULL = the PnP count.  Equal, byte for byte, to the steps done one at a time. */
+int airfe_track_pose_opt_batch_dev(airfe_ctx* ctx, const double* cam, const double* thr, int lost_num_match, const double* d_xyz, int capK,
+                                   const float* d_feat, int cap, const int32_t* d_tidx, const int* d_ntrack, int mcap, int B, const double* d_u_right,
+                                   const double* d_Twc_last, double* d_Twc, double* d_Rt, uint8_t* d_mask, int* d_num, int* d_ok, int* d_pnp_count,
+                                   void* stream);
+
 /* ---- next row after the path ---------------------------------------------------- */
 /* ≙ AssignPointsToLines (src/line_processor.cc:68-120), called on the path's own outputs (frame.cc:125,177,184).
  *   lines [L][4] doubles (x1,y1,x2,y2) = the std::vector<Eigen::Vector4d> storage; feat [N][259] rows (x,y = floats 1,2).
