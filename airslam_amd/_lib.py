@@ -34,6 +34,11 @@ class Stage0(C.Structure):
         "loi_features", "loi_features_thin", "loi_features_aux")]
 
 
+class BowdbFilter(C.Structure):
+    """airfe_bowdb_filter (include/airfe.h)"""
+    _fields_ = [("ratio", C.c_float), ("min_words", C.c_int), ("d_max_index", C.c_void_p), ("d_exclude", C.c_void_p), ("exclude_words", C.c_int)]
+
+
 class SeqPolicy(C.Structure):
     """airfe_seq_policy (include/airfe_seq.h)"""
     _fields_ = [("min_init_stereo_feature", C.c_int), ("min_num_match", C.c_int), ("max_num_match", C.c_int), ("tracking_point_rate", C.c_float),
@@ -117,6 +122,17 @@ SIGNATURES = {
     "airfe_bow_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "airfe_bow_transform": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "airfe_bow_transform_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "airfe_bow_vector": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
+    "airfe_bow_vector_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5),
+    "airfe_bowdb_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "airfe_bowdb_destroy": (C.c_int, [C.c_void_p]),
+    "airfe_bowdb_clear": (C.c_int, [C.c_void_p]),
+    "airfe_bowdb_size": (C.c_int, [C.c_void_p]),
+    "airfe_bowdb_add_batch_dev": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]),
+    "airfe_bowdb_add": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int]),
+    "airfe_bowdb_query_batch_dev": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.POINTER(BowdbFilter)] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4),
+    "airfe_bowdb_topk_dev": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "airfe_bowdb_match_candidates_batch_dev": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3),
     "airfe_set_rectify_maps": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "airfe_rectify_detect_points": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                               C.POINTER(C.c_int)]),

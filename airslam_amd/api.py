@@ -761,6 +761,24 @@ class Context:
         self._chk(self._l.airfe_bow_transform_dev(self._h, feat_t.data_ptr(), n, word_t.data_ptr(), weight_t.data_ptr(), self._stream(stream)),
                   "airfe_bow_transform_dev")
 
+    def bow_vector(self, feat_rows: np.ndarray, return_words: bool = False):
+        """≙ Database::FrameToBow to its end (src/bow/database.cc:57-89) on one frame's rows [n, 259] -> (ids uint32 [nw], values float64 [nw]) in ascending
+        word id, L1-normalised[, word_of_features uint32 [n]]."""
+        f = np.ascontiguousarray(feat_rows, np.float32).reshape(-1, FEAT)
+        n = f.shape[0]
+        ids = np.empty((max(n, 1),), np.uint32); vals = np.empty((max(n, 1),), np.float64); words = np.empty((max(n, 1),), np.uint32)
+        nw = C.c_int(0)
+        self._chk(self._l.airfe_bow_vector(self._h, f.ctypes.data, n, ids.ctypes.data, vals.ctypes.data, C.byref(nw), words.ctypes.data), "airfe_bow_vector")
+        out = (ids[:nw.value].copy(), vals[:nw.value].copy())
+        return out + (words[:n].copy(),) if return_words else out
+
+    def bow_vector_batch_dev(self, feat_t, n_t, ids_t, vals_t, nw_t, word_t=None, stream=None):
+        """FrameToBow over B device frames: feat [B][cap][259] f32, n [B] i32 -> ids [B][cap] (int32 storage of the uint32 ids), vals [B][cap] f64, nw [B] i32,
+        word [B][cap] or None (word_of_features)."""
+        b, cap = feat_t.shape[0], feat_t.shape[1]
+        self._chk(self._l.airfe_bow_vector_batch_dev(self._h, feat_t.data_ptr(), n_t.data_ptr(), b, cap, ids_t.data_ptr(), vals_t.data_ptr(), nw_t.data_ptr(),
+                                                     word_t.data_ptr() if word_t is not None else None, self._stream(stream)), "airfe_bow_vector_batch_dev")
+
     def copy_rows_plan(self, jobs):
         """jobs: [(src tensor / pointer, dst tensor / pointer, count tensor (int32, one element) / pointer / None, row_bytes, cap rows)] -> a reusable plan for
         copy_rows_dev (the five host arrays of airfe_copy_rows_dev, built once: the buffers of a pipeline do not move)"""
@@ -846,6 +864,77 @@ class Context:
         tab = np.zeros(slots[-1][1] + slots[-1][2], np.uint64) if (table and slots) else None
         self._chk(self._l.airfe_debug_trace_read(self._h, stream, dig.ctypes.data, tab.ctypes.data if tab is not None else None), "airfe_debug_trace_read")
         return dig, tab
+
+
+class BowDatabase:
+    """airfe_bowdb (include/airfe.h, "BoW keyframe database"): Database::AddFrame / Query / Score and the callers' sharing-word filters over keyframes
+    that live on the device.  A frame's handle is its insertion index.  Owned by `ctx` (needs ctx.bow_load first); close() before the context's."""
+
+    def __init__(self, ctx: Context, max_frames: int, cap: int, keep_features: bool = False):
+        self._ctx, self._l = ctx, ctx._l
+        self.max_frames, self.cap, self.keep_features = max_frames, cap, bool(keep_features)
+        h = C.c_void_p()
+        ctx._chk(self._l.airfe_bowdb_create(ctx._h, max_frames, cap, 1 if keep_features else 0, C.byref(h)), "airfe_bowdb_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._l.airfe_bowdb_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def size(self) -> int:
+        return self._l.airfe_bowdb_size(self._h)
+
+    def clear(self):
+        self._ctx._chk(self._l.airfe_bowdb_clear(self._h), "airfe_bowdb_clear")
+
+    def add(self, ids: np.ndarray, vals: np.ndarray, nw: np.ndarray, feat: np.ndarray = None, n: np.ndarray = None):
+        """host buffers: ids [B][cap] uint32, vals [B][cap] float64, nw [B] int32 (+ feat [B][cap][259] float32, n [B] int32 with keep_features)"""
+        ids = np.ascontiguousarray(ids, np.uint32); vals = np.ascontiguousarray(vals, np.float64); nw = np.ascontiguousarray(nw, np.int32)
+        feat = None if feat is None else np.ascontiguousarray(feat, np.float32)
+        n = None if n is None else np.ascontiguousarray(n, np.int32)
+        self._ctx._chk(self._l.airfe_bowdb_add(self._h, ids.ctypes.data, vals.ctypes.data, nw.ctypes.data, feat.ctypes.data if feat is not None else None,
+                                               n.ctypes.data if n is not None else None, ids.shape[0], ids.shape[1]), "airfe_bowdb_add")
+
+    def add_batch_dev(self, ids_t, vals_t, nw_t, feat_t=None, n_t=None, stream=None):
+        """≙ Database::AddFrame for B device vectors (Context.bow_vector_batch_dev's outputs); asynchronous on `stream`"""
+        self._ctx._chk(self._l.airfe_bowdb_add_batch_dev(self._h, ids_t.data_ptr(), vals_t.data_ptr(), nw_t.data_ptr(),
+                                                         feat_t.data_ptr() if feat_t is not None else None, n_t.data_ptr() if n_t is not None else None,
+                                                         ids_t.shape[0], ids_t.shape[1], self._ctx._stream(stream)), "airfe_bowdb_add_batch_dev")
+
+    def query_batch_dev(self, ids_t, vals_t, nw_t, cand_frame_t, cand_sharing_t, cand_score_t, ncand_t, max_sharing_t, ratio=0.3, min_words=8,
+                        max_index_t=None, exclude_t=None, sharing_t=None, stream=None):
+        """Q query vectors [Q][cap] against every stored frame -> per query the candidates in ascending frame index: cand_frame / cand_sharing i32 [Q][ccap],
+        cand_score f64 [Q][ccap], ncand [Q] (the full count), max_sharing [Q]; ratio 0.3 = relocalisation, 0.5 = loop detection; max_index [Q] i32 (frames
+        below it only), exclude [Q][words] i32 bit rows, sharing [Q][size] i32 (dense counts), all optional."""
+        from . import _lib
+        f = _lib.BowdbFilter(float(ratio), int(min_words), max_index_t.data_ptr() if max_index_t is not None else None,
+                             exclude_t.data_ptr() if exclude_t is not None else None, exclude_t.shape[1] if exclude_t is not None else 0)
+        self._ctx._chk(self._l.airfe_bowdb_query_batch_dev(self._h, ids_t.data_ptr(), vals_t.data_ptr(), nw_t.data_ptr(), ids_t.shape[0], ids_t.shape[1], C.byref(f),
+                                                           cand_frame_t.data_ptr(), cand_sharing_t.data_ptr(), cand_score_t.data_ptr(), cand_frame_t.shape[1],
+                                                           ncand_t.data_ptr(), max_sharing_t.data_ptr(), sharing_t.data_ptr() if sharing_t is not None else None,
+                                                           self._ctx._stream(stream)), "airfe_bowdb_query_batch_dev")
+
+    def topk_dev(self, cand_frame_t, cand_score_t, ncand_t, top_t, top_score_t=None, stream=None):
+        """the project's own ranking (not the reference's grouping): top [Q][K <= 8] i32 = the candidates by descending score, ties to the lower frame, -1 padded"""
+        self._ctx._chk(self._l.airfe_bowdb_topk_dev(self._h, cand_frame_t.data_ptr(), cand_score_t.data_ptr(), ncand_t.data_ptr(), cand_frame_t.shape[0],
+                                                    cand_frame_t.shape[1], top_t.shape[1], top_t.data_ptr(),
+                                                    top_score_t.data_ptr() if top_score_t is not None else None, self._ctx._stream(stream)), "airfe_bowdb_topk_dev")
+
+    def match_candidates_batch_dev(self, qfeat_t, qn_t, cand_t, best_t, idx_t, score_t, nmatch_t, nmatch_all_t=None, outlier_rejection=True, stream=None):
+        """map_user.cc:360-376 / map_refiner.cc:213-230: every query [Q][cap][259] against its candidates cand [Q][K <= 5] (in order, -1 = none) through
+        LightGlue (+ the F-matrix RANSAC) -> best [Q] (frame or -1), its list idx [Q][mcap][2] / score [Q][mcap] / nmatch [Q], nmatch_all [Q][K]."""
+        self._ctx._chk(self._l.airfe_bowdb_match_candidates_batch_dev(
+            self._ctx._h, self._h, qfeat_t.data_ptr(), qn_t.data_ptr(), qfeat_t.shape[0], qfeat_t.shape[1], cand_t.data_ptr(), cand_t.shape[1],
+            1 if outlier_rejection else 0, best_t.data_ptr(), idx_t.data_ptr(), score_t.data_ptr(), idx_t.shape[1], nmatch_t.data_ptr(),
+            nmatch_all_t.data_ptr() if nmatch_all_t is not None else None, self._ctx._stream(stream)), "airfe_bowdb_match_candidates_batch_dev")
 
 
 # ------------------------------------------------------------------------------------ reference-shaped façade

@@ -443,6 +443,11 @@ int airfe_bow_load(airfe_ctx* c, const float* node_desc, const int32_t* first_ch
   c->bow_first = dupload(c, fc); c->bow_nch = dupload(c, nc); c->bow_word = dupload(c, wi);
   c->bow_out = dalloc<unsigned>(c, 1024); c->bow_outw = dalloc<float>(c, 1024); c->bow_outn = dalloc<int>(c, 1024);
   c->bow_weight_h.assign(weight, weight + n_nodes);
+  c->bow_weight_d = dupload(c, c->bow_weight_h);            // WordValue is a double: the BoW vector sums these, not the float copy the descent compares with 0
+  if (!c->bow_weight_d) return fail(c, "bow_load: device allocation failed");
+  c->bow_nwords = 0;
+  for (int i = 0; i < n_nodes; ++i)
+    if (n_children[i] == 0 && word_id[i] >= 0) c->bow_nwords = std::max(c->bow_nwords, word_id[i] + 1);
   if (!c->bow_desc || !c->bow_weight || !c->bow_first || !c->bow_nch || !c->bow_word || !c->bow_out || !c->bow_outw || !c->bow_outn)
     return fail(c, "device allocation failed (vocabulary)");
   c->bow_nodes = n_nodes;
@@ -2240,6 +2245,258 @@ int airfe_debug_attention(airfe_ctx* c, const float* q, const float* k, const fl
   }
   for (void* p : tmp.allocs) (void)hipFree(p);
   return rc;
+} AIRFE_CATCH(c)
+
+/* ---- BoW keyframe database (include/airfe.h "BoW keyframe database"; kernels_bowdb.hip) ------------------------------------------------------------- */
+}  // extern "C" (the database object is a C++ struct behind an opaque pointer)
+
+struct airfe_bowdb {
+  airfe_ctx* c = nullptr;
+  int max_frames = 0, cap = 0, keep = 0, size = 0;
+  uint32_t* ids = nullptr; double* vals = nullptr; int* nw = nullptr;        // [max_frames][cap], [max_frames][cap], [max_frames]
+  float* feat = nullptr; int* n = nullptr;                                   // keep_features: [max_frames][cap][259], [max_frames]
+  uint8_t* q_scratch = nullptr; size_t q_bytes = 0; hipStream_t q_stream = nullptr;      // query: dense sharing + score [Q][N]
+  uint8_t* m_scratch = nullptr; size_t m_bytes = 0; hipStream_t m_stream = nullptr;      // composite: the pair batch
+};
+
+namespace {
+// a database's scratch grows only behind a synchronisation of the stream it was last used on (as fransac_queue's)
+int bowdb_scratch(airfe_bowdb* db, uint8_t*& blk, size_t& have, hipStream_t& last, size_t bytes, hipStream_t st) {
+  airfe_ctx* c = db->c;
+  if (bytes > have) {
+    if (last) HIPCHK(c, hipStreamSynchronize(last));
+    void* p = nullptr;
+    HIPCHK(c, hipMalloc(&p, bytes));
+    if (blk) (void)hipFree(blk);
+    blk = reinterpret_cast<uint8_t*>(p);
+    have = bytes;
+  }
+  last = st;
+  return 0;
+}
+
+int bow_vector_queue(airfe_ctx* c, const float* d_feat, const int* d_n, int B, int cap, uint32_t* d_ids, double* d_vals, int* d_nw, uint32_t* d_word,
+                     hipStream_t st) {
+  const size_t rows = (size_t)B * cap;
+  if (ensure_block(c, c->bv_scratch, c->bv_scratch_bytes, rows * 12 + 256, c->bv_scratch_stream)) return 1;
+  c->bv_scratch_stream = st;
+  unsigned* word = d_word ? d_word : reinterpret_cast<unsigned*>(c->bv_scratch);
+  float* wf = reinterpret_cast<float*>(c->bv_scratch + rows * 4);
+  int* node = reinterpret_cast<int*>(c->bv_scratch + rows * 8);
+  ProfScope ps(c, ST_BOW, st, 0, (double)rows * 259 * 4);
+  // the existing descent over every row of the batch (rows past a frame's count are descended too and ignored: the vector kernel reads n rows)
+  launch_bow_transform(d_feat, AIRFE_FEAT_DIM, 3, (int)rows, c->bow_desc, c->bow_first, c->bow_nch, c->bow_word, c->bow_weight, word, wf, node, st);
+  BowVecArgs a;
+  a.word = word; a.node = node; a.n = d_n; a.cap = cap; a.weight = c->bow_weight_d; a.ids = d_ids; a.vals = d_vals; a.nw = d_nw;
+  launch_bow_vector(a, B, st);
+  note_launch(c, ST_BOW);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int airfe_bow_vector_batch_dev(airfe_ctx* c, const float* d_feat, const int* d_n, int B, int cap, uint32_t* d_ids, double* d_vals, int* d_nw,
+                               uint32_t* d_word, void* stream) try {
+  AIRFE_ENTER(c);
+  if (!c->bow_nodes) return fail(c, "bow_vector_batch_dev: no vocabulary loaded (airfe_bow_load)");
+  if (B < 1 || cap < 1 || !d_feat || !d_n || !d_ids || !d_vals || !d_nw) return fail(c, "bow_vector_batch_dev: bad argument");
+  if (cap > BOW_MAX_FEATURES) return fail(c, "bow_vector_batch_dev: cap > 1024");
+  if ((size_t)B * cap > (size_t)INT32_MAX) return fail(c, "bow_vector_batch_dev: batch too large");
+  return bow_vector_queue(c, d_feat, d_n, B, cap, d_ids, d_vals, d_nw, d_word, stream ? (hipStream_t)stream : c->stream);
+} AIRFE_CATCH(c)
+
+int airfe_bow_vector(airfe_ctx* c, const float* feat, int n, uint32_t* ids, double* vals, int* nw, uint32_t* word_of_features) try {
+  AIRFE_ENTER(c);
+  if (!c->bow_nodes) return fail(c, "bow_vector: no vocabulary loaded (airfe_bow_load)");
+  if (n < 0 || !nw || (n > 0 && (!feat || !ids || !vals))) return fail(c, "bow_vector: bad argument");
+  if (n > BOW_MAX_FEATURES) return fail(c, "bow_vector: more than 1024 features");
+  *nw = 0;
+  if (n == 0) return 0;                                          // database.cc:60
+  const size_t fb = ((size_t)n * AIRFE_FEAT_DIM * 4 + 63) / 64 * 64, ib = ((size_t)n * 4 + 63) / 64 * 64;
+  if (ensure_block(c, c->bv_stage, c->bv_stage_bytes, 128 + fb + 2 * ib + (size_t)n * 8)) return 1;
+  int* d_n = reinterpret_cast<int*>(c->bv_stage);
+  int* d_nw = d_n + 16;
+  double* d_vals = reinterpret_cast<double*>(c->bv_stage + 128);
+  float* d_feat = reinterpret_cast<float*>(c->bv_stage + 128 + (size_t)n * 8);
+  uint32_t* d_ids = reinterpret_cast<uint32_t*>(c->bv_stage + 128 + (size_t)n * 8 + fb);
+  uint32_t* d_word = d_ids + ib / 4;
+  hipStream_t st = c->stream;
+  DrainOnError drain{c, true};
+  HIPCHK(c, hipMemcpyAsync(d_n, &n, 4, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_feat, feat, (size_t)n * AIRFE_FEAT_DIM * 4, hipMemcpyHostToDevice, st));
+  if (bow_vector_queue(c, d_feat, d_n, 1, n, d_ids, d_vals, d_nw, d_word, st)) return 1;
+  int k = 0;
+  HIPCHK(c, hipMemcpyAsync(&k, d_nw, 4, hipMemcpyDeviceToHost, st));
+  if (word_of_features) HIPCHK(c, hipMemcpyAsync(word_of_features, d_word, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (k > 0) {
+    HIPCHK(c, hipMemcpyAsync(ids, d_ids, (size_t)k * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(vals, d_vals, (size_t)k * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+  }
+  drain.armed = false;
+  *nw = k;
+  return 0;
+} AIRFE_CATCH(c)
+
+int airfe_bowdb_create(airfe_ctx* c, int max_frames, int cap, int keep_features, airfe_bowdb** out) try {
+  AIRFE_ENTER(c);
+  if (!out) return fail(c, "bowdb_create: null argument");
+  *out = nullptr;
+  if (max_frames < 1 || cap < 1) return fail(c, "bowdb_create: bad argument");
+  if (cap > BOW_MAX_FEATURES) return fail(c, "bowdb_create: cap > 1024");
+  if (!c->bow_nodes) return fail(c, "bowdb_create: no vocabulary loaded (airfe_bow_load): the database is sized by its word count");
+  struct Guard { airfe_bowdb* p; ~Guard() { if (p) (void)airfe_bowdb_destroy(p); } } guard{new airfe_bowdb()};
+  airfe_bowdb* db = guard.p;
+  db->c = c; db->max_frames = max_frames; db->cap = cap; db->keep = keep_features != 0;
+  const size_t rows = (size_t)max_frames * cap;
+  HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->ids), rows * 4));
+  HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->vals), rows * 8));
+  HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->nw), (size_t)max_frames * 4));
+  if (db->keep) {
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->feat), rows * AIRFE_FEAT_DIM * 4));
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->n), (size_t)max_frames * 4));
+  }
+  guard.p = nullptr;
+  *out = db;
+  return 0;
+} AIRFE_CATCH(c)
+
+int airfe_bowdb_destroy(airfe_bowdb* db) try {
+  if (!db) return 0;
+  if (db->c) { (void)enter_device(db->c); (void)hipDeviceSynchronize(); }
+  for (void* p : {(void*)db->ids, (void*)db->vals, (void*)db->nw, (void*)db->feat, (void*)db->n, (void*)db->q_scratch, (void*)db->m_scratch})
+    if (p) (void)hipFree(p);
+  delete db;
+  return 0;
+} AIRFE_CATCH(nullptr)
+
+int airfe_bowdb_clear(airfe_bowdb* db) try {
+  if (!db) return 1;
+  db->size = 0;
+  return 0;
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_size(const airfe_bowdb* db) try {
+  return db ? db->size : -1;
+} AIRFE_CATCH(nullptr)
+
+// Database::AddFrame: frame `size + b` = vector b.  kind = hipMemcpyDeviceToDevice (asynchronous on st) or hipMemcpyHostToDevice (synchronous)
+static int bowdb_add_impl(airfe_bowdb* db, const uint32_t* ids, const double* vals, const int* nw, const float* feat, const int* n, int B, int cap,
+                          hipMemcpyKind kind, hipStream_t st, const char* who) {
+  airfe_ctx* c = db->c;
+  if (B < 1 || !ids || !vals || !nw || cap != db->cap) return fail(c, std::string(who) + ": bad argument (cap must be the database's)");
+  if (db->keep && (!feat || !n)) return fail(c, std::string(who) + ": this database keeps the frames' features: d_feat / d_n are needed");
+  if (B > db->max_frames - db->size) return fail(c, std::string(who) + ": the database is full (max_frames)");
+  const size_t at = (size_t)db->size * cap, rows = (size_t)B * cap;
+  HIPCHK(c, hipMemcpyAsync(db->ids + at, ids, rows * 4, kind, st));
+  HIPCHK(c, hipMemcpyAsync(db->vals + at, vals, rows * 8, kind, st));
+  HIPCHK(c, hipMemcpyAsync(db->nw + db->size, nw, (size_t)B * 4, kind, st));
+  if (db->keep) {
+    HIPCHK(c, hipMemcpyAsync(db->feat + at * AIRFE_FEAT_DIM, feat, rows * AIRFE_FEAT_DIM * 4, kind, st));
+    HIPCHK(c, hipMemcpyAsync(db->n + db->size, n, (size_t)B * 4, kind, st));
+  }
+  if (kind == hipMemcpyHostToDevice) HIPCHK(c, hipStreamSynchronize(st));
+  db->size += B;
+  return 0;
+}
+
+int airfe_bowdb_add_batch_dev(airfe_bowdb* db, const uint32_t* d_ids, const double* d_vals, const int* d_nw, const float* d_feat, const int* d_n, int B,
+                              int cap, void* stream) try {
+  if (!db) return 1;
+  AIRFE_ENTER(db->c);
+  return bowdb_add_impl(db, d_ids, d_vals, d_nw, d_feat, d_n, B, cap, hipMemcpyDeviceToDevice, stream ? (hipStream_t)stream : db->c->stream, "bowdb_add_batch_dev");
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_add(airfe_bowdb* db, const uint32_t* ids, const double* vals, const int* nw, const float* feat, const int* n, int B, int cap) try {
+  if (!db) return 1;
+  AIRFE_ENTER(db->c);
+  return bowdb_add_impl(db, ids, vals, nw, feat, n, B, cap, hipMemcpyHostToDevice, db->c->stream, "bowdb_add");
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_query_batch_dev(airfe_bowdb* db, const uint32_t* d_ids, const double* d_vals, const int* d_nw, int Q, int cap,
+                                const airfe_bowdb_filter* filter, int32_t* d_cand_frame, int32_t* d_cand_sharing, double* d_cand_score, int ccap,
+                                int* d_ncand, int* d_max_sharing, int32_t* d_sharing, void* stream) try {
+  if (!db) return 1;
+  airfe_ctx* c = db->c;
+  AIRFE_ENTER(c);
+  if (Q < 1 || cap < 1 || ccap < 1 || !d_ids || !d_vals || !d_nw || !filter || !d_cand_frame || !d_cand_sharing || !d_cand_score || !d_ncand || !d_max_sharing)
+    return fail(c, "bowdb_query_batch_dev: bad argument");
+  if (cap > BOW_MAX_FEATURES) return fail(c, "bowdb_query_batch_dev: cap > 1024");
+  if (filter->d_exclude && filter->exclude_words < 1) return fail(c, "bowdb_query_batch_dev: d_exclude needs exclude_words");
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  const int N = db->size;
+  const size_t cells = (size_t)Q * std::max(N, 1);
+  if (bowdb_scratch(db, db->q_scratch, db->q_bytes, db->q_stream, cells * 12, st)) return 1;
+  BowQueryArgs a;
+  a.db_ids = db->ids; a.db_vals = db->vals; a.db_nw = db->nw; a.N = N; a.cap = db->cap;
+  a.q_ids = d_ids; a.q_vals = d_vals; a.q_nw = d_nw; a.qcap = cap; a.n_words = c->bow_nwords;
+  a.frames_per_wg = (size_t)Q * N >= (size_t)64 * 1024 ? 64 : 16;     // (how the frames are sliced changes no result)
+  a.score = reinterpret_cast<double*>(db->q_scratch);
+  a.sharing = d_sharing ? d_sharing : reinterpret_cast<int*>(db->q_scratch + cells * 8);
+  ProfScope ps(c, ST_BOW, st, 0, (double)Q * N * db->cap * 12);
+  if (launch_bowdb_query(a, Q, st)) return fail(c, "bowdb_query_batch_dev: the query table does not fit the workgroup's LDS");
+  BowSelectArgs s;
+  s.sharing = a.sharing; s.score = a.score; s.N = N; s.ratio = filter->ratio; s.min_words = filter->min_words;
+  s.max_index = filter->d_max_index; s.exclude = filter->d_exclude; s.exclude_words = filter->exclude_words;
+  s.cand_frame = d_cand_frame; s.cand_sharing = d_cand_sharing; s.cand_score = d_cand_score; s.ccap = ccap; s.ncand = d_ncand; s.max_sharing = d_max_sharing;
+  launch_bowdb_select(s, Q, st);
+  note_launch(c, ST_BOW);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_topk_dev(airfe_bowdb* db, const int32_t* d_cand_frame, const double* d_cand_score, const int* d_ncand, int Q, int ccap, int K,
+                         int32_t* d_top, double* d_top_score, void* stream) try {
+  if (!db) return 1;
+  airfe_ctx* c = db->c;
+  AIRFE_ENTER(c);
+  if (Q < 1 || ccap < 1 || K < 1 || K > 8 || !d_cand_frame || !d_cand_score || !d_ncand || !d_top) return fail(c, "bowdb_topk_dev: bad argument (K = 1..8)");
+  BowTopkArgs a;
+  a.cand_frame = d_cand_frame; a.cand_score = d_cand_score; a.ncand = d_ncand; a.ccap = ccap; a.K = K; a.top = d_top; a.top_score = d_top_score;
+  launch_bowdb_topk(a, Q, stream ? (hipStream_t)stream : c->stream);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_match_candidates_batch_dev(airfe_ctx* c, airfe_bowdb* db, const float* d_qfeat, const int* d_qn, int Q, int cap, const int32_t* d_cand, int K,
+                                           int outlier_rejection, int32_t* d_best, int32_t* d_idx, float* d_score, int mcap, int* d_nmatch,
+                                           int* d_nmatch_all, void* stream) try {
+  AIRFE_ENTER(c);
+  if (!db || db->c != c) return fail(c, "bowdb_match_candidates_batch_dev: the database belongs to another context");
+  if (Q < 1 || K < 1 || K > 5 || mcap < 1 || !d_qfeat || !d_qn || !d_cand || !d_best || !d_idx || !d_score || !d_nmatch)
+    return fail(c, "bowdb_match_candidates_batch_dev: bad argument (K = 1..5)");
+  if (!db->keep) return fail(c, "bowdb_match_candidates_batch_dev: the database was created without keep_features");
+  if (cap != db->cap) return fail(c, "bowdb_match_candidates_batch_dev: cap must be the database's");
+  if (mcap > FR_MAX_MATCHES) return fail(c, "bowdb_match_candidates_batch_dev: mcap > 1024");
+  if ((long long)Q * K > c->Pmax) return fail(c, "bowdb_match_candidates_batch_dev: Q * K pairs exceed cfg.max_batch");
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  const int P = Q * K;
+  const size_t fb = (size_t)P * cap * AIRFE_FEAT_DIM * 4, cb = ((size_t)P * 4 + 255) / 256 * 256, ib = (size_t)P * mcap * 8, sb = (size_t)P * mcap * 4;
+  if (bowdb_scratch(db, db->m_scratch, db->m_bytes, db->m_stream, 2 * fb + 3 * cb + ib + sb, st)) return 1;
+  uint8_t* q = db->m_scratch;
+  BowGatherArgs g;
+  g.f0 = reinterpret_cast<float*>(q); q += fb;
+  g.f1 = reinterpret_cast<float*>(q); q += fb;
+  int32_t* p_idx = reinterpret_cast<int32_t*>(q); q += ib;
+  float* p_score = reinterpret_cast<float*>(q); q += sb;
+  g.n0 = reinterpret_cast<int*>(q); q += cb;
+  g.n1 = reinterpret_cast<int*>(q); q += cb;
+  int* p_nm = reinterpret_cast<int*>(q);
+  g.qfeat = d_qfeat; g.qn = d_qn; g.db_feat = db->feat; g.db_n = db->n; g.N = db->size; g.cap = cap; g.cand = d_cand; g.K = K;
+  launch_bowdb_gather(g, P, st);
+  HIPCHK(c, hipGetLastError());
+  // MatchingPoints(query_features, good_candidate_features, matches, true) (map_user.cc:369): the context's own entries, called
+  if (lightglue_dev(c, g.f0, g.n0, g.f1, g.n1, P, cap, AIRFE_FEAT_DIM, 1, 1, p_idx, p_score, mcap, p_nm, nullptr, st)) return 1;
+  if (outlier_rejection && fransac_queue(c, g.f0, g.f1, P, cap, p_idx, p_score, mcap, p_nm, nullptr, st)) return 1;
+  BowBestArgs b;
+  b.cand = d_cand; b.K = K; b.N = db->size; b.mcap = mcap; b.idx_all = p_idx; b.score_all = p_score; b.nmatch_all = p_nm;
+  b.best = d_best; b.idx = d_idx; b.score = d_score; b.nmatch = d_nmatch; b.out_nmatch_all = d_nmatch_all;
+  launch_bowdb_best(b, Q, st);
+  HIPCHK(c, hipGetLastError());
+  return 0;
 } AIRFE_CATCH(c)
 
 }  // extern "C"

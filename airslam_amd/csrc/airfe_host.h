@@ -169,6 +169,10 @@ struct airfe_ctx {
   int *bow_first = nullptr, *bow_nch = nullptr, *bow_word = nullptr;
   unsigned* bow_out = nullptr;
   int bow_nodes = 0;
+  double* bow_weight_d = nullptr;     // the same weights on the device: the BoW vector's sums are double (airfe_bow_vector_batch_dev)
+  int bow_nwords = 0;                 // 1 + the largest word id
+  uint8_t* bv_scratch = nullptr; size_t bv_scratch_bytes = 0; hipStream_t bv_scratch_stream = nullptr;   // airfe_bow_vector_batch_dev: word / weight / node per feature
+  uint8_t* bv_stage = nullptr; size_t bv_stage_bytes = 0;                                                // airfe_bow_vector: the host entry's device block
   // rectification maps of Camera (camera.cc:60-75), one pair per side, and the rectified-image staging
   float* rmap[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
   int rmap_h[2] = {0, 0}, rmap_w[2] = {0, 0};

@@ -404,4 +404,50 @@ struct PoseoptGatherArgs {                      // the composite's glue: seed + 
 };
 void launch_poseopt_gather(const PoseoptGatherArgs& g, int B, hipStream_t st);
 
+// BoW keyframe database (src/bow/database.cc:57-124 + the callers' filters; kernels_bowdb.hip; contract: include/airfe.h)
+#define BOW_MAX_FEATURES 1024         // features per frame = entries per BoW vector the kernels hold in LDS (max_keypoints <= 1024)
+struct BowVecArgs {                             // the end of Database::FrameToBow on launch_bow_transform's per-feature outputs
+  const unsigned* word = nullptr;               // [B][cap] word per feature (UINT_MAX: stopped)
+  const int* node = nullptr;                    // [B][cap] leaf node per feature
+  const int* n = nullptr;                       // [B] features
+  int cap = 0;                                  // <= BOW_MAX_FEATURES
+  const double* weight = nullptr;               // [n_nodes] the vocabulary's WordValue weights
+  unsigned* ids = nullptr; double* vals = nullptr; int* nw = nullptr;       // [B][cap], [B][cap], [B]
+};
+void launch_bow_vector(const BowVecArgs& a, int B, hipStream_t st);
+struct BowQueryArgs {
+  const unsigned* db_ids = nullptr; const double* db_vals = nullptr; const int* db_nw = nullptr; int N = 0, cap = 0;      // [N][cap], [N][cap], [N]
+  const unsigned* q_ids = nullptr; const double* q_vals = nullptr; const int* q_nw = nullptr; int qcap = 0;               // [Q][qcap] (qcap <= BOW_MAX_FEATURES)
+  int n_words = 0, frames_per_wg = 64;
+  int* sharing = nullptr; double* score = nullptr;                                                                        // [Q][N]
+};
+int launch_bowdb_query(const BowQueryArgs& a, int Q, hipStream_t st);
+struct BowSelectArgs {
+  const int* sharing = nullptr; const double* score = nullptr; int N = 0;
+  float ratio = 0.3f; int min_words = 8;
+  const int* max_index = nullptr;               // [Q] or nullptr
+  const unsigned* exclude = nullptr; int exclude_words = 0;                  // [Q][exclude_words] bit rows or nullptr
+  int32_t *cand_frame = nullptr, *cand_sharing = nullptr; double* cand_score = nullptr; int ccap = 0;                     // [Q][ccap]
+  int *ncand = nullptr, *max_sharing = nullptr;                                                                           // [Q]
+};
+void launch_bowdb_select(const BowSelectArgs& a, int Q, hipStream_t st);
+struct BowTopkArgs {
+  const int32_t* cand_frame = nullptr; const double* cand_score = nullptr; const int* ncand = nullptr; int ccap = 0, K = 0;
+  int32_t* top = nullptr; double* top_score = nullptr;                       // [Q][K], [Q][K] or nullptr
+};
+void launch_bowdb_topk(const BowTopkArgs& a, int Q, hipStream_t st);
+struct BowGatherArgs {
+  const float* qfeat = nullptr; const int* qn = nullptr;                     // [Q][cap][259], [Q]
+  const float* db_feat = nullptr; const int* db_n = nullptr; int N = 0, cap = 0;
+  const int32_t* cand = nullptr; int K = 0;                                  // [Q][K]
+  float *f0 = nullptr, *f1 = nullptr; int *n0 = nullptr, *n1 = nullptr;      // [Q K][cap][259] x 2, [Q K] x 2
+};
+void launch_bowdb_gather(const BowGatherArgs& a, int pairs, hipStream_t st);
+struct BowBestArgs {
+  const int32_t* cand = nullptr; int K = 0, N = 0, mcap = 0;
+  const int32_t* idx_all = nullptr; const float* score_all = nullptr; const int* nmatch_all = nullptr;                    // the pair batch's lists
+  int32_t* best = nullptr; int32_t* idx = nullptr; float* score = nullptr; int* nmatch = nullptr; int* out_nmatch_all = nullptr;
+};
+void launch_bowdb_best(const BowBestArgs& a, int Q, hipStream_t st);
+
 }  // namespace airfe

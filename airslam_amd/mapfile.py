@@ -102,10 +102,17 @@ def scan_boost_archive(buf: bytes, max_cols: int = 4096) -> List[Tuple[int, np.n
     return out
 
 
-def loop_closure_pairs(n_frames: int, n_candidates: int = 5, stride: int = 7) -> List[Tuple[int, int]]:
+def loop_closure_pairs(n_frames: int, n_candidates: int = 5, stride: int = 7, candidates=None) -> List[Tuple[int, int]]:
     """The matcher workload of loop closure (map_refiner.cc:213-230): every query frame against its GoodCandidateNum <= 5
-    best group candidates.  Candidates here are a fixed pseudo-random choice of other frames (the BoW ranking is not on this path)."""
+    best group candidates.  Candidates here are a fixed pseudo-random choice of other frames (the BoW ranking is not on this path) — unless
+    `candidates` is given: per query frame a sequence of frame indices in ranking order, -1 = none (one row of api.BowDatabase.topk_dev's output,
+    copied to the host); the first n_candidates valid ones other than the query itself are taken."""
     pairs = []
+    if candidates is not None:
+        for q in range(n_frames):
+            row = [int(c) for c in candidates[q] if 0 <= int(c) < n_frames and int(c) != q]
+            pairs += [(q, c) for c in row[:n_candidates]]
+        return pairs
     for q in range(n_frames):
         for k in range(min(n_candidates, n_frames - 1)):
             c = (q + 1 + k * stride) % n_frames

@@ -412,9 +412,86 @@ int airfe_bow_load(airfe_ctx* ctx, const float* node_desc, const int32_t* first_
                    const double* weight, int n_nodes);
 /* ≙ the loop of Database::FrameToBow (src/bow/database.cc:66-84): TemplatedVocabulary::transform(feature, id, w) (…Vocabulary.h:1313-1352)
  *   for each of the N feature rows [N][259]: word_of_features[i] = leaf word id, or UINT_MAX where the leaf weight is <= 0;
- *   weight_of_features[i] = w (may be NULL).  bow_vector.addWeight / normalize and word_features (std::map work) stay reference code. */
+ *   weight_of_features[i] = w (may be NULL).  bow_vector.addWeight / normalize: airfe_bow_vector below; word_features (std::map work) stays reference code. */
 int airfe_bow_transform(airfe_ctx* ctx, const float* feat, int N, uint32_t* word_of_features, double* weight_of_features);
 int airfe_bow_transform_dev(airfe_ctx* ctx, const float* d_feat, int N, uint32_t* d_word, float* d_weight, void* stream);
+
+/* ---- BoW keyframe database: the link in front of the matcher in MapUser::Relocalization (src/map_user.cc:106-390) and MapRefiner::LoopDetection
+ * (src/map_refiner.cc:95-235) ---------------------------------------------------------------------------------------------------------------------------
+ *   Detect -> Database::FrameToBow -> Database::Query -> sharing-word filter -> Database::Score (L1) -> grouping -> top 3 / 5 candidates
+ *          -> MatchingPoints(query, candidate, matches, true) per candidate -> the candidate with the most matches -> SolvePnPWithCV
+ * RESTATED here, on the device, bit for bit (DBoW2 compiled unchanged is the test's reference for the vector; tests/bowdb_ref.py restates the rest):
+ * FrameToBow to its end, AddFrame, Query, the two callers' filters, L1Scoring::score, the best-candidate rule.  NOT restated: the GROUPING between
+ * the scores and the candidates (map_user.cc:177-264, map_refiner.cc:132-211) walks the map's covisibility graph and, for relocalisation, the junction
+ * "sentences" — map state this library does not hold.  It stays the caller's: the candidate list below IS the reference's frame_scores map, and the
+ * composite takes its candidates from the caller.  airfe_bowdb_topk_dev is the PROJECT'S OWN ranking for callers without a covisibility graph, not the
+ * reference's grouping.  Every floating-point sum is sequential in the order given; no fused multiply-adds.
+ *   vector   Database::FrameToBow (src/bow/database.cc:57-89): per feature the descent of airfe_bow_transform (the same kernel); a feature counts iff its
+ *            word's weight is > 0 (word_of_features = UINT_MAX otherwise).  The weights are the vocabulary's doubles (WordValue).  BowVector::addWeight:
+ *            one entry per distinct word, its weights added in ascending feature index, in double.  BowVector::normalize(L1): tot = the sum of |v| in
+ *            ascending word id, from +0; every v / tot (a division).  Output in ascending word id, nw entries; rows beyond nw are not written; a frame
+ *            whose every word is stopped, or with no feature, gives nw = 0.
+ *   add      Database::AddFrame (:98-106): a frame's handle is its insertion index (0, 1, ...), which the caller maps to its FramePtr.
+ *   sharing  sharing[q][f] = the number of words present in both vectors = what Database::Query (:108-120) leaves in frame_sharing_words[f]
+ *            (a frame with 0 is absent from that map and never a candidate).
+ *   filter   max_sharing[q] over ALL frames, before any other test (map_user.cc:142-145, map_refiner.cc:104-107);
+ *            thr = max((int)(max_sharing * ratio), min_words) with the product in float32, truncated (ratio 0.3f at map_user.cc:146, 0.5f at
+ *            map_refiner.cc:108; min_words 8).  Frame f is a candidate iff sharing >= thr and (d_max_index == NULL or f < d_max_index[q]:
+ *            map_refiner.cc:115's GetFrameId() >= frame_id) and (d_exclude == NULL or bit f of row q clear: the covisible frames of :115, a bit row of
+ *            exclude_words 32-bit words per query supplied by the caller; frames past the row are not excluded).
+ *   score    L1Scoring::score(v1 = the FRAME's vector, v2 = the QUERY's) as map_user.cc:165 passes them (3rdparty/DBoW2/src/ScoringObject.cpp:23-68):
+ *            s = +0; over the common words in ascending word id s += (fabs(v1 - v2) - fabs(v1)) - fabs(v2); score = -s / 2.0 (so two vectors without a
+ *            common word score -0.0).  The argument order matters to the last bit.
+ *   output   per query the candidates in ascending frame index — frame, sharing, score — up to ccap; d_ncand[q] = the full count (may exceed ccap:
+ *            the first ccap are written, entries past the count are not written); d_max_sharing[q].
+ *   best     map_user.cc:360-376 / map_refiner.cc:213-230: the candidates in the GIVEN order, each through MatchingPoints(query, candidate, ...,
+ *            outlier_rejection); a candidate replaces the best only with a STRICTLY longer list, starting from an empty one: the first of equals
+ *            wins, a candidate with 0 matches never does.
+ * A database belongs to one context (its stream rules apply) and must be destroyed before it.  Capacity errors are return codes. */
+typedef struct airfe_bowdb airfe_bowdb;
+typedef struct airfe_bowdb_filter {
+  float ratio;                  /* 0.3f relocalisation, 0.5f loop detection */
+  int min_words;                /* 8 */
+  const int* d_max_index;       /* DEVICE [Q] or NULL */
+  const uint32_t* d_exclude;    /* DEVICE [Q][exclude_words] bit rows (bit f & 31 of word f >> 5) or NULL */
+  int exclude_words;
+} airfe_bowdb_filter;
+/* ONE frame through host buffers: feat [n][259] (n <= 1024); ids / vals [>= n]; *nw; word_of_features [n] or NULL. */
+int airfe_bow_vector(airfe_ctx* ctx, const float* feat, int n, uint32_t* ids, double* vals, int* nw, uint32_t* word_of_features);
+/* B device frames, asynchronous on `stream`: d_feat [B][cap][259], d_n [B] (clamped to 0..cap), cap <= 1024; d_ids u32 [B][cap], d_vals f64 [B][cap],
+ * d_nw [B]; d_word u32 [B][cap] or NULL = word_of_features (only a frame's first n entries mean anything).  A frame's bytes do not depend on B or on
+ * its position in the batch. */
+int airfe_bow_vector_batch_dev(airfe_ctx* ctx, const float* d_feat, const int* d_n, int B, int cap, uint32_t* d_ids, double* d_vals, int* d_nw,
+                               uint32_t* d_word, void* stream);
+/* storage: fixed-stride rows [max_frames][cap] of ids / values (+ [max_frames][cap][259] feature rows and counts with keep_features, which the
+ * composite needs).  Needs a loaded vocabulary (its word count sizes the query table). */
+int airfe_bowdb_create(airfe_ctx* ctx, int max_frames, int cap, int keep_features, airfe_bowdb** out);
+int airfe_bowdb_destroy(airfe_bowdb* db);
+int airfe_bowdb_clear(airfe_bowdb* db);             /* size = 0; a query already queued must have completed */
+int airfe_bowdb_size(const airfe_bowdb* db);        /* frames added; -1 for NULL */
+/* B vectors (airfe_bow_vector_batch_dev's outputs, same cap as the database) become frames size .. size + B - 1; d_feat / d_n (the frames' rows and
+ * counts) are needed iff keep_features.  Asynchronous on `stream`; a full database is an error and adds nothing. */
+int airfe_bowdb_add_batch_dev(airfe_bowdb* db, const uint32_t* d_ids, const double* d_vals, const int* d_nw, const float* d_feat, const int* d_n, int B,
+                              int cap, void* stream);
+int airfe_bowdb_add(airfe_bowdb* db, const uint32_t* ids, const double* vals, const int* nw, const float* feat, const int* n, int B, int cap);   /* host buffers */
+/* Q query vectors [Q][cap] against all N = size frames, asynchronous on `stream`, no host synchronisation.  d_cand_frame / d_cand_sharing i32
+ * [Q][ccap], d_cand_score f64 [Q][ccap], d_ncand [Q], d_max_sharing [Q]; d_sharing i32 [Q][N] or NULL (the dense counts, for tests). */
+int airfe_bowdb_query_batch_dev(airfe_bowdb* db, const uint32_t* d_ids, const double* d_vals, const int* d_nw, int Q, int cap,
+                                const airfe_bowdb_filter* filter, int32_t* d_cand_frame, int32_t* d_cand_sharing, double* d_cand_score, int ccap,
+                                int* d_ncand, int* d_max_sharing, int32_t* d_sharing, void* stream);
+/* the project's own ranking (NOT the reference's grouping): per query the K <= 8 candidates (of the first min(ncand, ccap)) by descending score, ties
+ * to the lower frame index; d_top i32 [Q][K] padded with -1, d_top_score f64 [Q][K] or NULL (0 where padded). */
+int airfe_bowdb_topk_dev(airfe_bowdb* db, const int32_t* d_cand_frame, const double* d_cand_score, const int* d_ncand, int Q, int ccap, int K,
+                         int32_t* d_top, double* d_top_score, void* stream);
+/* "best" above for Q queries x K <= 5 candidates (d_cand i32 [Q][K], -1 or an index past the database = a hole, skipped), on the kept feature rows:
+ * the rows are gathered into a [Q K] pair batch, airfe_match_lightglue_batch_dev's code runs on it and, with outlier_rejection,
+ * airfe_fundamental_ransac_batch_dev's.  d_qfeat [Q][cap][259] (cap = the database's), d_qn [Q]; d_best [Q] (frame index or -1), the winner's list
+ * d_idx [Q][mcap][2] = (query index, candidate index) / d_score [Q][mcap] / d_nmatch [Q] (0 without a winner; entries past the count are not written),
+ * d_nmatch_all [Q][K] or NULL (0 for holes).  Q * K above cfg.max_batch is an error.  PnP and the refinement stay calls of the entries above: they
+ * need the candidate's map points, which the caller holds. */
+int airfe_bowdb_match_candidates_batch_dev(airfe_ctx* ctx, airfe_bowdb* db, const float* d_qfeat, const int* d_qn, int Q, int cap, const int32_t* d_cand,
+                                           int K, int outlier_rejection, int32_t* d_best, int32_t* d_idx, float* d_score, int mcap, int* d_nmatch,
+                                           int* d_nmatch_all, void* stream);
 
 /* ---- the step BEFORE the path: rectification ------------------------------------------------------- */
 /* ≙ the maps Camera's constructor builds with cv::initUndistortRectifyMap (src/camera.cc:60-75; _mapl1/_mapl2 = side 0, _mapr1/_mapr2 =
