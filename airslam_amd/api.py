@@ -402,6 +402,24 @@ class Context:
                                                 m1.ctypes.data), "airfe_debug_sg_decode")
         return i0, i1, m0, m1
 
+    def debug_sg_sinkhorn(self, sim_list, alpha: float, iters: int, form: int = 0):
+        """launch_sg_sinkhorn alone on a batch of host coupling matrices [n0, n1] (each its own shape) -> ([Z [n0+1, n1+1], ...], form_ran).
+        form: 0 the launcher's dispatch, 1 the per-half-iteration kernels, 2 the register-resident kernel (AirfeError where it does not apply);
+        form_ran: 1 per-half-iteration, 2 / 3 the register-resident instantiations <13, 7> / <9, 17>."""
+        sims = [np.asarray(s, dtype=np.float32) for s in sim_list]
+        b = len(sims)
+        ld = max(max(s.shape) for s in sims)
+        buf = np.full((b, ld, ld), np.nan, np.float32)
+        lens = np.empty((b, 2), np.int32)
+        for i, s in enumerate(sims):
+            buf[i, :s.shape[0], :s.shape[1]] = s
+            lens[i] = s.shape
+        z = np.full((b, ld + 1, ld + 1), np.nan, np.float32)
+        ran = C.c_int(0)
+        self._chk(self._l.airfe_debug_sg_sinkhorn(self._h, buf.ctypes.data, lens.ctypes.data, b, ld, float(alpha), int(iters), int(form), z.ctypes.data,
+                                                  C.byref(ran)), "airfe_debug_sg_sinkhorn")
+        return [z[i, :s.shape[0] + 1, :s.shape[1] + 1].copy() for i, s in enumerate(sims)], ran.value
+
     def detector_maps(self, b: int = 1):
         heat = np.empty((b, 512, 512), np.float32)
         nms = np.empty((b, 512, 512), np.float32)

@@ -1784,6 +1784,39 @@ int airfe_debug_sg_decode(airfe_ctx* c, const float* Z, int n0, int n1, int32_t*
   return 0;
 } AIRFE_CATCH(c)
 
+/* launch_sg_sinkhorn alone on B HOST coupling matrices (include/airfe_debug.h).  Everything of the arena outside each pair's valid n0 x n1 block is NaN when
+   the launch starts, and so is the output: a finite Z [0..n0][0..n1] was written in full and came from inside `lens` alone. */
+int airfe_debug_sg_sinkhorn(airfe_ctx* c, const float* sim, const int* lens, int B, int ld, float alpha, int iters, int form, float* Z, int* form_ran) try {
+  if (c && enter_device(c)) return 1;
+  if (!c || !c->has_sg) return fail(c, "debug_sg_sinkhorn: SuperGlue not loaded");
+  if (!sim || !lens || !Z || !form_ran || B < 1 || B > c->Pmax || ld < 1 || iters < 0 || form < 0 || form > 2)
+    return fail(c, "debug_sg_sinkhorn: bad argument (1 <= B <= max_batch, iters >= 0, form 0 / 1 / 2)");
+  const int nmax = std::min(ld, c->cfg.max_keypoints);
+  for (int i = 0; i < 2 * B; ++i)
+    if (lens[i] < 1 || lens[i] > nmax) return fail(c, "debug_sg_sinkhorn: every n0, n1 must lie in 1 .. min(ld, max_keypoints)");
+  *form_ran = 0;
+  const int Np = c->Np, Lz = c->Lz;
+  const size_t blk = (size_t)Np * Np, zblk = (size_t)Lz * Lz;
+  HIPCHK(c, hipMemcpyAsync(c->lens, lens, (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->simbuf, 0xFF, (size_t)B * blk * 4, c->stream));          // 0xFFFFFFFF: a NaN
+  HIPCHK(c, hipMemsetAsync(c->sg_Z, 0xFF, (size_t)B * zblk * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->sg_xch, 0xFF, (size_t)B * Lz * 64 * 4, c->stream));      // [B][2][16][Lz] float2: a partial read before it was written is a NaN
+  for (int b = 0; b < B; ++b)
+    HIPCHK(c, hipMemcpy2DAsync(c->simbuf + b * blk, (size_t)Np * 4, sim + (size_t)b * ld * ld, (size_t)ld * 4, (size_t)lens[2 * b + 1] * 4, lens[2 * b],
+                               hipMemcpyHostToDevice, c->stream));
+  launch_sg_sinkhorn(c->simbuf, c->lens, B, Np, Lz, alpha, iters, c->sg_u, c->sg_v, c->sg_Z, c->sg_cnt, c->sg_cnt + (size_t)c->Pmax * 16, c->sg_xch, c->stream,
+                     form, form_ran);
+  if (*form_ran == 0)
+    return fail(c, "debug_sg_sinkhorn: form 2 asked for, but no register-resident instantiation applies to this context (max_keypoints, B against the co-resident "
+                   "workgroups) or the cooperative launch was refused");
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (launch_status(c) || sinkhorn_failed(c)) return 1;
+  for (int b = 0; b < B; ++b)
+    HIPCHK(c, hipMemcpy2D(Z + (size_t)b * (ld + 1) * (ld + 1), (size_t)(ld + 1) * 4, c->sg_Z + b * zblk, (size_t)Lz * 4, (size_t)(lens[2 * b + 1] + 1) * 4,
+                          lens[2 * b] + 1, hipMemcpyDeviceToHost));
+  return 0;
+} AIRFE_CATCH(c)
+
 /* SuperGlue on B pairs of DEVICE feature matrices (259-float rows, original pixel coordinates; NormalizeKeypoints with scale 0.7 on
    the device): d_idx0 / d_idx1 [B][cap] (-1 = unmatched), d_ms0 / d_ms1 [B][cap] floats.  No reference counterpart (batch-1 there). */
 int airfe_match_superglue_batch_dev(airfe_ctx* c, const float* d_f0, const int* d_n0, const float* d_f1, const int* d_n1, int B, int cap,

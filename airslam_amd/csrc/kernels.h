@@ -287,7 +287,7 @@ void launch_sg_prepare(int prec, const float* f0, const float* f1, const int* n0
 // xch: B * 64 * Lz floats of scratch (the register-resident kernel's per-iteration exchange of column partials); nullptr = streaming kernels only
 void launch_sg_sinkhorn(const float* sim, const int* lens, int B, int Np, int Lz, float alpha, int iters, float* u, float* v,
                         float* Z, unsigned* counters /*B x 16 words*/, unsigned* fail_flag /*raised on a rendezvous time-out*/, float* xch,
-                        hipStream_t st);
+                        hipStream_t st, int form = 0 /*test hook: 1 per-half-iteration, 2 register-resident or nothing*/, int* form_ran = nullptr);
 void launch_sg_decode(const float* Z, const int* lens, int B, int Np, int Lz, float thr, int* idx0, float* max0, int* idx1,
                       int32_t* out0, int32_t* out1, float* ms0, float* ms1, hipStream_t st);
 

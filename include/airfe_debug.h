@@ -19,6 +19,16 @@ int airfe_debug_lightglue_scores(airfe_ctx* ctx, const float* f0, int n0, const 
  *   filter_matches (src/light_glue.cpp:214-266) on scores [n0][n1]; decode (src/super_glue.cpp:339-367) on Z [n0+1][n1+1] */
 int airfe_debug_lg_filter(airfe_ctx* ctx, const float* scores, int n0, int n1, int32_t* idx, float* score, int cap, int* nmatch);
 int airfe_debug_sg_decode(airfe_ctx* ctx, const float* Z, int n0, int n1, int32_t* idx0, int32_t* idx1, double* ms0, double* ms1);
+/* the Sinkhorn launcher alone (launch_sg_sinkhorn: the optimal-transport tail of SuperGlue) on B HOST coupling matrices, one form at a time
+ * (tests/test_gpu_sinkhorn.py).  Pair b's couplings sim[b][0..n0)[0..n1) go into the matcher's similarity buffer at its own stride; the REST of every pair's block,
+ * the output buffer and the partial-exchange buffer are NaN when the launch starts, so a finite Z proves that no form read outside `lens` and that every
+ * element was written.  alpha (the dustbin score) and iters come from the call, not from the context.  form: 0 = the launcher's own dispatch (what production
+ * runs), 1 = the per-half-iteration kernels, 2 = the register-resident cooperative kernel — an ERROR where no instantiation applies or the cooperative launch is
+ * refused, never a fall-back.  *form_ran: 1 = per-half-iteration, 2 = sg_sinkhorn_reg_kernel<13, 7>, 3 = sg_sinkhorn_reg_kernel<9, 17>.  B <= max_batch,
+ * 1 <= n0, n1 <= min(ld, max_keypoints).  Z[b] holds rows 0..n0, cols 0..n1 (row stride ld + 1); the rest of Z is not touched.  Reports a rendezvous
+ * time-out like the host entries do. */
+int airfe_debug_sg_sinkhorn(airfe_ctx* ctx, const float* sim, const int* lens /*[2B]: n0,n1 per pair*/, int B, int ld /*row stride and rows per pair of sim*/,
+                            float alpha, int iters, int form /*0 auto, 1 per-half-iteration, 2 register-resident*/, float* Z /*[B][ld+1][ld+1]*/, int* form_ran);
 /* kernel-level checks on HOST fp32 tensors (test only): NCHW conv3x3(+ReLU, optional 2x2 max-pool) and
  *   y[M][N] = x[M][K] w[N][K]^T + b through the same MFMA kernels the pipelines use. */
 /* SuperGlue on one HOST pair ([n][259] rows, normalised x,y): the engine's `scores` output [n0+1][n1+1] */
