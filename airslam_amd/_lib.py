@@ -39,6 +39,12 @@ class BowdbFilter(C.Structure):
     _fields_ = [("ratio", C.c_float), ("min_words", C.c_int), ("d_max_index", C.c_void_p), ("d_exclude", C.c_void_p), ("exclude_words", C.c_int)]
 
 
+class RelocCfg(C.Structure):
+    """airfe_reloc_cfg (include/airfe.h)"""
+    _fields_ = [("ratio", C.c_float), ("min_words", C.c_int), ("K", C.c_int), ("outlier_rejection", C.c_int), ("min_inlier", C.c_int),
+                ("pose_refinement", C.c_int), ("cam", C.c_double * 5), ("thr", C.c_double * 2)]
+
+
 class SeqPolicy(C.Structure):
     """airfe_seq_policy (include/airfe_seq.h)"""
     _fields_ = [("min_init_stereo_feature", C.c_int), ("min_num_match", C.c_int), ("max_num_match", C.c_int), ("tracking_point_rate", C.c_float),
@@ -133,6 +139,16 @@ SIGNATURES = {
     "airfe_bowdb_query_batch_dev": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.POINTER(BowdbFilter)] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4),
     "airfe_bowdb_topk_dev": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "airfe_bowdb_match_candidates_batch_dev": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3),
+    "airfe_bowdb_attach_map": (C.c_int, [C.c_void_p, C.c_int]),
+    "airfe_bowdb_set_points_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "airfe_bowdb_set_points": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "airfe_bowdb_get_points": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "airfe_bowdb_set_covisibility": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "airfe_bowdb_get_covisibility": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "airfe_bowdb_set_positions": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "airfe_bowdb_group_dev": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p] * 8),
+    "airfe_relocalize_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RelocCfg), C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9 +
+                                   [C.c_int] + [C.c_void_p] * 3),
     "airfe_set_rectify_maps": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "airfe_rectify_detect_points": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                               C.POINTER(C.c_int)]),

@@ -954,6 +954,70 @@ class BowDatabase:
             1 if outlier_rejection else 0, best_t.data_ptr(), idx_t.data_ptr(), score_t.data_ptr(), idx_t.shape[1], nmatch_t.data_ptr(),
             nmatch_all_t.data_ptr() if nmatch_all_t is not None else None, self._ctx._stream(stream)), "airfe_bowdb_match_candidates_batch_dev")
 
+    # ---- map state, the grouping and the relocalisation composite (include/airfe.h "Map state in the database", "Grouping", "Relocalisation composite")
+    def attach_map(self, max_edges: int):
+        """map points [max_frames][cap][3] (NaN = none), a covisibility table of up to max_edges entries and keyframe positions; needs keep_features"""
+        self._ctx._chk(self._l.airfe_bowdb_attach_map(self._h, int(max_edges)), "airfe_bowdb_attach_map")
+
+    def set_points(self, first_frame: int, xyz: np.ndarray):
+        """host buffer xyz [B][cap][3] float64 (world frame; NaN where the row has no valid map point) -> frames first_frame .. first_frame + B - 1"""
+        xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1, self.cap, 3)
+        self._ctx._chk(self._l.airfe_bowdb_set_points(self._h, int(first_frame), xyz.shape[0], xyz.ctypes.data), "airfe_bowdb_set_points")
+
+    def set_points_dev(self, first_frame: int, xyz_t, stream=None):
+        self._ctx._chk(self._l.airfe_bowdb_set_points_dev(self._h, int(first_frame), xyz_t.shape[0], xyz_t.data_ptr(), self._ctx._stream(stream)),
+                       "airfe_bowdb_set_points_dev")
+
+    def get_points(self, first_frame: int, B: int) -> np.ndarray:
+        xyz = np.empty((B, self.cap, 3), np.float64)
+        self._ctx._chk(self._l.airfe_bowdb_get_points(self._h, int(first_frame), B, xyz.ctypes.data), "airfe_bowdb_get_points")
+        return xyz
+
+    def set_covisibility(self, row_ptr: np.ndarray, nbr: np.ndarray, weight: np.ndarray):
+        """replaces the whole graph: CSR over len(row_ptr) - 1 frames, every row strictly ascending in nbr, the frames' own entries included as the map has them"""
+        row_ptr = np.ascontiguousarray(row_ptr, np.int32); nbr = np.ascontiguousarray(nbr, np.int32); weight = np.ascontiguousarray(weight, np.int32)
+        if len(row_ptr) < 1 or len(nbr) != len(weight) or (len(nbr) and int(row_ptr[-1]) > len(nbr)):
+            raise AirfeError("set_covisibility: row_ptr / nbr / weight do not describe one CSR table")
+        self._ctx._chk(self._l.airfe_bowdb_set_covisibility(self._h, row_ptr.ctypes.data, nbr.ctypes.data if len(nbr) else None,
+                                                            weight.ctypes.data if len(nbr) else None, len(row_ptr) - 1), "airfe_bowdb_set_covisibility")
+
+    def get_covisibility(self, edge_cap: int):
+        """-> (row_ptr [max_frames + 1], nbr [E], weight [E]) as the device holds them"""
+        row_ptr = np.zeros(self.max_frames + 1, np.int32); nbr = np.zeros(max(edge_cap, 1), np.int32); weight = np.zeros(max(edge_cap, 1), np.int32)
+        e = C.c_int(0)
+        self._ctx._chk(self._l.airfe_bowdb_get_covisibility(self._h, row_ptr.ctypes.data, nbr.ctypes.data, weight.ctypes.data, int(edge_cap), C.byref(e)),
+                       "airfe_bowdb_get_covisibility")
+        return row_ptr, nbr[:e.value].copy(), weight[:e.value].copy()
+
+    def set_positions(self, first_frame: int, pos: np.ndarray):
+        """host buffer pos [B][3] float64: the keyframes' positions, read by the loop form of group_dev"""
+        pos = np.ascontiguousarray(pos, np.float64).reshape(-1, 3)
+        self._ctx._chk(self._l.airfe_bowdb_set_positions(self._h, int(first_frame), pos.shape[0], pos.ctypes.data), "airfe_bowdb_set_positions")
+
+    def group_dev(self, mode, cand_frame_t, cand_score_t, ncand_t, group_frame_t, group_score_t, ngroups_t, status_t, extra_t=None, qpos_t=None,
+                  max_dist_t=None, stream=None):
+        """the grouping of map_user.cc:177-363 (mode 0, K <= 3) / map_refiner.cc:132-214 (mode 1, K <= 5) over query_batch_dev's candidate lists ->
+        group_frame i32 [Q][K] (the deputies, -1 padded: match_candidates_batch_dev's cand), group_score f64 [Q][K], ngroups [Q], status [Q] (0 ok, 1 no
+        group, 2 overflow); extra f64 [Q][size] (mode 0, optional), qpos f64 [Q][3] + max_dist f64 [Q] (mode 1)."""
+        opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self._ctx._chk(self._l.airfe_bowdb_group_dev(self._h, int(mode), cand_frame_t.data_ptr(), cand_score_t.data_ptr(), ncand_t.data_ptr(),
+                                                     cand_frame_t.shape[0], cand_frame_t.shape[1], group_frame_t.shape[1], opt(extra_t), opt(qpos_t),
+                                                     opt(max_dist_t), group_frame_t.data_ptr(), group_score_t.data_ptr(), ngroups_t.data_ptr(),
+                                                     status_t.data_ptr(), self._ctx._stream(stream)), "airfe_bowdb_group_dev")
+
+    def relocalize_batch_dev(self, qfeat_t, qn_t, cam, thr, min_inlier, ok_t, stage_t, Twc_t, best_t, num_t, mask_t, idx_t, score_t, nmatch_t,
+                             pnp_count_t=None, extra_t=None, pose_refinement=True, K=3, ratio=0.3, min_words=8, outlier_rejection=True, stream=None):
+        """airfe_relocalize_batch_dev (map_user.cc:129-460): qfeat [Q][cap][259] + qn [Q] -> ok / stage [Q] i32, Twc [Q][16] f64, best [Q], num [Q],
+        mask [Q][mcap] u8 by list entry, the winner's list idx [Q][mcap][2] / score [Q][mcap] / nmatch [Q], pnp_count [Q] (optional)."""
+        from . import _lib
+        cfg = _lib.RelocCfg(float(ratio), int(min_words), int(K), 1 if outlier_rejection else 0, int(min_inlier), 1 if pose_refinement else 0,
+                            (C.c_double * 5)(*[float(x) for x in cam]), (C.c_double * 2)(*[float(x) for x in thr]))
+        opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self._ctx._chk(self._l.airfe_relocalize_batch_dev(
+            self._ctx._h, self._h, C.byref(cfg), qfeat_t.data_ptr(), qn_t.data_ptr(), qfeat_t.shape[0], qfeat_t.shape[1], opt(extra_t), ok_t.data_ptr(),
+            stage_t.data_ptr(), Twc_t.data_ptr(), best_t.data_ptr(), num_t.data_ptr(), mask_t.data_ptr(), idx_t.data_ptr(), score_t.data_ptr(), idx_t.shape[1],
+            nmatch_t.data_ptr(), opt(pnp_count_t), self._ctx._stream(stream)), "airfe_relocalize_batch_dev")
+
 
 # ------------------------------------------------------------------------------------ reference-shaped façade
 class FeatureDetector:

@@ -4,6 +4,7 @@
 #include "fransac_core.h"
 #include "pnp_core.h"
 #include "poseopt_core.h"
+#include "bowgroup_core.h"
 
 namespace airfe_host {
 thread_local std::string g_err;
@@ -2290,6 +2291,12 @@ struct airfe_bowdb {
   float* feat = nullptr; int* n = nullptr;                                   // keep_features: [max_frames][cap][259], [max_frames]
   uint8_t* q_scratch = nullptr; size_t q_bytes = 0; hipStream_t q_stream = nullptr;      // query: dense sharing + score [Q][N]
   uint8_t* m_scratch = nullptr; size_t m_bytes = 0; hipStream_t m_stream = nullptr;      // composite: the pair batch
+  // map state (airfe_bowdb_attach_map): per-frame map points, the covisibility graph in CSR form, keyframe positions
+  int has_map = 0, max_edges = 0, has_pos = 0;
+  double* xyz = nullptr;                                                     // [max_frames][cap][3], NaN = no valid map point at this feature row
+  int32_t *cov_row = nullptr, *cov_nbr = nullptr, *cov_weight = nullptr;     // [max_frames + 1], [max_edges], [max_edges]
+  double* pos = nullptr;                                                     // [max_frames][3]
+  uint8_t* r_scratch = nullptr; size_t r_bytes = 0; hipStream_t r_stream = nullptr;      // relocalisation composite: everything between its kernels
 };
 
 namespace {
@@ -2400,7 +2407,8 @@ int airfe_bowdb_create(airfe_ctx* c, int max_frames, int cap, int keep_features,
 int airfe_bowdb_destroy(airfe_bowdb* db) try {
   if (!db) return 0;
   if (db->c) { (void)enter_device(db->c); (void)hipDeviceSynchronize(); }
-  for (void* p : {(void*)db->ids, (void*)db->vals, (void*)db->nw, (void*)db->feat, (void*)db->n, (void*)db->q_scratch, (void*)db->m_scratch})
+  for (void* p : {(void*)db->ids, (void*)db->vals, (void*)db->nw, (void*)db->feat, (void*)db->n, (void*)db->q_scratch, (void*)db->m_scratch, (void*)db->xyz,
+                  (void*)db->cov_row, (void*)db->cov_nbr, (void*)db->cov_weight, (void*)db->pos, (void*)db->r_scratch})
     if (p) (void)hipFree(p);
   delete db;
   return 0;
@@ -2449,17 +2457,12 @@ int airfe_bowdb_add(airfe_bowdb* db, const uint32_t* ids, const double* vals, co
   return bowdb_add_impl(db, ids, vals, nw, feat, n, B, cap, hipMemcpyHostToDevice, db->c->stream, "bowdb_add");
 } AIRFE_CATCH(db->c)
 
-int airfe_bowdb_query_batch_dev(airfe_bowdb* db, const uint32_t* d_ids, const double* d_vals, const int* d_nw, int Q, int cap,
-                                const airfe_bowdb_filter* filter, int32_t* d_cand_frame, int32_t* d_cand_sharing, double* d_cand_score, int ccap,
-                                int* d_ncand, int* d_max_sharing, int32_t* d_sharing, void* stream) try {
-  if (!db) return 1;
+// Database::Query + the sharing-word filter + Database::Score for Q device vectors on `st` (the body of airfe_bowdb_query_batch_dev; the relocalisation
+// composite queues the same code)
+static int bowdb_query_queue(airfe_bowdb* db, const uint32_t* d_ids, const double* d_vals, const int* d_nw, int Q, int cap, const airfe_bowdb_filter* filter,
+                             int32_t* d_cand_frame, int32_t* d_cand_sharing, double* d_cand_score, int ccap, int* d_ncand, int* d_max_sharing,
+                             int32_t* d_sharing, hipStream_t st) {
   airfe_ctx* c = db->c;
-  AIRFE_ENTER(c);
-  if (Q < 1 || cap < 1 || ccap < 1 || !d_ids || !d_vals || !d_nw || !filter || !d_cand_frame || !d_cand_sharing || !d_cand_score || !d_ncand || !d_max_sharing)
-    return fail(c, "bowdb_query_batch_dev: bad argument");
-  if (cap > BOW_MAX_FEATURES) return fail(c, "bowdb_query_batch_dev: cap > 1024");
-  if (filter->d_exclude && filter->exclude_words < 1) return fail(c, "bowdb_query_batch_dev: d_exclude needs exclude_words");
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
   const int N = db->size;
   const size_t cells = (size_t)Q * std::max(N, 1);
   if (bowdb_scratch(db, db->q_scratch, db->q_bytes, db->q_stream, cells * 12, st)) return 1;
@@ -2479,6 +2482,20 @@ int airfe_bowdb_query_batch_dev(airfe_bowdb* db, const uint32_t* d_ids, const do
   note_launch(c, ST_BOW);
   HIPCHK(c, hipGetLastError());
   return 0;
+}
+
+int airfe_bowdb_query_batch_dev(airfe_bowdb* db, const uint32_t* d_ids, const double* d_vals, const int* d_nw, int Q, int cap,
+                                const airfe_bowdb_filter* filter, int32_t* d_cand_frame, int32_t* d_cand_sharing, double* d_cand_score, int ccap,
+                                int* d_ncand, int* d_max_sharing, int32_t* d_sharing, void* stream) try {
+  if (!db) return 1;
+  airfe_ctx* c = db->c;
+  AIRFE_ENTER(c);
+  if (Q < 1 || cap < 1 || ccap < 1 || !d_ids || !d_vals || !d_nw || !filter || !d_cand_frame || !d_cand_sharing || !d_cand_score || !d_ncand || !d_max_sharing)
+    return fail(c, "bowdb_query_batch_dev: bad argument");
+  if (cap > BOW_MAX_FEATURES) return fail(c, "bowdb_query_batch_dev: cap > 1024");
+  if (filter->d_exclude && filter->exclude_words < 1) return fail(c, "bowdb_query_batch_dev: d_exclude needs exclude_words");
+  return bowdb_query_queue(db, d_ids, d_vals, d_nw, Q, cap, filter, d_cand_frame, d_cand_sharing, d_cand_score, ccap, d_ncand, d_max_sharing, d_sharing,
+                           stream ? (hipStream_t)stream : c->stream);
 } AIRFE_CATCH(db->c)
 
 int airfe_bowdb_topk_dev(airfe_bowdb* db, const int32_t* d_cand_frame, const double* d_cand_score, const int* d_ncand, int Q, int ccap, int K,
@@ -2494,18 +2511,11 @@ int airfe_bowdb_topk_dev(airfe_bowdb* db, const int32_t* d_cand_frame, const dou
   return 0;
 } AIRFE_CATCH(db->c)
 
-int airfe_bowdb_match_candidates_batch_dev(airfe_ctx* c, airfe_bowdb* db, const float* d_qfeat, const int* d_qn, int Q, int cap, const int32_t* d_cand, int K,
-                                           int outlier_rejection, int32_t* d_best, int32_t* d_idx, float* d_score, int mcap, int* d_nmatch,
-                                           int* d_nmatch_all, void* stream) try {
-  AIRFE_ENTER(c);
-  if (!db || db->c != c) return fail(c, "bowdb_match_candidates_batch_dev: the database belongs to another context");
-  if (Q < 1 || K < 1 || K > 5 || mcap < 1 || !d_qfeat || !d_qn || !d_cand || !d_best || !d_idx || !d_score || !d_nmatch)
-    return fail(c, "bowdb_match_candidates_batch_dev: bad argument (K = 1..5)");
-  if (!db->keep) return fail(c, "bowdb_match_candidates_batch_dev: the database was created without keep_features");
-  if (cap != db->cap) return fail(c, "bowdb_match_candidates_batch_dev: cap must be the database's");
-  if (mcap > FR_MAX_MATCHES) return fail(c, "bowdb_match_candidates_batch_dev: mcap > 1024");
-  if ((long long)Q * K > c->Pmax) return fail(c, "bowdb_match_candidates_batch_dev: Q * K pairs exceed cfg.max_batch");
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+// the best-candidate rule around the matcher for Q queries x K candidates on `st` (the body of airfe_bowdb_match_candidates_batch_dev; the relocalisation
+// composite queues the same code)
+static int bowdb_match_queue(airfe_ctx* c, airfe_bowdb* db, const float* d_qfeat, const int* d_qn, int Q, int cap, const int32_t* d_cand, int K,
+                             int outlier_rejection, int32_t* d_best, int32_t* d_idx, float* d_score, int mcap, int* d_nmatch, int* d_nmatch_all,
+                             hipStream_t st) {
   const int P = Q * K;
   const size_t fb = (size_t)P * cap * AIRFE_FEAT_DIM * 4, cb = ((size_t)P * 4 + 255) / 256 * 256, ib = (size_t)P * mcap * 8, sb = (size_t)P * mcap * 4;
   if (bowdb_scratch(db, db->m_scratch, db->m_bytes, db->m_stream, 2 * fb + 3 * cb + ib + sb, st)) return 1;
@@ -2528,6 +2538,233 @@ int airfe_bowdb_match_candidates_batch_dev(airfe_ctx* c, airfe_bowdb* db, const 
   b.cand = d_cand; b.K = K; b.N = db->size; b.mcap = mcap; b.idx_all = p_idx; b.score_all = p_score; b.nmatch_all = p_nm;
   b.best = d_best; b.idx = d_idx; b.score = d_score; b.nmatch = d_nmatch; b.out_nmatch_all = d_nmatch_all;
   launch_bowdb_best(b, Q, st);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+int airfe_bowdb_match_candidates_batch_dev(airfe_ctx* c, airfe_bowdb* db, const float* d_qfeat, const int* d_qn, int Q, int cap, const int32_t* d_cand, int K,
+                                           int outlier_rejection, int32_t* d_best, int32_t* d_idx, float* d_score, int mcap, int* d_nmatch,
+                                           int* d_nmatch_all, void* stream) try {
+  AIRFE_ENTER(c);
+  if (!db || db->c != c) return fail(c, "bowdb_match_candidates_batch_dev: the database belongs to another context");
+  if (Q < 1 || K < 1 || K > 5 || mcap < 1 || !d_qfeat || !d_qn || !d_cand || !d_best || !d_idx || !d_score || !d_nmatch)
+    return fail(c, "bowdb_match_candidates_batch_dev: bad argument (K = 1..5)");
+  if (!db->keep) return fail(c, "bowdb_match_candidates_batch_dev: the database was created without keep_features");
+  if (cap != db->cap) return fail(c, "bowdb_match_candidates_batch_dev: cap must be the database's");
+  if (mcap > FR_MAX_MATCHES) return fail(c, "bowdb_match_candidates_batch_dev: mcap > 1024");
+  if ((long long)Q * K > c->Pmax) return fail(c, "bowdb_match_candidates_batch_dev: Q * K pairs exceed cfg.max_batch");
+  return bowdb_match_queue(c, db, d_qfeat, d_qn, Q, cap, d_cand, K, outlier_rejection, d_best, d_idx, d_score, mcap, d_nmatch, d_nmatch_all,
+                           stream ? (hipStream_t)stream : c->stream);
+} AIRFE_CATCH(c)
+
+/* ---- map state in the database, the grouping and the relocalisation composite (include/airfe.h "Grouping", "Relocalisation composite";
+ * kernels_bowgroup.hip, bowgroup_core.h) ------------------------------------------------------------------------------------------------------------ */
+int airfe_bowdb_attach_map(airfe_bowdb* db, int max_edges) try {
+  if (!db) return 1;
+  airfe_ctx* c = db->c;
+  AIRFE_ENTER(c);
+  if (db->has_map) return fail(c, "bowdb_attach_map: the map state is attached already");
+  if (!db->keep) return fail(c, "bowdb_attach_map: the database was created without keep_features");
+  if (max_edges < 1) return fail(c, "bowdb_attach_map: bad argument");
+  const size_t rows = (size_t)db->max_frames * db->cap;
+  HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->xyz), rows * 24));
+  HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->cov_row), ((size_t)db->max_frames + 1) * 4));
+  HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->cov_nbr), (size_t)max_edges * 4));
+  HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->cov_weight), (size_t)max_edges * 4));
+  HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->pos), (size_t)db->max_frames * 24));
+  HIPCHK(c, hipMemsetAsync(db->xyz, 0xFF, rows * 24, c->stream));                         // every byte 0xFF: a NaN in every slot
+  HIPCHK(c, hipMemsetAsync(db->cov_row, 0, ((size_t)db->max_frames + 1) * 4, c->stream));  // an empty graph
+  HIPCHK(c, hipMemsetAsync(db->cov_nbr, 0, (size_t)max_edges * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(db->cov_weight, 0, (size_t)max_edges * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(db->pos, 0xFF, (size_t)db->max_frames * 24, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  db->max_edges = max_edges;
+  db->has_map = 1;
+  return 0;
+} AIRFE_CATCH(db->c)
+
+// rows first_frame .. first_frame + B - 1 of a [max_frames][per] f64 table
+static int bowdb_rows_copy(airfe_bowdb* db, double* table, size_t per, int first_frame, int B, const void* src, void* dst, hipMemcpyKind kind, hipStream_t st,
+                           const char* who) {
+  airfe_ctx* c = db->c;
+  if (!db->has_map) return fail(c, std::string(who) + ": no map state (airfe_bowdb_attach_map)");
+  if (first_frame < 0 || B < 1 || B > db->max_frames - first_frame || (!src && !dst)) return fail(c, std::string(who) + ": bad argument (frames beyond max_frames)");
+  double* at = table + (size_t)first_frame * per;
+  if (src) HIPCHK(c, hipMemcpyAsync(at, src, (size_t)B * per * 8, kind, st));
+  else HIPCHK(c, hipMemcpyAsync(dst, at, (size_t)B * per * 8, kind, st));
+  if (kind != hipMemcpyDeviceToDevice) HIPCHK(c, hipStreamSynchronize(st));
+  return 0;
+}
+
+int airfe_bowdb_set_points_dev(airfe_bowdb* db, int first_frame, int B, const double* d_xyz, void* stream) try {
+  if (!db) return 1;
+  AIRFE_ENTER(db->c);
+  return bowdb_rows_copy(db, db->xyz, (size_t)db->cap * 3, first_frame, B, d_xyz, nullptr, hipMemcpyDeviceToDevice,
+                         stream ? (hipStream_t)stream : db->c->stream, "bowdb_set_points_dev");
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_set_points(airfe_bowdb* db, int first_frame, int B, const double* xyz) try {
+  if (!db) return 1;
+  AIRFE_ENTER(db->c);
+  return bowdb_rows_copy(db, db->xyz, (size_t)db->cap * 3, first_frame, B, xyz, nullptr, hipMemcpyHostToDevice, db->c->stream, "bowdb_set_points");
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_get_points(airfe_bowdb* db, int first_frame, int B, double* xyz) try {
+  if (!db) return 1;
+  AIRFE_ENTER(db->c);
+  return bowdb_rows_copy(db, db->xyz, (size_t)db->cap * 3, first_frame, B, nullptr, xyz, hipMemcpyDeviceToHost, db->c->stream, "bowdb_get_points");
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_set_positions(airfe_bowdb* db, int first_frame, int B, const double* pos) try {
+  if (!db) return 1;
+  AIRFE_ENTER(db->c);
+  if (bowdb_rows_copy(db, db->pos, 3, first_frame, B, pos, nullptr, hipMemcpyHostToDevice, db->c->stream, "bowdb_set_positions")) return 1;
+  db->has_pos = 1;
+  return 0;
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_set_covisibility(airfe_bowdb* db, const int32_t* row_ptr, const int32_t* nbr, const int32_t* weight, int n_frames) try {
+  if (!db) return 1;
+  airfe_ctx* c = db->c;
+  AIRFE_ENTER(c);
+  if (!db->has_map) return fail(c, "bowdb_set_covisibility: no map state (airfe_bowdb_attach_map)");
+  if (n_frames < 0 || n_frames > db->max_frames || !row_ptr) return fail(c, "bowdb_set_covisibility: bad argument (n_frames beyond max_frames)");
+  if (row_ptr[0] != 0) return fail(c, "bowdb_set_covisibility: row_ptr[0] must be 0");
+  for (int f = 0; f < n_frames; ++f)
+    if (row_ptr[f + 1] < row_ptr[f]) return fail(c, "bowdb_set_covisibility: row_ptr must not decrease");
+  const int E = row_ptr[n_frames];
+  if (E > db->max_edges) return fail(c, "bowdb_set_covisibility: more entries than max_edges");
+  if (E > 0 && (!nbr || !weight)) return fail(c, "bowdb_set_covisibility: bad argument");
+  for (int f = 0; f < n_frames; ++f)
+    for (int e = row_ptr[f]; e < row_ptr[f + 1]; ++e)
+      if (nbr[e] < 0 || (e > row_ptr[f] && nbr[e] <= nbr[e - 1]))
+        return fail(c, "bowdb_set_covisibility: every row must be strictly ascending in nbr (nothing was changed)");
+  std::vector<int32_t> rows((size_t)db->max_frames + 1, E);                                // frames past n_frames: empty rows
+  std::copy(row_ptr, row_ptr + n_frames + 1, rows.begin());
+  hipStream_t st = c->stream;
+  HIPCHK(c, hipMemcpyAsync(db->cov_row, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, st));
+  if (E > 0) {
+    HIPCHK(c, hipMemcpyAsync(db->cov_nbr, nbr, (size_t)E * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(db->cov_weight, weight, (size_t)E * 4, hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(c, hipStreamSynchronize(st));
+  return 0;
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_get_covisibility(airfe_bowdb* db, int32_t* row_ptr, int32_t* nbr, int32_t* weight, int edge_cap, int* n_edges) try {
+  if (!db) return 1;
+  airfe_ctx* c = db->c;
+  AIRFE_ENTER(c);
+  if (!db->has_map) return fail(c, "bowdb_get_covisibility: no map state (airfe_bowdb_attach_map)");
+  if (!row_ptr || !n_edges || edge_cap < 0) return fail(c, "bowdb_get_covisibility: bad argument");
+  hipStream_t st = c->stream;
+  HIPCHK(c, hipMemcpyAsync(row_ptr, db->cov_row, ((size_t)db->max_frames + 1) * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  const int E = row_ptr[db->max_frames];
+  *n_edges = E;
+  if (E > edge_cap) return fail(c, "bowdb_get_covisibility: more entries than edge_cap");
+  if (E > 0) {
+    if (!nbr || !weight) return fail(c, "bowdb_get_covisibility: bad argument");
+    HIPCHK(c, hipMemcpyAsync(nbr, db->cov_nbr, (size_t)E * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(weight, db->cov_weight, (size_t)E * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+  }
+  return 0;
+} AIRFE_CATCH(db->c)
+
+// the grouping for Q candidate lists on `st`
+static int bowdb_group_queue(airfe_bowdb* db, int mode, const int32_t* d_cand_frame, const double* d_cand_score, const int* d_ncand, int Q, int ccap, int K,
+                             const double* d_extra, const double* d_qpos, const double* d_max_dist, int32_t* d_group_frame, double* d_group_score,
+                             int* d_ngroups, int* d_status, hipStream_t st) {
+  airfe_ctx* c = db->c;
+  BowGroupArgs a;
+  a.mode = mode; a.cand_frame = d_cand_frame; a.cand_score = d_cand_score; a.ncand = d_ncand; a.ccap = ccap; a.K = K;
+  a.row_ptr = db->cov_row; a.nbr = db->cov_nbr; a.weight = db->cov_weight; a.rows = db->max_frames;
+  a.extra = d_extra; a.n_extra = db->size; a.pos = db->pos; a.pos_rows = db->max_frames; a.qpos = d_qpos; a.max_dist = d_max_dist;
+  a.group_frame = d_group_frame; a.group_score = d_group_score; a.ngroups = d_ngroups; a.status = d_status;
+  if (launch_bowgroup(a, Q, st)) return fail(c, "bowdb_group_dev: the candidate list does not fit the workgroup's LDS");
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+int airfe_bowdb_group_dev(airfe_bowdb* db, int mode, const int32_t* d_cand_frame, const double* d_cand_score, const int* d_ncand, int Q, int ccap, int K,
+                          const double* d_extra, const double* d_qpos, const double* d_max_dist, int32_t* d_group_frame, double* d_group_score,
+                          int* d_ngroups, int* d_status, void* stream) try {
+  if (!db) return 1;
+  airfe_ctx* c = db->c;
+  AIRFE_ENTER(c);
+  if (!db->has_map) return fail(c, "bowdb_group_dev: no map state (airfe_bowdb_attach_map)");
+  if (Q < 1 || ccap < 1 || K < 1 || !d_cand_frame || !d_cand_score || !d_ncand || !d_group_frame || !d_group_score || !d_ngroups || !d_status)
+    return fail(c, "bowdb_group_dev: bad argument");
+  if (mode != BG_MODE_RELOC && mode != BG_MODE_LOOP) return fail(c, "bowdb_group_dev: mode is 0 (relocalisation) or 1 (loop detection)");
+  if (K > (mode == BG_MODE_RELOC ? 3 : 5)) return fail(c, "bowdb_group_dev: K <= 3 (relocalisation) / K <= 5 (loop detection)");
+  if (ccap > BG_MAX_CAND) return fail(c, "bowdb_group_dev: ccap > 4096");
+  if (mode == BG_MODE_LOOP && (!d_qpos || !d_max_dist || !db->has_pos))
+    return fail(c, "bowdb_group_dev: the loop form needs d_qpos, d_max_dist and the keyframe positions (airfe_bowdb_set_positions)");
+  return bowdb_group_queue(db, mode, d_cand_frame, d_cand_score, d_ncand, Q, ccap, K, d_extra, d_qpos, d_max_dist, d_group_frame, d_group_score, d_ngroups,
+                           d_status, stream ? (hipStream_t)stream : c->stream);
+} AIRFE_CATCH(db->c)
+
+int airfe_relocalize_batch_dev(airfe_ctx* c, airfe_bowdb* db, const airfe_reloc_cfg* cfg, const float* d_qfeat, const int* d_qn, int Q, int cap,
+                               const double* d_extra, int* d_ok, int* d_stage, double* d_Twc, int32_t* d_best, int* d_num, uint8_t* d_mask, int32_t* d_idx,
+                               float* d_score, int mcap, int* d_nmatch, int* d_pnp_count, void* stream) try {
+  AIRFE_ENTER(c);
+  if (!db || db->c != c) return fail(c, "relocalize_batch_dev: the database belongs to another context");
+  if (!db->has_map) return fail(c, "relocalize_batch_dev: no map state (airfe_bowdb_attach_map)");
+  if (!cfg || Q < 1 || mcap < 1 || !d_qfeat || !d_qn || !d_ok || !d_stage || !d_Twc || !d_best || !d_num || !d_mask || !d_idx || !d_score || !d_nmatch)
+    return fail(c, "relocalize_batch_dev: bad argument");
+  if (cfg->K < 1 || cfg->K > 3) return fail(c, "relocalize_batch_dev: cfg.K = 1..3");
+  if (cap != db->cap) return fail(c, "relocalize_batch_dev: cap must be the database's");
+  if (mcap > PNP_MAX_POINTS) return fail(c, "relocalize_batch_dev: mcap > 1024");
+  if ((long long)Q * cfg->K > c->Pmax) return fail(c, "relocalize_batch_dev: Q * K pairs exceed cfg.max_batch");
+  if (!c->bow_nodes) return fail(c, "relocalize_batch_dev: no vocabulary loaded (airfe_bow_load)");
+  const int N = db->size, ccap = std::max(N, 1), K = cfg->K;
+  if (ccap > BG_MAX_CAND) return fail(c, "relocalize_batch_dev: more than 4096 frames in the database");
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  // one block, every part 256-byte aligned
+  size_t off = 0;
+  auto take = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) / 256 * 256; return at; };
+  const size_t qc = (size_t)Q * cap, qm = (size_t)Q * mcap, qcc = (size_t)Q * ccap, qb = (size_t)Q * 4;
+  const size_t o_ids = take(qc * 4), o_vals = take(qc * 8), o_nw = take(qb), o_cf = take(qcc * 4), o_cs = take(qcc * 4), o_sc = take(qcc * 8), o_nc = take(qb),
+               o_ms = take(qb), o_gf = take((size_t)Q * K * 4), o_gs = take((size_t)Q * K * 8), o_ng = take(qb), o_gst = take(qb), o_obj = take(qm * 12),
+               o_img = take(qm * 8), o_map = take(qm * 4), o_X = take(qm * 24), o_obs = take(qm * 24), o_n = take(qb), o_nopt = take(qb), o_pre = take(qb),
+               o_pnp = take((size_t)Q * 128), o_pmask = take(qm), o_pcnt = take(qb);
+  if (bowdb_scratch(db, db->r_scratch, db->r_bytes, db->r_stream, off, st)) return 1;
+  uint8_t* r = db->r_scratch;
+  auto I = [r](size_t o) { return reinterpret_cast<int*>(r + o); };
+  auto D = [r](size_t o) { return reinterpret_cast<double*>(r + o); };
+  // map_user.cc:129-166: the vector, the query with the sharing-word filter, the scores
+  if (bow_vector_queue(c, d_qfeat, d_qn, Q, cap, reinterpret_cast<uint32_t*>(r + o_ids), D(o_vals), I(o_nw), nullptr, st)) return 1;
+  airfe_bowdb_filter flt;
+  flt.ratio = cfg->ratio; flt.min_words = cfg->min_words; flt.d_max_index = nullptr; flt.d_exclude = nullptr; flt.exclude_words = 0;
+  if (bowdb_query_queue(db, reinterpret_cast<uint32_t*>(r + o_ids), D(o_vals), I(o_nw), Q, cap, &flt, I(o_cf), I(o_cs), D(o_sc), ccap, I(o_nc), I(o_ms),
+                        nullptr, st)) return 1;
+  // :177-363: the grouping; :360-376: the matcher over the K deputies
+  if (bowdb_group_queue(db, BG_MODE_RELOC, I(o_cf), D(o_sc), I(o_nc), Q, ccap, K, d_extra, nullptr, nullptr, I(o_gf), D(o_gs), I(o_ng), I(o_gst), st)) return 1;
+  if (bowdb_match_queue(c, db, d_qfeat, d_qn, Q, cap, I(o_gf), K, cfg->outlier_rejection, d_best, d_idx, d_score, mcap, d_nmatch, nullptr, st)) return 1;
+  // :377-390: the first gate, the winner's map points, SolvePnPWithCV
+  const int refine = cfg->pose_refinement != 0;
+  RelocGatherArgs g;
+  g.xyz = db->xyz; g.N = N; g.cap = cap; g.qfeat = d_qfeat; g.best = d_best; g.idx = d_idx; g.nmatch = d_nmatch; g.mcap = mcap;
+  g.ncand = I(o_nc); g.gstatus = I(o_gst); g.ngroups = I(o_ng); g.min_inlier = cfg->min_inlier; g.refine = refine;
+  g.obj = reinterpret_cast<float*>(r + o_obj); g.img = reinterpret_cast<float*>(r + o_img); g.map = I(o_map); g.X = D(o_X); g.obs = D(o_obs);
+  g.n = I(o_n); g.n_opt = I(o_nopt); g.pre = I(o_pre);
+  launch_reloc_gather(g, Q, st);
+  HIPCHK(c, hipGetLastError());
+  RelocFinishArgs f;
+  f.pre = g.pre; f.num = d_num; f.min_inlier = cfg->min_inlier; f.stage = d_stage; f.ok = d_ok;
+  if (!refine) {
+    if (pnp_queue(c, g.obj, g.img, g.n, Q, mcap, cfg->cam, d_Twc, nullptr, d_mask, mcap, g.map, d_num, st)) return 1;
+    f.pnp_count = d_num; f.pnp_count_out = d_pnp_count;
+  } else {
+    // :392-457: the frame optimisation from the PnP pose, Tcb = identity, every constraint mono; fewer constraints than min_inlier: none are handed over
+    // and the kernel returns its start pose, PnP's
+    int* d_cnt = d_pnp_count ? d_pnp_count : I(o_pcnt);
+    if (pnp_queue(c, g.obj, g.img, g.n, Q, mcap, cfg->cam, D(o_pnp), nullptr, r + o_pmask, mcap, g.map, d_cnt, st)) return 1;
+    if (poseopt_queue(c, g.X, g.obs, g.n_opt, Q, mcap, D(o_pnp), cfg->cam, nullptr, cfg->thr, d_Twc, nullptr, d_mask, mcap, g.map, d_num, -1, nullptr, st))
+      return 1;
+  }
+  launch_reloc_finish(f, Q, st);
   HIPCHK(c, hipGetLastError());
   return 0;
 } AIRFE_CATCH(c)

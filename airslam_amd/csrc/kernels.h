@@ -450,4 +450,34 @@ struct BowBestArgs {
 };
 void launch_bowdb_best(const BowBestArgs& a, int Q, hipStream_t st);
 
+// Grouping + the relocalisation composite's glue (map_user.cc:177-270, 377-460, map_refiner.cc:132-214; kernels_bowgroup.hip, bowgroup_core.h;
+// contract: include/airfe.h)
+struct BowGroupArgs {
+  int mode = 0;                                                              // BG_MODE_RELOC / BG_MODE_LOOP
+  const int32_t* cand_frame = nullptr; const double* cand_score = nullptr; const int* ncand = nullptr; int ccap = 0, K = 0;   // [Q][ccap] x 2, [Q]
+  const int32_t *row_ptr = nullptr, *nbr = nullptr, *weight = nullptr; int rows = 0;                                          // covisibility CSR
+  const double* extra = nullptr; int n_extra = 0;                            // [Q][n_extra] or nullptr (relocalisation: the caller's junction term)
+  const double* pos = nullptr; int pos_rows = 0;                             // [pos_rows][3] keyframe positions (loop form)
+  const double *qpos = nullptr, *max_dist = nullptr;                         // [Q][3], [Q] (loop form)
+  int32_t* group_frame = nullptr; double* group_score = nullptr; int *ngroups = nullptr, *status = nullptr;                   // [Q][K] x 2, [Q] x 2
+};
+size_t bowgroup_lds(int ccap);
+int launch_bowgroup(const BowGroupArgs& a, int Q, hipStream_t st);
+struct RelocGatherArgs {
+  const double* xyz = nullptr; int N = 0, cap = 0;                           // the database's point table [max_frames][cap][3] (NaN: none), its size
+  const float* qfeat = nullptr;                                              // [Q][cap][259]
+  const int32_t *best = nullptr, *idx = nullptr; const int* nmatch = nullptr; int mcap = 0;     // the winner and its list (query index, candidate index)
+  const int *ncand = nullptr, *gstatus = nullptr, *ngroups = nullptr; int min_inlier = 0, refine = 0;
+  float *obj = nullptr, *img = nullptr; int* map = nullptr;                  // PnP: [Q][mcap][3], [Q][mcap][2], list entry of correspondence i
+  double *X = nullptr, *obs = nullptr;                                       // frame optimisation: [Q][mcap][3] x 2
+  int *n = nullptr, *n_opt = nullptr, *pre = nullptr;                        // [Q]: correspondences, constraints handed to the optimisation, stage so far
+};
+void launch_reloc_gather(const RelocGatherArgs& g, int Q, hipStream_t st);
+struct RelocFinishArgs {
+  const int *pre = nullptr, *num = nullptr; int min_inlier = 0;
+  const int* pnp_count = nullptr; int* pnp_count_out = nullptr;
+  int *stage = nullptr, *ok = nullptr;
+};
+void launch_reloc_finish(const RelocFinishArgs& f, int Q, hipStream_t st);
+
 }  // namespace airfe

@@ -421,11 +421,12 @@ int airfe_bow_transform_dev(airfe_ctx* ctx, const float* d_feat, int N, uint32_t
  *   Detect -> Database::FrameToBow -> Database::Query -> sharing-word filter -> Database::Score (L1) -> grouping -> top 3 / 5 candidates
  *          -> MatchingPoints(query, candidate, matches, true) per candidate -> the candidate with the most matches -> SolvePnPWithCV
  * RESTATED here, on the device, bit for bit (DBoW2 compiled unchanged is the test's reference for the vector; tests/bowdb_ref.py restates the rest):
- * FrameToBow to its end, AddFrame, Query, the two callers' filters, L1Scoring::score, the best-candidate rule.  NOT restated: the GROUPING between
- * the scores and the candidates (map_user.cc:177-264, map_refiner.cc:132-211) walks the map's covisibility graph and, for relocalisation, the junction
- * "sentences" — map state this library does not hold.  It stays the caller's: the candidate list below IS the reference's frame_scores map, and the
- * composite takes its candidates from the caller.  airfe_bowdb_topk_dev is the PROJECT'S OWN ranking for callers without a covisibility graph, not the
- * reference's grouping.  Every floating-point sum is sequential in the order given; no fused multiply-adds.
+ * FrameToBow to its end, AddFrame, Query, the two callers' filters, L1Scoring::score, the best-candidate rule — and, in the block "Grouping" below, the
+ * GROUPING between the scores and the candidates (map_user.cc:177-264, map_refiner.cc:132-211) over a covisibility table the caller hands to the
+ * database (airfe_bowdb_attach_map / airfe_bowdb_set_covisibility).  What stays the caller's: BUILDING that table from the map's observer lists, and
+ * relocalisation's junction "sentences" (the junction database, FindJunctionConnections), whose result enters the grouping as one number per frame
+ * (d_extra).  The candidate list below IS the reference's frame_scores map.  airfe_bowdb_topk_dev is the PROJECT'S OWN ranking for callers without a
+ * covisibility graph, not the reference's grouping.  Every floating-point sum is sequential in the order given; no fused multiply-adds.
  *   vector   Database::FrameToBow (src/bow/database.cc:57-89): per feature the descent of airfe_bow_transform (the same kernel); a feature counts iff its
  *            word's weight is > 0 (word_of_features = UINT_MAX otherwise).  The weights are the vocabulary's doubles (WordValue).  BowVector::addWeight:
  *            one entry per distinct word, its weights added in ascending feature index, in double.  BowVector::normalize(L1): tot = the sum of |v| in
@@ -487,11 +488,97 @@ int airfe_bowdb_topk_dev(airfe_bowdb* db, const int32_t* d_cand_frame, const dou
  * the rows are gathered into a [Q K] pair batch, airfe_match_lightglue_batch_dev's code runs on it and, with outlier_rejection,
  * airfe_fundamental_ransac_batch_dev's.  d_qfeat [Q][cap][259] (cap = the database's), d_qn [Q]; d_best [Q] (frame index or -1), the winner's list
  * d_idx [Q][mcap][2] = (query index, candidate index) / d_score [Q][mcap] / d_nmatch [Q] (0 without a winner; entries past the count are not written),
- * d_nmatch_all [Q][K] or NULL (0 for holes).  Q * K above cfg.max_batch is an error.  PnP and the refinement stay calls of the entries above: they
- * need the candidate's map points, which the caller holds. */
+ * d_nmatch_all [Q][K] or NULL (0 for holes).  Q * K above cfg.max_batch is an error.  PnP and the refinement behind it: airfe_relocalize_batch_dev
+ * below, on the map points the database holds once airfe_bowdb_attach_map was called (or the entries above, on points the caller holds). */
 int airfe_bowdb_match_candidates_batch_dev(airfe_ctx* ctx, airfe_bowdb* db, const float* d_qfeat, const int* d_qn, int Q, int cap, const int32_t* d_cand,
                                            int K, int outlier_rejection, int32_t* d_best, int32_t* d_idx, float* d_score, int mcap, int* d_nmatch,
                                            int* d_nmatch_all, void* stream);
+
+/* ---- Map state in the database (opt-in): what the grouping and the relocalisation composite read ----------------------------------------------------
+ * airfe_bowdb_attach_map (needs keep_features) allocates
+ *   points        [max_frames][cap][3] f64 in the map's world frame, one per FEATURE ROW of the stored frame, initialised to NaN; NaN (in x) = "no valid
+ *                 map point at this row" (the convention of airfe_stereo_points' xyz): the caller writes NaN where mpt == nullptr || !mpt->IsValid().
+ *   covisibility  CSR: row_ptr [max_frames + 1], nbr i32 [max_edges], weight i32 [max_edges]; initially empty.  airfe_bowdb_set_covisibility REPLACES the
+ *                 whole graph (as Map::UpdateCovisibilityGraph does) from HOST arrays of n_frames rows (frames past n_frames get empty rows); every row
+ *                 must be strictly ascending in nbr and row_ptr must start at 0 and not decrease, otherwise the call fails and changes nothing.  The
+ *                 table is the reference's _covisibile_frames as it is: it INCLUDES each frame's entry for itself (UpdateFrameCovisibility counts a
+ *                 frame among the observers of its own points); the library neither adds nor removes it.  Building it stays the caller's.
+ *   positions     [max_frames][3] f64, optional (airfe_bowdb_set_positions, host rows): the keyframes' twc, read by the loop form only.
+ * The set_* / get_* entries on host buffers synchronise the context's stream; a grouping queued on ANOTHER stream must have completed before the graph
+ * is replaced.  airfe_bowdb_set_points_dev is asynchronous on `stream`. */
+int airfe_bowdb_attach_map(airfe_bowdb* db, int max_edges);
+int airfe_bowdb_set_points_dev(airfe_bowdb* db, int first_frame, int B, const double* d_xyz, void* stream);   /* d_xyz [B][cap][3] -> frames first_frame .. */
+int airfe_bowdb_set_points(airfe_bowdb* db, int first_frame, int B, const double* xyz);                      /* host buffer */
+int airfe_bowdb_get_points(airfe_bowdb* db, int first_frame, int B, double* xyz);                            /* host buffer [B][cap][3] */
+int airfe_bowdb_set_covisibility(airfe_bowdb* db, const int32_t* row_ptr, const int32_t* nbr, const int32_t* weight, int n_frames);
+/* row_ptr [max_frames + 1]; nbr / weight [edge_cap] (may be NULL when the graph is empty); *n_edges = row_ptr[max_frames] (an error when > edge_cap) */
+int airfe_bowdb_get_covisibility(airfe_bowdb* db, int32_t* row_ptr, int32_t* nbr, int32_t* weight, int edge_cap, int* n_edges);
+int airfe_bowdb_set_positions(airfe_bowdb* db, int first_frame, int B, const double* pos);                   /* host buffer [B][3] */
+
+/* ---- Grouping: between the scores and the candidates of MapUser::Relocalization (src/map_user.cc:177-270, 331, 347-363) and MapRefiner::LoopDetection
+ * (src/map_refiner.cc:132-214) ---------------------------------------------------------------------------------------------------------------------
+ * Three statements that agree bit for bit: the host routine bowgroup_host (airslam_amd/csrc/bowgroup_core.h), the kernel (kernels_bowgroup.hip, which
+ * calls the same header's routines from its lanes) and tests/bowgroup_ref.py.  fp64, every sum sequential in the order written, no fused multiply-adds.
+ *   input    per query the candidate list of airfe_bowdb_query_batch_dev: (frame, score) in ascending frame index, the first min(ncand, ccap) entries;
+ *            ccap <= 4096 (beyond: a capacity error).  A query whose ncand > ccap gets status 2 (overflow) and no groups.
+ *   order    STATED DIFFERENCE: the reference iterates std::map<FramePtr, ...> and std::set<FramePtr> in POINTER order, which is unspecified.  Every such
+ *            iteration here is in ascending frame index.
+ *   per candidate i, in list order (map_user.cc:183-217 ≡ map_refiner.cc:138-172): score_i = 0 + s_i (group_score starts at 0), deputy = i, deputy_score = s_i; for each covisibility
+ *            entry of frame i in ascending neighbour index with weight > 10 whose neighbour is in the candidate list: score_i += s_nbr, and the
+ *            neighbour becomes the deputy iff s_nbr > deputy_score (strictly).  The frame's entry for ITSELF is an entry like any other: with a weight
+ *            above 10 the frame's own score is added twice, as in the reference.
+ *   replacement  sequentially in list order: group i is stored under its deputy iff that deputy has no group yet or its stored group_score < score_i;
+ *            best_group_score starts at -1 and is raised by every stored group that exceeds it.  best_group_score < 0: no groups (status 1; a query
+ *            without candidates ends here as well).
+ *   relocalisation form (mode 0; map_user.cc:221-270, 331, 347-363)
+ *            (1) every stored group is re-summed: its members are the stored candidate and its qualifying neighbours, each once; more than 5 members:
+ *            the five largest scores added in descending order, otherwise every score in ascending frame index; from +0.  (2) best = the maximum of
+ *            the re-summed scores, from 0.0.  (3) with more than 3 groups, those with score < best * 0.5 are dropped.  (4) d_extra (f64 [Q][N],
+ *            N = the database's size, or NULL): d_extra[q][deputy] is added to each remaining group's score — the caller's junction term
+ *            junction_frame_scores * (1 + rate) of :329-331.  (5) descending score, ties to the lower frame index (std::sort is not stable: the tie
+ *            rule is the project's, STATED DIFFERENCE).  (6) the first K <= 3 deputies are the candidates.
+ *   loop form (mode 1; map_refiner.cc:176-214)  no re-sum: a group keeps score_i.  (1) groups whose deputy lies farther than d_max_dist[q] from
+ *            d_qpos[q] are dropped: sqrt((dx dx + dy dy) + dz dz) in double, dropped iff > d_max_dist[q] (positions: airfe_bowdb_set_positions).
+ *            (2) with more than 3 groups LEFT, those with score < best_group_score * 0.5 are dropped — best_group_score is the replacement pass's,
+ *            taken before the distance filter, as in the reference.  (3) ranked as above; K <= 5.  d_extra is not read.
+ *   output   d_group_frame i32 [Q][K] (the deputies, -1 padded: the shape airfe_bowdb_match_candidates_batch_dev takes as d_cand), d_group_score f64
+ *            [Q][K] (0 where padded), d_ngroups [Q] (the groups left after the filters; may exceed K), d_status [Q]: 0 ok, 1 no group, 2 overflow.
+ * Asynchronous on `stream`, no host synchronisation; a query's bytes do not depend on Q or on its position in the batch. */
+int airfe_bowdb_group_dev(airfe_bowdb* db, int mode, const int32_t* d_cand_frame, const double* d_cand_score, const int* d_ncand, int Q, int ccap, int K,
+                          const double* d_extra, const double* d_qpos, const double* d_max_dist, int32_t* d_group_frame, double* d_group_score,
+                          int* d_ngroups, int* d_status, void* stream);
+
+/* ---- Relocalisation composite: MapUser::Relocalization from the query's feature rows to the pose (src/map_user.cc:129-460), on one stream, nothing
+ * copied to the host in between.  Per query, byte for byte the steps done one at a time through the entries above:
+ *   (1) airfe_bow_vector_batch_dev's code; airfe_bowdb_query_batch_dev's with (ratio, min_words) and no other filter, over every stored frame (at most
+ *       4096); the grouping in relocalisation form with d_extra; airfe_bowdb_match_candidates_batch_dev's code on the K deputies.
+ *   (2) no candidate: stage 1.  No group: stage 2.  nmatch < min_inlier (or no winner): stage 3 (:377).
+ *   (3) correspondences = the winner's list entries whose candidate row has a map point (x not NaN) in the database's point table, in list order — the
+ *       matcher's lists ascend in query index, SolvePnPWithCV's loop order; a repeated index is not deduplicated.  Object point = the map point rounded
+ *       to float, image point = the query row's (x, y).
+ *   (4) the PnP RANSAC above with K = cam[0..3]; the pose is PnP's, or the identity without a model.  There is no seed fallback here.
+ *   (5) pose_refinement: fewer correspondences than min_inlier: stage 4, the pose stays PnP's, num = 0 and the mask is 0 (:448).  Otherwise the frame
+ *       optimisation above from the PnP pose, Tcb = identity, every constraint mono (u_right = -1: the query has no right image); the pose is the
+ *       optimised one, num its num_inliers, the mask its flags.  Without pose_refinement num and the mask are PnP's.
+ *   (6) num < min_inlier: stage 5 (:460).
+ * d_ok [Q]; d_stage [Q] (0 = ok); d_Twc [Q][16] = what the reference's `pose` holds at the return (identity for stages 1 - 3); d_best [Q] (-1 without a
+ * winner); d_num [Q] (0 for stages 1 - 4); d_mask [Q][mcap] by LIST ENTRY (every entry written); the winner's list d_idx [Q][mcap][2] = (query index,
+ * candidate index) / d_score / d_nmatch as airfe_bowdb_match_candidates_batch_dev writes them; d_pnp_count [Q] or NULL.  mcap <= 1024; Q * K above
+ * cfg.max_batch, a database without airfe_bowdb_attach_map and one of more than 4096 frames are errors.  A query's bytes depend neither on Q nor on its
+ * position in the batch. */
+typedef struct airfe_reloc_cfg {
+  float ratio;            /* 0.3f */
+  int min_words;          /* 8 */
+  int K;                  /* 3 (GoodCandidateNum) */
+  int outlier_rejection;  /* 1: MatchingPoints(..., true) */
+  int min_inlier;         /* RelocalizationConfig::min_inlier */
+  int pose_refinement;    /* whether step 5 runs */
+  double cam[5];          /* fx, fy, cx, cy, bf */
+  double thr[2];          /* the chi-square values of `pose_estimation`: mono_point, stereo_point */
+} airfe_reloc_cfg;
+int airfe_relocalize_batch_dev(airfe_ctx* ctx, airfe_bowdb* db, const airfe_reloc_cfg* cfg, const float* d_qfeat, const int* d_qn, int Q, int cap,
+                               const double* d_extra, int* d_ok, int* d_stage, double* d_Twc, int32_t* d_best, int* d_num, uint8_t* d_mask, int32_t* d_idx,
+                               float* d_score, int mcap, int* d_nmatch, int* d_pnp_count, void* stream);
 
 /* ---- the step BEFORE the path: rectification ------------------------------------------------------- */
 /* ≙ the maps Camera's constructor builds with cv::initUndistortRectifyMap (src/camera.cc:60-75; _mapl1/_mapl2 = side 0, _mapr1/_mapr2 =
