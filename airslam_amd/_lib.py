@@ -76,6 +76,20 @@ class DebugLgBlockArgs(C.Structure):
                 + [("Np", C.c_int)] + [(n, C.c_void_p) for n in ("q", "k", "vt")] + [("rows_past", C.c_int * 5)])
 
 
+class DebugLgPrepareArgs(C.Structure):
+    """airfe_debug_lg_prepare_args (include/airfe_debug.h)"""
+    _fields_ = ([(n, C.c_int) for n in ("prec", "B", "cap", "ld", "kp_off", "normalize")] + [(n, C.c_float) for n in ("cx", "cy", "linv")]
+                + [(n, C.c_void_p) for n in ("f0", "f1", "n0", "n1", "wr", "f0x", "f1x")] + [(n, C.c_int) for n in ("n0x", "n1x", "slack_rows", "rows")]
+                + [(n, C.c_void_p) for n in ("x32", "xb", "rot_cos", "rot_sin", "lens")] + [("rows_past", C.c_int)])
+
+
+class DebugLgAssignArgs(C.Structure):
+    """airfe_debug_lg_assign_args (include/airfe_debug.h)"""
+    _fields_ = ([(n, C.c_int) for n in ("prec", "B", "n")] + [(n, C.c_void_p) for n in ("md", "x32", "w")] + [("b", C.c_float), ("lens", C.c_void_p), ("cap", C.c_int),
+                ("thr", C.c_float), ("form", C.c_int)]
+                + [(n, C.c_void_p) for n in ("pad", "z", "sim", "scores", "rowlse", "collse", "rowval", "rowarg", "colarg", "idx", "score", "nmatch")])
+
+
 # name -> (restype, argtypes); every symbol include/*.h declares
 SIGNATURES = {
     "airfe_copy_rows_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -203,6 +217,8 @@ SIGNATURES = {
     "airfe_debug_lg_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "airfe_debug_sg_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "airfe_debug_sg_sinkhorn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+    "airfe_debug_lg_prepare": (C.c_int, [C.c_void_p, C.POINTER(DebugLgPrepareArgs)]),
+    "airfe_debug_lg_assign": (C.c_int, [C.c_void_p, C.POINTER(DebugLgAssignArgs)]),
     "airfe_debug_plnet_stage0": (C.c_int, [C.c_void_p] + [C.c_void_p] * 10),
     "airfe_debug_plnet_s1": (C.c_int, [C.c_void_p, C.POINTER(Stage0), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "airfe_debug_plnet_s1_last": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),

@@ -420,6 +420,54 @@ class Context:
                                                   C.byref(ran)), "airfe_debug_sg_sinkhorn")
         return [z[i, :s.shape[0] + 1, :s.shape[1] + 1].copy() for i, s in enumerate(sims)], ran.value
 
+    def debug_lg_prepare(self, f0, f1, n0, n1, wr, prec, kp_off=1, normalize=None, second=None, slack_rows=0):
+        """launch_lg_prepare alone (include/airfe_debug.h, airfe_debug_lg_prepare): f0 / f1 [B, cap, ld] host rows, n0 / n1 [B], wr [32, 2]; normalize = (cx, cy,
+        linv) or None; second = (f0x [n0x, ld], f1x [n1x, ld]) with B = 1.  -> dict x32, xb [rows, 256], rot_cos, rot_sin [rows, 32], lens [2 Bt], rows_past, Np;
+        rows = 2 Bt Np + slack_rows."""
+        f32 = lambda t: np.ascontiguousarray(t, np.float32)
+        f0, f1, wr = f32(f0), f32(f1), f32(wr)
+        n0, n1 = np.ascontiguousarray(n0, np.int32), np.ascontiguousarray(n1, np.int32)
+        b, cap, ld = f0.shape
+        bt = 2 if second is not None else b
+        rows = 2 * bt * self.np_rows + int(slack_rows)
+        out = {"x32": np.empty((rows, 256), np.float32), "xb": np.empty((rows, 256), np.float32), "rot_cos": np.empty((rows, 32), np.float32),
+               "rot_sin": np.empty((rows, 32), np.float32), "lens": np.empty((2 * bt,), np.int32)}
+        cx, cy, linv = normalize if normalize is not None else (0.0, 0.0, 1.0)
+        a = _lib.DebugLgPrepareArgs(prec=prec, B=b, cap=cap, ld=ld, kp_off=kp_off, normalize=int(normalize is not None), cx=cx, cy=cy, linv=linv,
+                                    f0=f0.ctypes.data, f1=f1.ctypes.data, n0=n0.ctypes.data, n1=n1.ctypes.data, wr=wr.ctypes.data, slack_rows=int(slack_rows),
+                                    rows=rows, **{k: v.ctypes.data for k, v in out.items()})
+        if second is not None:
+            x0, x1 = f32(second[0]).reshape(-1, ld), f32(second[1]).reshape(-1, ld)
+            k0, k1 = np.zeros((max(len(x0), 1), ld), np.float32), np.zeros((max(len(x1), 1), ld), np.float32)      # (an empty side still needs an address)
+            k0[:len(x0)], k1[:len(x1)] = x0, x1
+            a.f0x, a.f1x, a.n0x, a.n1x = k0.ctypes.data, k1.ctypes.data, len(x0), len(x1)
+        self._chk(self._l.airfe_debug_lg_prepare(self._h, C.byref(a)), "airfe_debug_lg_prepare")
+        out["rows_past"], out["Np"] = int(a.rows_past), self.np_rows
+        return out
+
+    def debug_lg_assign(self, md, x32, lens, w, b, prec, form, cap=None, thr=0.1, pad=None):
+        """rowdot256 + the assignment tail alone (include/airfe_debug.h, airfe_debug_lg_assign): md, x32 [2B, n, 256], lens [2B] (0 allowed), w [256], b; form 0 the
+        similarity matrix + launch_lg_assign, 1 launch_lg_assign_fused.  -> dict z [2B, n], sim, scores [B, n, n], rowlse, collse, rowval, rowarg, colarg [B, n],
+        idx [B, cap, 2], score [B, cap], nmatch [B]: the device's buffers as the launches left them, their poison included."""
+        f32 = lambda t: np.ascontiguousarray(t, np.float32)
+        md, x32, w = f32(md), f32(x32), f32(w)
+        lens = np.ascontiguousarray(lens, np.int32).reshape(-1)
+        s, n, _ = md.shape
+        bb = s // 2
+        cap = self.np_rows if cap is None else int(cap)
+        out = {"z": np.empty((s, n), np.float32), "sim": np.empty((bb, n, n), np.float32), "scores": np.empty((bb, n, n), np.float32),
+               "rowlse": np.empty((bb, n), np.float32), "collse": np.empty((bb, n), np.float32), "rowval": np.empty((bb, n), np.float32),
+               "rowarg": np.empty((bb, n), np.int32), "colarg": np.empty((bb, n), np.int32), "idx": np.empty((bb, cap, 2), np.int32),
+               "score": np.empty((bb, cap), np.float32), "nmatch": np.empty((bb,), np.int32)}
+        assert x32.shape == md.shape and len(lens) == s and s % 2 == 0
+        a = _lib.DebugLgAssignArgs(prec=prec, B=bb, n=n, md=md.ctypes.data, x32=x32.ctypes.data, w=w.ctypes.data, b=float(b), lens=lens.ctypes.data, cap=cap,
+                                   thr=float(thr), form=int(form), **{k: v.ctypes.data for k, v in out.items()})
+        if pad is not None:
+            pad = f32(pad)
+            a.pad = pad.ctypes.data
+        self._chk(self._l.airfe_debug_lg_assign(self._h, C.byref(a)), "airfe_debug_lg_assign")
+        return out
+
     def detector_maps(self, b: int = 1):
         heat = np.empty((b, 512, 512), np.float32)
         nms = np.empty((b, 512, 512), np.float32)

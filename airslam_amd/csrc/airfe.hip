@@ -2281,6 +2281,166 @@ int airfe_debug_attention(airfe_ctx* c, const float* q, const float* k, const fl
   return rc;
 } AIRFE_CATCH(c)
 
+/* ---- LightGlue's head and tail one launcher at a time (include/airfe_debug.h; tests/test_gpu_lg_tail.py) */
+struct DbgTmp {                                  // device allocations of one hook call, freed on every way out
+  airfe_ctx h;
+  ~DbgTmp() { for (void* p : h.allocs) (void)hipFree(p); }
+};
+
+int airfe_debug_lg_prepare(airfe_ctx* c, airfe_debug_lg_prepare_args* a) try {
+  AIRFE_ENTER(c);
+  if (!c->has_arena) return fail(c, "debug_lg_prepare: no matcher loaded");
+  if (!a || !a->f0 || !a->f1 || !a->n0 || !a->n1 || !a->wr || !a->x32 || !a->xb || !a->rot_cos || !a->rot_sin || !a->lens || (!a->f0x) != (!a->f1x))
+    return fail(c, "debug_lg_prepare: null argument");
+  const int Np = c->Np, B = a->B, Bt = a->f0x ? 2 : B;
+  if ((a->prec != 0 && a->prec != 1) || B < 1 || B > c->Pmax || (a->f0x && (B != 1 || c->Pmax < 2)) || a->cap < 1 || a->cap > Np || a->kp_off < 0 ||
+      a->ld < a->kp_off + 258 || a->slack_rows < 0)
+    return fail(c, "debug_lg_prepare: bad argument (prec 0 / 1, 1 <= B <= max_batch, a second pair with B = 1 only, 1 <= cap <= Np, ld >= kp_off + 258)");
+  for (int b = 0; b < B; ++b)
+    if (a->n0[b] < 0 || a->n0[b] > a->cap || a->n1[b] < 0 || a->n1[b] > a->cap) return fail(c, "debug_lg_prepare: every n0, n1 must lie in 0 .. cap");
+  if (a->f0x && (a->n0x < 0 || a->n0x > Np || a->n1x < 0 || a->n1x > Np)) return fail(c, "debug_lg_prepare: the second pair's lengths must lie in 0 .. Np");
+  const size_t rows = (size_t)2 * Bt * Np + (size_t)a->slack_rows, R = c->arena_rows;
+  if (rows > R || (size_t)a->rows != rows) return fail(c, "debug_lg_prepare: rows must be 2 Bt Np + slack_rows and fit the arena");
+  DbgTmp t;
+  const size_t fl = (size_t)B * a->cap * a->ld;
+  std::vector<float> hf0(a->f0, a->f0 + fl), hf1(a->f1, a->f1 + fl), hwr(a->wr, a->wr + 64);
+  std::vector<int> hn(2 * B + 2);
+  for (int b = 0; b < B; ++b) { hn[b] = a->n0[b]; hn[B + b] = a->n1[b]; }
+  hn[2 * B] = a->n0x; hn[2 * B + 1] = a->n1x;
+  float *df0 = dupload(&t.h, hf0), *df1 = dupload(&t.h, hf1), *dwr = dupload(&t.h, hwr), *df0x = nullptr, *df1x = nullptr;
+  int* dn = dupload(&t.h, hn);
+  if (a->f0x) {
+    std::vector<float> x0(a->f0x, a->f0x + (size_t)a->n0x * a->ld), x1(a->f1x, a->f1x + (size_t)a->n1x * a->ld);
+    x0.resize(x0.size() + a->ld, 0.f); x1.resize(x1.size() + a->ld, 0.f);          // (never empty)
+    df0x = dupload(&t.h, x0); df1x = dupload(&t.h, x1);
+    if (!df0x || !df1x) return fail(c, "debug_lg_prepare: allocation failed");
+  }
+  if (!df0 || !df1 || !dwr || !dn) return fail(c, "debug_lg_prepare: allocation failed");
+  hipStream_t st = c->stream;
+  HIPCHK(c, hipMemsetAsync(c->x32, 0xFF, R * 256 * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->xb, 0xFF, R * 256 * 2, st));
+  HIPCHK(c, hipMemsetAsync(c->rot_cos, 0xFF, R * 32 * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->rot_sin, 0xFF, R * 32 * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->lens, 0xFF, (size_t)2 * c->Pmax * 4, st));
+  LgPrepArgs pa;
+  pa.f0 = df0; pa.f1 = df1; pa.n0 = dn; pa.n1 = dn + B; pa.ld = a->ld; pa.kp_off = a->kp_off; pa.normalize = a->normalize;
+  pa.cx = a->cx; pa.cy = a->cy; pa.linv = a->linv; pa.wr = dwr; pa.B = B; pa.cap = a->cap; pa.Np = Np;
+  pa.x32 = c->x32; pa.xb = c->xb; pa.rot_cos = c->rot_cos; pa.rot_sin = c->rot_sin; pa.lens = c->lens;
+  if (a->f0x) { pa.f0x = df0x; pa.f1x = df1x; pa.n0x = dn + 2 * B; pa.n1x = dn + 2 * B + 1; }
+  pa.slack_rows = a->slack_rows;
+  launch_lg_prepare(a->prec, pa, st);
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (launch_status(c)) return 1;
+  std::vector<float> hx(R * 256);
+  std::vector<uint16_t> hb(R * 256);
+  HIPCHK(c, hipMemcpy(hx.data(), c->x32, hx.size() * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(hb.data(), c->xb, hb.size() * 2, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->rot_cos, c->rot_cos, rows * 32 * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->rot_sin, c->rot_sin, rows * 32 * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->lens, c->lens, (size_t)2 * Bt * 4, hipMemcpyDeviceToHost));
+  memcpy(a->x32, hx.data(), rows * 256 * 4);
+  dbg_back2(hb, rows * 256, a->prec, a->xb);
+  int past = 0;
+  for (size_t r = rows; r < R; ++r) {
+    bool touched = false;
+    for (int k = 0; k < 256 && !touched; ++k) {
+      uint32_t u;
+      memcpy(&u, &hx[r * 256 + k], 4);
+      touched = u != 0xFFFFFFFFu || hb[r * 256 + k] != 0xFFFFu;
+    }
+    past += touched;
+  }
+  a->rows_past = past;
+  // the arena as alloc_matcher_arena left it: the pipelines reset only the slack rows their own kernels can reach
+  HIPCHK(c, hipMemsetAsync(c->x32, 0, R * 256 * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->xb, 0, R * 256 * 2, st));
+  HIPCHK(c, hipMemsetAsync(c->rot_cos, 0, R * 32 * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->rot_sin, 0, R * 32 * 4, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  return 0;
+} AIRFE_CATCH(c)
+
+int airfe_debug_lg_assign(airfe_ctx* c, airfe_debug_lg_assign_args* a) try {
+  AIRFE_ENTER(c);
+  if (!c->has_arena) return fail(c, "debug_lg_assign: no matcher loaded");
+  if (!a || !a->md || !a->x32 || !a->w || !a->lens || !a->z || !a->sim || !a->scores || !a->rowlse || !a->collse || !a->rowval || !a->rowarg || !a->colarg ||
+      !a->idx || !a->score || !a->nmatch)
+    return fail(c, "debug_lg_assign: null argument");
+  const int Np = c->Np, B = a->B, n = a->n, S = 2 * B, cap = a->cap, prec = a->prec;
+  if ((prec != 0 && prec != 1) || B < 1 || B > c->Pmax || n < 1 || n > Np || cap < 1 || cap > Np || (a->form != 0 && a->form != 1))
+    return fail(c, "debug_lg_assign: bad argument (prec 0 / 1, 1 <= B <= max_batch, 1 <= n, cap <= Np, form 0 / 1)");
+  for (int s = 0; s < S; ++s)
+    if (a->lens[s] < 0 || a->lens[s] > n) return fail(c, "debug_lg_assign: every length must lie in 0 .. n");
+  const size_t M = (size_t)S * Np, blk = (size_t)Np * Np, pf = lg_assign_part_floats(B, Np);
+  std::vector<uint16_t> hmd(M * 256, 0xFFFFu);
+  std::vector<float> hx(M * 256);
+  memset(hx.data(), 0xFF, hx.size() * 4);
+  for (int s = 0; s < S; ++s) {
+    for (int i = 0; i < a->lens[s]; ++i)
+      for (int k = 0; k < 256; ++k) {
+        hmd[((size_t)s * Np + i) * 256 + k] = cvt2(a->md[((size_t)s * n + i) * 256 + k], prec);
+        hx[((size_t)s * Np + i) * 256 + k] = a->x32[((size_t)s * n + i) * 256 + k];
+      }
+    if (a->pad)
+      for (int i = a->lens[s]; i < Np; ++i)
+        for (int k = 0; k < 256; ++k) hmd[((size_t)s * Np + i) * 256 + k] = cvt2(a->pad[k], prec);
+  }
+  DbgTmp t;
+  std::vector<float> hw(a->w, a->w + 256);
+  float* dw = dupload(&t.h, hw);
+  float* dscores = dalloc<float>(&t.h, (size_t)B * blk, false);
+  int32_t* didx = dalloc<int32_t>(&t.h, (size_t)B * cap * 2, false);
+  float* dscore = dalloc<float>(&t.h, (size_t)B * cap, false);
+  int* dnm = dalloc<int>(&t.h, (size_t)B, false);
+  if (!dw || !dscores || !didx || !dscore || !dnm) return fail(c, "debug_lg_assign: allocation failed");
+  hipStream_t st = c->stream;
+  HIPCHK(c, hipMemcpyAsync(c->mdb, hmd.data(), hmd.size() * 2, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->x32, hx.data(), hx.size() * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->lens, a->lens, (size_t)S * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(c->zbuf, 0xFF, M * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->simbuf, 0xFF, (size_t)B * blk * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->lg_part, 0xFF, pf * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->lg_argpart, 0xFF, pf * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->rowlse, 0xFF, (size_t)B * Np * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->collse, 0xFF, (size_t)B * Np * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->rowval, 0xFF, (size_t)B * Np * 4, st));
+  HIPCHK(c, hipMemsetAsync(dscores, 0xFF, (size_t)B * blk * 4, st));
+  HIPCHK(c, hipMemsetAsync(dscore, 0xFF, (size_t)B * cap * 4, st));
+  HIPCHK(c, hipMemsetAsync(dnm, 0xFF, (size_t)B * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->rowarg, 0, (size_t)B * Np * 4, st));          // zero, not -1: the value that passes for a valid index
+  HIPCHK(c, hipMemsetAsync(c->colarg, 0, (size_t)B * Np * 4, st));
+  HIPCHK(c, hipMemsetAsync(didx, 0, (size_t)B * cap * 8, st));
+  launch_rowdot256(c->x32, dw, a->b, c->zbuf, (int)M, st);
+  if (a->form == 1) {
+    launch_lg_assign_fused(prec, c->mdb, c->zbuf, c->lens, B, Np, cap, a->thr, c->lg_part, c->lg_argpart, c->rowlse, c->collse, c->simbuf, dscores, c->rowarg,
+                           c->rowval, c->colarg, didx, dscore, dnm, st);
+  } else {
+    launch_sim(prec, c->mdb, c->simbuf, B, Np, st);
+    launch_lg_assign(c->simbuf, c->zbuf, c->lens, B, Np, cap, a->thr, c->rowlse, c->collse, dscores, c->rowarg, c->rowval, c->colarg, didx, dscore, dnm, st);
+  }
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (launch_status(c)) return 1;
+  const size_t nb = (size_t)n * 4, npb = (size_t)Np * 4;
+  HIPCHK(c, hipMemcpy2D(a->z, nb, c->zbuf, npb, nb, S, hipMemcpyDeviceToHost));
+  for (int b = 0; b < B; ++b) {
+    HIPCHK(c, hipMemcpy2D(a->sim + (size_t)b * n * n, nb, c->simbuf + b * blk, npb, nb, n, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy2D(a->scores + (size_t)b * n * n, nb, dscores + b * blk, npb, nb, n, hipMemcpyDeviceToHost));
+  }
+  HIPCHK(c, hipMemcpy2D(a->rowlse, nb, c->rowlse, npb, nb, B, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy2D(a->collse, nb, c->collse, npb, nb, B, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy2D(a->rowval, nb, c->rowval, npb, nb, B, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy2D(a->rowarg, nb, c->rowarg, npb, nb, B, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy2D(a->colarg, nb, c->colarg, npb, nb, B, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->idx, didx, (size_t)B * cap * 8, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->score, dscore, (size_t)B * cap * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->nmatch, dnm, (size_t)B * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemsetAsync(c->mdb, 0, M * 256 * 2, st));          // no NaN token rows stay behind
+  HIPCHK(c, hipMemsetAsync(c->x32, 0, M * 256 * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->zbuf, 0, M * 4, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  return 0;
+} AIRFE_CATCH(c)
+
 /* ---- BoW keyframe database (include/airfe.h "BoW keyframe database"; kernels_bowdb.hip) ------------------------------------------------------------- */
 }  // extern "C" (the database object is a C++ struct behind an opaque pointer)
 

@@ -353,11 +353,13 @@ __global__ __launch_bounds__(1024) void lg_filter_kernel(const int* __restrict__
                                                          float* __restrict__ score, int* __restrict__ nmatch) {
   __shared__ unsigned wsum[16];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int n0 = lens[2 * b];
+  const int n0 = lens[2 * b], n1 = lens[2 * b + 1];
   bool ok = false;
   int col = 0;
   float e = 0.f;
-  if (tid < n0) {
+  // (n1 > 0 as in lg_filter_fused_kernel: an empty second image has no matches, point_matcher.cc:53-55 — its rows keep (0, 0.0f) and no column kernel wrote
+  // colarg, so that row 0 would pass on whatever an earlier call left in colarg[0], with exp(0) = 1 > thr)
+  if (tid < n0 && n1 > 0) {
     col = rowarg[(size_t)b * Np + tid];
     e = expf_like_glibc(rowval[(size_t)b * Np + tid]);
     ok = (colarg[(size_t)b * Np + col] == tid) && (e > thr);

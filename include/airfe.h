@@ -600,7 +600,10 @@ int airfe_detect_points_batch_dev(airfe_ctx* ctx, const uint8_t* d_gray, int B, 
                                   size_t img_stride, float* d_feat, int cap, int* d_n, void* stream);
 /* LightGlue on B pairs of device feature matrices (259-float rows, ORIGINAL pixel coords; NormalizeKeypoints with
  *   cfg.image_width/height is applied on the device exactly as src/point_matcher.cc:39-48 does on the host).
- *   d_idx [B][mcap][2], d_score [B][mcap], d_nmatch [B]. */
+ *   d_idx [B][mcap][2], d_score [B][mcap], d_nmatch [B].
+ *   Empty frames: d_n0[b] = 0 and / or d_n1[b] = 0 is valid input (a frame without detections; the counts are read on the device, there is no host-side
+ *   early-out).  Such a pair gets d_nmatch[b] = 0 and none of its d_idx / d_score entries is written, in either assignment form
+ *   (≙ src/point_matcher.cc:53-55, which returns before the engine runs); the other pairs of the batch are not affected. */
 int airfe_match_lightglue_batch_dev(airfe_ctx* ctx, const float* d_f0, const int* d_n0, const float* d_f1, const int* d_n1,
                                     int B, int cap, int32_t* d_idx, float* d_score, int mcap, int* d_nmatch, void* stream);
 /* SuperGlue on B pairs (as above; NormalizeKeypoints scale 0.7, src/point_matcher.cc:58): d_idx0 / d_idx1 [B][cap] (-1 = unmatched,

@@ -123,6 +123,55 @@ int airfe_debug_ln_gelu(airfe_ctx* ctx, int prec, float* h, const float* gamma, 
  * sequence s attends to sequence s ^ 1.  out [S][n][H*64] fp32.  n <= max_keypoints (rounded up to 16 inside); S * H a multiple of 8.  The way to drive the kernel's
  * re-centring path (a tile whose partial row sums leave the 2-byte range) with hand-built logits. */
 int airfe_debug_attention(airfe_ctx* ctx, const float* q, const float* k, const float* v, const int* lens, int S, int H, int n, int cross, float* out);
+/* ---- LightGlue's head and tail one launcher at a time (tests/test_gpu_lg_tail.py, tests/lg_tail_ref.py).  HOST tensors in, the production launchers on the
+ * context's own arena, HOST tensors out; nothing here has a kernel of its own, and no production launch path changes. */
+/* launch_lg_prepare alone.  EVERY token row of the arena (x32, xb, rot_cos, rot_sin, the slack included) is 0xFF bytes (NaN in every type) when the launch
+ * starts, so a finite output row was written by this launch; rows_past counts the arena rows at or beyond `rows` that the launch changed (0: none).  The arena is
+ * zero again when the hook returns.  Bt = B, or 2 with the second pair (f0x: B must be 1); rows = 2 Bt Np + slack_rows <= the arena's rows. */
+typedef struct airfe_debug_lg_prepare_args {
+  int prec;                       /* 0 = bf16, 1 = fp16 (the type of xb) */
+  int B, cap, ld, kp_off;         /* f0 / f1 [B][cap][ld] rows, x at column kp_off, the 256 descriptor floats from kp_off + 2 (ld 259: kp_off 1; ld 258: 0) */
+  int normalize;
+  float cx, cy, linv;
+  const float *f0, *f1;
+  const int *n0, *n1;             /* [B], each 0 .. cap */
+  const float* wr;                /* [32][2] */
+  const float *f0x, *f1x;         /* the second pair's rows [n0x][ld], [n1x][ld], or both NULL */
+  int n0x, n1x;
+  int slack_rows;
+  int rows;                       /* 2 Bt Np + slack_rows: the rows of the four outputs */
+  float *x32, *xb;                /* [rows][256]; xb widened to float */
+  float *rot_cos, *rot_sin;       /* [rows][32] */
+  int* lens;                      /* [2 Bt] */
+  int rows_past;
+} airfe_debug_lg_prepare_args;
+int airfe_debug_lg_prepare(airfe_ctx* ctx, airfe_debug_lg_prepare_args* a);
+/* launch_rowdot256, then form 0: launch_sim + launch_lg_assign (lg_lse_kernel / lg_arg_kernel for B <= 8, the four separate kernels above) or form 1:
+ * launch_lg_assign_fused with sim_out and scores_out set.  Sequence s (0 .. 2B-1; pair b = sequences 2b, 2b + 1) has lens[s] rows (0 allowed) of md and x32, n rows
+ * apart.  When the launches start: rows of mdb and x32 at or beyond a sequence's length are 0xFF bytes (NaN) — or, with `pad` [256] given, mdb's hold `pad` rounded to
+ * `prec` (a finite value that an unmasked maximum would pick up, which a NaN is not: fmaxf drops it); simbuf, both partial arrays, rowlse, collse, scores,
+ * rowval and score are NaN, nmatch is 0xFF, and rowarg, colarg and idx are ZERO — the value that passes for a valid index.  Outputs are dense per pair with stride
+ * n (cap for idx / score) and come back as the device left them, poison included, over all n rows and columns. */
+typedef struct airfe_debug_lg_assign_args {
+  int prec, B, n;                 /* n <= Np */
+  const float* md;                /* [2B][n][256], rounded to prec by the hook */
+  const float* x32;               /* [2B][n][256] */
+  const float* w;                 /* [256] matchability weight */
+  float b;
+  const int* lens;                /* [2B] */
+  int cap;                        /* 1 .. Np */
+  float thr;
+  int form;
+  const float* pad;               /* [256] or NULL */
+  float* z;                       /* [2B][n] */
+  float *sim, *scores;            /* [B][n][n] */
+  float *rowlse, *collse, *rowval;/* [B][n] */
+  int32_t *rowarg, *colarg;       /* [B][n] */
+  int32_t* idx;                   /* [B][cap][2] */
+  float* score;                   /* [B][cap] */
+  int32_t* nmatch;                /* [B] */
+} airfe_debug_lg_assign_args;
+int airfe_debug_lg_assign(airfe_ctx* ctx, airfe_debug_lg_assign_args* a);
 /* error-path test of cfg.check_launches: the NEXT group of launches of profiling stage `stage` (airfe_profile_stage_name's index) is preceded by one
  * deliberately invalid launch (4096 threads per workgroup), so that the entry that makes it must fail with "<stage name>: kernel launch failed: ..." —
  * with check_launches = 0 the same failure surfaces at the pipeline's end without the stage.  -1 disarms. */

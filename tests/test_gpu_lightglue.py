@@ -1,6 +1,9 @@
 """LightGlue parity on the GPU (C ABI) vs the CPU oracle.  The structured synthetic weights make the planted half of every
 pair match (203 matches at N = 400, 514 at N = 1024 in the oracle), so filter_matches, the match buffers and the batch paths
-are exercised on hundreds of entries; match INDEX SETS must be identical to the fp32 oracle's."""
+are exercised on hundreds of entries; match INDEX SETS must be identical to the fp32 oracle's.
+
+The gates here absorb a whole 2-byte network.  The kernels of the head and the tail (prepare, matchability, similarity, both assignment forms, the filters) are
+held to float64 references with derived bounds, one launcher at a time, in tests/test_gpu_lg_tail.py."""
 import math
 
 import numpy as np
@@ -507,5 +510,32 @@ def test_assignment_partials_cover_a_batch_of_ragged_pairs():
             want_idx, want_sc = ctx.match_lightglue(p[2], p[3])
             k = int(nm[i])
             assert k == len(want_idx), (fused, i, k, len(want_idx))
+            np.testing.assert_array_equal(idx[i, :k].cpu().numpy(), want_idx)
+            np.testing.assert_array_equal(sc[i, :k].cpu().numpy(), want_sc)
+
+
+def test_empty_frames_in_a_batch_have_no_matches():
+    """A frame without detections reaches the matcher (the batch entry reads the counts on the device: there is no host-side early-out): a pair with an empty
+    right or an empty left frame reports no match in either assignment form (include/airfe.h; the reference returns before its engine: point_matcher.cc:53-55),
+    and the pairs around it are what they are alone."""
+    import torch
+    lens = [(129, 200), (200, 0), (0, 150), (65, 97)]
+    B = len(lens)
+    for fused in (1, 0):
+        ctx, _, _ = context("lg", tuning={"assign_fused": fused}, max_batch=8)
+        pairs = [_pair(max(n0, 1), max(n1, 1), 950 + i) for i, (n0, n1) in enumerate(lens)]
+        f0 = torch.zeros((B, 400, 259)); f1 = torch.zeros((B, 400, 259))
+        for i, (p, (n0, n1)) in enumerate(zip(pairs, lens)):
+            f0[i, :n0] = torch.from_numpy(p[0][:n0]); f1[i, :n1] = torch.from_numpy(p[1][:n1])
+        n0t = torch.tensor([l[0] for l in lens], dtype=torch.int32); n1t = torch.tensor([l[1] for l in lens], dtype=torch.int32)
+        idx = torch.zeros((B, 400, 2), dtype=torch.int32).cuda(); sc = torch.zeros((B, 400)).cuda(); nm = torch.full((B,), -1, dtype=torch.int32).cuda()
+        ctx.match_lightglue_batch_dev(f0.cuda(), n0t.cuda(), f1.cuda(), n1t.cuda(), idx, sc, nm)
+        ctx.sync()
+        assert nm.cpu().tolist()[1:3] == [0, 0], (fused, nm.cpu().tolist(), idx[1:3, :1].cpu().tolist(), sc[1:3, :1].cpu().tolist())
+        assert not idx[1:3].any() and not sc[1:3].any()
+        for i in (0, 3):
+            want_idx, want_sc = ctx.match_lightglue(pairs[i][2], pairs[i][3])
+            k = int(nm[i])
+            assert k == len(want_idx) and k > 0, (fused, i, k, len(want_idx))
             np.testing.assert_array_equal(idx[i, :k].cpu().numpy(), want_idx)
             np.testing.assert_array_equal(sc[i, :k].cpu().numpy(), want_sc)
