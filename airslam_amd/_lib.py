@@ -90,6 +90,12 @@ class DebugLgAssignArgs(C.Structure):
                 + [(n, C.c_void_p) for n in ("pad", "z", "sim", "scores", "rowlse", "collse", "rowval", "rowarg", "colarg", "idx", "score", "nmatch")])
 
 
+class DebugAttentionArgs(C.Structure):
+    """airfe_debug_attn_args (include/airfe_debug.h)"""
+    _fields_ = ([(n, C.c_int) for n in ("prec", "S", "H", "n", "cross")] + [(n, C.c_void_p) for n in ("q", "k", "v", "lens")]
+                + [("canary", C.c_int), ("raw", C.c_int), ("out", C.c_void_p), ("Np", C.c_int), ("rows_past", C.c_int)])
+
+
 # name -> (restype, argtypes); every symbol include/*.h declares
 SIGNATURES = {
     "airfe_copy_rows_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -237,6 +243,7 @@ SIGNATURES = {
     "airfe_debug_qkv": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p] * 3),
     "airfe_debug_lg_block": (C.c_int, [C.c_void_p, C.POINTER(DebugLgBlockArgs)]),
     "airfe_debug_ln_gelu": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "airfe_debug_attention_args": (C.c_int, [C.c_void_p, C.POINTER(DebugAttentionArgs)]),
     "airfe_debug_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
 

@@ -601,16 +601,25 @@ class Context:
         self._chk(self._l.airfe_debug_ln_gelu(self._h, prec, h.ctypes.data, gamma.ctypes.data, beta.ctypes.data, h.shape[0]), "airfe_debug_ln_gelu")
         return h
 
-    def debug_attention(self, q, k, v, lens, cross=False):
-        """The matcher's flash attention alone (include/airfe_debug.h): q, k, v [S, H, n, 64] fp32 (scale and log2 e already inside q / k), lens [S] -> out [S, n, H * 64]."""
+    def debug_attention(self, q, k, v, lens, cross=False, prec=None, raw=False):
+        """The matcher's flash attention alone (include/airfe_debug.h): q, k, v [S, H, n, 64] fp32 (scale and log2 e already inside q / k), lens [S] -> out [S, n, H * 64].
+        prec None: airfe_debug_attention (the context's matcher_precision, an output buffer as the allocator left it).  prec 0 (bf16) / 1 (fp16):
+        airfe_debug_attention_args with the canary — rows that the launch did not write come back NaN; raw: -> (out [S, Np, H * 64] with every padded row, rows_past)."""
         q = np.ascontiguousarray(q, np.float32); k = np.ascontiguousarray(k, np.float32); v = np.ascontiguousarray(v, np.float32)
         lens = np.ascontiguousarray(lens, np.int32)
         s, h, n, d = q.shape
         assert d == 64 and k.shape == q.shape and v.shape == q.shape and lens.shape == (s,)
-        out = np.empty((s, n, h * 64), np.float32)
-        self._chk(self._l.airfe_debug_attention(self._h, q.ctypes.data, k.ctypes.data, v.ctypes.data, lens.ctypes.data, s, h, n, int(cross), out.ctypes.data),
-                  "airfe_debug_attention")
-        return out
+        if prec is None:
+            assert not raw, "raw rows come from airfe_debug_attention_args: give prec"
+            out = np.empty((s, n, h * 64), np.float32)
+            self._chk(self._l.airfe_debug_attention(self._h, q.ctypes.data, k.ctypes.data, v.ctypes.data, lens.ctypes.data, s, h, n, int(cross), out.ctypes.data),
+                      "airfe_debug_attention")
+            return out
+        out = np.empty((s, (n + 15) // 16 * 16 if raw else n, h * 64), np.float32)
+        a = _lib.DebugAttentionArgs(prec=int(prec), S=s, H=h, n=n, cross=int(cross), q=q.ctypes.data, k=k.ctypes.data, v=v.ctypes.data, lens=lens.ctypes.data,
+                                    canary=1, raw=int(raw), out=out.ctypes.data)
+        self._chk(self._l.airfe_debug_attention_args(self._h, C.byref(a)), "airfe_debug_attention_args")
+        return (out, a.rows_past) if raw else out
 
     # ---------------------------------------------------------------- device-resident batch (torch plumbing)
     def detect_batch_dev(self, gray_t, feat_t, n_t, stream=None):

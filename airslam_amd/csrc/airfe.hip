@@ -2236,57 +2236,78 @@ int airfe_debug_ln_gelu(airfe_ctx* c, int prec, float* h, const float* gamma, co
   for (void* p : tmp.allocs) (void)hipFree(p);
   return rc;
 } AIRFE_CATCH(c)
+}  // extern "C"
 
-int airfe_debug_attention(airfe_ctx* c, const float* q, const float* k, const float* v, const int* lens, int S, int H, int n, int cross, float* out) try {
-  AIRFE_ENTER(c);
-  if (c->mprec == 2) return fail(c, "debug_attention drives the 2-byte kernel (matcher_precision fp16 / bf16)");
-  if (S < 1 || H < 1 || n < 1 || (S * H) % 8 != 0 || (cross && (S & 1))) return fail(c, "debug_attention: S * H must be a multiple of 8 (cross: S even)");
-  if (!q || !k || !v || !lens || !out) return fail(c, "debug_attention: null argument");
+struct DbgTmp {                                  // device allocations of one hook call, freed on every way out
+  airfe_ctx h;
+  ~DbgTmp() { for (void* p : h.allocs) (void)hipFree(p); }
+};
+
+// the body of both attention hooks (the callers hold the context and catch)
+static int dbg_attention_run(airfe_ctx* c, airfe_debug_attn_args* a, const char* who) {
+  const std::string w = std::string(who) + ": ";
+  const int S = a->S, H = a->H, n = a->n, cross = a->cross, prec = a->prec;
+  if (prec != 0 && prec != 1) return fail(c, w + "prec must be 0 (bf16) or 1 (fp16)");
+  if (S < 1 || H < 1 || n < 1 || (S * H) % 8 != 0 || (cross && (S & 1))) return fail(c, w + "S * H must be a multiple of 8 (cross: S even)");
+  if (!a->q || !a->k || !a->v || !a->lens || !a->out) return fail(c, w + "null argument");
   for (int s = 0; s < S; ++s)
-    if (lens[s] < 0 || lens[s] > n) return fail(c, "debug_attention: lens[s] must lie in 0 .. n");
-  const int Np = (n + 15) / 16 * 16, prec = c->mprec;
-  const size_t rows = (size_t)S * H * Np + 128;                      // (+ slack: the last key tile reads up to 63 rows past a sequence)
+    if (a->lens[s] < 0 || a->lens[s] > n) return fail(c, w + "lens[s] must lie in 0 .. n");
+  const int Np = (n + 15) / 16 * 16;
+  a->Np = Np; a->rows_past = 0;
+  const size_t rows = (size_t)S * H * Np + 128;                      // (+ slack: the last key tile reads up to 63 rows past a sequence; it stays ZERO like the arena's)
   std::vector<uint16_t> hq(rows * 64, 0), hk(rows * 64, 0), hvt(rows * 64, 0);
   for (int s = 0; s < S; ++s)
     for (int h = 0; h < H; ++h)
       for (int i = 0; i < n; ++i)
         for (int d = 0; d < 64; ++d) {
           const size_t src = (((size_t)s * H + h) * n + i) * 64 + d;
-          hq[(((size_t)s * H + h) * Np + i) * 64 + d] = cvt2(q[src], prec);
-          hk[(((size_t)s * H + h) * Np + i) * 64 + d] = cvt2(k[src], prec);
-          hvt[(((size_t)s * H + h) * 64 + d) * Np + i] = cvt2(v[src], prec);       // V^T [S][H][64][Np]
+          hq[(((size_t)s * H + h) * Np + i) * 64 + d] = cvt2(a->q[src], prec);
+          hk[(((size_t)s * H + h) * Np + i) * 64 + d] = cvt2(a->k[src], prec);
+          hvt[(((size_t)s * H + h) * 64 + d) * Np + i] = cvt2(a->v[src], prec);       // V^T [S][H][64][Np]
         }
-  airfe_ctx tmp;   // only as an allocation list holder
-  uint16_t *dq = dupload(&tmp, hq), *dk = dupload(&tmp, hk), *dv = dupload(&tmp, hvt);
-  uint16_t* dout = dalloc<uint16_t>(&tmp, ((size_t)S * Np + 128) * H * 64);
-  std::vector<int> hl(lens, lens + S);
-  int* dl = dupload(&tmp, hl);
-  int rc = 0;
-  if (!dq || !dk || !dv || !dout || !dl) rc = fail(c, "debug_attention: allocation failed");
-  if (!rc) {
-    launch_attention32(prec, dq, dk, dv, dout, dl, S, H, Np, cross, c->stream);
-    if (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c)) rc = rc ? rc : fail(c, "debug_attention: kernel failed");
-  }
-  if (!rc) {
-    std::vector<uint16_t> ho((size_t)S * Np * H * 64);
-    (void)hipMemcpy(ho.data(), dout, ho.size() * 2, hipMemcpyDeviceToHost);
-    for (int s = 0; s < S; ++s)
-      for (int i = 0; i < n; ++i)
-        for (int f = 0; f < H * 64; ++f) {
-          const uint16_t u = ho[((size_t)s * Np + i) * H * 64 + f];
-          out[((size_t)s * n + i) * H * 64 + f] = back2(u, prec);
-        }
-  }
-  for (void* p : tmp.allocs) (void)hipFree(p);
-  return rc;
+  DbgTmp t;
+  airfe_ctx* tmp = &t.h;   // only as an allocation list holder
+  uint16_t *dq = dupload(tmp, hq), *dk = dupload(tmp, hk), *dv = dupload(tmp, hvt);
+  const size_t out_n = (size_t)S * Np * H * 64, slack_n = (size_t)128 * H * 64;
+  uint16_t* dout = dalloc<uint16_t>(tmp, out_n + slack_n);
+  std::vector<int> hl(a->lens, a->lens + S);
+  int* dl = dupload(tmp, hl);
+  if (!dq || !dk || !dv || !dout || !dl) return fail(c, w + "allocation failed");
+  if (a->canary && hipMemsetAsync(dout, 0xFF, (out_n + slack_n) * 2, c->stream) != hipSuccess) return fail(c, w + "memset failed");
+  launch_attention32(prec, dq, dk, dv, dout, dl, S, H, Np, cross, c->stream);
+  if (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c)) return fail(c, w + "kernel failed");
+  std::vector<uint16_t> ho(out_n + slack_n);
+  if (hipMemcpy(ho.data(), dout, ho.size() * 2, hipMemcpyDeviceToHost) != hipSuccess) return fail(c, w + "copy failed");
+  const int rows_out = a->raw ? Np : n;
+  for (int s = 0; s < S; ++s)
+    for (int i = 0; i < rows_out; ++i)
+      for (int f = 0; f < H * 64; ++f) a->out[((size_t)s * rows_out + i) * H * 64 + f] = back2(ho[((size_t)s * Np + i) * H * 64 + f], prec);
+  if (a->canary)
+    for (int r = 0; r < 128; ++r) {
+      bool changed = false;
+      for (int f = 0; f < H * 64 && !changed; ++f) changed = ho[out_n + (size_t)r * H * 64 + f] != 0xFFFFu;
+      a->rows_past += changed;
+    }
+  return 0;
+}
+
+extern "C" {
+int airfe_debug_attention(airfe_ctx* c, const float* q, const float* k, const float* v, const int* lens, int S, int H, int n, int cross, float* out) try {
+  AIRFE_ENTER(c);
+  if (c->mprec == 2) return fail(c, "debug_attention drives the 2-byte kernel (matcher_precision fp16 / bf16)");
+  airfe_debug_attn_args a = {};
+  a.prec = c->mprec; a.S = S; a.H = H; a.n = n; a.cross = cross;
+  a.q = q; a.k = k; a.v = v; a.lens = lens; a.out = out;                 // canary = 0, raw = 0: the output buffer as the allocator left it, the first n rows back
+  return dbg_attention_run(c, &a, "debug_attention");
+} AIRFE_CATCH(c)
+
+int airfe_debug_attention_args(airfe_ctx* c, airfe_debug_attn_args* a) try {
+  AIRFE_ENTER(c);
+  if (!a) return fail(c, "debug_attention_args: null argument");
+  return dbg_attention_run(c, a, "debug_attention_args");
 } AIRFE_CATCH(c)
 
 /* ---- LightGlue's head and tail one launcher at a time (include/airfe_debug.h; tests/test_gpu_lg_tail.py) */
-struct DbgTmp {                                  // device allocations of one hook call, freed on every way out
-  airfe_ctx h;
-  ~DbgTmp() { for (void* p : h.allocs) (void)hipFree(p); }
-};
-
 int airfe_debug_lg_prepare(airfe_ctx* c, airfe_debug_lg_prepare_args* a) try {
   AIRFE_ENTER(c);
   if (!c->has_arena) return fail(c, "debug_lg_prepare: no matcher loaded");

@@ -123,6 +123,22 @@ int airfe_debug_ln_gelu(airfe_ctx* ctx, int prec, float* h, const float* gamma, 
  * sequence s attends to sequence s ^ 1.  out [S][n][H*64] fp32.  n <= max_keypoints (rounded up to 16 inside); S * H a multiple of 8.  The way to drive the kernel's
  * re-centring path (a tile whose partial row sums leave the 2-byte range) with hand-built logits. */
 int airfe_debug_attention(airfe_ctx* ctx, const float* q, const float* k, const float* v, const int* lens, int S, int H, int n, int cross, float* out);
+/* the same launch with the 2-byte type per call (one context serves both instantiations) and, with canary = 1, an output buffer that is 0xFF bytes (NaN in both
+ * types), its 128 slack rows included, when the launch starts: the rows come back as the device left them, so a finite row is one that THIS launch wrote, and
+ * rows_past counts the slack rows behind the last sequence that it changed (0: none).  The K, Q and V^T slack behind the last sequence stays zero, as the arena's is:
+ * V^T is read there under a zero weight, and 0 * NaN would be NaN.  raw = 1: all Np = 16 ceil(n / 16) rows of every sequence come back (out [S][Np][H*64]) instead of
+ * the first n.  lens[s] = 0 is allowed on either side.  airfe_debug_attention is this entry with the context's matcher_precision, canary = 0 and raw = 0.  Nothing
+ * here has a kernel of its own, and no production launch path changes. */
+typedef struct airfe_debug_attn_args {
+  int prec;                       /* 0 = bf16, 1 = fp16 */
+  int S, H, n, cross;             /* S * H a multiple of 8; cross: S even */
+  const float *q, *k, *v;         /* [S][H][n][64] */
+  const int* lens;                /* [S], each 0 .. n */
+  int canary, raw;
+  float* out;                     /* [S][raw ? Np : n][H*64] */
+  int Np, rows_past;              /* out */
+} airfe_debug_attn_args;
+int airfe_debug_attention_args(airfe_ctx* ctx, airfe_debug_attn_args* a);
 /* ---- LightGlue's head and tail one launcher at a time (tests/test_gpu_lg_tail.py, tests/lg_tail_ref.py).  HOST tensors in, the production launchers on the
  * context's own arena, HOST tensors out; nothing here has a kernel of its own, and no production launch path changes. */
 /* launch_lg_prepare alone.  EVERY token row of the arena (x32, xb, rot_cos, rot_sin, the slack included) is 0xFF bytes (NaN in every type) when the launch
