@@ -45,6 +45,12 @@ class RelocCfg(C.Structure):
                 ("pose_refinement", C.c_int), ("cam", C.c_double * 5), ("thr", C.c_double * 2)]
 
 
+class LoopCfg(C.Structure):
+    """airfe_loop_cfg (include/airfe.h)"""
+    _fields_ = [("ratio", C.c_float), ("min_words", C.c_int), ("K", C.c_int), ("outlier_rejection", C.c_int), ("distance_rate", C.c_double),
+                ("min_matches", C.c_int), ("min_points", C.c_int), ("min_inliers", C.c_int), ("cam", C.c_double * 5), ("thr", C.c_double * 2)]
+
+
 class SeqPolicy(C.Structure):
     """airfe_seq_policy (include/airfe_seq.h)"""
     _fields_ = [("min_init_stereo_feature", C.c_int), ("min_num_match", C.c_int), ("max_num_match", C.c_int), ("tracking_point_rate", C.c_float),
@@ -169,6 +175,15 @@ SIGNATURES = {
     "airfe_bowdb_group_dev": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p] * 8),
     "airfe_relocalize_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RelocCfg), C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9 +
                                    [C.c_int] + [C.c_void_p] * 3),
+    "airfe_bowdb_set_poses": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "airfe_bowdb_get_poses": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "airfe_bowdb_set_u_right_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "airfe_bowdb_set_u_right": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "airfe_bowdb_get_u_right": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "airfe_bowdb_query_stored_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] +
+                                           [C.c_void_p] * 4),
+    "airfe_loop_detect_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(LoopCfg), C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_int] +
+                                    [C.c_void_p] * 3),
     "airfe_set_rectify_maps": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "airfe_rectify_detect_points": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                               C.POINTER(C.c_int)]),

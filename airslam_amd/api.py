@@ -1075,6 +1075,55 @@ class BowDatabase:
             stage_t.data_ptr(), Twc_t.data_ptr(), best_t.data_ptr(), num_t.data_ptr(), mask_t.data_ptr(), idx_t.data_ptr(), score_t.data_ptr(), idx_t.shape[1],
             nmatch_t.data_ptr(), opt(pnp_count_t), self._ctx._stream(stream)), "airfe_relocalize_batch_dev")
 
+    # ---- loop detection over a loaded map (include/airfe.h "Map state for loop detection", "Stored queries against their predecessors", "Loop detection
+    # composite")
+    def set_poses(self, first_frame: int, Twc: np.ndarray):
+        """host buffer Twc [B][16] (or [B][4][4]) float64 row-major -> the pose table; the translation columns also become the positions group_dev reads"""
+        Twc = np.ascontiguousarray(Twc, np.float64).reshape(-1, 16)
+        self._ctx._chk(self._l.airfe_bowdb_set_poses(self._h, int(first_frame), Twc.shape[0], Twc.ctypes.data), "airfe_bowdb_set_poses")
+
+    def get_poses(self, first_frame: int, B: int) -> np.ndarray:
+        Twc = np.empty((B, 16), np.float64)
+        self._ctx._chk(self._l.airfe_bowdb_get_poses(self._h, int(first_frame), B, Twc.ctypes.data), "airfe_bowdb_get_poses")
+        return Twc
+
+    def set_u_right(self, first_frame: int, u_right: np.ndarray):
+        """host buffer u_right [B][cap] float64: the stored frames' right-image columns (> 0: the row has a stereo match)"""
+        u_right = np.ascontiguousarray(u_right, np.float64).reshape(-1, self.cap)
+        self._ctx._chk(self._l.airfe_bowdb_set_u_right(self._h, int(first_frame), u_right.shape[0], u_right.ctypes.data), "airfe_bowdb_set_u_right")
+
+    def set_u_right_dev(self, first_frame: int, u_right_t, stream=None):
+        self._ctx._chk(self._l.airfe_bowdb_set_u_right_dev(self._h, int(first_frame), u_right_t.shape[0], u_right_t.data_ptr(), self._ctx._stream(stream)),
+                       "airfe_bowdb_set_u_right_dev")
+
+    def get_u_right(self, first_frame: int, B: int) -> np.ndarray:
+        u = np.empty((B, self.cap), np.float64)
+        self._ctx._chk(self._l.airfe_bowdb_get_u_right(self._h, int(first_frame), B, u.ctypes.data), "airfe_bowdb_get_u_right")
+        return u
+
+    def query_stored_batch_dev(self, qframe_t, cand_frame_t, cand_sharing_t, cand_score_t, ncand_t, max_sharing_t, ratio=0.5, min_words=8,
+                               exclude_covisible=False, sharing_t=None, stream=None):
+        """map_refiner.cc:95-130 for stored frames qframe [Q] i32: frame fq against frames 0 .. fq - 1 only (max_sharing and the threshold over that prefix),
+        optionally without its covisible frames -> query_batch_dev's outputs; sharing [Q][size] i32 (dense counts, 0 from fq on), optional."""
+        self._ctx._chk(self._l.airfe_bowdb_query_stored_batch_dev(
+            self._h, qframe_t.data_ptr(), qframe_t.shape[0], float(ratio), int(min_words), 1 if exclude_covisible else 0, cand_frame_t.data_ptr(),
+            cand_sharing_t.data_ptr(), cand_score_t.data_ptr(), cand_frame_t.shape[1], ncand_t.data_ptr(), max_sharing_t.data_ptr(),
+            sharing_t.data_ptr() if sharing_t is not None else None, self._ctx._stream(stream)), "airfe_bowdb_query_stored_batch_dev")
+
+    def loop_detect_batch_dev(self, qframe_t, cam, thr, ok_t, stage_t, loop_t, Twq_t, Rlq_t, tlq_t, num_t, mask_t, idx_t, score_t, nmatch_t, ncons_t=None,
+                              K=5, ratio=0.5, min_words=8, outlier_rejection=True, distance_rate=0.03, min_matches=50, min_points=50, min_inliers=50,
+                              stream=None):
+        """airfe_loop_detect_batch_dev (map_refiner.cc:65-333): stored frames qframe [Q] i32 -> ok / stage [Q] i32, loop [Q] i32 (the loop frame or -1),
+        Twq [Q][16], Rlq [Q][9], tlq [Q][3] f64, num [Q], mask [Q][mcap] u8 by list entry, the winner's list idx [Q][mcap][2] / score [Q][mcap] /
+        nmatch [Q], ncons [Q] (optional)."""
+        from . import _lib
+        cfg = _lib.LoopCfg(float(ratio), int(min_words), int(K), 1 if outlier_rejection else 0, float(distance_rate), int(min_matches), int(min_points),
+                           int(min_inliers), (C.c_double * 5)(*[float(x) for x in cam]), (C.c_double * 2)(*[float(x) for x in thr]))
+        self._ctx._chk(self._l.airfe_loop_detect_batch_dev(
+            self._ctx._h, self._h, C.byref(cfg), qframe_t.data_ptr(), qframe_t.shape[0], ok_t.data_ptr(), stage_t.data_ptr(), loop_t.data_ptr(),
+            Twq_t.data_ptr(), Rlq_t.data_ptr(), tlq_t.data_ptr(), num_t.data_ptr(), mask_t.data_ptr(), idx_t.data_ptr(), score_t.data_ptr(), idx_t.shape[1],
+            nmatch_t.data_ptr(), ncons_t.data_ptr() if ncons_t is not None else None, self._ctx._stream(stream)), "airfe_loop_detect_batch_dev")
+
 
 # ------------------------------------------------------------------------------------ reference-shaped façade
 class FeatureDetector:

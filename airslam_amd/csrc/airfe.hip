@@ -5,6 +5,7 @@
 #include "pnp_core.h"
 #include "poseopt_core.h"
 #include "bowgroup_core.h"
+#include "loopdet_core.h"
 
 namespace airfe_host {
 thread_local std::string g_err;
@@ -2478,6 +2479,11 @@ struct airfe_bowdb {
   int32_t *cov_row = nullptr, *cov_nbr = nullptr, *cov_weight = nullptr;     // [max_frames + 1], [max_edges], [max_edges]
   double* pos = nullptr;                                                     // [max_frames][3]
   uint8_t* r_scratch = nullptr; size_t r_bytes = 0; hipStream_t r_stream = nullptr;      // relocalisation composite: everything between its kernels
+  // loop detection (airfe_bowdb_set_poses / set_u_right): the keyframes' Twc and the right-image columns of their feature rows
+  int has_pose = 0;
+  double* pose = nullptr;                                                    // [max_frames][16], identity until set
+  double* u_right = nullptr;                                                 // [max_frames][cap], -1 until set (> 0: stereo)
+  uint8_t* l_scratch = nullptr; size_t l_bytes = 0; hipStream_t l_stream = nullptr;      // stored queries / loop detection composite
 };
 
 namespace {
@@ -2589,7 +2595,8 @@ int airfe_bowdb_destroy(airfe_bowdb* db) try {
   if (!db) return 0;
   if (db->c) { (void)enter_device(db->c); (void)hipDeviceSynchronize(); }
   for (void* p : {(void*)db->ids, (void*)db->vals, (void*)db->nw, (void*)db->feat, (void*)db->n, (void*)db->q_scratch, (void*)db->m_scratch, (void*)db->xyz,
-                  (void*)db->cov_row, (void*)db->cov_nbr, (void*)db->cov_weight, (void*)db->pos, (void*)db->r_scratch})
+                  (void*)db->cov_row, (void*)db->cov_nbr, (void*)db->cov_weight, (void*)db->pos, (void*)db->r_scratch, (void*)db->pose, (void*)db->u_right,
+                  (void*)db->l_scratch})
     if (p) (void)hipFree(p);
   delete db;
   return 0;
@@ -2753,11 +2760,15 @@ int airfe_bowdb_attach_map(airfe_bowdb* db, int max_edges) try {
   HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->cov_nbr), (size_t)max_edges * 4));
   HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->cov_weight), (size_t)max_edges * 4));
   HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->pos), (size_t)db->max_frames * 24));
+  HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->pose), (size_t)db->max_frames * 128));
+  HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->u_right), rows * 8));
   HIPCHK(c, hipMemsetAsync(db->xyz, 0xFF, rows * 24, c->stream));                         // every byte 0xFF: a NaN in every slot
   HIPCHK(c, hipMemsetAsync(db->cov_row, 0, ((size_t)db->max_frames + 1) * 4, c->stream));  // an empty graph
   HIPCHK(c, hipMemsetAsync(db->cov_nbr, 0, (size_t)max_edges * 4, c->stream));
   HIPCHK(c, hipMemsetAsync(db->cov_weight, 0, (size_t)max_edges * 4, c->stream));
   HIPCHK(c, hipMemsetAsync(db->pos, 0xFF, (size_t)db->max_frames * 24, c->stream));
+  launch_loopdet_init(db->pose, db->u_right, db->max_frames, db->cap, c->stream);          // identity poses, no right image anywhere
+  HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
   db->max_edges = max_edges;
   db->has_map = 1;
@@ -2946,6 +2957,160 @@ int airfe_relocalize_batch_dev(airfe_ctx* c, airfe_bowdb* db, const airfe_reloc_
       return 1;
   }
   launch_reloc_finish(f, Q, st);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+} AIRFE_CATCH(c)
+
+/* ---- loop detection over a loaded map (include/airfe.h "Map state for loop detection", "Stored queries against their predecessors", "Loop detection
+ * composite"; kernels_loopdet.hip, loopdet_core.h) -------------------------------------------------------------------------------------------------- */
+int airfe_bowdb_set_poses(airfe_bowdb* db, int first_frame, int B, const double* Twc) try {
+  if (!db) return 1;
+  airfe_ctx* c = db->c;
+  AIRFE_ENTER(c);
+  if (!db->has_map) return fail(c, "bowdb_set_poses: no map state (airfe_bowdb_attach_map)");
+  if (first_frame < 0 || B < 1 || B > db->max_frames - first_frame || !Twc) return fail(c, "bowdb_set_poses: bad argument (frames beyond max_frames)");
+  std::vector<double> t((size_t)B * 3);
+  for (int b = 0; b < B; ++b)
+    for (int k = 0; k < 3; ++k) t[(size_t)b * 3 + k] = Twc[(size_t)b * 16 + 4 * k + 3];
+  if (bowdb_rows_copy(db, db->pose, 16, first_frame, B, Twc, nullptr, hipMemcpyHostToDevice, c->stream, "bowdb_set_poses")) return 1;
+  if (bowdb_rows_copy(db, db->pos, 3, first_frame, B, t.data(), nullptr, hipMemcpyHostToDevice, c->stream, "bowdb_set_poses")) return 1;
+  db->has_pos = 1;
+  db->has_pose = 1;
+  return 0;
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_get_poses(airfe_bowdb* db, int first_frame, int B, double* Twc) try {
+  if (!db) return 1;
+  AIRFE_ENTER(db->c);
+  return bowdb_rows_copy(db, db->pose, 16, first_frame, B, nullptr, Twc, hipMemcpyDeviceToHost, db->c->stream, "bowdb_get_poses");
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_set_u_right_dev(airfe_bowdb* db, int first_frame, int B, const double* d_u_right, void* stream) try {
+  if (!db) return 1;
+  AIRFE_ENTER(db->c);
+  return bowdb_rows_copy(db, db->u_right, (size_t)db->cap, first_frame, B, d_u_right, nullptr, hipMemcpyDeviceToDevice,
+                         stream ? (hipStream_t)stream : db->c->stream, "bowdb_set_u_right_dev");
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_set_u_right(airfe_bowdb* db, int first_frame, int B, const double* u_right) try {
+  if (!db) return 1;
+  AIRFE_ENTER(db->c);
+  return bowdb_rows_copy(db, db->u_right, (size_t)db->cap, first_frame, B, u_right, nullptr, hipMemcpyHostToDevice, db->c->stream, "bowdb_set_u_right");
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_get_u_right(airfe_bowdb* db, int first_frame, int B, double* u_right) try {
+  if (!db) return 1;
+  AIRFE_ENTER(db->c);
+  return bowdb_rows_copy(db, db->u_right, (size_t)db->cap, first_frame, B, nullptr, u_right, hipMemcpyDeviceToHost, db->c->stream, "bowdb_get_u_right");
+} AIRFE_CATCH(db->c)
+
+// stored frames d_qframe [Q] against their predecessors on `st`: the stored vectors gathered into d_ids / d_vals / d_nw ([Q][cap] x 2, [Q]: the caller's
+// scratch), bowdb_query_kernel unchanged over the whole database, the prefix selection (the body of airfe_bowdb_query_stored_batch_dev; the loop
+// detection composite queues the same code)
+static int loopdet_query_queue(airfe_bowdb* db, const int32_t* d_qframe, int Q, float ratio, int min_words, int exclude_covisible, uint32_t* d_ids,
+                               double* d_vals, int* d_nw, int32_t* d_cand_frame, int32_t* d_cand_sharing, double* d_cand_score, int ccap, int* d_ncand,
+                               int* d_max_sharing, int32_t* d_sharing, hipStream_t st) {
+  airfe_ctx* c = db->c;
+  const int N = db->size;
+  const size_t cells = (size_t)Q * std::max(N, 1);
+  if (bowdb_scratch(db, db->q_scratch, db->q_bytes, db->q_stream, cells * 12, st)) return 1;
+  LoopQvecArgs v;
+  v.qframe = d_qframe; v.db_ids = db->ids; v.db_vals = db->vals; v.db_nw = db->nw; v.N = N; v.cap = db->cap; v.ids = d_ids; v.vals = d_vals; v.nw = d_nw;
+  launch_loopdet_qvec(v, Q, st);
+  BowQueryArgs a;
+  a.db_ids = db->ids; a.db_vals = db->vals; a.db_nw = db->nw; a.N = N; a.cap = db->cap;
+  a.q_ids = d_ids; a.q_vals = d_vals; a.q_nw = d_nw; a.qcap = db->cap; a.n_words = c->bow_nwords;
+  a.frames_per_wg = (size_t)Q * N >= (size_t)64 * 1024 ? 64 : 16;     // (how the frames are sliced changes no result)
+  a.score = reinterpret_cast<double*>(db->q_scratch);
+  a.sharing = d_sharing ? d_sharing : reinterpret_cast<int*>(db->q_scratch + cells * 8);
+  ProfScope ps(c, ST_BOW, st, 0, (double)Q * N * db->cap * 12);
+  if (launch_bowdb_query(a, Q, st)) return fail(c, "bowdb_query_stored_batch_dev: the query table does not fit the workgroup's LDS");
+  LoopSelectArgs s;
+  s.qframe = d_qframe; s.sharing = a.sharing; s.score = a.score; s.N = N; s.zero_tail = d_sharing ? 1 : 0; s.ratio = ratio; s.min_words = min_words;
+  if (exclude_covisible) { s.row_ptr = db->cov_row; s.nbr = db->cov_nbr; s.rows = db->max_frames; }
+  s.cand_frame = d_cand_frame; s.cand_sharing = d_cand_sharing; s.cand_score = d_cand_score; s.ccap = ccap; s.ncand = d_ncand; s.max_sharing = d_max_sharing;
+  launch_loopdet_select(s, Q, st);
+  note_launch(c, ST_BOW);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+int airfe_bowdb_query_stored_batch_dev(airfe_bowdb* db, const int32_t* d_qframe, int Q, float ratio, int min_words, int exclude_covisible,
+                                       int32_t* d_cand_frame, int32_t* d_cand_sharing, double* d_cand_score, int ccap, int* d_ncand, int* d_max_sharing,
+                                       int32_t* d_sharing, void* stream) try {
+  if (!db) return 1;
+  airfe_ctx* c = db->c;
+  AIRFE_ENTER(c);
+  if (Q < 1 || ccap < 1 || !d_qframe || !d_cand_frame || !d_cand_sharing || !d_cand_score || !d_ncand || !d_max_sharing)
+    return fail(c, "bowdb_query_stored_batch_dev: bad argument");
+  if (Q > LD_MAX_QUERIES) return fail(c, "bowdb_query_stored_batch_dev: Q > 4096");
+  if (exclude_covisible && !db->has_map) return fail(c, "bowdb_query_stored_batch_dev: exclude_covisible needs the map state (airfe_bowdb_attach_map)");
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  const size_t qc = ((size_t)Q * db->cap * 4 + 255) / 256 * 256;
+  if (bowdb_scratch(db, db->l_scratch, db->l_bytes, db->l_stream, 3 * qc + (size_t)Q * 4, st)) return 1;
+  uint8_t* l = db->l_scratch;
+  return loopdet_query_queue(db, d_qframe, Q, ratio, min_words, exclude_covisible, reinterpret_cast<uint32_t*>(l + 2 * qc), reinterpret_cast<double*>(l),
+                             reinterpret_cast<int*>(l + 3 * qc), d_cand_frame, d_cand_sharing, d_cand_score, ccap, d_ncand, d_max_sharing, d_sharing, st);
+} AIRFE_CATCH(db->c)
+
+int airfe_loop_detect_batch_dev(airfe_ctx* c, airfe_bowdb* db, const airfe_loop_cfg* cfg, const int32_t* d_qframe, int Q, int* d_ok, int* d_stage,
+                                int32_t* d_loop, double* d_Twq, double* d_Rlq, double* d_tlq, int* d_num, uint8_t* d_mask, int32_t* d_idx, float* d_score,
+                                int mcap, int* d_nmatch, int* d_ncons, void* stream) try {
+  AIRFE_ENTER(c);
+  if (!db || db->c != c) return fail(c, "loop_detect_batch_dev: the database belongs to another context");
+  if (!db->has_map) return fail(c, "loop_detect_batch_dev: no map state (airfe_bowdb_attach_map)");
+  if (!db->has_pose) return fail(c, "loop_detect_batch_dev: the keyframe poses were never set (airfe_bowdb_set_poses)");
+  if (!cfg || Q < 1 || mcap < 1 || !d_qframe || !d_ok || !d_stage || !d_loop || !d_Twq || !d_Rlq || !d_tlq || !d_num || !d_mask || !d_idx || !d_score ||
+      !d_nmatch)
+    return fail(c, "loop_detect_batch_dev: bad argument");
+  if (cfg->K < 1 || cfg->K > 5) return fail(c, "loop_detect_batch_dev: cfg.K = 1..5");
+  if (Q > LD_MAX_QUERIES) return fail(c, "loop_detect_batch_dev: Q > 4096");
+  if (mcap > PO_MAX_POINTS) return fail(c, "loop_detect_batch_dev: mcap > 1024");
+  if ((long long)Q * cfg->K > c->Pmax) return fail(c, "loop_detect_batch_dev: Q * K pairs exceed cfg.max_batch");
+  const int N = db->size, ccap = std::max(N, 1), K = cfg->K, cap = db->cap;
+  if (N > LD_MAX_FRAMES) return fail(c, "loop_detect_batch_dev: more than 4096 frames in the database");
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  // one block, every part 256-byte aligned
+  size_t off = 0;
+  auto take = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) / 256 * 256; return at; };
+  const size_t qc = (size_t)Q * cap, qm = (size_t)Q * mcap, qcc = (size_t)Q * ccap, qb = (size_t)Q * 4;
+  const size_t o_ids = take(qc * 4), o_vals = take(qc * 8), o_nw = take(qb), o_cf = take(qcc * 4), o_cs = take(qcc * 4), o_sc = take(qcc * 8), o_nc = take(qb),
+               o_ms = take(qb), o_odom = take((size_t)ccap * 8), o_feat = take(qc * AIRFE_FEAT_DIM * 4), o_qn = take(qb), o_qpos = take((size_t)Q * 24),
+               o_md = take((size_t)Q * 8), o_T0 = take((size_t)Q * 128), o_gf = take((size_t)Q * K * 4), o_gs = take((size_t)Q * K * 8), o_ng = take(qb),
+               o_gst = take(qb), o_map = take(qm * 4), o_X = take(qm * 24), o_obs = take(qm * 24), o_n = take(qb), o_nopt = take(qb), o_pre = take(qb);
+  if (bowdb_scratch(db, db->l_scratch, db->l_bytes, db->l_stream, off, st)) return 1;
+  uint8_t* r = db->l_scratch;
+  auto I = [r](size_t o) { return reinterpret_cast<int*>(r + o); };
+  auto D = [r](size_t o) { return reinterpret_cast<double*>(r + o); };
+  // map_refiner.cc:97-130 on the database of :88-89: frame fq against its predecessors, the covisible frames dropped
+  if (loopdet_query_queue(db, d_qframe, Q, cfg->ratio, cfg->min_words, 1, reinterpret_cast<uint32_t*>(r + o_ids), D(o_vals), I(o_nw), I(o_cf), I(o_cs),
+                          D(o_sc), ccap, I(o_nc), I(o_ms), nullptr, st)) return 1;
+  // :66-81: the odometry length, once per call; what the later steps read of frame fq
+  launch_loopdet_odom(db->pos, N, D(o_odom), st);
+  LoopStateArgs s;
+  s.qframe = d_qframe; s.N = N; s.cap = cap; s.db_feat = db->feat; s.db_n = db->n; s.pos = db->pos; s.pose = db->pose; s.odom = D(o_odom);
+  s.distance_rate = cfg->distance_rate; s.qfeat = reinterpret_cast<float*>(r + o_feat); s.qn = I(o_qn); s.qpos = D(o_qpos); s.max_dist = D(o_md);
+  s.Twc0 = D(o_T0);
+  launch_loopdet_state(s, Q, st);
+  HIPCHK(c, hipGetLastError());
+  // :132-214: the grouping in loop form; :213-230: the matcher over the K deputies
+  if (bowdb_group_queue(db, BG_MODE_LOOP, I(o_cf), D(o_sc), I(o_nc), Q, ccap, K, nullptr, D(o_qpos), D(o_md), I(o_gf), D(o_gs), I(o_ng), I(o_gst), st)) return 1;
+  if (bowdb_match_queue(c, db, s.qfeat, s.qn, Q, cap, I(o_gf), K, cfg->outlier_rejection, d_loop, d_idx, d_score, mcap, d_nmatch, nullptr, st)) return 1;
+  // :232, :241-301: the gates and the constraints
+  LoopGatherArgs g;
+  g.qframe = d_qframe; g.xyz = db->xyz; g.u_right = db->u_right; g.feat = db->feat; g.N = N; g.cap = cap; g.best = d_loop; g.idx = d_idx; g.nmatch = d_nmatch;
+  g.mcap = mcap; g.ncand = I(o_nc); g.gstatus = I(o_gst); g.ngroups = I(o_ng); g.min_matches = cfg->min_matches; g.min_points = cfg->min_points;
+  g.X = D(o_X); g.obs = D(o_obs); g.map = I(o_map); g.n = I(o_n); g.n_opt = I(o_nopt); g.pre = I(o_pre);
+  launch_loopdet_gather(g, Q, st);
+  HIPCHK(c, hipGetLastError());
+  // :262, :304: the frame optimisation from the stored pose, Tcb = identity; without constraints the kernel returns its start pose
+  if (poseopt_queue(c, g.X, g.obs, g.n_opt, Q, mcap, D(o_T0), cfg->cam, nullptr, cfg->thr, d_Twq, nullptr, d_mask, mcap, g.map, d_num, -1, nullptr, st))
+    return 1;
+  // :308, :327-333
+  LoopFinishArgs f;
+  f.pre = g.pre; f.ncons = g.n; f.num = d_num; f.min_points = cfg->min_points; f.min_inliers = cfg->min_inliers; f.best = d_loop; f.N = N;
+  f.pose = db->pose; f.Twq = d_Twq; f.stage = d_stage; f.ok = d_ok; f.ncons_out = d_ncons; f.Rlq = d_Rlq; f.tlq = d_tlq;
+  launch_loopdet_finish(f, Q, st);
   HIPCHK(c, hipGetLastError());
   return 0;
 } AIRFE_CATCH(c)

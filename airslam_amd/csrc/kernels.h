@@ -480,4 +480,48 @@ struct RelocFinishArgs {
 };
 void launch_reloc_finish(const RelocFinishArgs& f, int Q, hipStream_t st);
 
+// Batched loop detection (map_refiner.cc:65-333; kernels_loopdet.hip, loopdet_core.h; contract: include/airfe.h)
+void launch_loopdet_init(double* pose, double* u_right, int frames, int cap, hipStream_t st);     // [frames][16] identity, [frames][cap] -1
+struct LoopQvecArgs {
+  const int32_t* qframe = nullptr;                                           // [Q] stored frame indices
+  const unsigned* db_ids = nullptr; const double* db_vals = nullptr; const int* db_nw = nullptr; int N = 0, cap = 0;
+  unsigned* ids = nullptr; double* vals = nullptr; int* nw = nullptr;        // [Q][cap], [Q][cap], [Q]
+};
+void launch_loopdet_qvec(const LoopQvecArgs& a, int Q, hipStream_t st);
+struct LoopSelectArgs {
+  const int32_t* qframe = nullptr;
+  int* sharing = nullptr; const double* score = nullptr; int N = 0;          // [Q][N] of bowdb_query_kernel; zero_tail: sharing[q][f >= fq] = 0
+  int zero_tail = 0;
+  float ratio = 0.5f; int min_words = 8;
+  const int32_t *row_ptr = nullptr, *nbr = nullptr; int rows = 0;            // covisibility CSR, or nullptr: nothing is excluded
+  int32_t *cand_frame = nullptr, *cand_sharing = nullptr; double* cand_score = nullptr; int ccap = 0;                     // [Q][ccap]
+  int *ncand = nullptr, *max_sharing = nullptr;                                                                           // [Q]
+};
+void launch_loopdet_select(const LoopSelectArgs& a, int Q, hipStream_t st);
+void launch_loopdet_odom(const double* pos, int N, double* odom, hipStream_t st);                 // N <= 4096
+struct LoopStateArgs {
+  const int32_t* qframe = nullptr; int N = 0, cap = 0;
+  const float* db_feat = nullptr; const int* db_n = nullptr;
+  const double *pos = nullptr, *pose = nullptr, *odom = nullptr; double distance_rate = 0.03;
+  float* qfeat = nullptr; int* qn = nullptr;                                 // [Q][cap][259], [Q]
+  double *qpos = nullptr, *max_dist = nullptr, *Twc0 = nullptr;              // [Q][3], [Q], [Q][16]
+};
+void launch_loopdet_state(const LoopStateArgs& a, int Q, hipStream_t st);
+struct LoopGatherArgs {
+  const int32_t* qframe = nullptr;
+  const double *xyz = nullptr, *u_right = nullptr; const float* feat = nullptr; int N = 0, cap = 0;    // the database's tables, its size
+  const int32_t *best = nullptr, *idx = nullptr; const int* nmatch = nullptr; int mcap = 0;            // the winner and its list (query index, candidate index)
+  const int *ncand = nullptr, *gstatus = nullptr, *ngroups = nullptr; int min_matches = 50, min_points = 50;
+  double *X = nullptr, *obs = nullptr; int* map = nullptr;                   // [Q][mcap][3] x 2, list entry of constraint i
+  int *n = nullptr, *n_opt = nullptr, *pre = nullptr;                        // [Q]: constraints, those handed to the optimisation, stage before them
+};
+void launch_loopdet_gather(const LoopGatherArgs& g, int Q, hipStream_t st);
+struct LoopFinishArgs {
+  const int *pre = nullptr, *ncons = nullptr, *num = nullptr; int min_points = 50, min_inliers = 50;
+  const int32_t* best = nullptr; int N = 0;
+  const double *pose = nullptr, *Twq = nullptr;                              // the stored poses [max_frames][16], the optimised ones [Q][16]
+  int *stage = nullptr, *ok = nullptr, *ncons_out = nullptr; double *Rlq = nullptr, *tlq = nullptr;
+};
+void launch_loopdet_finish(const LoopFinishArgs& f, int Q, hipStream_t st);
+
 }  // namespace airfe

@@ -580,6 +580,79 @@ int airfe_relocalize_batch_dev(airfe_ctx* ctx, airfe_bowdb* db, const airfe_relo
                                const double* d_extra, int* d_ok, int* d_stage, double* d_Twc, int32_t* d_best, int* d_num, uint8_t* d_mask, int32_t* d_idx,
                                float* d_score, int mcap, int* d_nmatch, int* d_pnp_count, void* stream);
 
+/* ---- Map state for loop detection (opt-in, allocated by airfe_bowdb_attach_map): what MapRefiner::LoopDetection reads of a loaded map next to the
+ * tables above -----------------------------------------------------------------------------------------------------------------------------------------
+ *   poses     [max_frames][16] f64 row-major Twc, initialised to the identity.  airfe_bowdb_set_poses (host rows [B][16]) ALSO writes each pose's
+ *             translation column into the positions table and marks the positions as set, so one call serves the loop form of the grouping.
+ *   u_right   [max_frames][cap] f64, one per FEATURE ROW of the stored frame, initialised to -1.0: the stored frame's _u_right.  A value > 0 means the row
+ *             has a right-image match (the convention of "Frame optimisation").
+ * Stream and synchronisation rules are those of airfe_bowdb_set_points / _set_points_dev; frames beyond max_frames are a return code and change nothing. */
+int airfe_bowdb_set_poses(airfe_bowdb* db, int first_frame, int B, const double* Twc);                       /* host buffer [B][16] */
+int airfe_bowdb_get_poses(airfe_bowdb* db, int first_frame, int B, double* Twc);                             /* host buffer [B][16] */
+int airfe_bowdb_set_u_right_dev(airfe_bowdb* db, int first_frame, int B, const double* d_u_right, void* stream);   /* d_u_right [B][cap] */
+int airfe_bowdb_set_u_right(airfe_bowdb* db, int first_frame, int B, const double* u_right);                 /* host buffer [B][cap] */
+int airfe_bowdb_get_u_right(airfe_bowdb* db, int first_frame, int B, double* u_right);                       /* host buffer [B][cap] */
+
+/* ---- Stored queries against their predecessors: the query and the filter of MapRefiner::LoopDetection (src/map_refiner.cc:95-130) for frames that are
+ * ALREADY in the database.  The reference walks the keyframes of a loaded map and queries frame fq BEFORE it adds it (:88-89): the database then holds
+ * frames 0 .. fq - 1 only.  airfe_bowdb_query_batch_dev on a fully loaded database cannot express that: its max_sharing is taken over every stored frame,
+ * frame fq itself (which shares all of its words) and every later frame included, so the threshold comes out wrong even with d_max_index.  Here, for
+ * query q with fq = d_qframe[q] (i32 [Q], any order, repeats allowed, Q <= 4096):
+ *   query    the stored vector of frame fq, read from the database on the device.
+ *   exists   only frames f < fq.  sharing and score as in "BoW keyframe database" (v1 = the stored frame's vector, v2 = the query's, the same order).
+ *   thr      max_sharing over f < fq only; thr = max((int)((float)max_sharing * ratio), min_words), the product in float32.
+ *   filter   f is a candidate iff f < fq, sharing > 0, sharing >= thr and — with exclude_covisible — f is not a neighbour in row fq of the covisibility
+ *            CSR at ANY weight (covi_frames.count(fsw), :115; neighbours >= fq are ignored; needs airfe_bowdb_attach_map).
+ *   output   what airfe_bowdb_query_batch_dev writes: the candidates in ascending frame index up to ccap, d_ncand[q] = the full count (may exceed ccap),
+ *            d_max_sharing[q]; d_sharing i32 [Q][N] or NULL: the dense counts, 0 at f >= fq.  fq outside 0 .. size - 1: ncand = 0, max_sharing = 0.
+ * Three statements that agree bit for bit: loopdet_select_host (airslam_amd/csrc/loopdet_core.h), the kernels (kernels_loopdet.hip around the unchanged
+ * query kernel) and tests/loopdet_ref.py.  Asynchronous on `stream`, no host synchronisation; a query's bytes depend neither on Q nor on its position. */
+int airfe_bowdb_query_stored_batch_dev(airfe_bowdb* db, const int32_t* d_qframe, int Q, float ratio, int min_words, int exclude_covisible,
+                                       int32_t* d_cand_frame, int32_t* d_cand_sharing, double* d_cand_score, int ccap, int* d_ncand, int* d_max_sharing,
+                                       int32_t* d_sharing, void* stream);
+
+/* ---- Loop detection composite: MapRefiner::LoopDetection (src/map_refiner.cc:65-235) and the pose of RelativatePoseEstimation (:237-320, :327-333) for
+ * a list of stored frames, on one stream, nothing copied to the host in between.  Per query q with fq = d_qframe[q], byte for byte the steps done one at
+ * a time through the entries above:
+ *   (1) airfe_bowdb_query_stored_batch_dev's code with (ratio, min_words) and exclude_covisible = 1.
+ *   (2) odom(fq) = the sum over f = 1 .. fq of |pos[f] - pos[f - 1]|, added sequentially in ascending f from +0, each term sqrt((dx dx + dy dy) + dz dz)
+ *       in double (:66-81; pos = the positions table, which airfe_bowdb_set_poses fills); max_dist = odom(fq) * distance_rate; qpos = pos[fq].
+ *   (3) the grouping in loop form (mode 1) on the candidate list with qpos and max_dist; airfe_bowdb_match_candidates_batch_dev's code on the K <= 5
+ *       deputies, the query's feature rows and count being the STORED rows of fq.  The winner b: the first candidate with strictly the longest list.
+ *   (4) no candidate: stage 1.  No group: stage 2.  No winner or nmatch <= min_matches: stage 3 (:232 is a strict >).
+ *   (5) constraints = the winner's list entries (qi, ci), in list order, whose map point xyz[b][ci] exists (x not NaN): X = xyz[b][ci],
+ *       obs = (feat[fq][qi].x, feat[fq][qi].y, u) with u = u_right[fq][qi] if that is > 0, else -1.0.  STATED DIFFERENCE: a repeated index is not
+ *       deduplicated (the reference gates on distinct map-point ids, points.size(); the matcher's lists are one-to-one).  Fewer than min_points
+ *       constraints: stage 4, none are handed over.
+ *   (6) the frame optimisation above from the STORED pose of fq (AddFrameVertex(frame, ...), :262), Tcb = identity.  num < min_inliers: stage 5.
+ *   (7) from the optimised Twq and the stored Twl of b, in double, no fused multiply-adds, summed in the order written:
+ *       Rlq[i][j] = (Rwl[0][i] Rwq[0][j] + Rwl[1][i] Rwq[1][j]) + Rwl[2][i] Rwq[2][j];  d = twq - twl;  tlq[i] = (Rwl[0][i] d0 + Rwl[1][i] d1) + Rwl[2][i] d2.
+ * Every entry is written: d_ok [Q]; d_stage [Q] (0 = ok); d_loop [Q] = b or -1 (as airfe_bowdb_match_candidates_batch_dev's d_best); d_Twq [Q][16] = the
+ * stored pose for stages 1 - 4 (the identity for an fq outside the database), the optimised pose for stages 0 and 5; d_Rlq [Q][9] row-major / d_tlq [Q][3]
+ * = identity / zero for stages 1 - 4, from the optimised pose for stages 0 and 5; d_num [Q] (0 for stages 1 - 4); d_mask [Q][mcap] = the optimisation's
+ * flags by LIST ENTRY (0 where there is no point); the winner's list d_idx [Q][mcap][2] / d_score / d_nmatch as
+ * airfe_bowdb_match_candidates_batch_dev writes them; d_ncons [Q] or NULL = the constraints found (0 for stages 1 - 3).
+ * Return codes: no map state; poses never set (airfe_bowdb_set_poses); Q * K above cfg.max_batch; mcap > 1024; more than 4096 frames in the database;
+ * K outside 1 .. 5; Q > 4096.  A caller with a large map runs the stored query and airfe_bowdb_group_dev over all frames first (both are cheap) and hands
+ * the composite only the frames that kept a group, in chunks of max_batch / K: d_qframe is an arbitrary list for that reason.
+ * OUT OF SCOPE (the caller's, as in the reference): the "find more matches" search of :322-438, TriangulateMappoint, the mappoint merge, the pose graph,
+ * building the covisibility table, junction sentences. */
+typedef struct airfe_loop_cfg {
+  float ratio;            /* 0.5f */
+  int min_words;          /* 8 */
+  int K;                  /* <= 5 (GoodCandidateNum) */
+  int outlier_rejection;  /* 1: MatchingPoints(..., true) */
+  double distance_rate;   /* 0.03 (:179) */
+  int min_matches;        /* 50: a winner needs STRICTLY more matches (:232) */
+  int min_points;         /* 50 (:301) */
+  int min_inliers;        /* 50 (:308) */
+  double cam[5];          /* fx, fy, cx, cy, bf */
+  double thr[2];          /* the chi-square values of map_optimization_config: mono_point, stereo_point */
+} airfe_loop_cfg;
+int airfe_loop_detect_batch_dev(airfe_ctx* ctx, airfe_bowdb* db, const airfe_loop_cfg* cfg, const int32_t* d_qframe, int Q, int* d_ok, int* d_stage,
+                                int32_t* d_loop, double* d_Twq, double* d_Rlq, double* d_tlq, int* d_num, uint8_t* d_mask, int32_t* d_idx, float* d_score,
+                                int mcap, int* d_nmatch, int* d_ncons, void* stream);
+
 /* ---- the step BEFORE the path: rectification ------------------------------------------------------- */
 /* ≙ the maps Camera's constructor builds with cv::initUndistortRectifyMap (src/camera.cc:60-75; _mapl1/_mapl2 = side 0, _mapr1/_mapr2 =
  *   side 1): CV_32FC1 x / y maps [h][w], uploaded once.  The map CONSTRUCTION (stereoRectify etc.) stays reference code. */
