@@ -1,11 +1,6 @@
-// airfe — context life cycle, host staging and the C ABI of libairfe.so (include/airfe.h, include/airfe_debug.h); the pipelines behind it live in
-// airfe_load.hip / airfe_detect.hip / airfe_match.hip (see airfe_host.h).
+// airfe — context life cycle, scratch blocks, host staging and the C ABI of libairfe.so (include/airfe.h, include/airfe_debug.h); the pipelines behind it live in
+// airfe_load.hip / airfe_detect.hip / airfe_match.hip, the geometry, BoW and kernel-hook entries in airfe_geom.hip / airfe_bowdb.hip / airfe_debug.hip (see airfe_host.h).
 #include "airfe_host.h"
-#include "fransac_core.h"
-#include "pnp_core.h"
-#include "poseopt_core.h"
-#include "bowgroup_core.h"
-#include "loopdet_core.h"
 
 namespace airfe_host {
 thread_local std::string g_err;
@@ -64,12 +59,6 @@ void note_launch(airfe_ctx* c, int stage) {
 namespace { __global__ void never_launched_kernel() {} }
 void fail_launch_now(hipStream_t st) { hipLaunchKernelGGL(never_launched_kernel, dim3(1), dim3(4096), 0, st); }      // 4096 threads per workgroup: hipErrorInvalidConfiguration
 
-// Every extern "C" entry is a function-try-block ending in AIRFE_CATCH: std::bad_alloc from a std::vector / std::string of the host-side
-// bookkeeping (or anything else thrown below) becomes a non-zero return + airfe_last_error(), never an exception crossing the C ABI.
-#define AIRFE_CATCH(c)                                                                                                   \
-  catch (const std::exception& e_) { return airfe_host::fail_noexcept((c), __func__, e_.what()); }                       \
-  catch (...) { return airfe_host::fail_noexcept((c), __func__, nullptr); }
-
 void KfState::save(const airfe_ctx* c) {
   nms_map_valid = c->nms_map_valid; desc_normalised = c->desc_normalised; desc_dense_valid = c->desc_dense_valid; line_sparse = c->line_sparse; last_B = c->last_B;
 }
@@ -77,30 +66,33 @@ void KfState::restore(airfe_ctx* c) const {
   c->nms_map_valid = nms_map_valid; c->desc_normalised = desc_normalised; c->desc_dense_valid = desc_dense_valid; c->line_sparse = line_sparse; c->last_B = last_B;
 }
 
-namespace {
-
-// grow-on-demand staging block: the previous block is freed (it used to stay in `allocs` until destroy)
-// (user: a caller's stream the block's previous contents may still be in use on — the *_batch_dev entries run on the stream they are given)
-int ensure_block(airfe_ctx* c, uint8_t*& blk, size_t& have, size_t bytes, hipStream_t user = nullptr) {
-  if (bytes <= have) return 0;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (user && user != c->stream) HIPCHK(c, hipStreamSynchronize(user));
-  void* p = nullptr;
-  HIPCHK(c, hipMalloc(&p, bytes));
-  if (blk) {
-    auto it = std::find(c->allocs.begin(), c->allocs.end(), (void*)blk);
+void release(airfe_ctx* c, DevBlock& b) {
+  if (b.p) {
+    auto it = std::find(c->allocs.begin(), c->allocs.end(), (void*)b.p);
     if (it != c->allocs.end()) c->allocs.erase(it);
-    (void)hipFree(blk);
+    (void)hipFree(b.p);
   }
-  c->allocs.push_back(p);
-  blk = reinterpret_cast<uint8_t*>(p);
-  have = bytes;
+  b = DevBlock{};
+}
+
+int reserve(airfe_ctx* c, DevBlock& b, size_t bytes, hipStream_t st) {
+  if (bytes > b.bytes) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (b.last && b.last != c->stream) HIPCHK(c, hipStreamSynchronize(b.last));
+    c->allocs.push_back(nullptr);      // the slot first (nothing below throws: the new block is never lost between hipMalloc and the list)
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, bytes);
+    if (e != hipSuccess) c->allocs.pop_back();
+    HIPCHK(c, e);
+    release(c, b);                     // erases the old block's entry; the new slot stays the last
+    c->allocs.back() = p;
+    b.p = reinterpret_cast<uint8_t*>(p);
+    b.bytes = bytes;
+  }
+  b.last = st;
   return 0;
 }
-int ensure_stage_img(airfe_ctx* c, size_t bytes) { return ensure_block(c, c->st_img, c->st_img_bytes, bytes); }
 
-// host image -> c->st_img with the SAME row pitch: exactly (h - 1) * stride + w bytes are read (a cv::Mat ROI / numpy view has no
-// bytes behind its last row's w-th pixel that are ours to read)
 // the pinned host block (grows by replacement; the stream is idle whenever a host entry starts: they all end with a synchronisation)
 int ensure_pin(airfe_ctx* c, size_t bytes) {
   if (bytes <= c->pin_bytes) return 0;
@@ -113,39 +105,20 @@ int ensure_pin(airfe_ctx* c, size_t bytes) {
   return 0;
 }
 
-// A host entry that returns with an error AFTER it queued work must not leave that work in flight: the next call memcpy's into the pinned block a
-// pending D2H may still write, and reference rows that were only partly uploaded must not be matched against.  Armed once queueing starts,
-// disarmed on success.
-// A host entry reports the overflow of ITS OWN call: a saturation word an earlier asynchronous *_batch_dev call left behind (whose caller never asked: airfe_sync /
-// airfe_superglue_status) must not fail a later healthy call with a stale "left the fp16 range" (ADVICE r05).  Cleared where a host entry starts queueing.
-inline void clear_saturation(airfe_ctx* c) {
-  if (c->sat_host) c->sat_host[0] = c->sat_host[1] = 0;
-}
-struct DrainOnError {
-  airfe_ctx* c; bool armed = false, ref_uploaded = false;
-  explicit DrainOnError(airfe_ctx* c_, bool armed_ = false) : c(c_), armed(armed_) { clear_saturation(c_); }
-  ~DrainOnError() {
-    if (!armed) return;
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipStreamSynchronize(c->stream2);
-    if (ref_uploaded) c->ref_n = -1;
-  }
-};
-
+// host image -> c->st_img with the SAME row pitch: exactly (h - 1) * stride + w bytes are read (a cv::Mat ROI / numpy view has no
+// bytes behind its last row's w-th pixel that are ours to read)
 int upload_image(airfe_ctx* c, const uint8_t* gray, int h, int w, int stride) {
   if (!gray || h < 1 || w < 1) return fail(c, "empty image");     // plnet.cpp:247
   if (stride < w) return fail(c, "image stride smaller than its width");
   const size_t bytes = (size_t)(h - 1) * stride + w;
-  if (ensure_stage_img(c, (size_t)h * stride)) return 1;
+  if (reserve(c, c->st_img, (size_t)h * stride, c->stream)) return 1;
   // through the pinned block: a pageable hipMemcpyAsync is staged by the runtime in chunks, synchronously (measured: 2.4x the time)
   if (ensure_pin(c, bytes)) return 1;
   clear_saturation(c);
   memcpy(c->pin, gray, bytes);
-  HIPCHK(c, hipMemcpyAsync(c->st_img, c->pin, bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->st_img.p, c->pin, bytes, hipMemcpyHostToDevice, c->stream));
   return 0;
 }
-
-}  // namespace
 
 // ================================================================================== C ABI
 extern "C" {
@@ -179,16 +152,6 @@ void airfe_default_tuning(airfe_tuning* t) {
 }
 
 const char* airfe_last_error(const airfe_ctx* ctx) { return ctx ? ctx->err.c_str() : g_err.c_str(); }
-
-// Every entry that takes a context makes the context's device current first: a process may hold contexts on several devices (cfg.device)
-// and the calling thread's current device is whatever the application left it at.
-static inline int enter_device(airfe_ctx* c) {
-  int d = -1;
-  if (hipGetDevice(&d) == hipSuccess && d == c->cfg.device) return 0;
-  if (hipSetDevice(c->cfg.device) != hipSuccess) return fail(c, "hipSetDevice(cfg.device) failed");
-  return 0;
-}
-#define AIRFE_ENTER(c) do { if (!(c)) return 1; if (enter_device(c)) return 1; } while (0)
 
 int airfe_create(const airfe_cfg* cfg, airfe_ctx** out) try {
   if (!cfg || !out) return fail(nullptr, "airfe_create: null argument");
@@ -415,7 +378,7 @@ int airfe_detect_points(airfe_ctx* c, const uint8_t* gray, int h, int w, int str
   AIRFE_ENTER(c);
   if (cap < c->cfg.max_keypoints) return fail(c, "feature capacity < max_keypoints");
   if (upload_image(c, gray, h, w, stride)) return 1;
-  if (detect_dev(c, c->st_img, 1, h, w, stride, (size_t)h * stride, c->st_feat0, c->Np, c->st_n0, c->stream)) return 1;
+  if (detect_dev(c, c->st_img.p, 1, h, w, stride, (size_t)h * stride, c->st_feat0, c->Np, c->st_n0, c->stream)) return 1;
   // one D2H of [count | max_keypoints feature rows] into the pinned block (st_n0 and st_feat0 are one device block), rows copied out after the sync
   const size_t out_bytes = 64 + (size_t)c->cfg.max_keypoints * AIRFE_FEAT_DIM * 4;
   if (ensure_pin(c, out_bytes)) return 1;
@@ -524,14 +487,14 @@ int airfe_rectify_detect_points(airfe_ctx* c, int side, const uint8_t* raw, int 
   AIRFE_ENTER(c);
   if (feat && cap < c->cfg.max_keypoints) return fail(c, "feature capacity < max_keypoints");
   if (upload_image(c, raw, h, w, stride)) return 1;
-  if (ensure_block(c, c->st_rect, c->st_rect_bytes, (size_t)h * w)) return 1;
-  if (airfe_rectify_batch_dev(c, side, c->st_img, 1, h, w, stride, (size_t)h * stride, c->st_rect, w, (size_t)h * w, c->stream)) return 1;
+  if (reserve(c, c->st_rect, (size_t)h * w, c->stream)) return 1;
+  if (airfe_rectify_batch_dev(c, side, c->st_img.p, 1, h, w, stride, (size_t)h * stride, c->st_rect.p, w, (size_t)h * w, c->stream)) return 1;
   int nn = 0;
   if (feat) {
-    if (detect_dev(c, c->st_rect, 1, h, w, w, (size_t)h * w, c->st_feat0, c->Np, c->st_n0, c->stream)) return 1;
+    if (detect_dev(c, c->st_rect.p, 1, h, w, w, (size_t)h * w, c->st_feat0, c->Np, c->st_n0, c->stream)) return 1;
     HIPCHK(c, hipMemcpyAsync(&nn, c->st_n0, 4, hipMemcpyDeviceToHost, c->stream));
   }
-  if (rect_out) HIPCHK(c, hipMemcpyAsync(rect_out, c->st_rect, (size_t)h * w, hipMemcpyDeviceToHost, c->stream));
+  if (rect_out) HIPCHK(c, hipMemcpyAsync(rect_out, c->st_rect.p, (size_t)h * w, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (feat && saturation_status(c)) return 1;
   if (feat && nn > 0) HIPCHK(c, hipMemcpy(feat, c->st_feat0, (size_t)nn * AIRFE_FEAT_DIM * 4, hipMemcpyDeviceToHost));
@@ -666,17 +629,14 @@ int airfe_assign_points_to_lines(airfe_ctx* c, const double* lines, int L, const
   if (L == 0) { row_ptr[0] = 0; return 0; }
   if (!lines || (N > 0 && !feat)) return fail(c, "assign_points_to_lines: null input");
   // staging grows on demand (lines and points per frame are a few hundred); the kernels are the batch entry's with one frame
-  const size_t need = (size_t)L * 32 + (size_t)std::max(N, 1) * 259 * 4 + (size_t)(2 * L + 2) * 4 + (size_t)std::max(cap, 1) * 12 + 128;
-  if (ensure_block(c, c->pl_stage, c->pl_bytes, need)) return 1;      // grows by replacing (and freeing) the previous block
-  char* q = reinterpret_cast<char*>(c->pl_stage);
-  double* d_lines = reinterpret_cast<double*>(q); q += (size_t)L * 32;
-  double* d_dist = reinterpret_cast<double*>(q); q += (size_t)std::max(cap, 1) * 8;
-  float* d_feat = reinterpret_cast<float*>(q); q += (size_t)std::max(N, 1) * 259 * 4;
-  int* d_counts = reinterpret_cast<int*>(q); q += (size_t)L * 4;
-  int* d_rowptr = reinterpret_cast<int*>(q); q += (size_t)(L + 1) * 4;
-  int* d_idx = reinterpret_cast<int*>(q); q += (size_t)std::max(cap, 1) * 4;
-  int* d_cnt = reinterpret_cast<int*>(q);                              // {nlines, npts}
   hipStream_t st = c->stream;
+  Carve k;
+  const size_t o_lines = k.take((size_t)L * 32), o_dist = k.take((size_t)std::max(cap, 1) * 8), o_feat = k.take((size_t)std::max(N, 1) * 259 * 4),
+               o_counts = k.take((size_t)L * 4), o_rowptr = k.take((size_t)(L + 1) * 4), o_idx = k.take((size_t)std::max(cap, 1) * 4), o_cnt = k.take(8);
+  if (k.into(c, c->pl_stage, st)) return 1;      // grows by replacing (and freeing) the previous block
+  double *d_lines = k.d(o_lines), *d_dist = k.d(o_dist);
+  float* d_feat = k.at<float>(o_feat);
+  int *d_counts = k.i(o_counts), *d_rowptr = k.i(o_rowptr), *d_idx = k.i(o_idx), *d_cnt = k.i(o_cnt);      // d_cnt: {nlines, npts}
   const int cnt[2] = {L, N};
   HIPCHK(c, hipMemcpyAsync(d_cnt, cnt, sizeof(cnt), hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(d_lines, lines, (size_t)L * 32, hipMemcpyHostToDevice, st));
@@ -708,11 +668,10 @@ int airfe_assign_points_to_lines_batch_dev(airfe_ctx* c, const double* d_lines, 
   hipStream_t st = stream ? (hipStream_t)stream : c->stream;
   // scratch of THIS entry (airfe_match_lines_batch_dev has its own: the two may be in flight on different streams); it grows only behind a
   // synchronisation of the stream it was last used on.  One stream at a time per entry and context — the contract of every *_dev entry (one ctx = one calling thread).
-  if (ensure_block(c, c->pl_scratch, c->pl_scratch_bytes, (size_t)B * capL * 4, c->pl_scratch_stream)) return 1;
-  c->pl_scratch_stream = st;
+  if (reserve(c, c->pl_scratch, (size_t)B * capL * 4, st)) return 1;
   PlAssignArgs a;
   a.lines = d_lines; a.nlines = d_nlines; a.feat = d_feat; a.npts = d_n; a.capL = capL; a.cap = cap; a.capE = capE;
-  a.counts = reinterpret_cast<int*>(c->pl_scratch); a.row_ptr = d_row_ptr; a.pt_idx = d_pt_idx; a.pt_dist = d_pt_dist; a.total = d_total;
+  a.counts = c->pl_scratch.at<int>(0); a.row_ptr = d_row_ptr; a.pt_idx = d_pt_idx; a.pt_dist = d_pt_dist; a.total = d_total;
   ProfScope ps(c, ST_LINE_ASSOC, st, 0, (double)B * ((double)capL * 32 + (double)cap * 8));
   launch_assign_points_to_lines(a, B, st);
   HIPCHK(c, hipGetLastError());
@@ -745,20 +704,15 @@ int airfe_match_lines(airfe_ctx* c, const int32_t* row_ptr0, const int32_t* pt_i
   // the batch entry's kernels with one frame pair: one line capacity for both sides, the relation capacity = the larger relation
   const int capL = std::max(L0, L1), capE = std::max(std::max(t0, t1), 1), mcap = std::max(M, 1);
   const int W = (mcap + 31) / 32;
-  const size_t words = 2 * (size_t)(capL + 1) + 2 * (size_t)capE + (size_t)mcap * 2 + 2 * (size_t)capL * W + 2 * (size_t)capL + 8;
-  if (ensure_block(c, c->pl_stage, c->pl_bytes, words * 4 + 64)) return 1;      // grows by replacing (and freeing) the previous block
-  int* q = reinterpret_cast<int*>(c->pl_stage);
-  int* d_rp0 = q; q += capL + 1;
-  int* d_rp1 = q; q += capL + 1;
-  int* d_pi0 = q; q += capE;
-  int* d_pi1 = q; q += capE;
-  int* d_m = q; q += (size_t)mcap * 2;
-  unsigned* d_b0 = reinterpret_cast<unsigned*>(q); q += (size_t)capL * W;
-  unsigned* d_b1 = reinterpret_cast<unsigned*>(q); q += (size_t)capL * W;
-  int* d_rloc = q; q += capL;
-  int* d_lm = q; q += capL;
-  int* d_cnt = q;                                                        // {L0, L1, point_num0, point_num1, M}
   hipStream_t st = c->stream;
+  Carve k;
+  const size_t rp = ((size_t)capL + 1) * 4, pi = (size_t)capE * 4, bits = (size_t)capL * W * 4, lm = (size_t)capL * 4;
+  const size_t o_rp0 = k.take(rp), o_rp1 = k.take(rp), o_pi0 = k.take(pi), o_pi1 = k.take(pi), o_m = k.take((size_t)mcap * 8), o_b0 = k.take(bits),
+               o_b1 = k.take(bits), o_rloc = k.take(lm), o_lm = k.take(lm), o_cnt = k.take(20);
+  if (k.into(c, c->pl_stage, st)) return 1;      // grows by replacing (and freeing) the previous block
+  int *d_rp0 = k.i(o_rp0), *d_rp1 = k.i(o_rp1), *d_pi0 = k.i(o_pi0), *d_pi1 = k.i(o_pi1), *d_m = k.i(o_m), *d_rloc = k.i(o_rloc), *d_lm = k.i(o_lm);
+  unsigned *d_b0 = k.at<unsigned>(o_b0), *d_b1 = k.at<unsigned>(o_b1);
+  int* d_cnt = k.i(o_cnt);                                                // {L0, L1, point_num0, point_num1, M}
   const int cnt[5] = {L0, L1, point_num0, point_num1, M};
   HIPCHK(c, hipMemcpyAsync(d_cnt, cnt, sizeof(cnt), hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(d_rp0, row_ptr0, (size_t)(L0 + 1) * 4, hipMemcpyHostToDevice, st));
@@ -792,18 +746,15 @@ int airfe_match_lines_batch_dev(airfe_ctx* c, const int32_t* d_row_ptr0, const i
   const int W = (mcap + 31) / 32;
   hipStream_t st = stream ? (hipStream_t)stream : c->stream;
   // bit rows [2][B][capL][W] + row maxima [B][capL] (no vote matrix: the column pass recounts from the bit rows) — 7 MB at 64 frames x 1024 line slots
-  const size_t words = 2 * (size_t)B * capL * W + (size_t)B * capL;
-  if (ensure_block(c, c->ml_scratch, c->ml_scratch_bytes, words * 4, c->ml_scratch_stream)) return 1;
-  c->ml_scratch_stream = st;
-  unsigned* q = reinterpret_cast<unsigned*>(c->ml_scratch);
+  Carve k;
+  const size_t bits = (size_t)B * capL * W * 4, o_b0 = k.take(bits), o_b1 = k.take(bits), o_rloc = k.take((size_t)B * capL * 4);
+  if (k.into(c, c->ml_scratch, st)) return 1;
   MlArgs a;
   a.row_ptr0 = d_row_ptr0; a.pt_idx0 = d_pt_idx0; a.nlines0 = d_nlines0; a.npts0 = d_n0;
   a.row_ptr1 = d_row_ptr1; a.pt_idx1 = d_pt_idx1; a.nlines1 = d_nlines1; a.npts1 = d_n1;
   a.matches = d_matches; a.nmatch = d_nmatch; a.capL = capL; a.capE = capE; a.mcap = mcap; a.W = W; a.cap = cap;
   if (filter3) { a.filter_on = 1; a.min_x_diff = filter3[0]; a.max_x_diff = filter3[1]; a.max_y_diff = filter3[2]; a.feat0 = d_feat0; a.feat1 = d_feat1; }
-  a.bits0 = q; q += (size_t)B * capL * W;
-  a.bits1 = q; q += (size_t)B * capL * W;
-  a.row_loc = reinterpret_cast<int*>(q);
+  a.bits0 = k.at<unsigned>(o_b0); a.bits1 = k.at<unsigned>(o_b1); a.row_loc = k.i(o_rloc);
   a.line_matches = d_line_matches;
   ProfScope ps(c, ST_LINE_ASSOC, st, 0, (double)B * (double)capL * W * 8);
   launch_match_lines(a, B, st);
@@ -811,288 +762,6 @@ int airfe_match_lines_batch_dev(airfe_ctx* c, const int32_t* d_row_ptr0, const i
   return 0;
 } AIRFE_CATCH(c)
 
-// F-matrix RANSAC (src/point_matcher.cc:95-104) over B device match lists, in place, on `st` (kernels_fransac.hip).  Its scratch grows only behind
-// a synchronisation of the stream it was last used on (one stream at a time per context: the contract of every *_dev entry).
-static int fransac_queue(airfe_ctx* c, const float* d_f0, const float* d_f1, int B, int cap, int32_t* d_idx, float* d_score, int mcap, int* d_nmatch,
-                         double* d_F, hipStream_t st) {
-  const size_t score_bytes = (size_t)B * FR_RANSAC_ITERS * 3 * 4;
-  if (ensure_block(c, c->fr_scratch, c->fr_scratch_bytes, score_bytes + (size_t)B * 16, c->fr_scratch_stream)) return 1;
-  c->fr_scratch_stream = st;
-  FransacArgs a;
-  a.f0 = d_f0; a.f1 = d_f1; a.cap = cap; a.mcap = mcap; a.idx = d_idx; a.score = d_score; a.nmatch = d_nmatch; a.F = d_F;
-  a.scores = reinterpret_cast<int*>(c->fr_scratch);
-  a.state = reinterpret_cast<int*>(c->fr_scratch + score_bytes);
-  launch_fransac(a, B, st);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-
-int airfe_fundamental_ransac_batch_dev(airfe_ctx* c, const float* d_f0, const int* d_n0, const float* d_f1, const int* d_n1, int B, int cap, int32_t* d_idx,
-                                       float* d_score, int mcap, int* d_nmatch, double* d_F, void* stream) try {
-  AIRFE_ENTER(c);
-  (void)d_n0; (void)d_n1;
-  if (B < 1 || cap < 1 || mcap < 1 || !d_f0 || !d_f1 || !d_idx || !d_score || !d_nmatch) return fail(c, "fundamental_ransac_batch_dev: bad argument");
-  if (mcap > FR_MAX_MATCHES) return fail(c, "fundamental_ransac_batch_dev: mcap > 1024");
-  return fransac_queue(c, d_f0, d_f1, B, cap, d_idx, d_score, mcap, d_nmatch, d_F, stream ? (hipStream_t)stream : c->stream);
-} AIRFE_CATCH(c)
-
-int airfe_fundamental_ransac(airfe_ctx* c, const float* f0, int n0, const float* f1, int n1, int32_t* idx, float* score, int m, int* kept) try {
-  AIRFE_ENTER(c);
-  if (!kept || m < 0 || n0 < 0 || n1 < 0 || (m > 0 && (!idx || !score || !f0 || !f1))) return fail(c, "fundamental_ransac: bad argument");
-  if (m > FR_MAX_MATCHES) return fail(c, "fundamental_ransac: more than 1024 matches");
-  for (int i = 0; i < m; ++i)                                        // the reference indexes the feature matrices with these
-    if (idx[2 * i] < 0 || idx[2 * i] >= n0 || idx[2 * i + 1] < 0 || idx[2 * i + 1] >= n1) return fail(c, "fundamental_ransac: match index out of range");
-  *kept = m;
-  if (m < 9) return 0;                                               // point_matcher.cc:95: the list as it is (the kernels' gate says the same)
-  const int cap = std::max(n0, n1);
-  const size_t fb = (size_t)cap * AIRFE_FEAT_DIM * 4, mb = (size_t)m * 12;
-  if (ensure_block(c, c->fr_stage, c->fr_stage_bytes, 64 + 2 * fb + mb)) return 1;
-  int* d_nm = reinterpret_cast<int*>(c->fr_stage);
-  float* d_f0 = reinterpret_cast<float*>(c->fr_stage + 64);
-  float* d_f1 = reinterpret_cast<float*>(c->fr_stage + 64 + fb);
-  int32_t* d_idx = reinterpret_cast<int32_t*>(c->fr_stage + 64 + 2 * fb);
-  float* d_sc = reinterpret_cast<float*>(c->fr_stage + 64 + 2 * fb + (size_t)m * 8);
-  hipStream_t st = c->stream;
-  DrainOnError drain{c, true};
-  HIPCHK(c, hipMemcpyAsync(d_nm, &m, 4, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(d_f0, f0, (size_t)n0 * AIRFE_FEAT_DIM * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(d_f1, f1, (size_t)n1 * AIRFE_FEAT_DIM * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(d_idx, idx, (size_t)m * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(d_sc, score, (size_t)m * 4, hipMemcpyHostToDevice, st));
-  if (fransac_queue(c, d_f0, d_f1, 1, cap, d_idx, d_sc, m, d_nm, nullptr, st)) return 1;
-  int nk = 0;
-  HIPCHK(c, hipMemcpyAsync(&nk, d_nm, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  if (nk > 0) {
-    HIPCHK(c, hipMemcpyAsync(idx, d_idx, (size_t)nk * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(score, d_sc, (size_t)nk * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-  }
-  drain.armed = false;
-  *kept = nk;
-  return 0;
-} AIRFE_CATCH(c)
-
-int airfe_set_outlier_rejection(airfe_ctx* c, int on) try {
-  AIRFE_ENTER(c);
-  c->outlier_rejection = on != 0;
-  return 0;
-} AIRFE_CATCH(c)
-
-// PnP RANSAC (g2o_optimization.cc:1085-1134) over B device problems on `st` (kernels_pnp.hip): scores + models of the 100 samples in the context's
-// scratch (grown only behind a synchronisation of the stream it was last used on, as fransac_queue's).
-static int pnp_queue(airfe_ctx* c, const float* d_obj, const float* d_img, const int* d_n, int B, int ncap, const double* K, double* d_Twc, double* d_Rt,
-                     uint8_t* d_mask, int mcap, const int* d_map, int* d_count, hipStream_t st) {
-  const size_t score_bytes = ((size_t)B * PNP_MAX_ITERS * 4 + 255) / 256 * 256;
-  if (ensure_block(c, c->pn_scratch, c->pn_scratch_bytes, score_bytes + (size_t)B * PNP_MAX_ITERS * 12 * 8, c->pn_scratch_stream)) return 1;
-  c->pn_scratch_stream = st;
-  PnpArgs a;
-  a.obj = d_obj; a.img = d_img; a.n = d_n; a.ncap = ncap;
-  a.fx = K[0]; a.fy = K[1]; a.cx = K[2]; a.cy = K[3];
-  a.scores = reinterpret_cast<int*>(c->pn_scratch);
-  a.models = reinterpret_cast<double*>(c->pn_scratch + score_bytes);
-  a.Twc = d_Twc; a.Rt = d_Rt; a.mask = d_mask; a.mcap = mcap; a.map = d_map; a.count = d_count;
-  launch_pnp(a, B, st);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-
-int airfe_pnp_ransac_batch_dev(airfe_ctx* c, const float* d_obj, const float* d_img, const int* d_n, int B, int ncap, const double* K, double* d_Twc,
-                               double* d_Rt, uint8_t* d_inlier, int* d_count, void* stream) try {
-  AIRFE_ENTER(c);
-  if (B < 1 || ncap < 1 || !d_obj || !d_img || !d_n || !K || !d_Twc || !d_inlier || !d_count) return fail(c, "pnp_ransac_batch_dev: bad argument");
-  if (ncap > PNP_MAX_POINTS) return fail(c, "pnp_ransac_batch_dev: ncap > 1024");
-  return pnp_queue(c, d_obj, d_img, d_n, B, ncap, K, d_Twc, d_Rt, d_inlier, ncap, nullptr, d_count, stream ? (hipStream_t)stream : c->stream);
-} AIRFE_CATCH(c)
-
-int airfe_pnp_ransac(airfe_ctx* c, const double* obj, const double* img, int n, const double* K, double* Twc, double* Rt, uint8_t* inlier, int* count) try {
-  AIRFE_ENTER(c);
-  if (n < 0 || !K || !Twc || !count || (n > 0 && (!obj || !img || !inlier))) return fail(c, "pnp_ransac: bad argument");
-  if (n > PNP_MAX_POINTS) return fail(c, "pnp_ransac: more than 1024 correspondences");
-  const int ncap = std::max(n, 1);
-  // one block: n | Twc [16] | Rt [12] | count | obj [ncap][3] f32 | img [ncap][2] f32 | mask [ncap]
-  const size_t o_obj = 256, o_img = o_obj + (size_t)ncap * 12, o_mask = o_img + (size_t)ncap * 8;
-  if (ensure_block(c, c->pn_stage, c->pn_stage_bytes, o_mask + ncap)) return 1;
-  std::vector<float> h((size_t)ncap * 5, 0.f);
-  for (int i = 0; i < n; ++i) {                                      // cv::Point3f / cv::Point2f: the doubles rounded to float
-    for (int k = 0; k < 3; ++k) h[3 * i + k] = (float)obj[3 * i + k];
-    for (int k = 0; k < 2; ++k) h[(size_t)ncap * 3 + 2 * i + k] = (float)img[2 * i + k];
-  }
-  uint8_t* d = c->pn_stage;
-  int* d_n = reinterpret_cast<int*>(d);
-  double* d_Twc = reinterpret_cast<double*>(d + 8);
-  double* d_Rt = reinterpret_cast<double*>(d + 8 + 128);
-  int* d_count = reinterpret_cast<int*>(d + 8 + 128 + 96);
-  hipStream_t st = c->stream;
-  DrainOnError drain{c, true};
-  HIPCHK(c, hipMemcpyAsync(d_n, &n, 4, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(d + o_obj, h.data(), (size_t)ncap * 20, hipMemcpyHostToDevice, st));
-  if (pnp_queue(c, reinterpret_cast<float*>(d + o_obj), reinterpret_cast<float*>(d + o_img), d_n, 1, ncap, K, d_Twc, d_Rt, d + o_mask, ncap, nullptr,
-                d_count, st)) return 1;
-  double rt[12];
-  HIPCHK(c, hipMemcpyAsync(Twc, d_Twc, 128, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(rt, d_Rt, 96, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(count, d_count, 4, hipMemcpyDeviceToHost, st));
-  if (n > 0) HIPCHK(c, hipMemcpyAsync(inlier, d + o_mask, n, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  drain.armed = false;
-  if (Rt) memcpy(Rt, rt, 96);
-  return 0;
-} AIRFE_CATCH(c)
-
-int airfe_stereo_points(airfe_ctx* c, const double* cam, const float* featL, int nL, const float* featR, int nR, const int32_t* idx, int m, double* u_right,
-                        double* depth, double* xyz, int* good) try {
-  if (!c) return 1;
-  if (!cam || !good || nL < 0 || nR < 0 || m < 0 || (nL > 0 && (!featL || !u_right || !depth || !xyz)) || (m > 0 && (!idx || !featR)))
-    return fail(c, "stereo_points: bad argument");
-  for (int j = 0; j < m; ++j)                                        // Frame::AddRightFeatures indexes both feature matrices with these
-    if (idx[2 * j] < 0 || idx[2 * j] >= nL || idx[2 * j + 1] < 0 || idx[2 * j + 1] >= nR) return fail(c, "stereo_points: match index out of range");
-  *good = pnp_stereo_host(featL, nL, featR, idx, m, cam, u_right, depth, xyz);
-  return 0;
-} AIRFE_CATCH(c)
-
-int airfe_stereo_points_batch_dev(airfe_ctx* c, const double* cam, const float* d_featL, const int* d_nL, const float* d_featR, const int* d_nR, int B,
-                                  int cap, const int32_t* d_idx, const int* d_nmatch, int mcap, double* d_u_right, double* d_depth, double* d_xyz,
-                                  int* d_good, void* stream) try {
-  AIRFE_ENTER(c);
-  if (B < 1 || cap < 1 || mcap < 1 || !cam || !d_featL || !d_nL || !d_featR || !d_nR || !d_idx || !d_nmatch || !d_u_right || !d_depth || !d_xyz || !d_good)
-    return fail(c, "stereo_points_batch_dev: bad argument");
-  if (cap > PNP_STEREO_CAP) return fail(c, "stereo_points_batch_dev: cap > 4096");
-  StereoArgs s;
-  s.fl = d_featL; s.fr = d_featR; s.nl = d_nL; s.nr = d_nR; s.cap = cap; s.idx = d_idx; s.nmatch = d_nmatch; s.mcap = mcap;
-  s.min_x_diff = cam[0]; s.max_x_diff = cam[1]; s.max_y_diff = cam[2]; s.bf = cam[3]; s.fx = cam[4]; s.fy = cam[5]; s.cx = cam[6]; s.cy = cam[7];
-  s.u_right = d_u_right; s.depth = d_depth; s.xyz = d_xyz; s.good = d_good;
-  launch_stereo_points(s, B, stream ? (hipStream_t)stream : c->stream);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-} AIRFE_CATCH(c)
-
-int airfe_track_pose_batch_dev(airfe_ctx* c, const double* K, const double* d_xyz, int capK, const float* d_feat, int cap, const int32_t* d_tidx,
-                               const int* d_ntrack, int mcap, int B, double* d_Twc, double* d_Rt, uint8_t* d_mask, int* d_count, void* stream) try {
-  AIRFE_ENTER(c);
-  if (B < 1 || capK < 1 || cap < 1 || mcap < 1 || !K || !d_xyz || !d_feat || !d_tidx || !d_ntrack || !d_Twc || !d_mask || !d_count)
-    return fail(c, "track_pose_batch_dev: bad argument");
-  if (mcap > PNP_MAX_POINTS) return fail(c, "track_pose_batch_dev: mcap > 1024");
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-  // the gathered problems: obj [B][mcap][3] | img [B][mcap][2] f32 | map [B][mcap] | n [B]
-  const size_t per = (size_t)mcap * 24;
-  if (ensure_block(c, c->pn_gather, c->pn_gather_bytes, (size_t)B * per + (size_t)B * 4, c->pn_gather_stream)) return 1;
-  c->pn_gather_stream = st;
-  PnpGatherArgs g;
-  g.xyz = d_xyz; g.capK = capK; g.feat = d_feat; g.cap = cap; g.tidx = d_tidx; g.ntrack = d_ntrack; g.mcap = mcap; g.ncap = mcap;
-  g.obj = reinterpret_cast<float*>(c->pn_gather);
-  g.img = reinterpret_cast<float*>(c->pn_gather + (size_t)B * mcap * 12);
-  g.map = reinterpret_cast<int*>(c->pn_gather + (size_t)B * mcap * 20);
-  g.n = reinterpret_cast<int*>(c->pn_gather + (size_t)B * per);
-  launch_pnp_gather(g, B, st);
-  HIPCHK(c, hipGetLastError());
-  return pnp_queue(c, g.obj, g.img, g.n, B, mcap, K, d_Twc, d_Rt, d_mask, mcap, g.map, d_count, st);
-} AIRFE_CATCH(c)
-
-// Pose-only frame optimisation (g2o_optimization.cc:446-898, one free pose, point edges) over B device problems on `st` (kernels_poseopt.hip)
-static int poseopt_queue(airfe_ctx* c, const double* d_X, const double* d_obs, const int* d_n, int B, int ncap, const double* d_Twc0, const double* cam,
-                         const double* Tcb, const double* thr, double* d_Twc, double* d_Rt, uint8_t* d_inlier, int mcap, const int* d_map, int* d_num,
-                         int lost, int* d_ok, hipStream_t st) {
-  PoseoptArgs a;
-  a.X = d_X; a.obs = d_obs; a.n = d_n; a.ncap = ncap; a.Twc0 = d_Twc0;
-  for (int k = 0; k < 5; ++k) a.cam[k] = cam[k];
-  for (int k = 0; k < 2; ++k) a.thr[k] = thr[k];
-  if (Tcb) {
-    for (int k = 0; k < 12; ++k) a.Tcb[k] = Tcb[k];
-    a.has_tcb = 1;
-  }
-  a.Twc = d_Twc; a.Rt = d_Rt; a.inlier = d_inlier; a.mcap = mcap; a.map = d_map; a.num = d_num; a.lost = lost; a.ok = d_ok;
-  launch_poseopt(a, B, st);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-
-int airfe_frame_optimize_batch_dev(airfe_ctx* c, const double* d_X, const double* d_obs, const int* d_n, int B, int ncap, const double* d_Twc0,
-                                   const double* cam, const double* Tcb, const double* thr, double* d_Twc, double* d_Rt, uint8_t* d_inlier, int* d_num,
-                                   void* stream) try {
-  AIRFE_ENTER(c);
-  if (B < 1 || ncap < 1 || !d_X || !d_obs || !d_n || !d_Twc0 || !cam || !thr || !d_Twc || !d_inlier || !d_num)
-    return fail(c, "frame_optimize_batch_dev: bad argument");
-  if (ncap > PO_MAX_POINTS) return fail(c, "frame_optimize_batch_dev: ncap > 1024");
-  return poseopt_queue(c, d_X, d_obs, d_n, B, ncap, d_Twc0, cam, Tcb, thr, d_Twc, d_Rt, d_inlier, ncap, nullptr, d_num, -1, nullptr,
-                       stream ? (hipStream_t)stream : c->stream);
-} AIRFE_CATCH(c)
-
-int airfe_frame_optimize(airfe_ctx* c, const double* X, const double* obs, int n, const double* cam, const double* Tcb, const double* thr,
-                         const double* Twc0, double* Twc, double* Rt, uint8_t* inlier, int* num_inliers) try {
-  AIRFE_ENTER(c);
-  if (n < 0 || !cam || !thr || !Twc0 || !Twc || !num_inliers || (n > 0 && (!X || !obs || !inlier))) return fail(c, "frame_optimize: bad argument");
-  if (n > PO_MAX_POINTS) return fail(c, "frame_optimize: more than 1024 constraints");
-  const int ncap = std::max(n, 1);
-  // one block: n | Twc0 [16] | Twc [16] | Rt [12] | num | X [ncap][3] | obs [ncap][3] | inlier [ncap]
-  const size_t o_X = 512, o_obs = o_X + (size_t)ncap * 24, o_mask = o_obs + (size_t)ncap * 24;
-  if (ensure_block(c, c->po_stage, c->po_stage_bytes, o_mask + ncap)) return 1;
-  uint8_t* d = c->po_stage;
-  int* d_n = reinterpret_cast<int*>(d);
-  double* d_Twc0 = reinterpret_cast<double*>(d + 8);
-  double* d_Twc = reinterpret_cast<double*>(d + 8 + 128);
-  double* d_Rt = reinterpret_cast<double*>(d + 8 + 256);
-  int* d_num = reinterpret_cast<int*>(d + 8 + 256 + 96);
-  hipStream_t st = c->stream;
-  DrainOnError drain{c, true};
-  HIPCHK(c, hipMemcpyAsync(d_n, &n, 4, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(d_Twc0, Twc0, 128, hipMemcpyHostToDevice, st));
-  if (n > 0) {
-    HIPCHK(c, hipMemcpyAsync(d + o_X, X, (size_t)n * 24, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(d + o_obs, obs, (size_t)n * 24, hipMemcpyHostToDevice, st));
-  }
-  if (poseopt_queue(c, reinterpret_cast<double*>(d + o_X), reinterpret_cast<double*>(d + o_obs), d_n, 1, ncap, d_Twc0, cam, Tcb, thr, d_Twc, d_Rt,
-                    d + o_mask, ncap, nullptr, d_num, -1, nullptr, st)) return 1;
-  double rt[12];
-  HIPCHK(c, hipMemcpyAsync(Twc, d_Twc, 128, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(rt, d_Rt, 96, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(num_inliers, d_num, 4, hipMemcpyDeviceToHost, st));
-  if (n > 0) HIPCHK(c, hipMemcpyAsync(inlier, d + o_mask, n, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  drain.armed = false;
-  if (Rt) memcpy(Rt, rt, 96);
-  return 0;
-} AIRFE_CATCH(c)
-
-int airfe_track_pose_opt_batch_dev(airfe_ctx* c, const double* cam, const double* thr, int lost_num_match, const double* d_xyz, int capK,
-                                   const float* d_feat, int cap, const int32_t* d_tidx, const int* d_ntrack, int mcap, int B, const double* d_u_right,
-                                   const double* d_Twc_last, double* d_Twc, double* d_Rt, uint8_t* d_mask, int* d_num, int* d_ok, int* d_pnp_count,
-                                   void* stream) try {
-  AIRFE_ENTER(c);
-  if (B < 1 || capK < 1 || cap < 1 || mcap < 1 || lost_num_match < 0 || !cam || !thr || !d_xyz || !d_feat || !d_tidx || !d_ntrack || !d_Twc || !d_mask ||
-      !d_num || !d_ok)
-    return fail(c, "track_pose_opt_batch_dev: bad argument");
-  if (mcap > PNP_MAX_POINTS) return fail(c, "track_pose_opt_batch_dev: mcap > 1024");
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-  // the PnP gather's block (as airfe_track_pose_batch_dev): obj [B][mcap][3] | img [B][mcap][2] f32 | map [B][mcap] | n [B]
-  const size_t per = (size_t)mcap * 24;
-  if (ensure_block(c, c->pn_gather, c->pn_gather_bytes, (size_t)B * per + (size_t)B * 4, c->pn_gather_stream)) return 1;
-  c->pn_gather_stream = st;
-  // this entry's block: X [B][mcap][3] | obs [B][mcap][3] | Twc_pnp [B][16] | Twc0 [B][16] f64 | pnp count [B] | pnp mask [B][mcap]
-  const size_t o_obs = (size_t)B * per, o_pnp = 2 * o_obs, o_seed = o_pnp + (size_t)B * 128, o_cnt = o_seed + (size_t)B * 128;
-  const size_t o_msk = o_cnt + ((size_t)B * 4 + 7) / 8 * 8;
-  if (ensure_block(c, c->po_gather, c->po_gather_bytes, o_msk + (size_t)B * mcap, c->po_gather_stream)) return 1;
-  c->po_gather_stream = st;
-  PnpGatherArgs g;
-  g.xyz = d_xyz; g.capK = capK; g.feat = d_feat; g.cap = cap; g.tidx = d_tidx; g.ntrack = d_ntrack; g.mcap = mcap; g.ncap = mcap;
-  g.obj = reinterpret_cast<float*>(c->pn_gather);
-  g.img = reinterpret_cast<float*>(c->pn_gather + (size_t)B * mcap * 12);
-  g.map = reinterpret_cast<int*>(c->pn_gather + (size_t)B * mcap * 20);
-  g.n = reinterpret_cast<int*>(c->pn_gather + (size_t)B * per);
-  launch_pnp_gather(g, B, st);
-  HIPCHK(c, hipGetLastError());
-  double* d_pnp = reinterpret_cast<double*>(c->po_gather + o_pnp);
-  int* d_cnt = d_pnp_count ? d_pnp_count : reinterpret_cast<int*>(c->po_gather + o_cnt);
-  if (pnp_queue(c, g.obj, g.img, g.n, B, mcap, cam, d_pnp, nullptr, c->po_gather + o_msk, mcap, g.map, d_cnt, st)) return 1;
-  PoseoptGatherArgs q;
-  q.xyz = d_xyz; q.capK = capK; q.feat = d_feat; q.cap = cap; q.tidx = d_tidx; q.mcap = mcap; q.map = g.map; q.n = g.n; q.ncap = mcap;
-  q.u_right = d_u_right; q.Twc_pnp = d_pnp; q.Twc_last = d_Twc_last; q.pnp_count = d_cnt; q.lost = lost_num_match;
-  q.X = reinterpret_cast<double*>(c->po_gather); q.obs = reinterpret_cast<double*>(c->po_gather + o_obs);
-  q.Twc0 = reinterpret_cast<double*>(c->po_gather + o_seed);
-  launch_poseopt_gather(q, B, st);
-  HIPCHK(c, hipGetLastError());
-  return poseopt_queue(c, q.X, q.obs, g.n, B, mcap, q.Twc0, cam, nullptr, thr, d_Twc, d_Rt, d_mask, mcap, g.map, d_num, lost_num_match, d_ok, st);
-} AIRFE_CATCH(c)
 
 int airfe_has_line_branch(const airfe_ctx* c) { return c && c->has_s0 && c->has_s1; }
 
@@ -1126,7 +795,7 @@ int airfe_detect_plnet(airfe_ctx* c, const uint8_t* gray, int h, int w, int stri
   // point branch (plnet.cpp:560), line branch + tail, then [count | feature rows] and the three line / junction counts come back in one wait.
   hipStream_t st = c->stream;
   if (upload_image(c, gray, h, w, stride)) return 1;
-  if (detect_dev(c, c->st_img, 1, h, w, stride, (size_t)h * stride, c->st_feat0, c->Np, c->st_n0, st)) return 1;
+  if (detect_dev(c, c->st_img.p, 1, h, w, stride, (size_t)h * stride, c->st_feat0, c->Np, c->st_n0, st)) return 1;
   if (s0) {
     if (upload_stage0(c, s0, st)) return 1;
   } else if (line_branch_dev(c, st, 0, 1, false)) {   // the stage-0 line branch on the device: nothing crosses PCIe (the reference moves
@@ -1340,13 +1009,13 @@ static int stereo_keyframe_impl(airfe_ctx* c, const uint8_t* left, const uint8_t
   // device block: [counts 64 B | featL | featR | idx | score] — the part that comes back in the first copy — then [lines 2 x capLd | junctions]
   const size_t fb = (size_t)Np * AIRFE_FEAT_DIM * 4, head = 64 + 2 * fb + (size_t)Np * 24;      // (idx | score of TWO pairs: stereo, then the temporal one)
   const size_t lb = (size_t)capLd * 32, total = head + 2 * lb + (size_t)capJd * AIRFE_FEAT_DIM * 4;
-  if (ensure_block(c, c->kf_blk, c->kf_bytes, total)) return 1;
-  int* cnt = reinterpret_cast<int*>(c->kf_blk);                 // {nL, nR, nlines[2], -, njunc, found: lines[2] junc[1], -, nmatch: stereo, temporal}
-  float *d_fL = reinterpret_cast<float*>(c->kf_blk + 64), *d_fR = reinterpret_cast<float*>(c->kf_blk + 64 + fb);
-  int32_t* d_idx = reinterpret_cast<int32_t*>(c->kf_blk + 64 + 2 * fb);
-  float* d_sc = reinterpret_cast<float*>(c->kf_blk + 64 + 2 * fb + (size_t)Np * 16);               // [2][Np] behind idx [2][Np][2]
-  double* d_ln = reinterpret_cast<double*>(c->kf_blk + head);
-  float* d_jn = reinterpret_cast<float*>(c->kf_blk + head + 2 * lb);
+  if (reserve(c, c->kf_blk, total, c->stream)) return 1;
+  int* cnt = c->kf_blk.at<int>(0);                 // {nL, nR, nlines[2], -, njunc, found: lines[2] junc[1], -, nmatch: stereo, temporal}
+  float *d_fL = c->kf_blk.at<float>(64), *d_fR = c->kf_blk.at<float>(64 + fb);
+  int32_t* d_idx = c->kf_blk.at<int32_t>(64 + 2 * fb);
+  float* d_sc = c->kf_blk.at<float>(64 + 2 * fb + (size_t)Np * 16);               // [2][Np] behind idx [2][Np][2]
+  double* d_ln = c->kf_blk.at<double>(head);
+  float* d_jn = c->kf_blk.at<float>(head + 2 * lb);
   // both images through the pinned block in one copy (same row pitch; the right image starts at h * stride)
   const size_t ib = (size_t)(h - 1) * stride + w, pitch = (size_t)h * stride;
   // pinned block: [counts | featL | featR] — copied back on the side stream as soon as the detector is done, beside the matcher — then the final
@@ -1355,13 +1024,13 @@ static int stereo_keyframe_impl(airfe_ctx* c, const uint8_t* left, const uint8_t
   // the usual keyframe (a few hundred lines and junctions) needs no second round trip for them
   const int capS = std::min(capLd, c->kf_spec_lines), capJS = want_j ? std::min(capJd, c->kf_spec_juncs) : 0;
   const size_t early = 64 + 2 * fb, late = early + 64, spec = late + (size_t)Np * 24, spec_l = (size_t)capS * 32, spec_j = (size_t)capJS * AIRFE_FEAT_DIM * 4;
-  if (ensure_stage_img(c, 2 * pitch)) return 1;
+  if (reserve(c, c->st_img, 2 * pitch, c->stream)) return 1;
   // (sized for the line / junction rows of the second round trip too: the block must not move between calls, a captured graph holds its address)
   if (ensure_pin(c, std::max(std::max(pitch + ib, spec + 2 * spec_l + spec_j), 2 * lb + (size_t)capJd * AIRFE_FEAT_DIM * 4))) return 1;
   memcpy(c->pin, left, ib);
   memcpy(c->pin + pitch, right, ib);
   const std::function<int(hipStream_t)> early_copy = [&](hipStream_t s2) -> int {
-    HIPCHK(c, hipMemcpyAsync(c->pin, c->kf_blk, early, hipMemcpyDeviceToHost, s2));
+    HIPCHK(c, hipMemcpyAsync(c->pin, c->kf_blk.p, early, hipMemcpyDeviceToHost, s2));
     HIPCHK(c, hipEventRecord(c->ev_feat, s2));
     return 0;
   };
@@ -1370,8 +1039,8 @@ static int stereo_keyframe_impl(airfe_ctx* c, const uint8_t* left, const uint8_t
   LgSecondPair x2{};
   size_t ref_off = 0;
   if (track) {
-    if (ensure_block(c, c->ref_blk, c->ref_bytes, 64 + fb)) return 1;
-    x2.f0 = reinterpret_cast<const float*>(c->ref_blk + 64); x2.n0 = reinterpret_cast<const int*>(c->ref_blk);
+    if (reserve(c, c->ref_blk, 64 + fb, c->stream)) return 1;
+    x2.f0 = c->ref_blk.at<const float>(64); x2.n0 = c->ref_blk.at<const int>(0);
     x2.f1 = d_fL; x2.n1 = cnt;
     if (ref_feat) {
       ref_off = (std::max(pitch + ib, spec + 2 * spec_l + spec_j) + 63) / 64 * 64;
@@ -1392,14 +1061,14 @@ static int stereo_keyframe_impl(airfe_ctx* c, const uint8_t* left, const uint8_t
   auto queue_all = [&]() -> int {
     drain.armed = true;
     HIPCHK(c, hipMemsetAsync(cnt, 0, 64, st));
-    HIPCHK(c, hipMemcpyAsync(c->st_img, c->pin, pitch + ib, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->st_img.p, c->pin, pitch + ib, hipMemcpyHostToDevice, st));
     if (track && ref_feat) {
       drain.ref_uploaded = true;       // (the reference count becomes valid with the queued upload; an error below takes it back)
-      HIPCHK(c, hipMemcpyAsync(c->ref_blk, c->pin + ref_off, 64 + (size_t)n_ref * AIRFE_FEAT_DIM * 4, hipMemcpyHostToDevice, st));
+      HIPCHK(c, hipMemcpyAsync(c->ref_blk.p, c->pin + ref_off, 64 + (size_t)n_ref * AIRFE_FEAT_DIM * 4, hipMemcpyHostToDevice, st));
       c->ref_n = n_ref;
     }
     // (match counts: cnt[10] = stereo, cnt[11] = temporal — LightGlue writes d_nmatch[pair])
-    if (stereo_plnet_dev(c, c->st_img, c->st_img + pitch, 1, h, w, stride, pitch, d_fL, d_fR, Np, cnt, cnt + 1, d_ln, capLd, cnt + 2,
+    if (stereo_plnet_dev(c, c->st_img.p, c->st_img.p + pitch, 1, h, w, stride, pitch, d_fL, d_fR, Np, cnt, cnt + 1, d_ln, capLd, cnt + 2,
                          want_j ? d_jn : nullptr, capJd, want_j ? cnt + 5 : nullptr, cnt + 6, match ? d_idx : nullptr, d_sc, Np, cnt + 10, st, &early_copy, &rows_copy,
                          track ? &x2 : nullptr))
       return 1;
@@ -1418,7 +1087,7 @@ static int stereo_keyframe_impl(airfe_ctx* c, const uint8_t* left, const uint8_t
   // (Measured: <= 1 % per keyframe, profiles/r04_keyframe_graph_ab.txt — the queue is bound by the GPU's ~4.7 us per dependent launch, not by the
   // host's launch calls; the default stays the plain queue.)
   KfGraph& G = c->kf_graph;
-  const KfGraph::Key key{h, w, stride, capLd, capJd, want_j, match, c->pin, c->kf_blk, c->st_img};
+  const KfGraph::Key key{h, w, stride, capLd, capJd, want_j, match, c->pin, c->kf_blk.p, c->st_img.p};
   const bool graph_ok = c->kf_graph_on && c->prof_mask == 0 && !c->trace_on && !track;
   if (!(G.key == key)) { G.reset(); G.key = key; }
   bool replay = false;
@@ -1532,33 +1201,33 @@ int airfe_track_frame(airfe_ctx* c, const uint8_t* gray, int h, int w, int strid
   hipStream_t st = c->stream;
   const size_t fb = (size_t)Np * AIRFE_FEAT_DIM * 4, early = 64 + fb, late = early + 64;
   // device block: [counts | new rows | idx | score] and the reference block [count | reference rows] (kept from call to call)
-  if (ensure_block(c, c->tk_blk, c->tk_bytes, 64 + fb + (size_t)Np * 12)) return 1;
-  if (ensure_block(c, c->ref_blk, c->ref_bytes, 64 + fb)) return 1;
-  int* cnt = reinterpret_cast<int*>(c->tk_blk);                       // {n_new, -, nmatch}
-  float* d_new = reinterpret_cast<float*>(c->tk_blk + 64);
-  int32_t* d_idx = reinterpret_cast<int32_t*>(c->tk_blk + 64 + fb);
-  float* d_sc = reinterpret_cast<float*>(c->tk_blk + 64 + fb + (size_t)Np * 8);
-  int* d_nref = reinterpret_cast<int*>(c->ref_blk);
-  float* d_ref = reinterpret_cast<float*>(c->ref_blk + 64);
+  if (reserve(c, c->tk_blk, 64 + fb + (size_t)Np * 12, c->stream)) return 1;
+  if (reserve(c, c->ref_blk, 64 + fb, c->stream)) return 1;
+  int* cnt = c->tk_blk.at<int>(0);                       // {n_new, -, nmatch}
+  float* d_new = c->tk_blk.at<float>(64);
+  int32_t* d_idx = c->tk_blk.at<int32_t>(64 + fb);
+  float* d_sc = c->tk_blk.at<float>(64 + fb + (size_t)Np * 8);
+  int* d_nref = c->ref_blk.at<int>(0);
+  float* d_ref = c->ref_blk.at<float>(64);
   const size_t ib = (size_t)(h - 1) * stride + w, ioff = (ib + 63) / 64 * 64;
-  if (ensure_stage_img(c, (size_t)h * stride)) return 1;
+  if (reserve(c, c->st_img, (size_t)h * stride, c->stream)) return 1;
   if (ensure_pin(c, std::max(ioff + 64 + fb, late + (size_t)Np * 12))) return 1;
   if (!ref_feat && c->ref_n < 0) return fail(c, "track_frame: no reference features were ever given (ref_feat == NULL on the first call)");
   memcpy(c->pin, gray, ib);
   DrainOnError drain{c, true};
   HIPCHK(c, hipMemsetAsync(cnt, 0, 64, st));
-  HIPCHK(c, hipMemcpyAsync(c->st_img, c->pin, ib, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->st_img.p, c->pin, ib, hipMemcpyHostToDevice, st));
   if (ref_feat) {
     *reinterpret_cast<int*>(c->pin + ioff) = n_ref;
     if (n_ref > 0) memcpy(c->pin + ioff + 64, ref_feat, (size_t)n_ref * AIRFE_FEAT_DIM * 4);
     drain.ref_uploaded = true;
-    HIPCHK(c, hipMemcpyAsync(c->ref_blk, c->pin + ioff, 64 + (size_t)n_ref * AIRFE_FEAT_DIM * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->ref_blk.p, c->pin + ioff, 64 + (size_t)n_ref * AIRFE_FEAT_DIM * 4, hipMemcpyHostToDevice, st));
     c->ref_n = n_ref;
   }
-  if (detect_dev(c, c->st_img, 1, h, w, stride, (size_t)h * stride, d_new, Np, cnt, st)) return 1;
+  if (detect_dev(c, c->st_img.p, 1, h, w, stride, (size_t)h * stride, d_new, Np, cnt, st)) return 1;
   HIPCHK(c, hipEventRecord(c->ev_fork, st));                         // the new rows go home on the side stream, beside the matcher
   HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-  HIPCHK(c, hipMemcpyAsync(c->pin, c->tk_blk, early, hipMemcpyDeviceToHost, c->stream2));
+  HIPCHK(c, hipMemcpyAsync(c->pin, c->tk_blk.p, early, hipMemcpyDeviceToHost, c->stream2));
   HIPCHK(c, hipEventRecord(c->ev_feat, c->stream2));
   if (lightglue_dev(c, d_ref, d_nref, d_new, cnt, 1, Np, AIRFE_FEAT_DIM, 1, 1, d_idx, d_sc, Np, cnt + 2, nullptr, st)) return 1;
   if (c->outlier_rejection && fransac_queue(c, d_ref, d_new, 1, Np, d_idx, d_sc, Np, cnt + 2, nullptr, st)) return 1;   // point_matcher.cc:95-104
@@ -1593,29 +1262,29 @@ int airfe_promote_frame(airfe_ctx* c, const uint8_t* right, int h, int w, int st
   if (cap < c->cfg.max_keypoints || mcap < c->cfg.max_keypoints) return fail(c, "feature / match capacity < max_keypoints");
   if (!c->has_lg) return fail(c, "promote_frame: LightGlue weights were not loaded (cfg.lightglue_pack)");
   if (c->mprec == 2 || c->prec == 2) return fail(c, "promote_frame runs in fp16 / bf16");
-  if (c->tk_n < 0 || !c->tk_blk) return fail(c, "promote_frame: no airfe_track_frame preceded it (the left features live on the device since that call)");
+  if (c->tk_n < 0 || !c->tk_blk.p) return fail(c, "promote_frame: no airfe_track_frame preceded it (the left features live on the device since that call)");
   const int Np = c->cfg.max_keypoints;
   *nR = 0; *nmatch = 0;
   hipStream_t st = c->stream;
   const size_t fb = (size_t)Np * AIRFE_FEAT_DIM * 4, early = 64 + fb, late = early + 64;
-  if (ensure_block(c, c->pr_blk, c->pr_bytes, 64 + fb + (size_t)Np * 12)) return 1;
-  int* cnt = reinterpret_cast<int*>(c->pr_blk);                       // {n_right, -, nmatch}
-  float* d_right = reinterpret_cast<float*>(c->pr_blk + 64);
-  int32_t* d_idx = reinterpret_cast<int32_t*>(c->pr_blk + 64 + fb);
-  float* d_sc = reinterpret_cast<float*>(c->pr_blk + 64 + fb + (size_t)Np * 8);
-  const int* d_nleft = reinterpret_cast<const int*>(c->tk_blk);
-  const float* d_left = reinterpret_cast<const float*>(c->tk_blk + 64);
+  if (reserve(c, c->pr_blk, 64 + fb + (size_t)Np * 12, c->stream)) return 1;
+  int* cnt = c->pr_blk.at<int>(0);                       // {n_right, -, nmatch}
+  float* d_right = c->pr_blk.at<float>(64);
+  int32_t* d_idx = c->pr_blk.at<int32_t>(64 + fb);
+  float* d_sc = c->pr_blk.at<float>(64 + fb + (size_t)Np * 8);
+  const int* d_nleft = c->tk_blk.at<const int>(0);
+  const float* d_left = c->tk_blk.at<const float>(64);
   const size_t ib = (size_t)(h - 1) * stride + w;
-  if (ensure_stage_img(c, (size_t)h * stride)) return 1;
+  if (reserve(c, c->st_img, (size_t)h * stride, c->stream)) return 1;
   if (ensure_pin(c, std::max(ib, late + (size_t)Np * 12))) return 1;
   memcpy(c->pin, right, ib);
   DrainOnError drain{c, true};
   HIPCHK(c, hipMemsetAsync(cnt, 0, 64, st));
-  HIPCHK(c, hipMemcpyAsync(c->st_img, c->pin, ib, hipMemcpyHostToDevice, st));
-  if (detect_dev(c, c->st_img, 1, h, w, stride, (size_t)h * stride, d_right, Np, cnt, st)) return 1;
+  HIPCHK(c, hipMemcpyAsync(c->st_img.p, c->pin, ib, hipMemcpyHostToDevice, st));
+  if (detect_dev(c, c->st_img.p, 1, h, w, stride, (size_t)h * stride, d_right, Np, cnt, st)) return 1;
   HIPCHK(c, hipEventRecord(c->ev_fork, st));
   HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-  HIPCHK(c, hipMemcpyAsync(c->pin, c->pr_blk, early, hipMemcpyDeviceToHost, c->stream2));
+  HIPCHK(c, hipMemcpyAsync(c->pin, c->pr_blk.p, early, hipMemcpyDeviceToHost, c->stream2));
   HIPCHK(c, hipEventRecord(c->ev_feat, c->stream2));
   if (lightglue_dev(c, d_left, d_nleft, d_right, cnt, 1, Np, AIRFE_FEAT_DIM, 1, 1, d_idx, d_sc, Np, cnt + 2, nullptr, st)) return 1;
   HIPCHK(c, hipMemcpyAsync(c->pin + early, cnt, 64, hipMemcpyDeviceToHost, st));
@@ -1639,11 +1308,11 @@ int airfe_promote_frame(airfe_ctx* c, const uint8_t* right, int h, int w, int st
 
 int airfe_adopt_reference(airfe_ctx* c) try {
   AIRFE_ENTER(c);
-  if (c->tk_n < 0 || !c->tk_blk) return fail(c, "adopt_reference: no airfe_track_frame preceded it");
+  if (c->tk_n < 0 || !c->tk_blk.p) return fail(c, "adopt_reference: no airfe_track_frame preceded it");
   const size_t fb = (size_t)c->cfg.max_keypoints * AIRFE_FEAT_DIM * 4;
-  if (ensure_block(c, c->ref_blk, c->ref_bytes, 64 + fb)) return 1;
+  if (reserve(c, c->ref_blk, 64 + fb, c->stream)) return 1;
   // [count | rows] have the same layout in both blocks (the count's word 0; words 1.. of the header are scratch of the entries)
-  HIPCHK(c, hipMemcpyAsync(c->ref_blk, c->tk_blk, 64 + (size_t)std::max(c->tk_n, 0) * AIRFE_FEAT_DIM * 4, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->ref_blk.p, c->tk_blk.p, 64 + (size_t)std::max(c->tk_n, 0) * AIRFE_FEAT_DIM * 4, hipMemcpyDeviceToDevice, c->stream));
   c->ref_n = c->tk_n;
   return 0;
 } AIRFE_CATCH(c)
@@ -1838,1281 +1507,6 @@ int airfe_match_superglue_batch_dev(airfe_ctx* c, const float* d_f0, const int* 
 int airfe_debug_superglue_scores(airfe_ctx* c, const float* f0, int n0, const float* f1, int n1, float* scores) try {
   if (c && enter_device(c)) return 1;
   return sg_host(c, f0, n0, f1, n1, nullptr, nullptr, nullptr, nullptr, scores);
-} AIRFE_CATCH(c)
-
-// ---- kernel-level test hooks ------------------------------------------------------------------------------
-int airfe_debug_preprocess(airfe_ctx* c, const uint8_t* gray, int h, int w, int stride, float* out) try {
-  if (c && enter_device(c)) return 1;
-  if (!c || !c->has_sp) return fail(c, "debug_preprocess: detector not loaded");
-  const size_t bytes = (size_t)h * stride;
-  if (upload_image(c, gray, h, w, stride) || ensure_tables(c, h, w)) return 1;
-  const int R = AIRFE_INTERNAL_SIZE;
-  launch_preprocess(c->st_img, 1, h, w, stride, bytes, c->xtab, c->ytab, c->lut, c->img32, R, R, c->stream);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy2D(out, (size_t)R * 4, c->img32 + (R + 2) + 1, (size_t)(R + 2) * 4, (size_t)R * 4, R, hipMemcpyDeviceToHost));
-  return 0;
-} AIRFE_CATCH(c)
-
-int airfe_debug_conv3x3(airfe_ctx* c, const float* x, int B, int cin, int H, int W, const float* w, const float* b, int cout,
-                        int pool, float* y) try {
-  AIRFE_ENTER(c);
-  if ((cin != 64 && cin != 128) || cout % 64 || W % 16 || H % 16) return fail(c, "debug_conv3x3: unsupported shape");
-  const int prec = c->prec;
-  std::vector<uint16_t> xin((size_t)B * (H + 2) * (W + 2) * cin, 0);
-  for (int bb = 0; bb < B; ++bb)
-    for (int ci = 0; ci < cin; ++ci)
-      for (int yy = 0; yy < H; ++yy)
-        for (int xx = 0; xx < W; ++xx)
-          xin[(((size_t)bb * (H + 2) + yy + 1) * (W + 2) + xx + 1) * cin + ci] = cvt2(x[(((size_t)bb * cin + ci) * H + yy) * W + xx], prec);
-  const int nci = cin / 64;
-  auto slabs = pack_slabs(cout / 64, 9 * nci, prec, [&](int feat, int s, int k) {
-    const int tap = s / nci, cc = s % nci, ci = cc * 64 + k;
-    return w[((size_t)feat * cin + ci) * 9 + tap];
-  });
-  const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
-  uint16_t *dx = nullptr, *dw = nullptr, *dy = nullptr;
-  float* db = nullptr;
-  const size_t ybytes = (size_t)B * (Ho + 2) * (Wo + 2) * cout * 2;
-  HIPCHK(c, hipMalloc((void**)&dx, xin.size() * 2));
-  HIPCHK(c, hipMalloc((void**)&dw, slabs.size() * 2));
-  HIPCHK(c, hipMalloc((void**)&dy, ybytes));
-  HIPCHK(c, hipMalloc((void**)&db, (size_t)cout * 4));
-  HIPCHK(c, hipMemcpy(dx, xin.data(), xin.size() * 2, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(dw, slabs.data(), slabs.size() * 2, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(db, b, (size_t)cout * 4, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemset(dy, 0, ybytes));
-  ConvArgs a;
-  a.X = dx; a.Wp = dw; a.bias = db; a.Y = dy; a.B = B; a.H = H; a.W = W; a.CIN = cin; a.COUT = cout;
-  a.pool = pool; a.out_pad = 1; a.relu = 1;
-  launch_conv3x3(prec, a, c->stream);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  std::vector<uint16_t> yo(ybytes / 2);
-  HIPCHK(c, hipMemcpy(yo.data(), dy, ybytes, hipMemcpyDeviceToHost));
-  for (int bb = 0; bb < B; ++bb)
-    for (int co = 0; co < cout; ++co)
-      for (int yy = 0; yy < Ho; ++yy)
-        for (int xx = 0; xx < Wo; ++xx)
-          y[(((size_t)bb * cout + co) * Ho + yy) * Wo + xx] = back2(yo[(((size_t)bb * (Ho + 2) + yy + 1) * (Wo + 2) + xx + 1) * cout + co], prec);
-  (void)hipFree(dx); (void)hipFree(dw); (void)hipFree(dy); (void)hipFree(db);
-  return 0;
-} AIRFE_CATCH(c)
-
-int airfe_debug_fail_next_launch(airfe_ctx* c, int stage) try {
-  AIRFE_ENTER(c);
-  if (stage < -1 || stage >= ST_COUNT) return fail(c, "debug_fail_next_launch: no such stage");
-  c->fail_stage = stage;
-  return 0;
-} AIRFE_CATCH(c)
-
-int airfe_debug_gemm(airfe_ctx* c, const float* x, int M, int K, const float* w, const float* b, int N, int relu, float* y) try {
-  AIRFE_ENTER(c);
-  if (K != 128 && K != 256 && K != 512) return fail(c, "debug_gemm: K must be 128, 256 or 512");
-  const int prec = c->prec, Mp = (M + 127) / 128 * 128, Np8 = (N + 7) / 8 * 8;
-  std::vector<uint16_t> xin((size_t)Mp * K, 0);
-  for (size_t i = 0; i < (size_t)M * K; ++i) xin[i] = cvt2(x[i], prec);
-  airfe_ctx tmp;   // only as an allocation list holder
-  tmp.prec = prec;
-  tmp.pack_prec = prec;
-  LinW lw;
-  if (!make_linear(&tmp, w, b, K, N, lw)) return fail(c, "debug_gemm: allocation failed");
-  uint16_t* dx = dupload(&tmp, xin);
-  float* dy = dalloc<float>(&tmp, (size_t)Mp * Np8);
-  int rc = 0;
-  if (!dx || !dy) rc = fail(c, "debug_gemm: allocation failed");
-  if (!rc) {
-    GemmArgs g;
-    g.X1 = dx; g.ld1 = K; g.K1 = K; g.Wp = lw.w; g.bias = lw.b; g.M = Mp; g.N = N; g.cb_total = lw.cbt;
-    g.epi = EPI_STORE_F32; g.act = relu ? ACT_RELU : ACT_NONE; g.out = dy; g.ldo = Np8;
-    g.small_max = c->gemm_small_max; g.g8_min = c->gemm8_min; g.gr_min = c->gemmr_min; g.gr_wgs = c->gemmr_wgs;
-    launch_gemm(prec, K, false, g, c->stream);
-    if (hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, "debug_gemm: kernel failed");
-  }
-  if (!rc) {
-    std::vector<float> yo((size_t)Mp * Np8);
-    (void)hipMemcpy(yo.data(), dy, yo.size() * 4, hipMemcpyDeviceToHost);
-    for (int m = 0; m < M; ++m)
-      for (int n = 0; n < N; ++n) y[(size_t)m * N + n] = yo[(size_t)m * Np8 + n];
-  }
-  for (void* p : tmp.allocs) (void)hipFree(p);
-  return rc;
-} AIRFE_CATCH(c)
-
-}  // extern "C"
-
-// ---- the GEMM family one form at a time (include/airfe_debug.h): host tensors -> the production launchers -> host tensors
-static std::vector<uint16_t> dbg_rows2(const float* x, int rows, int cols, int rows_cap, int prec) {
-  std::vector<uint16_t> v((size_t)rows_cap * cols, 0);
-  if (x)
-    for (size_t i = 0; i < (size_t)rows * cols; ++i) v[i] = cvt2(x[i], prec);
-  return v;
-}
-static std::vector<float> dbg_rows4(const float* x, int rows, int cols, int rows_cap) {
-  std::vector<float> v((size_t)rows_cap * cols, 0.f);
-  if (x) memcpy(v.data(), x, (size_t)rows * cols * sizeof(float));
-  return v;
-}
-template <class T>
-static T* dbg_canary(airfe_ctx* tmp, size_t n) {       // an output buffer whose every byte starts as 0xFF (NaN in fp32, fp16 and bf16)
-  T* p = dalloc<T>(tmp, n, false);
-  if (p) (void)hipMemset(p, 0xFF, std::max<size_t>(n, 1) * sizeof(T));
-  return p;
-}
-static void dbg_back2(const std::vector<uint16_t>& v, size_t n, int prec, float* out) {
-  for (size_t i = 0; i < n; ++i) out[i] = back2(v[i], prec);
-}
-
-extern "C" {
-
-int airfe_debug_linear(airfe_ctx* c, const airfe_debug_linear_args* a) try {
-  AIRFE_ENTER(c);
-  if (!a || !a->x1 || !a->w || !a->b || !a->out) return fail(c, "debug_linear: null argument");
-  const int prec = a->prec, M = a->M, K = a->K, N = a->N, epi = a->epi, kern = a->kernel, K1 = a->x2 ? a->K1 : K;
-  if ((prec != 0 && prec != 1) || M < 1 || N < 1 || (K != 128 && K != 256 && K != 512) || K1 < 32 || K1 % 32 || K1 > K || (a->x2 && K1 == K) ||
-      epi < EPI_STORE || epi > EPI_SOFTMAX_D2S || kern < AIRFE_DEBUG_KERNEL_DISPATCH || kern > AIRFE_DEBUG_KERNEL_GEMMR_GATHER128 || (a->act != ACT_NONE && a->act != ACT_RELU))
-    return fail(c, "debug_linear: bad argument");
-  const bool trans = epi == EPI_HEADS_T, heads = epi == EPI_HEADS || trans, d2s = epi == EPI_SOFTMAX_D2S;
-  if (heads && ((a->H != 4 && a->H != 0) || a->Np < 16 || a->Np % 16 || M % a->Np || (epi == EPI_HEADS ? (N != 256 && N != 512) || (N == 512 && !a->out2) : N != 256)))
-    return fail(c, "debug_linear: head layouts need H = 4, M = S * Np with Np a multiple of 16, N = 256 (or 512 with out2 for EPI_HEADS)");
-  if ((a->rot_cos || a->rot_sin) && (epi != EPI_HEADS || !a->rot_cos || !a->rot_sin)) return fail(c, "debug_linear: rotary is an EPI_HEADS form");
-  if (epi == EPI_RESID && (!a->x32 || N % 64)) return fail(c, "debug_linear: EPI_RESID needs x32 and N a multiple of 64");
-  if (d2s && (K != 256 || N != 65 || a->x2 || a->rowidx || a->act || a->d2s_hc < 1 || a->d2s_wc < 1 || M % (a->d2s_hc * a->d2s_wc) || M % 16 ||
-              (kern != AIRFE_DEBUG_KERNEL_DISPATCH && kern != AIRFE_DEBUG_KERNEL_GEMM8)))
-    return fail(c, "debug_linear: EPI_SOFTMAX_D2S is launch_gemm8's head kernel: K = 256, N = 65, dense rows, M = B * hc * wc, M % 16 == 0");
-  if (a->rowidx) {
-    if (kern != AIRFE_DEBUG_KERNEL_GEMM8 && kern != AIRFE_DEBUG_KERNEL_GEMMR_GATHER && kern != AIRFE_DEBUG_KERNEL_GEMMR_GATHER128)
-      return fail(c, "debug_linear: a row gather runs in gemm8, gemmr_gather or gemmr_gather128 only");
-    if (a->src_rows < 1) return fail(c, "debug_linear: rowidx needs src_rows");
-    for (int r = 0; r < M; ++r)
-      if (a->rowidx[r] < 0 || a->rowidx[r] >= a->src_rows) return fail(c, "debug_linear: rowidx entry outside 0 .. src_rows - 1");
-  }
-  static const int row_tile[7] = {128, 32, 128, 256, 32, 32, 64};
-  const int Mp = d2s ? M : (M + row_tile[kern] - 1) / row_tile[kern] * row_tile[kern];
-  const int xrows = a->rowidx ? a->src_rows : Mp;
-  const int ldo = (epi == EPI_STORE || epi == EPI_STORE_F32) ? (N + 7) / 8 * 8 : N;
-  const int Sg = heads ? (Mp + a->Np - 1) / a->Np : 0, S = heads ? M / a->Np : 0;
-  airfe_ctx tmp;   // only as an allocation list holder
-  tmp.prec = prec;
-  tmp.pack_prec = prec;
-  LinW lw;
-  if (!make_linear(&tmp, a->w, a->b, K, N, lw)) { for (void* p : tmp.allocs) (void)hipFree(p); return fail(c, "debug_linear: allocation failed"); }
-  GemmArgs g;
-  g.X1 = dupload(&tmp, dbg_rows2(a->x1, a->rowidx ? a->src_rows : M, K1, xrows, prec)); g.ld1 = K1; g.K1 = K1;
-  if (a->x2) { g.X2 = dupload(&tmp, dbg_rows2(a->x2, M, K - K1, Mp, prec)); g.ld2 = K - K1; }
-  g.Wp = lw.w; g.bias = lw.b; g.M = Mp; g.N = N; g.cb_total = lw.cbt; g.epi = epi; g.act = a->act; g.ldo = ldo; g.Np = a->Np; g.H = 4;
-  g.small_max = c->gemm_small_max; g.g8_min = c->gemm8_min; g.gr_min = c->gemmr_min; g.gr_wgs = a->gr_wgs > 0 ? a->gr_wgs : c->gemmr_wgs;
-  if (a->rot_cos) { g.rot_cos = dupload(&tmp, dbg_rows4(a->rot_cos, M, 32, Mp)); g.rot_sin = dupload(&tmp, dbg_rows4(a->rot_sin, M, 32, Mp)); }
-  if (a->rowidx) { std::vector<int> ri(Mp, 0); memcpy(ri.data(), a->rowidx, (size_t)M * sizeof(int)); g.rowidx = dupload(&tmp, ri); }
-  size_t out_elems = 0;
-  if (epi == EPI_STORE || epi == EPI_RESID) out_elems = (size_t)Mp * ldo;
-  else if (heads) out_elems = (size_t)Sg * 4 * a->Np * 64;
-  if (epi == EPI_STORE_F32) g.out = dbg_canary<float>(&tmp, (size_t)Mp * ldo);
-  else if (d2s) g.out = dbg_canary<float>(&tmp, (size_t)M * 64);
-  else g.out = dbg_canary<uint16_t>(&tmp, out_elems);
-  if (epi == EPI_HEADS && N == 512) g.out2 = dbg_canary<uint16_t>(&tmp, out_elems);
-  if (epi == EPI_RESID) g.x32 = dupload(&tmp, dbg_rows4(a->x32, M, N, Mp));
-  if (d2s) { g.d2s_hc = a->d2s_hc; g.d2s_wc = a->d2s_wc; g.flag = dalloc<int>(&tmp, 1); }
-  bool ok = g.X1 && (!a->x2 || g.X2) && g.out && (!(epi == EPI_HEADS && N == 512) || g.out2) && (epi != EPI_RESID || g.x32) && (!a->rot_cos || (g.rot_cos && g.rot_sin)) &&
-            (!a->rowidx || g.rowidx) && (!d2s || g.flag);
-  int rc = ok ? 0 : fail(c, "debug_linear: allocation failed");
-  // a forced kernel runs only where its own applicability test says yes: never a silent fall-back to another kernel
-  const char* refused = nullptr;
-  if (!rc) switch (kern) {
-    case AIRFE_DEBUG_KERNEL_DISPATCH:
-      if (d2s) launch_gemm8(prec, K, false, g, c->stream);
-      else launch_gemm(prec, K, trans, g, c->stream);
-      break;
-    case AIRFE_DEBUG_KERNEL_SMALL:                       // launch_gemm's own row test with every other path moved out of reach
-      if (d2s || a->rowidx) refused = "gemm_small";
-      else { g.small_max = 1 << 30; g.g8_min = 1 << 30; g.gr_min = 1 << 30; launch_gemm(prec, K, trans, g, c->stream); }
-      break;
-    case AIRFE_DEBUG_KERNEL_TILED:
-      if (d2s || a->rowidx || K1 % 64) refused = "gemm_kernel";
-      else { g.small_max = -1; g.g8_min = 1 << 30; g.gr_min = 1 << 30; launch_gemm(prec, K, trans, g, c->stream); }
-      break;
-    case AIRFE_DEBUG_KERNEL_GEMM8:
-      if (K1 % 64) refused = "gemm8";
-      else launch_gemm8(prec, K, trans, g, c->stream);
-      break;
-    case AIRFE_DEBUG_KERNEL_GEMMR:
-      if (a->rowidx || !gemmr_applicable(K, trans, g)) refused = "gemmr";
-      else launch_gemmr(prec, trans, g, c->stream);
-      break;
-    case AIRFE_DEBUG_KERNEL_GEMMR_GATHER:
-      if (!gemmr_gather_applicable(K, g)) refused = "gemmr_gather";
-      else launch_gemmr_gather(prec, g, c->stream);
-      break;
-    default:
-      if (!gemmr_gather128_applicable(g)) refused = "gemmr_gather128";
-      else launch_gemmr_gather128(prec, g, c->stream);
-      break;
-  }
-  if (refused) rc = fail(c, std::string("debug_linear: ") + refused + " does not apply to this form");
-  if (!rc && (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c))) rc = fail(c, "debug_linear: kernel failed");
-  if (!rc) {
-    if (epi == EPI_STORE_F32 || d2s) {
-      std::vector<float> ho(d2s ? (size_t)M * 64 : (size_t)Mp * ldo);
-      (void)hipMemcpy(ho.data(), g.out, ho.size() * 4, hipMemcpyDeviceToHost);
-      if (d2s) memcpy(a->out, ho.data(), ho.size() * 4);
-      else
-        for (int m = 0; m < M; ++m) memcpy(a->out + (size_t)m * N, ho.data() + (size_t)m * ldo, (size_t)N * 4);
-      if (d2s && a->flag) (void)hipMemcpy(a->flag, g.flag, sizeof(int), hipMemcpyDeviceToHost);
-    } else if (heads) {
-      std::vector<uint16_t> ho(out_elems);
-      const size_t n = (size_t)S * 4 * a->Np * 64;
-      (void)hipMemcpy(ho.data(), g.out, ho.size() * 2, hipMemcpyDeviceToHost);
-      dbg_back2(ho, n, prec, a->out);
-      if (g.out2) {
-        (void)hipMemcpy(ho.data(), g.out2, ho.size() * 2, hipMemcpyDeviceToHost);
-        dbg_back2(ho, n, prec, a->out2);
-      }
-    } else {
-      std::vector<uint16_t> ho(out_elems);
-      (void)hipMemcpy(ho.data(), g.out, ho.size() * 2, hipMemcpyDeviceToHost);
-      for (int m = 0; m < M; ++m)
-        for (int n = 0; n < N; ++n) a->out[(size_t)m * N + n] = back2(ho[(size_t)m * ldo + n], prec);
-      if (epi == EPI_RESID) (void)hipMemcpy(a->x32, g.x32, (size_t)M * N * 4, hipMemcpyDeviceToHost);
-    }
-  }
-  for (void* p : tmp.allocs) (void)hipFree(p);
-  return rc;
-} AIRFE_CATCH(c)
-
-int airfe_debug_qkv(airfe_ctx* c, int prec, int M, int Np, const float* x, const float* wqk, const float* bqk, int nqk, const float* wv, const float* bv,
-                    const float* rot_cos, const float* rot_sin, int pair, int gr_wgs, float* q, float* k, float* vt) try {
-  AIRFE_ENTER(c);
-  if ((prec != 0 && prec != 1) || M < 1 || Np < 16 || Np % 16 || M % Np || (nqk != 256 && nqk != 512) || !x || !wqk || !bqk || !wv || !bv || !q || !vt ||
-      (nqk == 512 && !k) || (!rot_cos) != (!rot_sin))
-    return fail(c, "debug_qkv: bad argument");
-  const int Mp = (M + 127) / 128 * 128, Sg = (Mp + Np - 1) / Np, S = M / Np;
-  const size_t elems = (size_t)Sg * 4 * Np * 64, n = (size_t)S * 4 * Np * 64;
-  airfe_ctx tmp;
-  tmp.prec = prec;
-  tmp.pack_prec = prec;
-  LinW lqk, lv;
-  const bool packed = make_linear(&tmp, wqk, bqk, 256, nqk, lqk) && make_linear(&tmp, wv, bv, 256, 256, lv);
-  GemmArgs ga, gb;
-  const uint16_t* dx = dupload(&tmp, dbg_rows2(x, M, 256, Mp, prec));
-  ga.X1 = gb.X1 = dx; ga.ld1 = gb.ld1 = 256; ga.K1 = gb.K1 = 256; ga.M = gb.M = Mp; ga.Np = gb.Np = Np; ga.H = gb.H = 4;
-  ga.Wp = lqk.w; ga.bias = lqk.b; ga.N = nqk; ga.cb_total = lqk.cbt; ga.epi = EPI_HEADS; ga.ldo = nqk;
-  gb.Wp = lv.w; gb.bias = lv.b; gb.N = 256; gb.cb_total = lv.cbt; gb.epi = EPI_HEADS_T; gb.ldo = 256;
-  ga.out = dbg_canary<uint16_t>(&tmp, elems);
-  if (nqk == 512) ga.out2 = dbg_canary<uint16_t>(&tmp, elems);
-  gb.out = dbg_canary<uint16_t>(&tmp, elems);
-  if (rot_cos) { ga.rot_cos = dupload(&tmp, dbg_rows4(rot_cos, M, 32, Mp)); ga.rot_sin = dupload(&tmp, dbg_rows4(rot_sin, M, 32, Mp)); }
-  for (GemmArgs* g : {&ga, &gb}) {
-    g->small_max = c->gemm_small_max; g->g8_min = c->gemm8_min; g->gr_min = c->gemmr_min; g->gr_wgs = gr_wgs > 0 ? gr_wgs : c->gemmr_wgs;
-  }
-  int rc = (packed && dx && ga.out && gb.out && (nqk != 512 || ga.out2) && (!rot_cos || (ga.rot_cos && ga.rot_sin))) ? 0 : fail(c, "debug_qkv: allocation failed");
-  if (!rc) {
-    if (pair) {
-      if (!gemmr_pair_applicable(ga, gb)) rc = fail(c, "debug_qkv: gemmr_pair does not apply to this form");
-      else launch_gemmr_pair(prec, ga, gb, c->stream);
-    } else {
-      launch_gemm(prec, 256, false, ga, c->stream);
-      launch_gemm(prec, 256, true, gb, c->stream);
-    }
-  }
-  if (!rc && (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c))) rc = fail(c, "debug_qkv: kernel failed");
-  if (!rc) {
-    std::vector<uint16_t> ho(elems);
-    (void)hipMemcpy(ho.data(), ga.out, elems * 2, hipMemcpyDeviceToHost);
-    dbg_back2(ho, n, prec, q);
-    if (nqk == 512) {
-      (void)hipMemcpy(ho.data(), ga.out2, elems * 2, hipMemcpyDeviceToHost);
-      dbg_back2(ho, n, prec, k);
-    }
-    (void)hipMemcpy(ho.data(), gb.out, elems * 2, hipMemcpyDeviceToHost);
-    dbg_back2(ho, n, prec, vt);
-  }
-  for (void* p : tmp.allocs) (void)hipFree(p);
-  return rc;
-} AIRFE_CATCH(c)
-
-int airfe_debug_lg_block(airfe_ctx* c, airfe_debug_lg_block_args* a) try {
-  AIRFE_ENTER(c);
-  if (!a || !a->attn || !a->x32 || !a->xb || !a->w1 || !a->b1 || !a->w2 || !a->b2 || (!a->relu && (!a->gamma || !a->beta)) || (!a->wo) != (!a->bo))
-    return fail(c, "debug_lg_block: null argument");
-  const int prec = a->prec, M = a->M, T = a->tokens_per_wg, nq = a->nqk_n, Np = a->Np;
-  if ((prec != 0 && prec != 1) || M < 1 || (T != 32 && T != 64 && T != 112 && T != 128) || (nq != 0 && nq != 256 && nq != 512) || (a->relu && nq))
-    return fail(c, "debug_lg_block: bad argument");
-  if (a->mixed) {                                        // the two-round split or nothing: launch_lg_blockf would quietly run uniform passes
-    const int tiles = (M + 15) / 16, W = c->n_cu;
-    if (a->wo || T != 112 || W <= 0 || tiles <= 7 * W || tiles > 13 * W) return fail(c, "debug_lg_block: the mixed split does not apply to this form");
-  }
-  if (nq && (!a->nqk_w || !a->nqk_b || !a->nv_w || !a->nv_b || !a->q || !a->vt || (nq == 512) != (a->rot_cos && a->rot_sin) || (nq == 512 && !a->k) || Np < 16 ||
-             Np % 16 || M % Np))
-    return fail(c, "debug_lg_block: the next projection needs its weights and outputs, rotary exactly when nqk_n = 512, and M = S * Np (Np a multiple of 16)");
-  const int cap = M + 256;                               // every pass form stays below M + 127 rows
-  const int Sg = nq ? (cap + Np - 1) / Np : 0, S = nq ? M / Np : 0;
-  const size_t helems = (size_t)Sg * 4 * Np * 64;
-  airfe_ctx tmp;
-  tmp.prec = prec;
-  tmp.pack_prec = prec;
-  LinW lo, l1, l2, lq, lv;
-  bool ok = (!a->wo || make_linear(&tmp, a->wo, a->bo, 256, 256, lo)) && make_linear(&tmp, a->w1, a->b1, 512, 512, l1) && make_linear(&tmp, a->w2, a->b2, 512, 256, l2) &&
-            (!nq || (make_linear(&tmp, a->nqk_w, a->nqk_b, 256, nq, lq) && make_linear(&tmp, a->nv_w, a->nv_b, 256, 256, lv)));
-  const bool fr = lg_blockf_frag_weights();
-  std::vector<float> x32h = dbg_rows4(a->x32, M, 256, cap);
-  std::vector<uint16_t> xbh((size_t)cap * 256);
-  for (size_t i = 0; i < xbh.size(); ++i) xbh[i] = cvt2(x32h[i], prec);
-  std::vector<float> gb(1024, 0.f);
-  if (!a->relu) { memcpy(gb.data(), a->gamma, 512 * 4); memcpy(gb.data() + 512, a->beta, 512 * 4); }
-  LgBlockFArgs g;
-  g.attn = dupload(&tmp, dbg_rows2(a->attn, M, 256, cap, prec));
-  g.xb = dupload(&tmp, xbh);
-  g.x32 = dupload(&tmp, x32h);
-  const float* dgb = dupload(&tmp, gb);
-  g.wo = a->wo ? (fr ? lo.wf : lo.w) : nullptr; g.bo = a->wo ? lo.b : nullptr;
-  g.w1 = fr ? l1.wf : l1.w; g.b1 = l1.b; g.w2 = fr ? l2.wf : l2.w; g.b2 = l2.b;
-  g.gamma = dgb; g.beta = dgb ? dgb + 512 : nullptr;
-  g.M = M; g.tokens_per_wg = T; g.mixed = a->mixed; g.n_cu = c->n_cu; g.relu = a->relu;
-  if (nq) {
-    g.nqk_w = fr ? lq.wf : lq.w; g.nqk_b = lq.b; g.nqk_n = nq; g.nv_w = fr ? lv.wf : lv.w; g.nv_b = lv.b; g.Np = Np; g.H = 4;
-    if (nq == 512) { g.rot_cos = dupload(&tmp, dbg_rows4(a->rot_cos, M, 32, cap)); g.rot_sin = dupload(&tmp, dbg_rows4(a->rot_sin, M, 32, cap)); }
-    g.q_out = dbg_canary<uint16_t>(&tmp, helems);
-    if (nq == 512) g.k_out = dbg_canary<uint16_t>(&tmp, helems);
-    g.vt_out = dbg_canary<uint16_t>(&tmp, helems);
-  }
-  ok = ok && g.attn && g.xb && g.x32 && dgb && (!nq || (g.q_out && g.vt_out && (nq != 512 || (g.k_out && g.rot_cos && g.rot_sin))));
-  int rc = ok ? 0 : fail(c, "debug_lg_block: allocation failed");
-  if (!rc) {
-    launch_lg_blockf(prec, g, c->stream);
-    if (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c)) rc = fail(c, "debug_lg_block: kernel failed");
-  }
-  if (!rc) {
-    // rows past M that the launch changed: x32 / xb against their initial (zero) rows, q / k / v^T against the 0xFFFF fill
-    std::vector<float> x32o((size_t)cap * 256);
-    std::vector<uint16_t> xbo((size_t)cap * 256);
-    (void)hipMemcpy(x32o.data(), g.x32, x32o.size() * 4, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(xbo.data(), g.xb, xbo.size() * 2, hipMemcpyDeviceToHost);
-    memcpy(a->x32, x32o.data(), (size_t)M * 256 * 4);
-    dbg_back2(xbo, (size_t)M * 256, prec, a->xb);
-    for (int i = 0; i < 5; ++i) a->rows_past[i] = 0;
-    for (int r = M; r < cap; ++r)
-      for (int f = 0; f < 256; ++f) {
-        const size_t e = (size_t)r * 256 + f;
-        if (memcmp(&x32o[e], &x32h[e], 4)) a->rows_past[0] = r - M + 1;
-        if (xbo[e] != xbh[e]) a->rows_past[1] = r - M + 1;
-      }
-    if (nq) {
-      uint16_t* dev[3] = {g.q_out, g.k_out, g.vt_out};
-      float* host[3] = {a->q, a->k, a->vt};
-      std::vector<uint16_t> ho(helems);
-      for (int j = 0; j < 3; ++j) {
-        if (!dev[j]) continue;
-        (void)hipMemcpy(ho.data(), dev[j], helems * 2, hipMemcpyDeviceToHost);
-        dbg_back2(ho, (size_t)S * 4 * Np * 64, prec, host[j]);
-        for (size_t e = (size_t)S * 4 * Np * 64; e < helems; ++e) {
-          if (ho[e] == 0xFFFF) continue;
-          const size_t s = e / ((size_t)4 * Np * 64), w = e % ((size_t)Np * 64);
-          const int row = (int)(s * Np + (j == 2 ? w % Np : w / 64));          // q / k [s][h][n][64], v^T [s][h][d][n]
-          a->rows_past[2 + j] = std::max(a->rows_past[2 + j], row - M + 1);
-        }
-      }
-    }
-  }
-  for (void* p : tmp.allocs) (void)hipFree(p);
-  return rc;
-} AIRFE_CATCH(c)
-
-int airfe_debug_ln_gelu(airfe_ctx* c, int prec, float* h, const float* gamma, const float* beta, int M) try {
-  AIRFE_ENTER(c);
-  if ((prec != 0 && prec != 1) || M < 1 || !h || !gamma || !beta) return fail(c, "debug_ln_gelu: bad argument");
-  airfe_ctx tmp;
-  std::vector<float> gb(1024);
-  memcpy(gb.data(), gamma, 512 * 4);
-  memcpy(gb.data() + 512, beta, 512 * 4);
-  uint16_t* dh = dupload(&tmp, dbg_rows2(h, M, 512, M, prec));
-  float* dgb = dupload(&tmp, gb);
-  int rc = dh && dgb ? 0 : fail(c, "debug_ln_gelu: allocation failed");
-  if (!rc) {
-    launch_ln_gelu(prec, dh, dgb, dgb + 512, M, c->stream);
-    if (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c)) rc = fail(c, "debug_ln_gelu: kernel failed");
-  }
-  if (!rc) {
-    std::vector<uint16_t> ho((size_t)M * 512);
-    (void)hipMemcpy(ho.data(), dh, ho.size() * 2, hipMemcpyDeviceToHost);
-    dbg_back2(ho, ho.size(), prec, h);
-  }
-  for (void* p : tmp.allocs) (void)hipFree(p);
-  return rc;
-} AIRFE_CATCH(c)
-}  // extern "C"
-
-struct DbgTmp {                                  // device allocations of one hook call, freed on every way out
-  airfe_ctx h;
-  ~DbgTmp() { for (void* p : h.allocs) (void)hipFree(p); }
-};
-
-// the body of both attention hooks (the callers hold the context and catch)
-static int dbg_attention_run(airfe_ctx* c, airfe_debug_attn_args* a, const char* who) {
-  const std::string w = std::string(who) + ": ";
-  const int S = a->S, H = a->H, n = a->n, cross = a->cross, prec = a->prec;
-  if (prec != 0 && prec != 1) return fail(c, w + "prec must be 0 (bf16) or 1 (fp16)");
-  if (S < 1 || H < 1 || n < 1 || (S * H) % 8 != 0 || (cross && (S & 1))) return fail(c, w + "S * H must be a multiple of 8 (cross: S even)");
-  if (!a->q || !a->k || !a->v || !a->lens || !a->out) return fail(c, w + "null argument");
-  for (int s = 0; s < S; ++s)
-    if (a->lens[s] < 0 || a->lens[s] > n) return fail(c, w + "lens[s] must lie in 0 .. n");
-  const int Np = (n + 15) / 16 * 16;
-  a->Np = Np; a->rows_past = 0;
-  const size_t rows = (size_t)S * H * Np + 128;                      // (+ slack: the last key tile reads up to 63 rows past a sequence; it stays ZERO like the arena's)
-  std::vector<uint16_t> hq(rows * 64, 0), hk(rows * 64, 0), hvt(rows * 64, 0);
-  for (int s = 0; s < S; ++s)
-    for (int h = 0; h < H; ++h)
-      for (int i = 0; i < n; ++i)
-        for (int d = 0; d < 64; ++d) {
-          const size_t src = (((size_t)s * H + h) * n + i) * 64 + d;
-          hq[(((size_t)s * H + h) * Np + i) * 64 + d] = cvt2(a->q[src], prec);
-          hk[(((size_t)s * H + h) * Np + i) * 64 + d] = cvt2(a->k[src], prec);
-          hvt[(((size_t)s * H + h) * 64 + d) * Np + i] = cvt2(a->v[src], prec);       // V^T [S][H][64][Np]
-        }
-  DbgTmp t;
-  airfe_ctx* tmp = &t.h;   // only as an allocation list holder
-  uint16_t *dq = dupload(tmp, hq), *dk = dupload(tmp, hk), *dv = dupload(tmp, hvt);
-  const size_t out_n = (size_t)S * Np * H * 64, slack_n = (size_t)128 * H * 64;
-  uint16_t* dout = dalloc<uint16_t>(tmp, out_n + slack_n);
-  std::vector<int> hl(a->lens, a->lens + S);
-  int* dl = dupload(tmp, hl);
-  if (!dq || !dk || !dv || !dout || !dl) return fail(c, w + "allocation failed");
-  if (a->canary && hipMemsetAsync(dout, 0xFF, (out_n + slack_n) * 2, c->stream) != hipSuccess) return fail(c, w + "memset failed");
-  launch_attention32(prec, dq, dk, dv, dout, dl, S, H, Np, cross, c->stream);
-  if (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c)) return fail(c, w + "kernel failed");
-  std::vector<uint16_t> ho(out_n + slack_n);
-  if (hipMemcpy(ho.data(), dout, ho.size() * 2, hipMemcpyDeviceToHost) != hipSuccess) return fail(c, w + "copy failed");
-  const int rows_out = a->raw ? Np : n;
-  for (int s = 0; s < S; ++s)
-    for (int i = 0; i < rows_out; ++i)
-      for (int f = 0; f < H * 64; ++f) a->out[((size_t)s * rows_out + i) * H * 64 + f] = back2(ho[((size_t)s * Np + i) * H * 64 + f], prec);
-  if (a->canary)
-    for (int r = 0; r < 128; ++r) {
-      bool changed = false;
-      for (int f = 0; f < H * 64 && !changed; ++f) changed = ho[out_n + (size_t)r * H * 64 + f] != 0xFFFFu;
-      a->rows_past += changed;
-    }
-  return 0;
-}
-
-extern "C" {
-int airfe_debug_attention(airfe_ctx* c, const float* q, const float* k, const float* v, const int* lens, int S, int H, int n, int cross, float* out) try {
-  AIRFE_ENTER(c);
-  if (c->mprec == 2) return fail(c, "debug_attention drives the 2-byte kernel (matcher_precision fp16 / bf16)");
-  airfe_debug_attn_args a = {};
-  a.prec = c->mprec; a.S = S; a.H = H; a.n = n; a.cross = cross;
-  a.q = q; a.k = k; a.v = v; a.lens = lens; a.out = out;                 // canary = 0, raw = 0: the output buffer as the allocator left it, the first n rows back
-  return dbg_attention_run(c, &a, "debug_attention");
-} AIRFE_CATCH(c)
-
-int airfe_debug_attention_args(airfe_ctx* c, airfe_debug_attn_args* a) try {
-  AIRFE_ENTER(c);
-  if (!a) return fail(c, "debug_attention_args: null argument");
-  return dbg_attention_run(c, a, "debug_attention_args");
-} AIRFE_CATCH(c)
-
-/* ---- LightGlue's head and tail one launcher at a time (include/airfe_debug.h; tests/test_gpu_lg_tail.py) */
-int airfe_debug_lg_prepare(airfe_ctx* c, airfe_debug_lg_prepare_args* a) try {
-  AIRFE_ENTER(c);
-  if (!c->has_arena) return fail(c, "debug_lg_prepare: no matcher loaded");
-  if (!a || !a->f0 || !a->f1 || !a->n0 || !a->n1 || !a->wr || !a->x32 || !a->xb || !a->rot_cos || !a->rot_sin || !a->lens || (!a->f0x) != (!a->f1x))
-    return fail(c, "debug_lg_prepare: null argument");
-  const int Np = c->Np, B = a->B, Bt = a->f0x ? 2 : B;
-  if ((a->prec != 0 && a->prec != 1) || B < 1 || B > c->Pmax || (a->f0x && (B != 1 || c->Pmax < 2)) || a->cap < 1 || a->cap > Np || a->kp_off < 0 ||
-      a->ld < a->kp_off + 258 || a->slack_rows < 0)
-    return fail(c, "debug_lg_prepare: bad argument (prec 0 / 1, 1 <= B <= max_batch, a second pair with B = 1 only, 1 <= cap <= Np, ld >= kp_off + 258)");
-  for (int b = 0; b < B; ++b)
-    if (a->n0[b] < 0 || a->n0[b] > a->cap || a->n1[b] < 0 || a->n1[b] > a->cap) return fail(c, "debug_lg_prepare: every n0, n1 must lie in 0 .. cap");
-  if (a->f0x && (a->n0x < 0 || a->n0x > Np || a->n1x < 0 || a->n1x > Np)) return fail(c, "debug_lg_prepare: the second pair's lengths must lie in 0 .. Np");
-  const size_t rows = (size_t)2 * Bt * Np + (size_t)a->slack_rows, R = c->arena_rows;
-  if (rows > R || (size_t)a->rows != rows) return fail(c, "debug_lg_prepare: rows must be 2 Bt Np + slack_rows and fit the arena");
-  DbgTmp t;
-  const size_t fl = (size_t)B * a->cap * a->ld;
-  std::vector<float> hf0(a->f0, a->f0 + fl), hf1(a->f1, a->f1 + fl), hwr(a->wr, a->wr + 64);
-  std::vector<int> hn(2 * B + 2);
-  for (int b = 0; b < B; ++b) { hn[b] = a->n0[b]; hn[B + b] = a->n1[b]; }
-  hn[2 * B] = a->n0x; hn[2 * B + 1] = a->n1x;
-  float *df0 = dupload(&t.h, hf0), *df1 = dupload(&t.h, hf1), *dwr = dupload(&t.h, hwr), *df0x = nullptr, *df1x = nullptr;
-  int* dn = dupload(&t.h, hn);
-  if (a->f0x) {
-    std::vector<float> x0(a->f0x, a->f0x + (size_t)a->n0x * a->ld), x1(a->f1x, a->f1x + (size_t)a->n1x * a->ld);
-    x0.resize(x0.size() + a->ld, 0.f); x1.resize(x1.size() + a->ld, 0.f);          // (never empty)
-    df0x = dupload(&t.h, x0); df1x = dupload(&t.h, x1);
-    if (!df0x || !df1x) return fail(c, "debug_lg_prepare: allocation failed");
-  }
-  if (!df0 || !df1 || !dwr || !dn) return fail(c, "debug_lg_prepare: allocation failed");
-  hipStream_t st = c->stream;
-  HIPCHK(c, hipMemsetAsync(c->x32, 0xFF, R * 256 * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->xb, 0xFF, R * 256 * 2, st));
-  HIPCHK(c, hipMemsetAsync(c->rot_cos, 0xFF, R * 32 * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->rot_sin, 0xFF, R * 32 * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->lens, 0xFF, (size_t)2 * c->Pmax * 4, st));
-  LgPrepArgs pa;
-  pa.f0 = df0; pa.f1 = df1; pa.n0 = dn; pa.n1 = dn + B; pa.ld = a->ld; pa.kp_off = a->kp_off; pa.normalize = a->normalize;
-  pa.cx = a->cx; pa.cy = a->cy; pa.linv = a->linv; pa.wr = dwr; pa.B = B; pa.cap = a->cap; pa.Np = Np;
-  pa.x32 = c->x32; pa.xb = c->xb; pa.rot_cos = c->rot_cos; pa.rot_sin = c->rot_sin; pa.lens = c->lens;
-  if (a->f0x) { pa.f0x = df0x; pa.f1x = df1x; pa.n0x = dn + 2 * B; pa.n1x = dn + 2 * B + 1; }
-  pa.slack_rows = a->slack_rows;
-  launch_lg_prepare(a->prec, pa, st);
-  HIPCHK(c, hipStreamSynchronize(st));
-  if (launch_status(c)) return 1;
-  std::vector<float> hx(R * 256);
-  std::vector<uint16_t> hb(R * 256);
-  HIPCHK(c, hipMemcpy(hx.data(), c->x32, hx.size() * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(hb.data(), c->xb, hb.size() * 2, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->rot_cos, c->rot_cos, rows * 32 * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->rot_sin, c->rot_sin, rows * 32 * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->lens, c->lens, (size_t)2 * Bt * 4, hipMemcpyDeviceToHost));
-  memcpy(a->x32, hx.data(), rows * 256 * 4);
-  dbg_back2(hb, rows * 256, a->prec, a->xb);
-  int past = 0;
-  for (size_t r = rows; r < R; ++r) {
-    bool touched = false;
-    for (int k = 0; k < 256 && !touched; ++k) {
-      uint32_t u;
-      memcpy(&u, &hx[r * 256 + k], 4);
-      touched = u != 0xFFFFFFFFu || hb[r * 256 + k] != 0xFFFFu;
-    }
-    past += touched;
-  }
-  a->rows_past = past;
-  // the arena as alloc_matcher_arena left it: the pipelines reset only the slack rows their own kernels can reach
-  HIPCHK(c, hipMemsetAsync(c->x32, 0, R * 256 * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->xb, 0, R * 256 * 2, st));
-  HIPCHK(c, hipMemsetAsync(c->rot_cos, 0, R * 32 * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->rot_sin, 0, R * 32 * 4, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  return 0;
-} AIRFE_CATCH(c)
-
-int airfe_debug_lg_assign(airfe_ctx* c, airfe_debug_lg_assign_args* a) try {
-  AIRFE_ENTER(c);
-  if (!c->has_arena) return fail(c, "debug_lg_assign: no matcher loaded");
-  if (!a || !a->md || !a->x32 || !a->w || !a->lens || !a->z || !a->sim || !a->scores || !a->rowlse || !a->collse || !a->rowval || !a->rowarg || !a->colarg ||
-      !a->idx || !a->score || !a->nmatch)
-    return fail(c, "debug_lg_assign: null argument");
-  const int Np = c->Np, B = a->B, n = a->n, S = 2 * B, cap = a->cap, prec = a->prec;
-  if ((prec != 0 && prec != 1) || B < 1 || B > c->Pmax || n < 1 || n > Np || cap < 1 || cap > Np || (a->form != 0 && a->form != 1))
-    return fail(c, "debug_lg_assign: bad argument (prec 0 / 1, 1 <= B <= max_batch, 1 <= n, cap <= Np, form 0 / 1)");
-  for (int s = 0; s < S; ++s)
-    if (a->lens[s] < 0 || a->lens[s] > n) return fail(c, "debug_lg_assign: every length must lie in 0 .. n");
-  const size_t M = (size_t)S * Np, blk = (size_t)Np * Np, pf = lg_assign_part_floats(B, Np);
-  std::vector<uint16_t> hmd(M * 256, 0xFFFFu);
-  std::vector<float> hx(M * 256);
-  memset(hx.data(), 0xFF, hx.size() * 4);
-  for (int s = 0; s < S; ++s) {
-    for (int i = 0; i < a->lens[s]; ++i)
-      for (int k = 0; k < 256; ++k) {
-        hmd[((size_t)s * Np + i) * 256 + k] = cvt2(a->md[((size_t)s * n + i) * 256 + k], prec);
-        hx[((size_t)s * Np + i) * 256 + k] = a->x32[((size_t)s * n + i) * 256 + k];
-      }
-    if (a->pad)
-      for (int i = a->lens[s]; i < Np; ++i)
-        for (int k = 0; k < 256; ++k) hmd[((size_t)s * Np + i) * 256 + k] = cvt2(a->pad[k], prec);
-  }
-  DbgTmp t;
-  std::vector<float> hw(a->w, a->w + 256);
-  float* dw = dupload(&t.h, hw);
-  float* dscores = dalloc<float>(&t.h, (size_t)B * blk, false);
-  int32_t* didx = dalloc<int32_t>(&t.h, (size_t)B * cap * 2, false);
-  float* dscore = dalloc<float>(&t.h, (size_t)B * cap, false);
-  int* dnm = dalloc<int>(&t.h, (size_t)B, false);
-  if (!dw || !dscores || !didx || !dscore || !dnm) return fail(c, "debug_lg_assign: allocation failed");
-  hipStream_t st = c->stream;
-  HIPCHK(c, hipMemcpyAsync(c->mdb, hmd.data(), hmd.size() * 2, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->x32, hx.data(), hx.size() * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->lens, a->lens, (size_t)S * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemsetAsync(c->zbuf, 0xFF, M * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->simbuf, 0xFF, (size_t)B * blk * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->lg_part, 0xFF, pf * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->lg_argpart, 0xFF, pf * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->rowlse, 0xFF, (size_t)B * Np * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->collse, 0xFF, (size_t)B * Np * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->rowval, 0xFF, (size_t)B * Np * 4, st));
-  HIPCHK(c, hipMemsetAsync(dscores, 0xFF, (size_t)B * blk * 4, st));
-  HIPCHK(c, hipMemsetAsync(dscore, 0xFF, (size_t)B * cap * 4, st));
-  HIPCHK(c, hipMemsetAsync(dnm, 0xFF, (size_t)B * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->rowarg, 0, (size_t)B * Np * 4, st));          // zero, not -1: the value that passes for a valid index
-  HIPCHK(c, hipMemsetAsync(c->colarg, 0, (size_t)B * Np * 4, st));
-  HIPCHK(c, hipMemsetAsync(didx, 0, (size_t)B * cap * 8, st));
-  launch_rowdot256(c->x32, dw, a->b, c->zbuf, (int)M, st);
-  if (a->form == 1) {
-    launch_lg_assign_fused(prec, c->mdb, c->zbuf, c->lens, B, Np, cap, a->thr, c->lg_part, c->lg_argpart, c->rowlse, c->collse, c->simbuf, dscores, c->rowarg,
-                           c->rowval, c->colarg, didx, dscore, dnm, st);
-  } else {
-    launch_sim(prec, c->mdb, c->simbuf, B, Np, st);
-    launch_lg_assign(c->simbuf, c->zbuf, c->lens, B, Np, cap, a->thr, c->rowlse, c->collse, dscores, c->rowarg, c->rowval, c->colarg, didx, dscore, dnm, st);
-  }
-  HIPCHK(c, hipStreamSynchronize(st));
-  if (launch_status(c)) return 1;
-  const size_t nb = (size_t)n * 4, npb = (size_t)Np * 4;
-  HIPCHK(c, hipMemcpy2D(a->z, nb, c->zbuf, npb, nb, S, hipMemcpyDeviceToHost));
-  for (int b = 0; b < B; ++b) {
-    HIPCHK(c, hipMemcpy2D(a->sim + (size_t)b * n * n, nb, c->simbuf + b * blk, npb, nb, n, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy2D(a->scores + (size_t)b * n * n, nb, dscores + b * blk, npb, nb, n, hipMemcpyDeviceToHost));
-  }
-  HIPCHK(c, hipMemcpy2D(a->rowlse, nb, c->rowlse, npb, nb, B, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy2D(a->collse, nb, c->collse, npb, nb, B, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy2D(a->rowval, nb, c->rowval, npb, nb, B, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy2D(a->rowarg, nb, c->rowarg, npb, nb, B, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy2D(a->colarg, nb, c->colarg, npb, nb, B, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->idx, didx, (size_t)B * cap * 8, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->score, dscore, (size_t)B * cap * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->nmatch, dnm, (size_t)B * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemsetAsync(c->mdb, 0, M * 256 * 2, st));          // no NaN token rows stay behind
-  HIPCHK(c, hipMemsetAsync(c->x32, 0, M * 256 * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->zbuf, 0, M * 4, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  return 0;
-} AIRFE_CATCH(c)
-
-/* ---- BoW keyframe database (include/airfe.h "BoW keyframe database"; kernels_bowdb.hip) ------------------------------------------------------------- */
-}  // extern "C" (the database object is a C++ struct behind an opaque pointer)
-
-struct airfe_bowdb {
-  airfe_ctx* c = nullptr;
-  int max_frames = 0, cap = 0, keep = 0, size = 0;
-  uint32_t* ids = nullptr; double* vals = nullptr; int* nw = nullptr;        // [max_frames][cap], [max_frames][cap], [max_frames]
-  float* feat = nullptr; int* n = nullptr;                                   // keep_features: [max_frames][cap][259], [max_frames]
-  uint8_t* q_scratch = nullptr; size_t q_bytes = 0; hipStream_t q_stream = nullptr;      // query: dense sharing + score [Q][N]
-  uint8_t* m_scratch = nullptr; size_t m_bytes = 0; hipStream_t m_stream = nullptr;      // composite: the pair batch
-  // map state (airfe_bowdb_attach_map): per-frame map points, the covisibility graph in CSR form, keyframe positions
-  int has_map = 0, max_edges = 0, has_pos = 0;
-  double* xyz = nullptr;                                                     // [max_frames][cap][3], NaN = no valid map point at this feature row
-  int32_t *cov_row = nullptr, *cov_nbr = nullptr, *cov_weight = nullptr;     // [max_frames + 1], [max_edges], [max_edges]
-  double* pos = nullptr;                                                     // [max_frames][3]
-  uint8_t* r_scratch = nullptr; size_t r_bytes = 0; hipStream_t r_stream = nullptr;      // relocalisation composite: everything between its kernels
-  // loop detection (airfe_bowdb_set_poses / set_u_right): the keyframes' Twc and the right-image columns of their feature rows
-  int has_pose = 0;
-  double* pose = nullptr;                                                    // [max_frames][16], identity until set
-  double* u_right = nullptr;                                                 // [max_frames][cap], -1 until set (> 0: stereo)
-  uint8_t* l_scratch = nullptr; size_t l_bytes = 0; hipStream_t l_stream = nullptr;      // stored queries / loop detection composite
-};
-
-namespace {
-// a database's scratch grows only behind a synchronisation of the stream it was last used on (as fransac_queue's)
-int bowdb_scratch(airfe_bowdb* db, uint8_t*& blk, size_t& have, hipStream_t& last, size_t bytes, hipStream_t st) {
-  airfe_ctx* c = db->c;
-  if (bytes > have) {
-    if (last) HIPCHK(c, hipStreamSynchronize(last));
-    void* p = nullptr;
-    HIPCHK(c, hipMalloc(&p, bytes));
-    if (blk) (void)hipFree(blk);
-    blk = reinterpret_cast<uint8_t*>(p);
-    have = bytes;
-  }
-  last = st;
-  return 0;
-}
-
-int bow_vector_queue(airfe_ctx* c, const float* d_feat, const int* d_n, int B, int cap, uint32_t* d_ids, double* d_vals, int* d_nw, uint32_t* d_word,
-                     hipStream_t st) {
-  const size_t rows = (size_t)B * cap;
-  if (ensure_block(c, c->bv_scratch, c->bv_scratch_bytes, rows * 12 + 256, c->bv_scratch_stream)) return 1;
-  c->bv_scratch_stream = st;
-  unsigned* word = d_word ? d_word : reinterpret_cast<unsigned*>(c->bv_scratch);
-  float* wf = reinterpret_cast<float*>(c->bv_scratch + rows * 4);
-  int* node = reinterpret_cast<int*>(c->bv_scratch + rows * 8);
-  ProfScope ps(c, ST_BOW, st, 0, (double)rows * 259 * 4);
-  // the existing descent over every row of the batch (rows past a frame's count are descended too and ignored: the vector kernel reads n rows)
-  launch_bow_transform(d_feat, AIRFE_FEAT_DIM, 3, (int)rows, c->bow_desc, c->bow_first, c->bow_nch, c->bow_word, c->bow_weight, word, wf, node, st);
-  BowVecArgs a;
-  a.word = word; a.node = node; a.n = d_n; a.cap = cap; a.weight = c->bow_weight_d; a.ids = d_ids; a.vals = d_vals; a.nw = d_nw;
-  launch_bow_vector(a, B, st);
-  note_launch(c, ST_BOW);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-}  // namespace
-
-extern "C" {
-
-int airfe_bow_vector_batch_dev(airfe_ctx* c, const float* d_feat, const int* d_n, int B, int cap, uint32_t* d_ids, double* d_vals, int* d_nw,
-                               uint32_t* d_word, void* stream) try {
-  AIRFE_ENTER(c);
-  if (!c->bow_nodes) return fail(c, "bow_vector_batch_dev: no vocabulary loaded (airfe_bow_load)");
-  if (B < 1 || cap < 1 || !d_feat || !d_n || !d_ids || !d_vals || !d_nw) return fail(c, "bow_vector_batch_dev: bad argument");
-  if (cap > BOW_MAX_FEATURES) return fail(c, "bow_vector_batch_dev: cap > 1024");
-  if ((size_t)B * cap > (size_t)INT32_MAX) return fail(c, "bow_vector_batch_dev: batch too large");
-  return bow_vector_queue(c, d_feat, d_n, B, cap, d_ids, d_vals, d_nw, d_word, stream ? (hipStream_t)stream : c->stream);
-} AIRFE_CATCH(c)
-
-int airfe_bow_vector(airfe_ctx* c, const float* feat, int n, uint32_t* ids, double* vals, int* nw, uint32_t* word_of_features) try {
-  AIRFE_ENTER(c);
-  if (!c->bow_nodes) return fail(c, "bow_vector: no vocabulary loaded (airfe_bow_load)");
-  if (n < 0 || !nw || (n > 0 && (!feat || !ids || !vals))) return fail(c, "bow_vector: bad argument");
-  if (n > BOW_MAX_FEATURES) return fail(c, "bow_vector: more than 1024 features");
-  *nw = 0;
-  if (n == 0) return 0;                                          // database.cc:60
-  const size_t fb = ((size_t)n * AIRFE_FEAT_DIM * 4 + 63) / 64 * 64, ib = ((size_t)n * 4 + 63) / 64 * 64;
-  if (ensure_block(c, c->bv_stage, c->bv_stage_bytes, 128 + fb + 2 * ib + (size_t)n * 8)) return 1;
-  int* d_n = reinterpret_cast<int*>(c->bv_stage);
-  int* d_nw = d_n + 16;
-  double* d_vals = reinterpret_cast<double*>(c->bv_stage + 128);
-  float* d_feat = reinterpret_cast<float*>(c->bv_stage + 128 + (size_t)n * 8);
-  uint32_t* d_ids = reinterpret_cast<uint32_t*>(c->bv_stage + 128 + (size_t)n * 8 + fb);
-  uint32_t* d_word = d_ids + ib / 4;
-  hipStream_t st = c->stream;
-  DrainOnError drain{c, true};
-  HIPCHK(c, hipMemcpyAsync(d_n, &n, 4, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(d_feat, feat, (size_t)n * AIRFE_FEAT_DIM * 4, hipMemcpyHostToDevice, st));
-  if (bow_vector_queue(c, d_feat, d_n, 1, n, d_ids, d_vals, d_nw, d_word, st)) return 1;
-  int k = 0;
-  HIPCHK(c, hipMemcpyAsync(&k, d_nw, 4, hipMemcpyDeviceToHost, st));
-  if (word_of_features) HIPCHK(c, hipMemcpyAsync(word_of_features, d_word, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  if (k > 0) {
-    HIPCHK(c, hipMemcpyAsync(ids, d_ids, (size_t)k * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(vals, d_vals, (size_t)k * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-  }
-  drain.armed = false;
-  *nw = k;
-  return 0;
-} AIRFE_CATCH(c)
-
-int airfe_bowdb_create(airfe_ctx* c, int max_frames, int cap, int keep_features, airfe_bowdb** out) try {
-  AIRFE_ENTER(c);
-  if (!out) return fail(c, "bowdb_create: null argument");
-  *out = nullptr;
-  if (max_frames < 1 || cap < 1) return fail(c, "bowdb_create: bad argument");
-  if (cap > BOW_MAX_FEATURES) return fail(c, "bowdb_create: cap > 1024");
-  if (!c->bow_nodes) return fail(c, "bowdb_create: no vocabulary loaded (airfe_bow_load): the database is sized by its word count");
-  struct Guard { airfe_bowdb* p; ~Guard() { if (p) (void)airfe_bowdb_destroy(p); } } guard{new airfe_bowdb()};
-  airfe_bowdb* db = guard.p;
-  db->c = c; db->max_frames = max_frames; db->cap = cap; db->keep = keep_features != 0;
-  const size_t rows = (size_t)max_frames * cap;
-  HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->ids), rows * 4));
-  HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->vals), rows * 8));
-  HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->nw), (size_t)max_frames * 4));
-  if (db->keep) {
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->feat), rows * AIRFE_FEAT_DIM * 4));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->n), (size_t)max_frames * 4));
-  }
-  guard.p = nullptr;
-  *out = db;
-  return 0;
-} AIRFE_CATCH(c)
-
-int airfe_bowdb_destroy(airfe_bowdb* db) try {
-  if (!db) return 0;
-  if (db->c) { (void)enter_device(db->c); (void)hipDeviceSynchronize(); }
-  for (void* p : {(void*)db->ids, (void*)db->vals, (void*)db->nw, (void*)db->feat, (void*)db->n, (void*)db->q_scratch, (void*)db->m_scratch, (void*)db->xyz,
-                  (void*)db->cov_row, (void*)db->cov_nbr, (void*)db->cov_weight, (void*)db->pos, (void*)db->r_scratch, (void*)db->pose, (void*)db->u_right,
-                  (void*)db->l_scratch})
-    if (p) (void)hipFree(p);
-  delete db;
-  return 0;
-} AIRFE_CATCH(nullptr)
-
-int airfe_bowdb_clear(airfe_bowdb* db) try {
-  if (!db) return 1;
-  db->size = 0;
-  return 0;
-} AIRFE_CATCH(db->c)
-
-int airfe_bowdb_size(const airfe_bowdb* db) try {
-  return db ? db->size : -1;
-} AIRFE_CATCH(nullptr)
-
-// Database::AddFrame: frame `size + b` = vector b.  kind = hipMemcpyDeviceToDevice (asynchronous on st) or hipMemcpyHostToDevice (synchronous)
-static int bowdb_add_impl(airfe_bowdb* db, const uint32_t* ids, const double* vals, const int* nw, const float* feat, const int* n, int B, int cap,
-                          hipMemcpyKind kind, hipStream_t st, const char* who) {
-  airfe_ctx* c = db->c;
-  if (B < 1 || !ids || !vals || !nw || cap != db->cap) return fail(c, std::string(who) + ": bad argument (cap must be the database's)");
-  if (db->keep && (!feat || !n)) return fail(c, std::string(who) + ": this database keeps the frames' features: d_feat / d_n are needed");
-  if (B > db->max_frames - db->size) return fail(c, std::string(who) + ": the database is full (max_frames)");
-  const size_t at = (size_t)db->size * cap, rows = (size_t)B * cap;
-  HIPCHK(c, hipMemcpyAsync(db->ids + at, ids, rows * 4, kind, st));
-  HIPCHK(c, hipMemcpyAsync(db->vals + at, vals, rows * 8, kind, st));
-  HIPCHK(c, hipMemcpyAsync(db->nw + db->size, nw, (size_t)B * 4, kind, st));
-  if (db->keep) {
-    HIPCHK(c, hipMemcpyAsync(db->feat + at * AIRFE_FEAT_DIM, feat, rows * AIRFE_FEAT_DIM * 4, kind, st));
-    HIPCHK(c, hipMemcpyAsync(db->n + db->size, n, (size_t)B * 4, kind, st));
-  }
-  if (kind == hipMemcpyHostToDevice) HIPCHK(c, hipStreamSynchronize(st));
-  db->size += B;
-  return 0;
-}
-
-int airfe_bowdb_add_batch_dev(airfe_bowdb* db, const uint32_t* d_ids, const double* d_vals, const int* d_nw, const float* d_feat, const int* d_n, int B,
-                              int cap, void* stream) try {
-  if (!db) return 1;
-  AIRFE_ENTER(db->c);
-  return bowdb_add_impl(db, d_ids, d_vals, d_nw, d_feat, d_n, B, cap, hipMemcpyDeviceToDevice, stream ? (hipStream_t)stream : db->c->stream, "bowdb_add_batch_dev");
-} AIRFE_CATCH(db->c)
-
-int airfe_bowdb_add(airfe_bowdb* db, const uint32_t* ids, const double* vals, const int* nw, const float* feat, const int* n, int B, int cap) try {
-  if (!db) return 1;
-  AIRFE_ENTER(db->c);
-  return bowdb_add_impl(db, ids, vals, nw, feat, n, B, cap, hipMemcpyHostToDevice, db->c->stream, "bowdb_add");
-} AIRFE_CATCH(db->c)
-
-// Database::Query + the sharing-word filter + Database::Score for Q device vectors on `st` (the body of airfe_bowdb_query_batch_dev; the relocalisation
-// composite queues the same code)
-static int bowdb_query_queue(airfe_bowdb* db, const uint32_t* d_ids, const double* d_vals, const int* d_nw, int Q, int cap, const airfe_bowdb_filter* filter,
-                             int32_t* d_cand_frame, int32_t* d_cand_sharing, double* d_cand_score, int ccap, int* d_ncand, int* d_max_sharing,
-                             int32_t* d_sharing, hipStream_t st) {
-  airfe_ctx* c = db->c;
-  const int N = db->size;
-  const size_t cells = (size_t)Q * std::max(N, 1);
-  if (bowdb_scratch(db, db->q_scratch, db->q_bytes, db->q_stream, cells * 12, st)) return 1;
-  BowQueryArgs a;
-  a.db_ids = db->ids; a.db_vals = db->vals; a.db_nw = db->nw; a.N = N; a.cap = db->cap;
-  a.q_ids = d_ids; a.q_vals = d_vals; a.q_nw = d_nw; a.qcap = cap; a.n_words = c->bow_nwords;
-  a.frames_per_wg = (size_t)Q * N >= (size_t)64 * 1024 ? 64 : 16;     // (how the frames are sliced changes no result)
-  a.score = reinterpret_cast<double*>(db->q_scratch);
-  a.sharing = d_sharing ? d_sharing : reinterpret_cast<int*>(db->q_scratch + cells * 8);
-  ProfScope ps(c, ST_BOW, st, 0, (double)Q * N * db->cap * 12);
-  if (launch_bowdb_query(a, Q, st)) return fail(c, "bowdb_query_batch_dev: the query table does not fit the workgroup's LDS");
-  BowSelectArgs s;
-  s.sharing = a.sharing; s.score = a.score; s.N = N; s.ratio = filter->ratio; s.min_words = filter->min_words;
-  s.max_index = filter->d_max_index; s.exclude = filter->d_exclude; s.exclude_words = filter->exclude_words;
-  s.cand_frame = d_cand_frame; s.cand_sharing = d_cand_sharing; s.cand_score = d_cand_score; s.ccap = ccap; s.ncand = d_ncand; s.max_sharing = d_max_sharing;
-  launch_bowdb_select(s, Q, st);
-  note_launch(c, ST_BOW);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-
-int airfe_bowdb_query_batch_dev(airfe_bowdb* db, const uint32_t* d_ids, const double* d_vals, const int* d_nw, int Q, int cap,
-                                const airfe_bowdb_filter* filter, int32_t* d_cand_frame, int32_t* d_cand_sharing, double* d_cand_score, int ccap,
-                                int* d_ncand, int* d_max_sharing, int32_t* d_sharing, void* stream) try {
-  if (!db) return 1;
-  airfe_ctx* c = db->c;
-  AIRFE_ENTER(c);
-  if (Q < 1 || cap < 1 || ccap < 1 || !d_ids || !d_vals || !d_nw || !filter || !d_cand_frame || !d_cand_sharing || !d_cand_score || !d_ncand || !d_max_sharing)
-    return fail(c, "bowdb_query_batch_dev: bad argument");
-  if (cap > BOW_MAX_FEATURES) return fail(c, "bowdb_query_batch_dev: cap > 1024");
-  if (filter->d_exclude && filter->exclude_words < 1) return fail(c, "bowdb_query_batch_dev: d_exclude needs exclude_words");
-  return bowdb_query_queue(db, d_ids, d_vals, d_nw, Q, cap, filter, d_cand_frame, d_cand_sharing, d_cand_score, ccap, d_ncand, d_max_sharing, d_sharing,
-                           stream ? (hipStream_t)stream : c->stream);
-} AIRFE_CATCH(db->c)
-
-int airfe_bowdb_topk_dev(airfe_bowdb* db, const int32_t* d_cand_frame, const double* d_cand_score, const int* d_ncand, int Q, int ccap, int K,
-                         int32_t* d_top, double* d_top_score, void* stream) try {
-  if (!db) return 1;
-  airfe_ctx* c = db->c;
-  AIRFE_ENTER(c);
-  if (Q < 1 || ccap < 1 || K < 1 || K > 8 || !d_cand_frame || !d_cand_score || !d_ncand || !d_top) return fail(c, "bowdb_topk_dev: bad argument (K = 1..8)");
-  BowTopkArgs a;
-  a.cand_frame = d_cand_frame; a.cand_score = d_cand_score; a.ncand = d_ncand; a.ccap = ccap; a.K = K; a.top = d_top; a.top_score = d_top_score;
-  launch_bowdb_topk(a, Q, stream ? (hipStream_t)stream : c->stream);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-} AIRFE_CATCH(db->c)
-
-// the best-candidate rule around the matcher for Q queries x K candidates on `st` (the body of airfe_bowdb_match_candidates_batch_dev; the relocalisation
-// composite queues the same code)
-static int bowdb_match_queue(airfe_ctx* c, airfe_bowdb* db, const float* d_qfeat, const int* d_qn, int Q, int cap, const int32_t* d_cand, int K,
-                             int outlier_rejection, int32_t* d_best, int32_t* d_idx, float* d_score, int mcap, int* d_nmatch, int* d_nmatch_all,
-                             hipStream_t st) {
-  const int P = Q * K;
-  const size_t fb = (size_t)P * cap * AIRFE_FEAT_DIM * 4, cb = ((size_t)P * 4 + 255) / 256 * 256, ib = (size_t)P * mcap * 8, sb = (size_t)P * mcap * 4;
-  if (bowdb_scratch(db, db->m_scratch, db->m_bytes, db->m_stream, 2 * fb + 3 * cb + ib + sb, st)) return 1;
-  uint8_t* q = db->m_scratch;
-  BowGatherArgs g;
-  g.f0 = reinterpret_cast<float*>(q); q += fb;
-  g.f1 = reinterpret_cast<float*>(q); q += fb;
-  int32_t* p_idx = reinterpret_cast<int32_t*>(q); q += ib;
-  float* p_score = reinterpret_cast<float*>(q); q += sb;
-  g.n0 = reinterpret_cast<int*>(q); q += cb;
-  g.n1 = reinterpret_cast<int*>(q); q += cb;
-  int* p_nm = reinterpret_cast<int*>(q);
-  g.qfeat = d_qfeat; g.qn = d_qn; g.db_feat = db->feat; g.db_n = db->n; g.N = db->size; g.cap = cap; g.cand = d_cand; g.K = K;
-  launch_bowdb_gather(g, P, st);
-  HIPCHK(c, hipGetLastError());
-  // MatchingPoints(query_features, good_candidate_features, matches, true) (map_user.cc:369): the context's own entries, called
-  if (lightglue_dev(c, g.f0, g.n0, g.f1, g.n1, P, cap, AIRFE_FEAT_DIM, 1, 1, p_idx, p_score, mcap, p_nm, nullptr, st)) return 1;
-  if (outlier_rejection && fransac_queue(c, g.f0, g.f1, P, cap, p_idx, p_score, mcap, p_nm, nullptr, st)) return 1;
-  BowBestArgs b;
-  b.cand = d_cand; b.K = K; b.N = db->size; b.mcap = mcap; b.idx_all = p_idx; b.score_all = p_score; b.nmatch_all = p_nm;
-  b.best = d_best; b.idx = d_idx; b.score = d_score; b.nmatch = d_nmatch; b.out_nmatch_all = d_nmatch_all;
-  launch_bowdb_best(b, Q, st);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-
-int airfe_bowdb_match_candidates_batch_dev(airfe_ctx* c, airfe_bowdb* db, const float* d_qfeat, const int* d_qn, int Q, int cap, const int32_t* d_cand, int K,
-                                           int outlier_rejection, int32_t* d_best, int32_t* d_idx, float* d_score, int mcap, int* d_nmatch,
-                                           int* d_nmatch_all, void* stream) try {
-  AIRFE_ENTER(c);
-  if (!db || db->c != c) return fail(c, "bowdb_match_candidates_batch_dev: the database belongs to another context");
-  if (Q < 1 || K < 1 || K > 5 || mcap < 1 || !d_qfeat || !d_qn || !d_cand || !d_best || !d_idx || !d_score || !d_nmatch)
-    return fail(c, "bowdb_match_candidates_batch_dev: bad argument (K = 1..5)");
-  if (!db->keep) return fail(c, "bowdb_match_candidates_batch_dev: the database was created without keep_features");
-  if (cap != db->cap) return fail(c, "bowdb_match_candidates_batch_dev: cap must be the database's");
-  if (mcap > FR_MAX_MATCHES) return fail(c, "bowdb_match_candidates_batch_dev: mcap > 1024");
-  if ((long long)Q * K > c->Pmax) return fail(c, "bowdb_match_candidates_batch_dev: Q * K pairs exceed cfg.max_batch");
-  return bowdb_match_queue(c, db, d_qfeat, d_qn, Q, cap, d_cand, K, outlier_rejection, d_best, d_idx, d_score, mcap, d_nmatch, d_nmatch_all,
-                           stream ? (hipStream_t)stream : c->stream);
-} AIRFE_CATCH(c)
-
-/* ---- map state in the database, the grouping and the relocalisation composite (include/airfe.h "Grouping", "Relocalisation composite";
- * kernels_bowgroup.hip, bowgroup_core.h) ------------------------------------------------------------------------------------------------------------ */
-int airfe_bowdb_attach_map(airfe_bowdb* db, int max_edges) try {
-  if (!db) return 1;
-  airfe_ctx* c = db->c;
-  AIRFE_ENTER(c);
-  if (db->has_map) return fail(c, "bowdb_attach_map: the map state is attached already");
-  if (!db->keep) return fail(c, "bowdb_attach_map: the database was created without keep_features");
-  if (max_edges < 1) return fail(c, "bowdb_attach_map: bad argument");
-  const size_t rows = (size_t)db->max_frames * db->cap;
-  HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->xyz), rows * 24));
-  HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->cov_row), ((size_t)db->max_frames + 1) * 4));
-  HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->cov_nbr), (size_t)max_edges * 4));
-  HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->cov_weight), (size_t)max_edges * 4));
-  HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->pos), (size_t)db->max_frames * 24));
-  HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->pose), (size_t)db->max_frames * 128));
-  HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&db->u_right), rows * 8));
-  HIPCHK(c, hipMemsetAsync(db->xyz, 0xFF, rows * 24, c->stream));                         // every byte 0xFF: a NaN in every slot
-  HIPCHK(c, hipMemsetAsync(db->cov_row, 0, ((size_t)db->max_frames + 1) * 4, c->stream));  // an empty graph
-  HIPCHK(c, hipMemsetAsync(db->cov_nbr, 0, (size_t)max_edges * 4, c->stream));
-  HIPCHK(c, hipMemsetAsync(db->cov_weight, 0, (size_t)max_edges * 4, c->stream));
-  HIPCHK(c, hipMemsetAsync(db->pos, 0xFF, (size_t)db->max_frames * 24, c->stream));
-  launch_loopdet_init(db->pose, db->u_right, db->max_frames, db->cap, c->stream);          // identity poses, no right image anywhere
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  db->max_edges = max_edges;
-  db->has_map = 1;
-  return 0;
-} AIRFE_CATCH(db->c)
-
-// rows first_frame .. first_frame + B - 1 of a [max_frames][per] f64 table
-static int bowdb_rows_copy(airfe_bowdb* db, double* table, size_t per, int first_frame, int B, const void* src, void* dst, hipMemcpyKind kind, hipStream_t st,
-                           const char* who) {
-  airfe_ctx* c = db->c;
-  if (!db->has_map) return fail(c, std::string(who) + ": no map state (airfe_bowdb_attach_map)");
-  if (first_frame < 0 || B < 1 || B > db->max_frames - first_frame || (!src && !dst)) return fail(c, std::string(who) + ": bad argument (frames beyond max_frames)");
-  double* at = table + (size_t)first_frame * per;
-  if (src) HIPCHK(c, hipMemcpyAsync(at, src, (size_t)B * per * 8, kind, st));
-  else HIPCHK(c, hipMemcpyAsync(dst, at, (size_t)B * per * 8, kind, st));
-  if (kind != hipMemcpyDeviceToDevice) HIPCHK(c, hipStreamSynchronize(st));
-  return 0;
-}
-
-int airfe_bowdb_set_points_dev(airfe_bowdb* db, int first_frame, int B, const double* d_xyz, void* stream) try {
-  if (!db) return 1;
-  AIRFE_ENTER(db->c);
-  return bowdb_rows_copy(db, db->xyz, (size_t)db->cap * 3, first_frame, B, d_xyz, nullptr, hipMemcpyDeviceToDevice,
-                         stream ? (hipStream_t)stream : db->c->stream, "bowdb_set_points_dev");
-} AIRFE_CATCH(db->c)
-
-int airfe_bowdb_set_points(airfe_bowdb* db, int first_frame, int B, const double* xyz) try {
-  if (!db) return 1;
-  AIRFE_ENTER(db->c);
-  return bowdb_rows_copy(db, db->xyz, (size_t)db->cap * 3, first_frame, B, xyz, nullptr, hipMemcpyHostToDevice, db->c->stream, "bowdb_set_points");
-} AIRFE_CATCH(db->c)
-
-int airfe_bowdb_get_points(airfe_bowdb* db, int first_frame, int B, double* xyz) try {
-  if (!db) return 1;
-  AIRFE_ENTER(db->c);
-  return bowdb_rows_copy(db, db->xyz, (size_t)db->cap * 3, first_frame, B, nullptr, xyz, hipMemcpyDeviceToHost, db->c->stream, "bowdb_get_points");
-} AIRFE_CATCH(db->c)
-
-int airfe_bowdb_set_positions(airfe_bowdb* db, int first_frame, int B, const double* pos) try {
-  if (!db) return 1;
-  AIRFE_ENTER(db->c);
-  if (bowdb_rows_copy(db, db->pos, 3, first_frame, B, pos, nullptr, hipMemcpyHostToDevice, db->c->stream, "bowdb_set_positions")) return 1;
-  db->has_pos = 1;
-  return 0;
-} AIRFE_CATCH(db->c)
-
-int airfe_bowdb_set_covisibility(airfe_bowdb* db, const int32_t* row_ptr, const int32_t* nbr, const int32_t* weight, int n_frames) try {
-  if (!db) return 1;
-  airfe_ctx* c = db->c;
-  AIRFE_ENTER(c);
-  if (!db->has_map) return fail(c, "bowdb_set_covisibility: no map state (airfe_bowdb_attach_map)");
-  if (n_frames < 0 || n_frames > db->max_frames || !row_ptr) return fail(c, "bowdb_set_covisibility: bad argument (n_frames beyond max_frames)");
-  if (row_ptr[0] != 0) return fail(c, "bowdb_set_covisibility: row_ptr[0] must be 0");
-  for (int f = 0; f < n_frames; ++f)
-    if (row_ptr[f + 1] < row_ptr[f]) return fail(c, "bowdb_set_covisibility: row_ptr must not decrease");
-  const int E = row_ptr[n_frames];
-  if (E > db->max_edges) return fail(c, "bowdb_set_covisibility: more entries than max_edges");
-  if (E > 0 && (!nbr || !weight)) return fail(c, "bowdb_set_covisibility: bad argument");
-  for (int f = 0; f < n_frames; ++f)
-    for (int e = row_ptr[f]; e < row_ptr[f + 1]; ++e)
-      if (nbr[e] < 0 || (e > row_ptr[f] && nbr[e] <= nbr[e - 1]))
-        return fail(c, "bowdb_set_covisibility: every row must be strictly ascending in nbr (nothing was changed)");
-  std::vector<int32_t> rows((size_t)db->max_frames + 1, E);                                // frames past n_frames: empty rows
-  std::copy(row_ptr, row_ptr + n_frames + 1, rows.begin());
-  hipStream_t st = c->stream;
-  HIPCHK(c, hipMemcpyAsync(db->cov_row, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, st));
-  if (E > 0) {
-    HIPCHK(c, hipMemcpyAsync(db->cov_nbr, nbr, (size_t)E * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(db->cov_weight, weight, (size_t)E * 4, hipMemcpyHostToDevice, st));
-  }
-  HIPCHK(c, hipStreamSynchronize(st));
-  return 0;
-} AIRFE_CATCH(db->c)
-
-int airfe_bowdb_get_covisibility(airfe_bowdb* db, int32_t* row_ptr, int32_t* nbr, int32_t* weight, int edge_cap, int* n_edges) try {
-  if (!db) return 1;
-  airfe_ctx* c = db->c;
-  AIRFE_ENTER(c);
-  if (!db->has_map) return fail(c, "bowdb_get_covisibility: no map state (airfe_bowdb_attach_map)");
-  if (!row_ptr || !n_edges || edge_cap < 0) return fail(c, "bowdb_get_covisibility: bad argument");
-  hipStream_t st = c->stream;
-  HIPCHK(c, hipMemcpyAsync(row_ptr, db->cov_row, ((size_t)db->max_frames + 1) * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  const int E = row_ptr[db->max_frames];
-  *n_edges = E;
-  if (E > edge_cap) return fail(c, "bowdb_get_covisibility: more entries than edge_cap");
-  if (E > 0) {
-    if (!nbr || !weight) return fail(c, "bowdb_get_covisibility: bad argument");
-    HIPCHK(c, hipMemcpyAsync(nbr, db->cov_nbr, (size_t)E * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(weight, db->cov_weight, (size_t)E * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-  }
-  return 0;
-} AIRFE_CATCH(db->c)
-
-// the grouping for Q candidate lists on `st`
-static int bowdb_group_queue(airfe_bowdb* db, int mode, const int32_t* d_cand_frame, const double* d_cand_score, const int* d_ncand, int Q, int ccap, int K,
-                             const double* d_extra, const double* d_qpos, const double* d_max_dist, int32_t* d_group_frame, double* d_group_score,
-                             int* d_ngroups, int* d_status, hipStream_t st) {
-  airfe_ctx* c = db->c;
-  BowGroupArgs a;
-  a.mode = mode; a.cand_frame = d_cand_frame; a.cand_score = d_cand_score; a.ncand = d_ncand; a.ccap = ccap; a.K = K;
-  a.row_ptr = db->cov_row; a.nbr = db->cov_nbr; a.weight = db->cov_weight; a.rows = db->max_frames;
-  a.extra = d_extra; a.n_extra = db->size; a.pos = db->pos; a.pos_rows = db->max_frames; a.qpos = d_qpos; a.max_dist = d_max_dist;
-  a.group_frame = d_group_frame; a.group_score = d_group_score; a.ngroups = d_ngroups; a.status = d_status;
-  if (launch_bowgroup(a, Q, st)) return fail(c, "bowdb_group_dev: the candidate list does not fit the workgroup's LDS");
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-
-int airfe_bowdb_group_dev(airfe_bowdb* db, int mode, const int32_t* d_cand_frame, const double* d_cand_score, const int* d_ncand, int Q, int ccap, int K,
-                          const double* d_extra, const double* d_qpos, const double* d_max_dist, int32_t* d_group_frame, double* d_group_score,
-                          int* d_ngroups, int* d_status, void* stream) try {
-  if (!db) return 1;
-  airfe_ctx* c = db->c;
-  AIRFE_ENTER(c);
-  if (!db->has_map) return fail(c, "bowdb_group_dev: no map state (airfe_bowdb_attach_map)");
-  if (Q < 1 || ccap < 1 || K < 1 || !d_cand_frame || !d_cand_score || !d_ncand || !d_group_frame || !d_group_score || !d_ngroups || !d_status)
-    return fail(c, "bowdb_group_dev: bad argument");
-  if (mode != BG_MODE_RELOC && mode != BG_MODE_LOOP) return fail(c, "bowdb_group_dev: mode is 0 (relocalisation) or 1 (loop detection)");
-  if (K > (mode == BG_MODE_RELOC ? 3 : 5)) return fail(c, "bowdb_group_dev: K <= 3 (relocalisation) / K <= 5 (loop detection)");
-  if (ccap > BG_MAX_CAND) return fail(c, "bowdb_group_dev: ccap > 4096");
-  if (mode == BG_MODE_LOOP && (!d_qpos || !d_max_dist || !db->has_pos))
-    return fail(c, "bowdb_group_dev: the loop form needs d_qpos, d_max_dist and the keyframe positions (airfe_bowdb_set_positions)");
-  return bowdb_group_queue(db, mode, d_cand_frame, d_cand_score, d_ncand, Q, ccap, K, d_extra, d_qpos, d_max_dist, d_group_frame, d_group_score, d_ngroups,
-                           d_status, stream ? (hipStream_t)stream : c->stream);
-} AIRFE_CATCH(db->c)
-
-int airfe_relocalize_batch_dev(airfe_ctx* c, airfe_bowdb* db, const airfe_reloc_cfg* cfg, const float* d_qfeat, const int* d_qn, int Q, int cap,
-                               const double* d_extra, int* d_ok, int* d_stage, double* d_Twc, int32_t* d_best, int* d_num, uint8_t* d_mask, int32_t* d_idx,
-                               float* d_score, int mcap, int* d_nmatch, int* d_pnp_count, void* stream) try {
-  AIRFE_ENTER(c);
-  if (!db || db->c != c) return fail(c, "relocalize_batch_dev: the database belongs to another context");
-  if (!db->has_map) return fail(c, "relocalize_batch_dev: no map state (airfe_bowdb_attach_map)");
-  if (!cfg || Q < 1 || mcap < 1 || !d_qfeat || !d_qn || !d_ok || !d_stage || !d_Twc || !d_best || !d_num || !d_mask || !d_idx || !d_score || !d_nmatch)
-    return fail(c, "relocalize_batch_dev: bad argument");
-  if (cfg->K < 1 || cfg->K > 3) return fail(c, "relocalize_batch_dev: cfg.K = 1..3");
-  if (cap != db->cap) return fail(c, "relocalize_batch_dev: cap must be the database's");
-  if (mcap > PNP_MAX_POINTS) return fail(c, "relocalize_batch_dev: mcap > 1024");
-  if ((long long)Q * cfg->K > c->Pmax) return fail(c, "relocalize_batch_dev: Q * K pairs exceed cfg.max_batch");
-  if (!c->bow_nodes) return fail(c, "relocalize_batch_dev: no vocabulary loaded (airfe_bow_load)");
-  const int N = db->size, ccap = std::max(N, 1), K = cfg->K;
-  if (ccap > BG_MAX_CAND) return fail(c, "relocalize_batch_dev: more than 4096 frames in the database");
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-  // one block, every part 256-byte aligned
-  size_t off = 0;
-  auto take = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) / 256 * 256; return at; };
-  const size_t qc = (size_t)Q * cap, qm = (size_t)Q * mcap, qcc = (size_t)Q * ccap, qb = (size_t)Q * 4;
-  const size_t o_ids = take(qc * 4), o_vals = take(qc * 8), o_nw = take(qb), o_cf = take(qcc * 4), o_cs = take(qcc * 4), o_sc = take(qcc * 8), o_nc = take(qb),
-               o_ms = take(qb), o_gf = take((size_t)Q * K * 4), o_gs = take((size_t)Q * K * 8), o_ng = take(qb), o_gst = take(qb), o_obj = take(qm * 12),
-               o_img = take(qm * 8), o_map = take(qm * 4), o_X = take(qm * 24), o_obs = take(qm * 24), o_n = take(qb), o_nopt = take(qb), o_pre = take(qb),
-               o_pnp = take((size_t)Q * 128), o_pmask = take(qm), o_pcnt = take(qb);
-  if (bowdb_scratch(db, db->r_scratch, db->r_bytes, db->r_stream, off, st)) return 1;
-  uint8_t* r = db->r_scratch;
-  auto I = [r](size_t o) { return reinterpret_cast<int*>(r + o); };
-  auto D = [r](size_t o) { return reinterpret_cast<double*>(r + o); };
-  // map_user.cc:129-166: the vector, the query with the sharing-word filter, the scores
-  if (bow_vector_queue(c, d_qfeat, d_qn, Q, cap, reinterpret_cast<uint32_t*>(r + o_ids), D(o_vals), I(o_nw), nullptr, st)) return 1;
-  airfe_bowdb_filter flt;
-  flt.ratio = cfg->ratio; flt.min_words = cfg->min_words; flt.d_max_index = nullptr; flt.d_exclude = nullptr; flt.exclude_words = 0;
-  if (bowdb_query_queue(db, reinterpret_cast<uint32_t*>(r + o_ids), D(o_vals), I(o_nw), Q, cap, &flt, I(o_cf), I(o_cs), D(o_sc), ccap, I(o_nc), I(o_ms),
-                        nullptr, st)) return 1;
-  // :177-363: the grouping; :360-376: the matcher over the K deputies
-  if (bowdb_group_queue(db, BG_MODE_RELOC, I(o_cf), D(o_sc), I(o_nc), Q, ccap, K, d_extra, nullptr, nullptr, I(o_gf), D(o_gs), I(o_ng), I(o_gst), st)) return 1;
-  if (bowdb_match_queue(c, db, d_qfeat, d_qn, Q, cap, I(o_gf), K, cfg->outlier_rejection, d_best, d_idx, d_score, mcap, d_nmatch, nullptr, st)) return 1;
-  // :377-390: the first gate, the winner's map points, SolvePnPWithCV
-  const int refine = cfg->pose_refinement != 0;
-  RelocGatherArgs g;
-  g.xyz = db->xyz; g.N = N; g.cap = cap; g.qfeat = d_qfeat; g.best = d_best; g.idx = d_idx; g.nmatch = d_nmatch; g.mcap = mcap;
-  g.ncand = I(o_nc); g.gstatus = I(o_gst); g.ngroups = I(o_ng); g.min_inlier = cfg->min_inlier; g.refine = refine;
-  g.obj = reinterpret_cast<float*>(r + o_obj); g.img = reinterpret_cast<float*>(r + o_img); g.map = I(o_map); g.X = D(o_X); g.obs = D(o_obs);
-  g.n = I(o_n); g.n_opt = I(o_nopt); g.pre = I(o_pre);
-  launch_reloc_gather(g, Q, st);
-  HIPCHK(c, hipGetLastError());
-  RelocFinishArgs f;
-  f.pre = g.pre; f.num = d_num; f.min_inlier = cfg->min_inlier; f.stage = d_stage; f.ok = d_ok;
-  if (!refine) {
-    if (pnp_queue(c, g.obj, g.img, g.n, Q, mcap, cfg->cam, d_Twc, nullptr, d_mask, mcap, g.map, d_num, st)) return 1;
-    f.pnp_count = d_num; f.pnp_count_out = d_pnp_count;
-  } else {
-    // :392-457: the frame optimisation from the PnP pose, Tcb = identity, every constraint mono; fewer constraints than min_inlier: none are handed over
-    // and the kernel returns its start pose, PnP's
-    int* d_cnt = d_pnp_count ? d_pnp_count : I(o_pcnt);
-    if (pnp_queue(c, g.obj, g.img, g.n, Q, mcap, cfg->cam, D(o_pnp), nullptr, r + o_pmask, mcap, g.map, d_cnt, st)) return 1;
-    if (poseopt_queue(c, g.X, g.obs, g.n_opt, Q, mcap, D(o_pnp), cfg->cam, nullptr, cfg->thr, d_Twc, nullptr, d_mask, mcap, g.map, d_num, -1, nullptr, st))
-      return 1;
-  }
-  launch_reloc_finish(f, Q, st);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-} AIRFE_CATCH(c)
-
-/* ---- loop detection over a loaded map (include/airfe.h "Map state for loop detection", "Stored queries against their predecessors", "Loop detection
- * composite"; kernels_loopdet.hip, loopdet_core.h) -------------------------------------------------------------------------------------------------- */
-int airfe_bowdb_set_poses(airfe_bowdb* db, int first_frame, int B, const double* Twc) try {
-  if (!db) return 1;
-  airfe_ctx* c = db->c;
-  AIRFE_ENTER(c);
-  if (!db->has_map) return fail(c, "bowdb_set_poses: no map state (airfe_bowdb_attach_map)");
-  if (first_frame < 0 || B < 1 || B > db->max_frames - first_frame || !Twc) return fail(c, "bowdb_set_poses: bad argument (frames beyond max_frames)");
-  std::vector<double> t((size_t)B * 3);
-  for (int b = 0; b < B; ++b)
-    for (int k = 0; k < 3; ++k) t[(size_t)b * 3 + k] = Twc[(size_t)b * 16 + 4 * k + 3];
-  if (bowdb_rows_copy(db, db->pose, 16, first_frame, B, Twc, nullptr, hipMemcpyHostToDevice, c->stream, "bowdb_set_poses")) return 1;
-  if (bowdb_rows_copy(db, db->pos, 3, first_frame, B, t.data(), nullptr, hipMemcpyHostToDevice, c->stream, "bowdb_set_poses")) return 1;
-  db->has_pos = 1;
-  db->has_pose = 1;
-  return 0;
-} AIRFE_CATCH(db->c)
-
-int airfe_bowdb_get_poses(airfe_bowdb* db, int first_frame, int B, double* Twc) try {
-  if (!db) return 1;
-  AIRFE_ENTER(db->c);
-  return bowdb_rows_copy(db, db->pose, 16, first_frame, B, nullptr, Twc, hipMemcpyDeviceToHost, db->c->stream, "bowdb_get_poses");
-} AIRFE_CATCH(db->c)
-
-int airfe_bowdb_set_u_right_dev(airfe_bowdb* db, int first_frame, int B, const double* d_u_right, void* stream) try {
-  if (!db) return 1;
-  AIRFE_ENTER(db->c);
-  return bowdb_rows_copy(db, db->u_right, (size_t)db->cap, first_frame, B, d_u_right, nullptr, hipMemcpyDeviceToDevice,
-                         stream ? (hipStream_t)stream : db->c->stream, "bowdb_set_u_right_dev");
-} AIRFE_CATCH(db->c)
-
-int airfe_bowdb_set_u_right(airfe_bowdb* db, int first_frame, int B, const double* u_right) try {
-  if (!db) return 1;
-  AIRFE_ENTER(db->c);
-  return bowdb_rows_copy(db, db->u_right, (size_t)db->cap, first_frame, B, u_right, nullptr, hipMemcpyHostToDevice, db->c->stream, "bowdb_set_u_right");
-} AIRFE_CATCH(db->c)
-
-int airfe_bowdb_get_u_right(airfe_bowdb* db, int first_frame, int B, double* u_right) try {
-  if (!db) return 1;
-  AIRFE_ENTER(db->c);
-  return bowdb_rows_copy(db, db->u_right, (size_t)db->cap, first_frame, B, nullptr, u_right, hipMemcpyDeviceToHost, db->c->stream, "bowdb_get_u_right");
-} AIRFE_CATCH(db->c)
-
-// stored frames d_qframe [Q] against their predecessors on `st`: the stored vectors gathered into d_ids / d_vals / d_nw ([Q][cap] x 2, [Q]: the caller's
-// scratch), bowdb_query_kernel unchanged over the whole database, the prefix selection (the body of airfe_bowdb_query_stored_batch_dev; the loop
-// detection composite queues the same code)
-static int loopdet_query_queue(airfe_bowdb* db, const int32_t* d_qframe, int Q, float ratio, int min_words, int exclude_covisible, uint32_t* d_ids,
-                               double* d_vals, int* d_nw, int32_t* d_cand_frame, int32_t* d_cand_sharing, double* d_cand_score, int ccap, int* d_ncand,
-                               int* d_max_sharing, int32_t* d_sharing, hipStream_t st) {
-  airfe_ctx* c = db->c;
-  const int N = db->size;
-  const size_t cells = (size_t)Q * std::max(N, 1);
-  if (bowdb_scratch(db, db->q_scratch, db->q_bytes, db->q_stream, cells * 12, st)) return 1;
-  LoopQvecArgs v;
-  v.qframe = d_qframe; v.db_ids = db->ids; v.db_vals = db->vals; v.db_nw = db->nw; v.N = N; v.cap = db->cap; v.ids = d_ids; v.vals = d_vals; v.nw = d_nw;
-  launch_loopdet_qvec(v, Q, st);
-  BowQueryArgs a;
-  a.db_ids = db->ids; a.db_vals = db->vals; a.db_nw = db->nw; a.N = N; a.cap = db->cap;
-  a.q_ids = d_ids; a.q_vals = d_vals; a.q_nw = d_nw; a.qcap = db->cap; a.n_words = c->bow_nwords;
-  a.frames_per_wg = (size_t)Q * N >= (size_t)64 * 1024 ? 64 : 16;     // (how the frames are sliced changes no result)
-  a.score = reinterpret_cast<double*>(db->q_scratch);
-  a.sharing = d_sharing ? d_sharing : reinterpret_cast<int*>(db->q_scratch + cells * 8);
-  ProfScope ps(c, ST_BOW, st, 0, (double)Q * N * db->cap * 12);
-  if (launch_bowdb_query(a, Q, st)) return fail(c, "bowdb_query_stored_batch_dev: the query table does not fit the workgroup's LDS");
-  LoopSelectArgs s;
-  s.qframe = d_qframe; s.sharing = a.sharing; s.score = a.score; s.N = N; s.zero_tail = d_sharing ? 1 : 0; s.ratio = ratio; s.min_words = min_words;
-  if (exclude_covisible) { s.row_ptr = db->cov_row; s.nbr = db->cov_nbr; s.rows = db->max_frames; }
-  s.cand_frame = d_cand_frame; s.cand_sharing = d_cand_sharing; s.cand_score = d_cand_score; s.ccap = ccap; s.ncand = d_ncand; s.max_sharing = d_max_sharing;
-  launch_loopdet_select(s, Q, st);
-  note_launch(c, ST_BOW);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-
-int airfe_bowdb_query_stored_batch_dev(airfe_bowdb* db, const int32_t* d_qframe, int Q, float ratio, int min_words, int exclude_covisible,
-                                       int32_t* d_cand_frame, int32_t* d_cand_sharing, double* d_cand_score, int ccap, int* d_ncand, int* d_max_sharing,
-                                       int32_t* d_sharing, void* stream) try {
-  if (!db) return 1;
-  airfe_ctx* c = db->c;
-  AIRFE_ENTER(c);
-  if (Q < 1 || ccap < 1 || !d_qframe || !d_cand_frame || !d_cand_sharing || !d_cand_score || !d_ncand || !d_max_sharing)
-    return fail(c, "bowdb_query_stored_batch_dev: bad argument");
-  if (Q > LD_MAX_QUERIES) return fail(c, "bowdb_query_stored_batch_dev: Q > 4096");
-  if (exclude_covisible && !db->has_map) return fail(c, "bowdb_query_stored_batch_dev: exclude_covisible needs the map state (airfe_bowdb_attach_map)");
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-  const size_t qc = ((size_t)Q * db->cap * 4 + 255) / 256 * 256;
-  if (bowdb_scratch(db, db->l_scratch, db->l_bytes, db->l_stream, 3 * qc + (size_t)Q * 4, st)) return 1;
-  uint8_t* l = db->l_scratch;
-  return loopdet_query_queue(db, d_qframe, Q, ratio, min_words, exclude_covisible, reinterpret_cast<uint32_t*>(l + 2 * qc), reinterpret_cast<double*>(l),
-                             reinterpret_cast<int*>(l + 3 * qc), d_cand_frame, d_cand_sharing, d_cand_score, ccap, d_ncand, d_max_sharing, d_sharing, st);
-} AIRFE_CATCH(db->c)
-
-int airfe_loop_detect_batch_dev(airfe_ctx* c, airfe_bowdb* db, const airfe_loop_cfg* cfg, const int32_t* d_qframe, int Q, int* d_ok, int* d_stage,
-                                int32_t* d_loop, double* d_Twq, double* d_Rlq, double* d_tlq, int* d_num, uint8_t* d_mask, int32_t* d_idx, float* d_score,
-                                int mcap, int* d_nmatch, int* d_ncons, void* stream) try {
-  AIRFE_ENTER(c);
-  if (!db || db->c != c) return fail(c, "loop_detect_batch_dev: the database belongs to another context");
-  if (!db->has_map) return fail(c, "loop_detect_batch_dev: no map state (airfe_bowdb_attach_map)");
-  if (!db->has_pose) return fail(c, "loop_detect_batch_dev: the keyframe poses were never set (airfe_bowdb_set_poses)");
-  if (!cfg || Q < 1 || mcap < 1 || !d_qframe || !d_ok || !d_stage || !d_loop || !d_Twq || !d_Rlq || !d_tlq || !d_num || !d_mask || !d_idx || !d_score ||
-      !d_nmatch)
-    return fail(c, "loop_detect_batch_dev: bad argument");
-  if (cfg->K < 1 || cfg->K > 5) return fail(c, "loop_detect_batch_dev: cfg.K = 1..5");
-  if (Q > LD_MAX_QUERIES) return fail(c, "loop_detect_batch_dev: Q > 4096");
-  if (mcap > PO_MAX_POINTS) return fail(c, "loop_detect_batch_dev: mcap > 1024");
-  if ((long long)Q * cfg->K > c->Pmax) return fail(c, "loop_detect_batch_dev: Q * K pairs exceed cfg.max_batch");
-  const int N = db->size, ccap = std::max(N, 1), K = cfg->K, cap = db->cap;
-  if (N > LD_MAX_FRAMES) return fail(c, "loop_detect_batch_dev: more than 4096 frames in the database");
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-  // one block, every part 256-byte aligned
-  size_t off = 0;
-  auto take = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) / 256 * 256; return at; };
-  const size_t qc = (size_t)Q * cap, qm = (size_t)Q * mcap, qcc = (size_t)Q * ccap, qb = (size_t)Q * 4;
-  const size_t o_ids = take(qc * 4), o_vals = take(qc * 8), o_nw = take(qb), o_cf = take(qcc * 4), o_cs = take(qcc * 4), o_sc = take(qcc * 8), o_nc = take(qb),
-               o_ms = take(qb), o_odom = take((size_t)ccap * 8), o_feat = take(qc * AIRFE_FEAT_DIM * 4), o_qn = take(qb), o_qpos = take((size_t)Q * 24),
-               o_md = take((size_t)Q * 8), o_T0 = take((size_t)Q * 128), o_gf = take((size_t)Q * K * 4), o_gs = take((size_t)Q * K * 8), o_ng = take(qb),
-               o_gst = take(qb), o_map = take(qm * 4), o_X = take(qm * 24), o_obs = take(qm * 24), o_n = take(qb), o_nopt = take(qb), o_pre = take(qb);
-  if (bowdb_scratch(db, db->l_scratch, db->l_bytes, db->l_stream, off, st)) return 1;
-  uint8_t* r = db->l_scratch;
-  auto I = [r](size_t o) { return reinterpret_cast<int*>(r + o); };
-  auto D = [r](size_t o) { return reinterpret_cast<double*>(r + o); };
-  // map_refiner.cc:97-130 on the database of :88-89: frame fq against its predecessors, the covisible frames dropped
-  if (loopdet_query_queue(db, d_qframe, Q, cfg->ratio, cfg->min_words, 1, reinterpret_cast<uint32_t*>(r + o_ids), D(o_vals), I(o_nw), I(o_cf), I(o_cs),
-                          D(o_sc), ccap, I(o_nc), I(o_ms), nullptr, st)) return 1;
-  // :66-81: the odometry length, once per call; what the later steps read of frame fq
-  launch_loopdet_odom(db->pos, N, D(o_odom), st);
-  LoopStateArgs s;
-  s.qframe = d_qframe; s.N = N; s.cap = cap; s.db_feat = db->feat; s.db_n = db->n; s.pos = db->pos; s.pose = db->pose; s.odom = D(o_odom);
-  s.distance_rate = cfg->distance_rate; s.qfeat = reinterpret_cast<float*>(r + o_feat); s.qn = I(o_qn); s.qpos = D(o_qpos); s.max_dist = D(o_md);
-  s.Twc0 = D(o_T0);
-  launch_loopdet_state(s, Q, st);
-  HIPCHK(c, hipGetLastError());
-  // :132-214: the grouping in loop form; :213-230: the matcher over the K deputies
-  if (bowdb_group_queue(db, BG_MODE_LOOP, I(o_cf), D(o_sc), I(o_nc), Q, ccap, K, nullptr, D(o_qpos), D(o_md), I(o_gf), D(o_gs), I(o_ng), I(o_gst), st)) return 1;
-  if (bowdb_match_queue(c, db, s.qfeat, s.qn, Q, cap, I(o_gf), K, cfg->outlier_rejection, d_loop, d_idx, d_score, mcap, d_nmatch, nullptr, st)) return 1;
-  // :232, :241-301: the gates and the constraints
-  LoopGatherArgs g;
-  g.qframe = d_qframe; g.xyz = db->xyz; g.u_right = db->u_right; g.feat = db->feat; g.N = N; g.cap = cap; g.best = d_loop; g.idx = d_idx; g.nmatch = d_nmatch;
-  g.mcap = mcap; g.ncand = I(o_nc); g.gstatus = I(o_gst); g.ngroups = I(o_ng); g.min_matches = cfg->min_matches; g.min_points = cfg->min_points;
-  g.X = D(o_X); g.obs = D(o_obs); g.map = I(o_map); g.n = I(o_n); g.n_opt = I(o_nopt); g.pre = I(o_pre);
-  launch_loopdet_gather(g, Q, st);
-  HIPCHK(c, hipGetLastError());
-  // :262, :304: the frame optimisation from the stored pose, Tcb = identity; without constraints the kernel returns its start pose
-  if (poseopt_queue(c, g.X, g.obs, g.n_opt, Q, mcap, D(o_T0), cfg->cam, nullptr, cfg->thr, d_Twq, nullptr, d_mask, mcap, g.map, d_num, -1, nullptr, st))
-    return 1;
-  // :308, :327-333
-  LoopFinishArgs f;
-  f.pre = g.pre; f.ncons = g.n; f.num = d_num; f.min_points = cfg->min_points; f.min_inliers = cfg->min_inliers; f.best = d_loop; f.N = N;
-  f.pose = db->pose; f.Twq = d_Twq; f.stage = d_stage; f.ok = d_ok; f.ncons_out = d_ncons; f.Rlq = d_Rlq; f.tlq = d_tlq;
-  launch_loopdet_finish(f, Q, st);
-  HIPCHK(c, hipGetLastError());
-  return 0;
 } AIRFE_CATCH(c)
 
 }  // extern "C"

@@ -1,0 +1,624 @@
+// airfe — the kernel-level test hooks of libairfe.so (include/airfe_debug.h): host tensors -> one production launcher -> host tensors.  Every device allocation
+// of a hook lives in a DbgTmp and is freed on every way out, an exception caught by AIRFE_CATCH included.
+#include "airfe_host.h"
+
+struct DbgTmp {                                  // device allocations of one hook call, freed on every way out
+  airfe_ctx h;                                   // only as an allocation list holder (dalloc / dupload / make_linear)
+  DbgTmp() {}
+  explicit DbgTmp(int prec) { h.prec = h.pack_prec = prec; }      // the storage type make_linear packs for
+  ~DbgTmp() { for (void* p : h.allocs) (void)hipFree(p); }
+};
+
+extern "C" {
+
+// ---- kernel-level test hooks ------------------------------------------------------------------------------
+int airfe_debug_preprocess(airfe_ctx* c, const uint8_t* gray, int h, int w, int stride, float* out) try {
+  if (c && enter_device(c)) return 1;
+  if (!c || !c->has_sp) return fail(c, "debug_preprocess: detector not loaded");
+  const size_t bytes = (size_t)h * stride;
+  if (upload_image(c, gray, h, w, stride) || ensure_tables(c, h, w)) return 1;
+  const int R = AIRFE_INTERNAL_SIZE;
+  launch_preprocess(c->st_img.p, 1, h, w, stride, bytes, c->xtab, c->ytab, c->lut, c->img32, R, R, c->stream);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy2D(out, (size_t)R * 4, c->img32 + (R + 2) + 1, (size_t)(R + 2) * 4, (size_t)R * 4, R, hipMemcpyDeviceToHost));
+  return 0;
+} AIRFE_CATCH(c)
+
+int airfe_debug_conv3x3(airfe_ctx* c, const float* x, int B, int cin, int H, int W, const float* w, const float* b, int cout,
+                        int pool, float* y) try {
+  AIRFE_ENTER(c);
+  if ((cin != 64 && cin != 128) || cout % 64 || W % 16 || H % 16) return fail(c, "debug_conv3x3: unsupported shape");
+  const int prec = c->prec;
+  std::vector<uint16_t> xin((size_t)B * (H + 2) * (W + 2) * cin, 0);
+  for (int bb = 0; bb < B; ++bb)
+    for (int ci = 0; ci < cin; ++ci)
+      for (int yy = 0; yy < H; ++yy)
+        for (int xx = 0; xx < W; ++xx)
+          xin[(((size_t)bb * (H + 2) + yy + 1) * (W + 2) + xx + 1) * cin + ci] = cvt2(x[(((size_t)bb * cin + ci) * H + yy) * W + xx], prec);
+  const int nci = cin / 64;
+  auto slabs = pack_slabs(cout / 64, 9 * nci, prec, [&](int feat, int s, int k) {
+    const int tap = s / nci, cc = s % nci, ci = cc * 64 + k;
+    return w[((size_t)feat * cin + ci) * 9 + tap];
+  });
+  const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
+  uint16_t *dx = nullptr, *dw = nullptr, *dy = nullptr;
+  float* db = nullptr;
+  const size_t ybytes = (size_t)B * (Ho + 2) * (Wo + 2) * cout * 2;
+  HIPCHK(c, hipMalloc((void**)&dx, xin.size() * 2));
+  HIPCHK(c, hipMalloc((void**)&dw, slabs.size() * 2));
+  HIPCHK(c, hipMalloc((void**)&dy, ybytes));
+  HIPCHK(c, hipMalloc((void**)&db, (size_t)cout * 4));
+  HIPCHK(c, hipMemcpy(dx, xin.data(), xin.size() * 2, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dw, slabs.data(), slabs.size() * 2, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(db, b, (size_t)cout * 4, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemset(dy, 0, ybytes));
+  ConvArgs a;
+  a.X = dx; a.Wp = dw; a.bias = db; a.Y = dy; a.B = B; a.H = H; a.W = W; a.CIN = cin; a.COUT = cout;
+  a.pool = pool; a.out_pad = 1; a.relu = 1;
+  launch_conv3x3(prec, a, c->stream);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<uint16_t> yo(ybytes / 2);
+  HIPCHK(c, hipMemcpy(yo.data(), dy, ybytes, hipMemcpyDeviceToHost));
+  for (int bb = 0; bb < B; ++bb)
+    for (int co = 0; co < cout; ++co)
+      for (int yy = 0; yy < Ho; ++yy)
+        for (int xx = 0; xx < Wo; ++xx)
+          y[(((size_t)bb * cout + co) * Ho + yy) * Wo + xx] = back2(yo[(((size_t)bb * (Ho + 2) + yy + 1) * (Wo + 2) + xx + 1) * cout + co], prec);
+  (void)hipFree(dx); (void)hipFree(dw); (void)hipFree(dy); (void)hipFree(db);
+  return 0;
+} AIRFE_CATCH(c)
+
+int airfe_debug_fail_next_launch(airfe_ctx* c, int stage) try {
+  AIRFE_ENTER(c);
+  if (stage < -1 || stage >= ST_COUNT) return fail(c, "debug_fail_next_launch: no such stage");
+  c->fail_stage = stage;
+  return 0;
+} AIRFE_CATCH(c)
+
+int airfe_debug_gemm(airfe_ctx* c, const float* x, int M, int K, const float* w, const float* b, int N, int relu, float* y) try {
+  AIRFE_ENTER(c);
+  if (K != 128 && K != 256 && K != 512) return fail(c, "debug_gemm: K must be 128, 256 or 512");
+  const int prec = c->prec, Mp = (M + 127) / 128 * 128, Np8 = (N + 7) / 8 * 8;
+  std::vector<uint16_t> xin((size_t)Mp * K, 0);
+  for (size_t i = 0; i < (size_t)M * K; ++i) xin[i] = cvt2(x[i], prec);
+  DbgTmp t(prec);
+  airfe_ctx& tmp = t.h;
+  LinW lw;
+  if (!make_linear(&tmp, w, b, K, N, lw)) return fail(c, "debug_gemm: allocation failed");
+  uint16_t* dx = dupload(&tmp, xin);
+  float* dy = dalloc<float>(&tmp, (size_t)Mp * Np8);
+  int rc = 0;
+  if (!dx || !dy) rc = fail(c, "debug_gemm: allocation failed");
+  if (!rc) {
+    GemmArgs g;
+    g.X1 = dx; g.ld1 = K; g.K1 = K; g.Wp = lw.w; g.bias = lw.b; g.M = Mp; g.N = N; g.cb_total = lw.cbt;
+    g.epi = EPI_STORE_F32; g.act = relu ? ACT_RELU : ACT_NONE; g.out = dy; g.ldo = Np8;
+    g.small_max = c->gemm_small_max; g.g8_min = c->gemm8_min; g.gr_min = c->gemmr_min; g.gr_wgs = c->gemmr_wgs;
+    launch_gemm(prec, K, false, g, c->stream);
+    if (hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, "debug_gemm: kernel failed");
+  }
+  if (!rc) {
+    std::vector<float> yo((size_t)Mp * Np8);
+    (void)hipMemcpy(yo.data(), dy, yo.size() * 4, hipMemcpyDeviceToHost);
+    for (int m = 0; m < M; ++m)
+      for (int n = 0; n < N; ++n) y[(size_t)m * N + n] = yo[(size_t)m * Np8 + n];
+  }
+  return rc;
+} AIRFE_CATCH(c)
+
+}  // extern "C"
+
+// ---- the GEMM family one form at a time (include/airfe_debug.h): host tensors -> the production launchers -> host tensors
+static std::vector<uint16_t> dbg_rows2(const float* x, int rows, int cols, int rows_cap, int prec) {
+  std::vector<uint16_t> v((size_t)rows_cap * cols, 0);
+  if (x)
+    for (size_t i = 0; i < (size_t)rows * cols; ++i) v[i] = cvt2(x[i], prec);
+  return v;
+}
+static std::vector<float> dbg_rows4(const float* x, int rows, int cols, int rows_cap) {
+  std::vector<float> v((size_t)rows_cap * cols, 0.f);
+  if (x) memcpy(v.data(), x, (size_t)rows * cols * sizeof(float));
+  return v;
+}
+template <class T>
+static T* dbg_canary(airfe_ctx* tmp, size_t n) {       // an output buffer whose every byte starts as 0xFF (NaN in fp32, fp16 and bf16)
+  T* p = dalloc<T>(tmp, n, false);
+  if (p) (void)hipMemset(p, 0xFF, std::max<size_t>(n, 1) * sizeof(T));
+  return p;
+}
+static void dbg_back2(const std::vector<uint16_t>& v, size_t n, int prec, float* out) {
+  for (size_t i = 0; i < n; ++i) out[i] = back2(v[i], prec);
+}
+
+extern "C" {
+
+int airfe_debug_linear(airfe_ctx* c, const airfe_debug_linear_args* a) try {
+  AIRFE_ENTER(c);
+  if (!a || !a->x1 || !a->w || !a->b || !a->out) return fail(c, "debug_linear: null argument");
+  const int prec = a->prec, M = a->M, K = a->K, N = a->N, epi = a->epi, kern = a->kernel, K1 = a->x2 ? a->K1 : K;
+  if ((prec != 0 && prec != 1) || M < 1 || N < 1 || (K != 128 && K != 256 && K != 512) || K1 < 32 || K1 % 32 || K1 > K || (a->x2 && K1 == K) ||
+      epi < EPI_STORE || epi > EPI_SOFTMAX_D2S || kern < AIRFE_DEBUG_KERNEL_DISPATCH || kern > AIRFE_DEBUG_KERNEL_GEMMR_GATHER128 || (a->act != ACT_NONE && a->act != ACT_RELU))
+    return fail(c, "debug_linear: bad argument");
+  const bool trans = epi == EPI_HEADS_T, heads = epi == EPI_HEADS || trans, d2s = epi == EPI_SOFTMAX_D2S;
+  if (heads && ((a->H != 4 && a->H != 0) || a->Np < 16 || a->Np % 16 || M % a->Np || (epi == EPI_HEADS ? (N != 256 && N != 512) || (N == 512 && !a->out2) : N != 256)))
+    return fail(c, "debug_linear: head layouts need H = 4, M = S * Np with Np a multiple of 16, N = 256 (or 512 with out2 for EPI_HEADS)");
+  if ((a->rot_cos || a->rot_sin) && (epi != EPI_HEADS || !a->rot_cos || !a->rot_sin)) return fail(c, "debug_linear: rotary is an EPI_HEADS form");
+  if (epi == EPI_RESID && (!a->x32 || N % 64)) return fail(c, "debug_linear: EPI_RESID needs x32 and N a multiple of 64");
+  if (d2s && (K != 256 || N != 65 || a->x2 || a->rowidx || a->act || a->d2s_hc < 1 || a->d2s_wc < 1 || M % (a->d2s_hc * a->d2s_wc) || M % 16 ||
+              (kern != AIRFE_DEBUG_KERNEL_DISPATCH && kern != AIRFE_DEBUG_KERNEL_GEMM8)))
+    return fail(c, "debug_linear: EPI_SOFTMAX_D2S is launch_gemm8's head kernel: K = 256, N = 65, dense rows, M = B * hc * wc, M % 16 == 0");
+  if (a->rowidx) {
+    if (kern != AIRFE_DEBUG_KERNEL_GEMM8 && kern != AIRFE_DEBUG_KERNEL_GEMMR_GATHER && kern != AIRFE_DEBUG_KERNEL_GEMMR_GATHER128)
+      return fail(c, "debug_linear: a row gather runs in gemm8, gemmr_gather or gemmr_gather128 only");
+    if (a->src_rows < 1) return fail(c, "debug_linear: rowidx needs src_rows");
+    for (int r = 0; r < M; ++r)
+      if (a->rowidx[r] < 0 || a->rowidx[r] >= a->src_rows) return fail(c, "debug_linear: rowidx entry outside 0 .. src_rows - 1");
+  }
+  static const int row_tile[7] = {128, 32, 128, 256, 32, 32, 64};
+  const int Mp = d2s ? M : (M + row_tile[kern] - 1) / row_tile[kern] * row_tile[kern];
+  const int xrows = a->rowidx ? a->src_rows : Mp;
+  const int ldo = (epi == EPI_STORE || epi == EPI_STORE_F32) ? (N + 7) / 8 * 8 : N;
+  const int Sg = heads ? (Mp + a->Np - 1) / a->Np : 0, S = heads ? M / a->Np : 0;
+  DbgTmp t(prec);
+  airfe_ctx& tmp = t.h;
+  LinW lw;
+  if (!make_linear(&tmp, a->w, a->b, K, N, lw)) return fail(c, "debug_linear: allocation failed");
+  GemmArgs g;
+  g.X1 = dupload(&tmp, dbg_rows2(a->x1, a->rowidx ? a->src_rows : M, K1, xrows, prec)); g.ld1 = K1; g.K1 = K1;
+  if (a->x2) { g.X2 = dupload(&tmp, dbg_rows2(a->x2, M, K - K1, Mp, prec)); g.ld2 = K - K1; }
+  g.Wp = lw.w; g.bias = lw.b; g.M = Mp; g.N = N; g.cb_total = lw.cbt; g.epi = epi; g.act = a->act; g.ldo = ldo; g.Np = a->Np; g.H = 4;
+  g.small_max = c->gemm_small_max; g.g8_min = c->gemm8_min; g.gr_min = c->gemmr_min; g.gr_wgs = a->gr_wgs > 0 ? a->gr_wgs : c->gemmr_wgs;
+  if (a->rot_cos) { g.rot_cos = dupload(&tmp, dbg_rows4(a->rot_cos, M, 32, Mp)); g.rot_sin = dupload(&tmp, dbg_rows4(a->rot_sin, M, 32, Mp)); }
+  if (a->rowidx) { std::vector<int> ri(Mp, 0); memcpy(ri.data(), a->rowidx, (size_t)M * sizeof(int)); g.rowidx = dupload(&tmp, ri); }
+  size_t out_elems = 0;
+  if (epi == EPI_STORE || epi == EPI_RESID) out_elems = (size_t)Mp * ldo;
+  else if (heads) out_elems = (size_t)Sg * 4 * a->Np * 64;
+  if (epi == EPI_STORE_F32) g.out = dbg_canary<float>(&tmp, (size_t)Mp * ldo);
+  else if (d2s) g.out = dbg_canary<float>(&tmp, (size_t)M * 64);
+  else g.out = dbg_canary<uint16_t>(&tmp, out_elems);
+  if (epi == EPI_HEADS && N == 512) g.out2 = dbg_canary<uint16_t>(&tmp, out_elems);
+  if (epi == EPI_RESID) g.x32 = dupload(&tmp, dbg_rows4(a->x32, M, N, Mp));
+  if (d2s) { g.d2s_hc = a->d2s_hc; g.d2s_wc = a->d2s_wc; g.flag = dalloc<int>(&tmp, 1); }
+  bool ok = g.X1 && (!a->x2 || g.X2) && g.out && (!(epi == EPI_HEADS && N == 512) || g.out2) && (epi != EPI_RESID || g.x32) && (!a->rot_cos || (g.rot_cos && g.rot_sin)) &&
+            (!a->rowidx || g.rowidx) && (!d2s || g.flag);
+  int rc = ok ? 0 : fail(c, "debug_linear: allocation failed");
+  // a forced kernel runs only where its own applicability test says yes: never a silent fall-back to another kernel
+  const char* refused = nullptr;
+  if (!rc) switch (kern) {
+    case AIRFE_DEBUG_KERNEL_DISPATCH:
+      if (d2s) launch_gemm8(prec, K, false, g, c->stream);
+      else launch_gemm(prec, K, trans, g, c->stream);
+      break;
+    case AIRFE_DEBUG_KERNEL_SMALL:                       // launch_gemm's own row test with every other path moved out of reach
+      if (d2s || a->rowidx) refused = "gemm_small";
+      else { g.small_max = 1 << 30; g.g8_min = 1 << 30; g.gr_min = 1 << 30; launch_gemm(prec, K, trans, g, c->stream); }
+      break;
+    case AIRFE_DEBUG_KERNEL_TILED:
+      if (d2s || a->rowidx || K1 % 64) refused = "gemm_kernel";
+      else { g.small_max = -1; g.g8_min = 1 << 30; g.gr_min = 1 << 30; launch_gemm(prec, K, trans, g, c->stream); }
+      break;
+    case AIRFE_DEBUG_KERNEL_GEMM8:
+      if (K1 % 64) refused = "gemm8";
+      else launch_gemm8(prec, K, trans, g, c->stream);
+      break;
+    case AIRFE_DEBUG_KERNEL_GEMMR:
+      if (a->rowidx || !gemmr_applicable(K, trans, g)) refused = "gemmr";
+      else launch_gemmr(prec, trans, g, c->stream);
+      break;
+    case AIRFE_DEBUG_KERNEL_GEMMR_GATHER:
+      if (!gemmr_gather_applicable(K, g)) refused = "gemmr_gather";
+      else launch_gemmr_gather(prec, g, c->stream);
+      break;
+    default:
+      if (!gemmr_gather128_applicable(g)) refused = "gemmr_gather128";
+      else launch_gemmr_gather128(prec, g, c->stream);
+      break;
+  }
+  if (refused) rc = fail(c, std::string("debug_linear: ") + refused + " does not apply to this form");
+  if (!rc && (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c))) rc = fail(c, "debug_linear: kernel failed");
+  if (!rc) {
+    if (epi == EPI_STORE_F32 || d2s) {
+      std::vector<float> ho(d2s ? (size_t)M * 64 : (size_t)Mp * ldo);
+      (void)hipMemcpy(ho.data(), g.out, ho.size() * 4, hipMemcpyDeviceToHost);
+      if (d2s) memcpy(a->out, ho.data(), ho.size() * 4);
+      else
+        for (int m = 0; m < M; ++m) memcpy(a->out + (size_t)m * N, ho.data() + (size_t)m * ldo, (size_t)N * 4);
+      if (d2s && a->flag) (void)hipMemcpy(a->flag, g.flag, sizeof(int), hipMemcpyDeviceToHost);
+    } else if (heads) {
+      std::vector<uint16_t> ho(out_elems);
+      const size_t n = (size_t)S * 4 * a->Np * 64;
+      (void)hipMemcpy(ho.data(), g.out, ho.size() * 2, hipMemcpyDeviceToHost);
+      dbg_back2(ho, n, prec, a->out);
+      if (g.out2) {
+        (void)hipMemcpy(ho.data(), g.out2, ho.size() * 2, hipMemcpyDeviceToHost);
+        dbg_back2(ho, n, prec, a->out2);
+      }
+    } else {
+      std::vector<uint16_t> ho(out_elems);
+      (void)hipMemcpy(ho.data(), g.out, ho.size() * 2, hipMemcpyDeviceToHost);
+      for (int m = 0; m < M; ++m)
+        for (int n = 0; n < N; ++n) a->out[(size_t)m * N + n] = back2(ho[(size_t)m * ldo + n], prec);
+      if (epi == EPI_RESID) (void)hipMemcpy(a->x32, g.x32, (size_t)M * N * 4, hipMemcpyDeviceToHost);
+    }
+  }
+  return rc;
+} AIRFE_CATCH(c)
+
+int airfe_debug_qkv(airfe_ctx* c, int prec, int M, int Np, const float* x, const float* wqk, const float* bqk, int nqk, const float* wv, const float* bv,
+                    const float* rot_cos, const float* rot_sin, int pair, int gr_wgs, float* q, float* k, float* vt) try {
+  AIRFE_ENTER(c);
+  if ((prec != 0 && prec != 1) || M < 1 || Np < 16 || Np % 16 || M % Np || (nqk != 256 && nqk != 512) || !x || !wqk || !bqk || !wv || !bv || !q || !vt ||
+      (nqk == 512 && !k) || (!rot_cos) != (!rot_sin))
+    return fail(c, "debug_qkv: bad argument");
+  const int Mp = (M + 127) / 128 * 128, Sg = (Mp + Np - 1) / Np, S = M / Np;
+  const size_t elems = (size_t)Sg * 4 * Np * 64, n = (size_t)S * 4 * Np * 64;
+  DbgTmp t(prec);
+  airfe_ctx& tmp = t.h;
+  LinW lqk, lv;
+  const bool packed = make_linear(&tmp, wqk, bqk, 256, nqk, lqk) && make_linear(&tmp, wv, bv, 256, 256, lv);
+  GemmArgs ga, gb;
+  const uint16_t* dx = dupload(&tmp, dbg_rows2(x, M, 256, Mp, prec));
+  ga.X1 = gb.X1 = dx; ga.ld1 = gb.ld1 = 256; ga.K1 = gb.K1 = 256; ga.M = gb.M = Mp; ga.Np = gb.Np = Np; ga.H = gb.H = 4;
+  ga.Wp = lqk.w; ga.bias = lqk.b; ga.N = nqk; ga.cb_total = lqk.cbt; ga.epi = EPI_HEADS; ga.ldo = nqk;
+  gb.Wp = lv.w; gb.bias = lv.b; gb.N = 256; gb.cb_total = lv.cbt; gb.epi = EPI_HEADS_T; gb.ldo = 256;
+  ga.out = dbg_canary<uint16_t>(&tmp, elems);
+  if (nqk == 512) ga.out2 = dbg_canary<uint16_t>(&tmp, elems);
+  gb.out = dbg_canary<uint16_t>(&tmp, elems);
+  if (rot_cos) { ga.rot_cos = dupload(&tmp, dbg_rows4(rot_cos, M, 32, Mp)); ga.rot_sin = dupload(&tmp, dbg_rows4(rot_sin, M, 32, Mp)); }
+  for (GemmArgs* g : {&ga, &gb}) {
+    g->small_max = c->gemm_small_max; g->g8_min = c->gemm8_min; g->gr_min = c->gemmr_min; g->gr_wgs = gr_wgs > 0 ? gr_wgs : c->gemmr_wgs;
+  }
+  int rc = (packed && dx && ga.out && gb.out && (nqk != 512 || ga.out2) && (!rot_cos || (ga.rot_cos && ga.rot_sin))) ? 0 : fail(c, "debug_qkv: allocation failed");
+  if (!rc) {
+    if (pair) {
+      if (!gemmr_pair_applicable(ga, gb)) rc = fail(c, "debug_qkv: gemmr_pair does not apply to this form");
+      else launch_gemmr_pair(prec, ga, gb, c->stream);
+    } else {
+      launch_gemm(prec, 256, false, ga, c->stream);
+      launch_gemm(prec, 256, true, gb, c->stream);
+    }
+  }
+  if (!rc && (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c))) rc = fail(c, "debug_qkv: kernel failed");
+  if (!rc) {
+    std::vector<uint16_t> ho(elems);
+    (void)hipMemcpy(ho.data(), ga.out, elems * 2, hipMemcpyDeviceToHost);
+    dbg_back2(ho, n, prec, q);
+    if (nqk == 512) {
+      (void)hipMemcpy(ho.data(), ga.out2, elems * 2, hipMemcpyDeviceToHost);
+      dbg_back2(ho, n, prec, k);
+    }
+    (void)hipMemcpy(ho.data(), gb.out, elems * 2, hipMemcpyDeviceToHost);
+    dbg_back2(ho, n, prec, vt);
+  }
+  return rc;
+} AIRFE_CATCH(c)
+
+int airfe_debug_lg_block(airfe_ctx* c, airfe_debug_lg_block_args* a) try {
+  AIRFE_ENTER(c);
+  if (!a || !a->attn || !a->x32 || !a->xb || !a->w1 || !a->b1 || !a->w2 || !a->b2 || (!a->relu && (!a->gamma || !a->beta)) || (!a->wo) != (!a->bo))
+    return fail(c, "debug_lg_block: null argument");
+  const int prec = a->prec, M = a->M, T = a->tokens_per_wg, nq = a->nqk_n, Np = a->Np;
+  if ((prec != 0 && prec != 1) || M < 1 || (T != 32 && T != 64 && T != 112 && T != 128) || (nq != 0 && nq != 256 && nq != 512) || (a->relu && nq))
+    return fail(c, "debug_lg_block: bad argument");
+  if (a->mixed) {                                        // the two-round split or nothing: launch_lg_blockf would quietly run uniform passes
+    const int tiles = (M + 15) / 16, W = c->n_cu;
+    if (a->wo || T != 112 || W <= 0 || tiles <= 7 * W || tiles > 13 * W) return fail(c, "debug_lg_block: the mixed split does not apply to this form");
+  }
+  if (nq && (!a->nqk_w || !a->nqk_b || !a->nv_w || !a->nv_b || !a->q || !a->vt || (nq == 512) != (a->rot_cos && a->rot_sin) || (nq == 512 && !a->k) || Np < 16 ||
+             Np % 16 || M % Np))
+    return fail(c, "debug_lg_block: the next projection needs its weights and outputs, rotary exactly when nqk_n = 512, and M = S * Np (Np a multiple of 16)");
+  const int cap = M + 256;                               // every pass form stays below M + 127 rows
+  const int Sg = nq ? (cap + Np - 1) / Np : 0, S = nq ? M / Np : 0;
+  const size_t helems = (size_t)Sg * 4 * Np * 64;
+  DbgTmp t(prec);
+  airfe_ctx& tmp = t.h;
+  LinW lo, l1, l2, lq, lv;
+  bool ok = (!a->wo || make_linear(&tmp, a->wo, a->bo, 256, 256, lo)) && make_linear(&tmp, a->w1, a->b1, 512, 512, l1) && make_linear(&tmp, a->w2, a->b2, 512, 256, l2) &&
+            (!nq || (make_linear(&tmp, a->nqk_w, a->nqk_b, 256, nq, lq) && make_linear(&tmp, a->nv_w, a->nv_b, 256, 256, lv)));
+  const bool fr = lg_blockf_frag_weights();
+  std::vector<float> x32h = dbg_rows4(a->x32, M, 256, cap);
+  std::vector<uint16_t> xbh((size_t)cap * 256);
+  for (size_t i = 0; i < xbh.size(); ++i) xbh[i] = cvt2(x32h[i], prec);
+  std::vector<float> gb(1024, 0.f);
+  if (!a->relu) { memcpy(gb.data(), a->gamma, 512 * 4); memcpy(gb.data() + 512, a->beta, 512 * 4); }
+  LgBlockFArgs g;
+  g.attn = dupload(&tmp, dbg_rows2(a->attn, M, 256, cap, prec));
+  g.xb = dupload(&tmp, xbh);
+  g.x32 = dupload(&tmp, x32h);
+  const float* dgb = dupload(&tmp, gb);
+  g.wo = a->wo ? (fr ? lo.wf : lo.w) : nullptr; g.bo = a->wo ? lo.b : nullptr;
+  g.w1 = fr ? l1.wf : l1.w; g.b1 = l1.b; g.w2 = fr ? l2.wf : l2.w; g.b2 = l2.b;
+  g.gamma = dgb; g.beta = dgb ? dgb + 512 : nullptr;
+  g.M = M; g.tokens_per_wg = T; g.mixed = a->mixed; g.n_cu = c->n_cu; g.relu = a->relu;
+  if (nq) {
+    g.nqk_w = fr ? lq.wf : lq.w; g.nqk_b = lq.b; g.nqk_n = nq; g.nv_w = fr ? lv.wf : lv.w; g.nv_b = lv.b; g.Np = Np; g.H = 4;
+    if (nq == 512) { g.rot_cos = dupload(&tmp, dbg_rows4(a->rot_cos, M, 32, cap)); g.rot_sin = dupload(&tmp, dbg_rows4(a->rot_sin, M, 32, cap)); }
+    g.q_out = dbg_canary<uint16_t>(&tmp, helems);
+    if (nq == 512) g.k_out = dbg_canary<uint16_t>(&tmp, helems);
+    g.vt_out = dbg_canary<uint16_t>(&tmp, helems);
+  }
+  ok = ok && g.attn && g.xb && g.x32 && dgb && (!nq || (g.q_out && g.vt_out && (nq != 512 || (g.k_out && g.rot_cos && g.rot_sin))));
+  int rc = ok ? 0 : fail(c, "debug_lg_block: allocation failed");
+  if (!rc) {
+    launch_lg_blockf(prec, g, c->stream);
+    if (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c)) rc = fail(c, "debug_lg_block: kernel failed");
+  }
+  if (!rc) {
+    // rows past M that the launch changed: x32 / xb against their initial (zero) rows, q / k / v^T against the 0xFFFF fill
+    std::vector<float> x32o((size_t)cap * 256);
+    std::vector<uint16_t> xbo((size_t)cap * 256);
+    (void)hipMemcpy(x32o.data(), g.x32, x32o.size() * 4, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(xbo.data(), g.xb, xbo.size() * 2, hipMemcpyDeviceToHost);
+    memcpy(a->x32, x32o.data(), (size_t)M * 256 * 4);
+    dbg_back2(xbo, (size_t)M * 256, prec, a->xb);
+    for (int i = 0; i < 5; ++i) a->rows_past[i] = 0;
+    for (int r = M; r < cap; ++r)
+      for (int f = 0; f < 256; ++f) {
+        const size_t e = (size_t)r * 256 + f;
+        if (memcmp(&x32o[e], &x32h[e], 4)) a->rows_past[0] = r - M + 1;
+        if (xbo[e] != xbh[e]) a->rows_past[1] = r - M + 1;
+      }
+    if (nq) {
+      uint16_t* dev[3] = {g.q_out, g.k_out, g.vt_out};
+      float* host[3] = {a->q, a->k, a->vt};
+      std::vector<uint16_t> ho(helems);
+      for (int j = 0; j < 3; ++j) {
+        if (!dev[j]) continue;
+        (void)hipMemcpy(ho.data(), dev[j], helems * 2, hipMemcpyDeviceToHost);
+        dbg_back2(ho, (size_t)S * 4 * Np * 64, prec, host[j]);
+        for (size_t e = (size_t)S * 4 * Np * 64; e < helems; ++e) {
+          if (ho[e] == 0xFFFF) continue;
+          const size_t s = e / ((size_t)4 * Np * 64), w = e % ((size_t)Np * 64);
+          const int row = (int)(s * Np + (j == 2 ? w % Np : w / 64));          // q / k [s][h][n][64], v^T [s][h][d][n]
+          a->rows_past[2 + j] = std::max(a->rows_past[2 + j], row - M + 1);
+        }
+      }
+    }
+  }
+  return rc;
+} AIRFE_CATCH(c)
+
+int airfe_debug_ln_gelu(airfe_ctx* c, int prec, float* h, const float* gamma, const float* beta, int M) try {
+  AIRFE_ENTER(c);
+  if ((prec != 0 && prec != 1) || M < 1 || !h || !gamma || !beta) return fail(c, "debug_ln_gelu: bad argument");
+  DbgTmp t;
+  airfe_ctx& tmp = t.h;
+  std::vector<float> gb(1024);
+  memcpy(gb.data(), gamma, 512 * 4);
+  memcpy(gb.data() + 512, beta, 512 * 4);
+  uint16_t* dh = dupload(&tmp, dbg_rows2(h, M, 512, M, prec));
+  float* dgb = dupload(&tmp, gb);
+  int rc = dh && dgb ? 0 : fail(c, "debug_ln_gelu: allocation failed");
+  if (!rc) {
+    launch_ln_gelu(prec, dh, dgb, dgb + 512, M, c->stream);
+    if (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c)) rc = fail(c, "debug_ln_gelu: kernel failed");
+  }
+  if (!rc) {
+    std::vector<uint16_t> ho((size_t)M * 512);
+    (void)hipMemcpy(ho.data(), dh, ho.size() * 2, hipMemcpyDeviceToHost);
+    dbg_back2(ho, ho.size(), prec, h);
+  }
+  return rc;
+} AIRFE_CATCH(c)
+}  // extern "C"
+
+// the body of both attention hooks (the callers hold the context and catch)
+static int dbg_attention_run(airfe_ctx* c, airfe_debug_attn_args* a, const char* who) {
+  const std::string w = std::string(who) + ": ";
+  const int S = a->S, H = a->H, n = a->n, cross = a->cross, prec = a->prec;
+  if (prec != 0 && prec != 1) return fail(c, w + "prec must be 0 (bf16) or 1 (fp16)");
+  if (S < 1 || H < 1 || n < 1 || (S * H) % 8 != 0 || (cross && (S & 1))) return fail(c, w + "S * H must be a multiple of 8 (cross: S even)");
+  if (!a->q || !a->k || !a->v || !a->lens || !a->out) return fail(c, w + "null argument");
+  for (int s = 0; s < S; ++s)
+    if (a->lens[s] < 0 || a->lens[s] > n) return fail(c, w + "lens[s] must lie in 0 .. n");
+  const int Np = (n + 15) / 16 * 16;
+  a->Np = Np; a->rows_past = 0;
+  const size_t rows = (size_t)S * H * Np + 128;                      // (+ slack: the last key tile reads up to 63 rows past a sequence; it stays ZERO like the arena's)
+  std::vector<uint16_t> hq(rows * 64, 0), hk(rows * 64, 0), hvt(rows * 64, 0);
+  for (int s = 0; s < S; ++s)
+    for (int h = 0; h < H; ++h)
+      for (int i = 0; i < n; ++i)
+        for (int d = 0; d < 64; ++d) {
+          const size_t src = (((size_t)s * H + h) * n + i) * 64 + d;
+          hq[(((size_t)s * H + h) * Np + i) * 64 + d] = cvt2(a->q[src], prec);
+          hk[(((size_t)s * H + h) * Np + i) * 64 + d] = cvt2(a->k[src], prec);
+          hvt[(((size_t)s * H + h) * 64 + d) * Np + i] = cvt2(a->v[src], prec);       // V^T [S][H][64][Np]
+        }
+  DbgTmp t;
+  airfe_ctx* tmp = &t.h;   // only as an allocation list holder
+  uint16_t *dq = dupload(tmp, hq), *dk = dupload(tmp, hk), *dv = dupload(tmp, hvt);
+  const size_t out_n = (size_t)S * Np * H * 64, slack_n = (size_t)128 * H * 64;
+  uint16_t* dout = dalloc<uint16_t>(tmp, out_n + slack_n);
+  std::vector<int> hl(a->lens, a->lens + S);
+  int* dl = dupload(tmp, hl);
+  if (!dq || !dk || !dv || !dout || !dl) return fail(c, w + "allocation failed");
+  if (a->canary && hipMemsetAsync(dout, 0xFF, (out_n + slack_n) * 2, c->stream) != hipSuccess) return fail(c, w + "memset failed");
+  launch_attention32(prec, dq, dk, dv, dout, dl, S, H, Np, cross, c->stream);
+  if (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c)) return fail(c, w + "kernel failed");
+  std::vector<uint16_t> ho(out_n + slack_n);
+  if (hipMemcpy(ho.data(), dout, ho.size() * 2, hipMemcpyDeviceToHost) != hipSuccess) return fail(c, w + "copy failed");
+  const int rows_out = a->raw ? Np : n;
+  for (int s = 0; s < S; ++s)
+    for (int i = 0; i < rows_out; ++i)
+      for (int f = 0; f < H * 64; ++f) a->out[((size_t)s * rows_out + i) * H * 64 + f] = back2(ho[((size_t)s * Np + i) * H * 64 + f], prec);
+  if (a->canary)
+    for (int r = 0; r < 128; ++r) {
+      bool changed = false;
+      for (int f = 0; f < H * 64 && !changed; ++f) changed = ho[out_n + (size_t)r * H * 64 + f] != 0xFFFFu;
+      a->rows_past += changed;
+    }
+  return 0;
+}
+
+extern "C" {
+int airfe_debug_attention(airfe_ctx* c, const float* q, const float* k, const float* v, const int* lens, int S, int H, int n, int cross, float* out) try {
+  AIRFE_ENTER(c);
+  if (c->mprec == 2) return fail(c, "debug_attention drives the 2-byte kernel (matcher_precision fp16 / bf16)");
+  airfe_debug_attn_args a = {};
+  a.prec = c->mprec; a.S = S; a.H = H; a.n = n; a.cross = cross;
+  a.q = q; a.k = k; a.v = v; a.lens = lens; a.out = out;                 // canary = 0, raw = 0: the output buffer as the allocator left it, the first n rows back
+  return dbg_attention_run(c, &a, "debug_attention");
+} AIRFE_CATCH(c)
+
+int airfe_debug_attention_args(airfe_ctx* c, airfe_debug_attn_args* a) try {
+  AIRFE_ENTER(c);
+  if (!a) return fail(c, "debug_attention_args: null argument");
+  return dbg_attention_run(c, a, "debug_attention_args");
+} AIRFE_CATCH(c)
+
+/* ---- LightGlue's head and tail one launcher at a time (include/airfe_debug.h; tests/test_gpu_lg_tail.py) */
+int airfe_debug_lg_prepare(airfe_ctx* c, airfe_debug_lg_prepare_args* a) try {
+  AIRFE_ENTER(c);
+  if (!c->has_arena) return fail(c, "debug_lg_prepare: no matcher loaded");
+  if (!a || !a->f0 || !a->f1 || !a->n0 || !a->n1 || !a->wr || !a->x32 || !a->xb || !a->rot_cos || !a->rot_sin || !a->lens || (!a->f0x) != (!a->f1x))
+    return fail(c, "debug_lg_prepare: null argument");
+  const int Np = c->Np, B = a->B, Bt = a->f0x ? 2 : B;
+  if ((a->prec != 0 && a->prec != 1) || B < 1 || B > c->Pmax || (a->f0x && (B != 1 || c->Pmax < 2)) || a->cap < 1 || a->cap > Np || a->kp_off < 0 ||
+      a->ld < a->kp_off + 258 || a->slack_rows < 0)
+    return fail(c, "debug_lg_prepare: bad argument (prec 0 / 1, 1 <= B <= max_batch, a second pair with B = 1 only, 1 <= cap <= Np, ld >= kp_off + 258)");
+  for (int b = 0; b < B; ++b)
+    if (a->n0[b] < 0 || a->n0[b] > a->cap || a->n1[b] < 0 || a->n1[b] > a->cap) return fail(c, "debug_lg_prepare: every n0, n1 must lie in 0 .. cap");
+  if (a->f0x && (a->n0x < 0 || a->n0x > Np || a->n1x < 0 || a->n1x > Np)) return fail(c, "debug_lg_prepare: the second pair's lengths must lie in 0 .. Np");
+  const size_t rows = (size_t)2 * Bt * Np + (size_t)a->slack_rows, R = c->arena_rows;
+  if (rows > R || (size_t)a->rows != rows) return fail(c, "debug_lg_prepare: rows must be 2 Bt Np + slack_rows and fit the arena");
+  DbgTmp t;
+  const size_t fl = (size_t)B * a->cap * a->ld;
+  std::vector<float> hf0(a->f0, a->f0 + fl), hf1(a->f1, a->f1 + fl), hwr(a->wr, a->wr + 64);
+  std::vector<int> hn(2 * B + 2);
+  for (int b = 0; b < B; ++b) { hn[b] = a->n0[b]; hn[B + b] = a->n1[b]; }
+  hn[2 * B] = a->n0x; hn[2 * B + 1] = a->n1x;
+  float *df0 = dupload(&t.h, hf0), *df1 = dupload(&t.h, hf1), *dwr = dupload(&t.h, hwr), *df0x = nullptr, *df1x = nullptr;
+  int* dn = dupload(&t.h, hn);
+  if (a->f0x) {
+    std::vector<float> x0(a->f0x, a->f0x + (size_t)a->n0x * a->ld), x1(a->f1x, a->f1x + (size_t)a->n1x * a->ld);
+    x0.resize(x0.size() + a->ld, 0.f); x1.resize(x1.size() + a->ld, 0.f);          // (never empty)
+    df0x = dupload(&t.h, x0); df1x = dupload(&t.h, x1);
+    if (!df0x || !df1x) return fail(c, "debug_lg_prepare: allocation failed");
+  }
+  if (!df0 || !df1 || !dwr || !dn) return fail(c, "debug_lg_prepare: allocation failed");
+  hipStream_t st = c->stream;
+  HIPCHK(c, hipMemsetAsync(c->x32, 0xFF, R * 256 * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->xb, 0xFF, R * 256 * 2, st));
+  HIPCHK(c, hipMemsetAsync(c->rot_cos, 0xFF, R * 32 * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->rot_sin, 0xFF, R * 32 * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->lens, 0xFF, (size_t)2 * c->Pmax * 4, st));
+  LgPrepArgs pa;
+  pa.f0 = df0; pa.f1 = df1; pa.n0 = dn; pa.n1 = dn + B; pa.ld = a->ld; pa.kp_off = a->kp_off; pa.normalize = a->normalize;
+  pa.cx = a->cx; pa.cy = a->cy; pa.linv = a->linv; pa.wr = dwr; pa.B = B; pa.cap = a->cap; pa.Np = Np;
+  pa.x32 = c->x32; pa.xb = c->xb; pa.rot_cos = c->rot_cos; pa.rot_sin = c->rot_sin; pa.lens = c->lens;
+  if (a->f0x) { pa.f0x = df0x; pa.f1x = df1x; pa.n0x = dn + 2 * B; pa.n1x = dn + 2 * B + 1; }
+  pa.slack_rows = a->slack_rows;
+  launch_lg_prepare(a->prec, pa, st);
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (launch_status(c)) return 1;
+  std::vector<float> hx(R * 256);
+  std::vector<uint16_t> hb(R * 256);
+  HIPCHK(c, hipMemcpy(hx.data(), c->x32, hx.size() * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(hb.data(), c->xb, hb.size() * 2, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->rot_cos, c->rot_cos, rows * 32 * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->rot_sin, c->rot_sin, rows * 32 * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->lens, c->lens, (size_t)2 * Bt * 4, hipMemcpyDeviceToHost));
+  memcpy(a->x32, hx.data(), rows * 256 * 4);
+  dbg_back2(hb, rows * 256, a->prec, a->xb);
+  int past = 0;
+  for (size_t r = rows; r < R; ++r) {
+    bool touched = false;
+    for (int k = 0; k < 256 && !touched; ++k) {
+      uint32_t u;
+      memcpy(&u, &hx[r * 256 + k], 4);
+      touched = u != 0xFFFFFFFFu || hb[r * 256 + k] != 0xFFFFu;
+    }
+    past += touched;
+  }
+  a->rows_past = past;
+  // the arena as alloc_matcher_arena left it: the pipelines reset only the slack rows their own kernels can reach
+  HIPCHK(c, hipMemsetAsync(c->x32, 0, R * 256 * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->xb, 0, R * 256 * 2, st));
+  HIPCHK(c, hipMemsetAsync(c->rot_cos, 0, R * 32 * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->rot_sin, 0, R * 32 * 4, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  return 0;
+} AIRFE_CATCH(c)
+
+int airfe_debug_lg_assign(airfe_ctx* c, airfe_debug_lg_assign_args* a) try {
+  AIRFE_ENTER(c);
+  if (!c->has_arena) return fail(c, "debug_lg_assign: no matcher loaded");
+  if (!a || !a->md || !a->x32 || !a->w || !a->lens || !a->z || !a->sim || !a->scores || !a->rowlse || !a->collse || !a->rowval || !a->rowarg || !a->colarg ||
+      !a->idx || !a->score || !a->nmatch)
+    return fail(c, "debug_lg_assign: null argument");
+  const int Np = c->Np, B = a->B, n = a->n, S = 2 * B, cap = a->cap, prec = a->prec;
+  if ((prec != 0 && prec != 1) || B < 1 || B > c->Pmax || n < 1 || n > Np || cap < 1 || cap > Np || (a->form != 0 && a->form != 1))
+    return fail(c, "debug_lg_assign: bad argument (prec 0 / 1, 1 <= B <= max_batch, 1 <= n, cap <= Np, form 0 / 1)");
+  for (int s = 0; s < S; ++s)
+    if (a->lens[s] < 0 || a->lens[s] > n) return fail(c, "debug_lg_assign: every length must lie in 0 .. n");
+  const size_t M = (size_t)S * Np, blk = (size_t)Np * Np, pf = lg_assign_part_floats(B, Np);
+  std::vector<uint16_t> hmd(M * 256, 0xFFFFu);
+  std::vector<float> hx(M * 256);
+  memset(hx.data(), 0xFF, hx.size() * 4);
+  for (int s = 0; s < S; ++s) {
+    for (int i = 0; i < a->lens[s]; ++i)
+      for (int k = 0; k < 256; ++k) {
+        hmd[((size_t)s * Np + i) * 256 + k] = cvt2(a->md[((size_t)s * n + i) * 256 + k], prec);
+        hx[((size_t)s * Np + i) * 256 + k] = a->x32[((size_t)s * n + i) * 256 + k];
+      }
+    if (a->pad)
+      for (int i = a->lens[s]; i < Np; ++i)
+        for (int k = 0; k < 256; ++k) hmd[((size_t)s * Np + i) * 256 + k] = cvt2(a->pad[k], prec);
+  }
+  DbgTmp t;
+  std::vector<float> hw(a->w, a->w + 256);
+  float* dw = dupload(&t.h, hw);
+  float* dscores = dalloc<float>(&t.h, (size_t)B * blk, false);
+  int32_t* didx = dalloc<int32_t>(&t.h, (size_t)B * cap * 2, false);
+  float* dscore = dalloc<float>(&t.h, (size_t)B * cap, false);
+  int* dnm = dalloc<int>(&t.h, (size_t)B, false);
+  if (!dw || !dscores || !didx || !dscore || !dnm) return fail(c, "debug_lg_assign: allocation failed");
+  hipStream_t st = c->stream;
+  HIPCHK(c, hipMemcpyAsync(c->mdb, hmd.data(), hmd.size() * 2, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->x32, hx.data(), hx.size() * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->lens, a->lens, (size_t)S * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(c->zbuf, 0xFF, M * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->simbuf, 0xFF, (size_t)B * blk * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->lg_part, 0xFF, pf * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->lg_argpart, 0xFF, pf * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->rowlse, 0xFF, (size_t)B * Np * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->collse, 0xFF, (size_t)B * Np * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->rowval, 0xFF, (size_t)B * Np * 4, st));
+  HIPCHK(c, hipMemsetAsync(dscores, 0xFF, (size_t)B * blk * 4, st));
+  HIPCHK(c, hipMemsetAsync(dscore, 0xFF, (size_t)B * cap * 4, st));
+  HIPCHK(c, hipMemsetAsync(dnm, 0xFF, (size_t)B * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->rowarg, 0, (size_t)B * Np * 4, st));          // zero, not -1: the value that passes for a valid index
+  HIPCHK(c, hipMemsetAsync(c->colarg, 0, (size_t)B * Np * 4, st));
+  HIPCHK(c, hipMemsetAsync(didx, 0, (size_t)B * cap * 8, st));
+  launch_rowdot256(c->x32, dw, a->b, c->zbuf, (int)M, st);
+  if (a->form == 1) {
+    launch_lg_assign_fused(prec, c->mdb, c->zbuf, c->lens, B, Np, cap, a->thr, c->lg_part, c->lg_argpart, c->rowlse, c->collse, c->simbuf, dscores, c->rowarg,
+                           c->rowval, c->colarg, didx, dscore, dnm, st);
+  } else {
+    launch_sim(prec, c->mdb, c->simbuf, B, Np, st);
+    launch_lg_assign(c->simbuf, c->zbuf, c->lens, B, Np, cap, a->thr, c->rowlse, c->collse, dscores, c->rowarg, c->rowval, c->colarg, didx, dscore, dnm, st);
+  }
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (launch_status(c)) return 1;
+  const size_t nb = (size_t)n * 4, npb = (size_t)Np * 4;
+  HIPCHK(c, hipMemcpy2D(a->z, nb, c->zbuf, npb, nb, S, hipMemcpyDeviceToHost));
+  for (int b = 0; b < B; ++b) {
+    HIPCHK(c, hipMemcpy2D(a->sim + (size_t)b * n * n, nb, c->simbuf + b * blk, npb, nb, n, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy2D(a->scores + (size_t)b * n * n, nb, dscores + b * blk, npb, nb, n, hipMemcpyDeviceToHost));
+  }
+  HIPCHK(c, hipMemcpy2D(a->rowlse, nb, c->rowlse, npb, nb, B, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy2D(a->collse, nb, c->collse, npb, nb, B, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy2D(a->rowval, nb, c->rowval, npb, nb, B, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy2D(a->rowarg, nb, c->rowarg, npb, nb, B, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy2D(a->colarg, nb, c->colarg, npb, nb, B, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->idx, didx, (size_t)B * cap * 8, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->score, dscore, (size_t)B * cap * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->nmatch, dnm, (size_t)B * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemsetAsync(c->mdb, 0, M * 256 * 2, st));          // no NaN token rows stay behind
+  HIPCHK(c, hipMemsetAsync(c->x32, 0, M * 256 * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->zbuf, 0, M * 4, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  return 0;
+} AIRFE_CATCH(c)
+
+}  // extern "C"

@@ -3,7 +3,11 @@
 //   airfe_load.hip    weight-pack loading and slab packing (≙ TensorRT engine build, src/plnet.cpp:24-196), the matcher arena
 //   airfe_detect.hip  the detector pipeline (encoder, heads, NMS, top-K, descriptors) and the PLNet line path
 //   airfe_match.hip   LightGlue / SuperGlue forwards and the fault-hunting trace
-//   airfe.hip         context life cycle and the C ABI (include/airfe.h, include/airfe_debug.h)
+//   airfe.hip         context life cycle, scratch blocks, profiling / trace entries and the C ABI of detection, rectification, matching, lines, PLNet and the
+//                     keyframe / track / promote entries (include/airfe.h), with the inspection hooks that share a body with one of them
+//   airfe_geom.hip    F-RANSAC, PnP, stereo points, track pose, frame optimisation
+//   airfe_bowdb.hip   the BoW vector, the keyframe database, the relocalisation and loop detection composites
+//   airfe_debug.hip   the kernel-level test hooks (include/airfe_debug.h)
 #pragma once
 #include "../../include/airfe.h"
 #include "../../include/airfe_debug.h"
@@ -60,8 +64,32 @@ constexpr size_t SG_JUNCS = 0, SG_LP = 600, SG_KEEP = SG_LP + (size_t)KEEP_CAP *
 }  // namespace airfe_host
 using namespace airfe_host;
 
-// airfe_stereo_keyframe's captured queue (one configuration at a time) and the host-side flags that describe what the queue leaves on the device
+// One grow-on-demand device block.  Ownership, one rule: the memory is registered in its context's `allocs` by the reserve() that made it and freed with
+// everything else there by airfe_destroy; an owner that dies before its context (airfe_bowdb) hands its blocks back with release().
+struct DevBlock {
+  uint8_t* p = nullptr; size_t bytes = 0;
+  hipStream_t last = nullptr;    // the stream the block was last handed out for (reserve): synchronised before the block is replaced
+  template <class T> T* at(size_t o) const { return reinterpret_cast<T*>(p + o); }
+};
 struct airfe_ctx;
+// st = the stream the caller is about to use the block on (one stream at a time per entry and context: the contract of every *_dev entry).  Grows by
+// replacement, only when bytes > b.bytes and only behind a synchronisation of the context's stream and of b.last; no synchronisation otherwise.
+int reserve(airfe_ctx* c, DevBlock& b, size_t bytes, hipStream_t st);      // airfe.hip
+void release(airfe_ctx* c, DevBlock& b);                                    // airfe.hip
+// A block's arrays in two phases: take() while sizing (every part starts on a 256-byte boundary, sizes in size_t), into() reserves the block, then at<T>() / i() /
+// d() address the parts.  over() is into() for memory of size() bytes that is no DevBlock (the sequence driver's pinned staging).
+struct Carve {
+  size_t off = 0; uint8_t* base = nullptr;
+  size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; }
+  size_t size() const { return off; }
+  int into(airfe_ctx* c, DevBlock& b, hipStream_t st) { if (reserve(c, b, off, st)) return 1; base = b.p; return 0; }
+  void over(uint8_t* p) { base = p; }
+  template <class T> T* at(size_t o) const { return reinterpret_cast<T*>(base + o); }
+  int* i(size_t o) const { return at<int>(o); }
+  double* d(size_t o) const { return at<double>(o); }
+};
+
+// airfe_stereo_keyframe's captured queue (one configuration at a time) and the host-side flags that describe what the queue leaves on the device
 struct KfState {
   bool nms_map_valid, desc_normalised, desc_dense_valid, line_sparse; int last_B;
   void save(const airfe_ctx* c);
@@ -110,22 +138,15 @@ struct airfe_ctx {
   size_t arena_rows = 0;         // token rows of the matcher arena, slack included (alloc_matcher_arena)
   int Dmax = 1;                  // images the detector arena holds: 2 x Bmax when a stereo step detects left and right as one batch
   bool has_sp = false, has_lg = false;
-  uint8_t* pl_stage = nullptr;   // staging of airfe_assign_points_to_lines / airfe_match_lines
-  size_t pl_bytes = 0;
-  uint8_t *pl_scratch = nullptr, *ml_scratch = nullptr;   // scratch of airfe_assign_points_to_lines_batch_dev (counts) / airfe_match_lines_batch_dev (bit rows, row maxima): one each
-  size_t pl_scratch_bytes = 0, ml_scratch_bytes = 0;
-  hipStream_t pl_scratch_stream = nullptr, ml_scratch_stream = nullptr;   // the stream each was last used on (synchronised before the block is replaced)
-  uint8_t* fr_scratch = nullptr; size_t fr_scratch_bytes = 0;           // airfe_fundamental_ransac_batch_dev: per-model scores [B][1000][3] + state [B][4]
-  hipStream_t fr_scratch_stream = nullptr;
-  uint8_t* fr_stage = nullptr; size_t fr_stage_bytes = 0;               // airfe_fundamental_ransac: the one pair's rows and list on the device
-  uint8_t* pn_scratch = nullptr; size_t pn_scratch_bytes = 0;           // airfe_pnp_ransac_batch_dev: per-sample scores [B][100] + models [B][100][12]
-  hipStream_t pn_scratch_stream = nullptr;
-  uint8_t* pn_gather = nullptr; size_t pn_gather_bytes = 0;             // airfe_track_pose_batch_dev: the gathered correspondences
-  hipStream_t pn_gather_stream = nullptr;
-  uint8_t* pn_stage = nullptr; size_t pn_stage_bytes = 0;               // airfe_pnp_ransac: the one problem on the device
-  uint8_t* po_stage = nullptr; size_t po_stage_bytes = 0;               // airfe_frame_optimize: the one problem on the device
-  uint8_t* po_gather = nullptr; size_t po_gather_bytes = 0;             // airfe_track_pose_opt_batch_dev: PnP results, seeds and gathered constraints
-  hipStream_t po_gather_stream = nullptr;
+  DevBlock pl_stage;             // staging of airfe_assign_points_to_lines / airfe_match_lines
+  DevBlock pl_scratch, ml_scratch;   // scratch of airfe_assign_points_to_lines_batch_dev (counts) / airfe_match_lines_batch_dev (bit rows, row maxima): one each
+  DevBlock fr_scratch;           // airfe_fundamental_ransac_batch_dev: per-model scores [B][1000][3] + state [B][4]
+  DevBlock fr_stage;             // airfe_fundamental_ransac: the one pair's rows and list on the device
+  DevBlock pn_scratch;           // airfe_pnp_ransac_batch_dev: per-sample scores [B][100] + models [B][100][12]
+  DevBlock pn_gather;            // airfe_track_pose_batch_dev: the gathered correspondences (pnp_gather_queue)
+  DevBlock pn_stage;             // airfe_pnp_ransac: the one problem on the device
+  DevBlock po_stage;             // airfe_frame_optimize: the one problem on the device
+  DevBlock po_gather;            // airfe_track_pose_opt_batch_dev: PnP results, seeds and gathered constraints
   bool outlier_rejection = false;                                       // airfe_set_outlier_rejection: F-RANSAC behind the temporal match of track_frame / stereo_keyframe_tracked
   bool nms_map_valid = true;     // heat_nms holds the last batch's NMS'd maps (large batches skip writing them)
   bool force_nms_map = false;    // the batched PLNet path reads junction scores from them: written at every batch size while set
@@ -171,19 +192,19 @@ struct airfe_ctx {
   int bow_nodes = 0;
   double* bow_weight_d = nullptr;     // the same weights on the device: the BoW vector's sums are double (airfe_bow_vector_batch_dev)
   int bow_nwords = 0;                 // 1 + the largest word id
-  uint8_t* bv_scratch = nullptr; size_t bv_scratch_bytes = 0; hipStream_t bv_scratch_stream = nullptr;   // airfe_bow_vector_batch_dev: word / weight / node per feature
-  uint8_t* bv_stage = nullptr; size_t bv_stage_bytes = 0;                                                // airfe_bow_vector: the host entry's device block
+  DevBlock bv_scratch;                // airfe_bow_vector_batch_dev: word / weight / node per feature
+  DevBlock bv_stage;                  // airfe_bow_vector: the host entry's device block
   // rectification maps of Camera (camera.cc:60-75), one pair per side, and the rectified-image staging
   float* rmap[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
   int rmap_h[2] = {0, 0}, rmap_w[2] = {0, 0};
-  uint8_t* st_rect = nullptr; size_t st_rect_bytes = 0;
+  DevBlock st_rect;
   // host-API staging
-  uint8_t* st_img = nullptr; size_t st_img_bytes = 0;
-  uint8_t* kf_blk = nullptr; size_t kf_bytes = 0;   // airfe_stereo_keyframe's device block (grows on demand)
-  uint8_t *tk_blk = nullptr, *ref_blk = nullptr; size_t tk_bytes = 0, ref_bytes = 0;   // airfe_track_frame: outputs; the last keyframe's features
+  DevBlock st_img;
+  DevBlock kf_blk;                                  // airfe_stereo_keyframe's device block (grows on demand)
+  DevBlock tk_blk, ref_blk;                         // airfe_track_frame: outputs; the last keyframe's features
   int ref_n = -1;
   int tk_n = -1;                                    // keypoints of the last airfe_track_frame's frame (its rows are still in tk_blk); -1: none
-  uint8_t* pr_blk = nullptr; size_t pr_bytes = 0;   // airfe_promote_frame: [counts | right rows | idx | score]
+  DevBlock pr_blk;                                  // airfe_promote_frame: [counts | right rows | idx | score]
   int kf_spec_lines = 1024, kf_spec_juncs = 512;   // line / junction rows airfe_stereo_keyframe copies back before it knows the counts (airfe_tuning::kf_spec_rows)
   bool kf_graph_on = false;                         // airfe_tuning::kf_graph
   KfGraph kf_graph;
@@ -386,3 +407,46 @@ int lightglue_dev(airfe_ctx* c, const float* f0, const int* n0, const float* f1,
 int superglue_dev(airfe_ctx* c, const float* f0, const int* n0, const float* f1, const int* n1, int B, int cap, int normalize, hipStream_t st);
 
 }  // namespace airfe_host
+
+// ---- airfe.hip
+// Every extern "C" entry is a function-try-block ending in AIRFE_CATCH: std::bad_alloc from a std::vector / std::string of the host-side
+// bookkeeping (or anything else thrown below) becomes a non-zero return + airfe_last_error(), never an exception crossing the C ABI.
+#define AIRFE_CATCH(c)                                                                                                   \
+  catch (const std::exception& e_) { return airfe_host::fail_noexcept((c), __func__, e_.what()); }                       \
+  catch (...) { return airfe_host::fail_noexcept((c), __func__, nullptr); }
+// Every entry that takes a context makes the context's device current first: a process may hold contexts on several devices (cfg.device)
+// and the calling thread's current device is whatever the application left it at.
+inline int enter_device(airfe_ctx* c) {
+  int d = -1;
+  if (hipGetDevice(&d) == hipSuccess && d == c->cfg.device) return 0;
+  if (hipSetDevice(c->cfg.device) != hipSuccess) return fail(c, "hipSetDevice(cfg.device) failed");
+  return 0;
+}
+#define AIRFE_ENTER(c) do { if (!(c)) return 1; if (enter_device(c)) return 1; } while (0)
+int ensure_pin(airfe_ctx* c, size_t bytes);
+int upload_image(airfe_ctx* c, const uint8_t* gray, int h, int w, int stride);
+// A host entry that returns with an error AFTER it queued work must not leave that work in flight: the next call memcpy's into the pinned block a
+// pending D2H may still write, and reference rows that were only partly uploaded must not be matched against.  Armed once queueing starts,
+// disarmed on success.
+// A host entry reports the overflow of ITS OWN call: a saturation word an earlier asynchronous *_batch_dev call left behind (whose caller never asked: airfe_sync /
+// airfe_superglue_status) must not fail a later healthy call with a stale "left the fp16 range" (ADVICE r05).  Cleared where a host entry starts queueing.
+inline void clear_saturation(airfe_ctx* c) {
+  if (c->sat_host) c->sat_host[0] = c->sat_host[1] = 0;
+}
+struct DrainOnError {
+  airfe_ctx* c; bool armed = false, ref_uploaded = false;
+  explicit DrainOnError(airfe_ctx* c_, bool armed_ = false) : c(c_), armed(armed_) { clear_saturation(c_); }
+  ~DrainOnError() {
+    if (!armed) return;
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipStreamSynchronize(c->stream2);
+    if (ref_uploaded) c->ref_n = -1;
+  }
+};
+// ---- airfe_geom.hip: the pipelines on a stream, queued by their own entries, by the keyframe / track entries and by the composites of airfe_bowdb.hip
+int fransac_queue(airfe_ctx* c, const float* d_f0, const float* d_f1, int B, int cap, int32_t* d_idx, float* d_score, int mcap, int* d_nmatch, double* d_F,
+                  hipStream_t st);
+int pnp_queue(airfe_ctx* c, const float* d_obj, const float* d_img, const int* d_n, int B, int ncap, const double* K, double* d_Twc, double* d_Rt, uint8_t* d_mask,
+              int mcap, const int* d_map, int* d_count, hipStream_t st);
+int poseopt_queue(airfe_ctx* c, const double* d_X, const double* d_obs, const int* d_n, int B, int ncap, const double* d_Twc0, const double* cam, const double* Tcb,
+                  const double* thr, double* d_Twc, double* d_Rt, uint8_t* d_inlier, int mcap, const int* d_map, int* d_num, int lost, int* d_ok, hipStream_t st);

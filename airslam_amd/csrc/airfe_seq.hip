@@ -380,22 +380,24 @@ int airfe_seq_create(airfe_ctx* kf, airfe_ctx* nf, int S, const airfe_seq_policy
     return sfail(s, "airfe_seq_create: device allocation failed");
   // two staging sets of pinned, device-visible memory
   for (Staging& t : s->stg) {
-    const size_t bytes = 4 * (F * 4 + 256) + (size_t)S * CJ * ROW + (size_t)2 * S * CL * 32 + 6 * ((size_t)S * K * 8 + 256) + (size_t)14 * S * 4 + 16 * 256;
+    // one block, carved before it is allocated (every part 256-byte aligned)
+    Carve k;
+    const size_t o_cur = k.take(F * 4), o_kr = k.take(F * 4), o_pr = k.take(F * 4), o_kjunc = k.take((size_t)S * CJ * ROW), o_klines = k.take((size_t)2 * S * CL * 32),
+                 o_kidx = k.take((size_t)S * K * 8), o_tidx = k.take((size_t)S * K * 8), o_pidx = k.take((size_t)S * K * 8), o_ksc = k.take((size_t)S * K * 4),
+                 o_tsc = k.take((size_t)S * K * 4), o_psc = k.take((size_t)S * K * 4), o_counts = k.take((size_t)14 * S * 4);
     // host-mapped, coherent (like the contexts' saturation words): the packing kernel's stores land in host memory, the host reads them after its stream
     // synchronisation; on this runtime a pinned block's device address is its host address (checked)
-    SEQ_HIP(s, hipHostMalloc(reinterpret_cast<void**>(&t.base), bytes, hipHostMallocMapped | hipHostMallocCoherent));
+    SEQ_HIP(s, hipHostMalloc(reinterpret_cast<void**>(&t.base), k.size(), hipHostMallocMapped | hipHostMallocCoherent));
     void* dp = nullptr;
     SEQ_HIP(s, hipHostGetDevicePointer(&dp, t.base, 0));
     if (dp != (void*)t.base) return sfail(s, "airfe_seq_create: pinned memory is not mapped at its host address");
-    memset(t.base, 0, bytes);
-    uint8_t* p = t.base;
-    auto take = [&](size_t b) { uint8_t* r = p; p += (b + 255) & ~(size_t)255; return r; };
-    t.cur = (float*)take(F * 4); t.kr = (float*)take(F * 4); t.pr = (float*)take(F * 4);
-    t.kjunc = (float*)take((size_t)S * CJ * ROW); t.klines = (double*)take((size_t)2 * S * CL * 32);
-    t.kidx = (int32_t*)take((size_t)S * K * 8); t.tidx = (int32_t*)take((size_t)S * K * 8); t.pidx = (int32_t*)take((size_t)S * K * 8);
-    t.ksc = (float*)take((size_t)S * K * 4); t.tsc = (float*)take((size_t)S * K * 4); t.psc = (float*)take((size_t)S * K * 4);
-    t.counts = (int*)take((size_t)14 * S * 4);
-    if ((size_t)(p - t.base) > bytes) return sfail(s, "airfe_seq_create: staging layout overflow");
+    memset(t.base, 0, k.size());
+    k.over(t.base);
+    t.cur = k.at<float>(o_cur); t.kr = k.at<float>(o_kr); t.pr = k.at<float>(o_pr);
+    t.kjunc = k.at<float>(o_kjunc); t.klines = k.d(o_klines);
+    t.kidx = k.at<int32_t>(o_kidx); t.tidx = k.at<int32_t>(o_tidx); t.pidx = k.at<int32_t>(o_pidx);
+    t.ksc = k.at<float>(o_ksc); t.tsc = k.at<float>(o_tsc); t.psc = k.at<float>(o_psc);
+    t.counts = k.i(o_counts);
   }
   s->job_slots = 16; s->job_cap = 16 * S + 64;
   SEQ_HIP(s, hipHostMalloc(reinterpret_cast<void**>(&s->jobs_h), (size_t)s->job_slots * s->job_cap * sizeof(SeqJob), hipHostMallocMapped | hipHostMallocCoherent));

@@ -174,7 +174,7 @@ NEW = ["airfe_bow_vector", "airfe_bow_vector_batch_dev", "airfe_bowdb_create", "
 def test_new_entries_are_declared_exported_and_fail_cleanly(libpath):
     from airslam_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "airfe.h")).read()
-    src = open(os.path.join(ROOT, "airslam_amd", "csrc", "airfe.hip")).read()
+    src = open(os.path.join(ROOT, "airslam_amd", "csrc", "airfe_bowdb.hip")).read()
     lib = _lib.lib()
     for n in NEW:
         assert re.search(r"\bint " + n + r"\(", hdr), n
