@@ -873,9 +873,7 @@ static int plnet_batch_f32(airfe_ctx* c, const uint8_t* d_gray, int B, int h, in
   if (nj < 0 || nj > B || (nj > 0 && (!d_junc || !d_njunc || capJ < 1))) return fail(c, "detect_plnet_batch: bad junction arguments");
   for (int b = 0; b < B; ++b) {
     const bool jn = b < nj;
-    c->force_nms_map = jn;
-    const int rc = detect_dev(c, d_gray + (size_t)b * img_stride, 1, h, w, stride, img_stride, d_feat + (size_t)b * cap * AIRFE_FEAT_DIM, cap, d_n + b, st);
-    c->force_nms_map = false;
+    const int rc = detect_dev(c, d_gray + (size_t)b * img_stride, 1, h, w, stride, img_stride, d_feat + (size_t)b * cap * AIRFE_FEAT_DIM, cap, d_n + b, st);      // (one image: the dense NMS'd map is written)
     if (rc || line_branch_dev(c, st, 0, 1, false)) return 1;
     if (line_tail_dev(c, 0, 1, nullptr, h, w, d_lines + (size_t)b * capL * 4, capL, d_nlines + b, lfound ? lfound + b : c->d_nlines + c->Lmax,
                       jn ? d_junc + (size_t)b * capJ * AIRFE_FEAT_DIM : nullptr, capJ, jn ? d_njunc + b : nullptr, jn ? (jfound ? jfound + b : c->d_njunc + c->Lmax) : nullptr,
@@ -893,10 +891,7 @@ int airfe_detect_plnet_batch_dev(airfe_ctx* c, const uint8_t* d_gray, int B, int
   if (c->prec == 2)
     return plnet_batch_f32(c, d_gray, B, h, w, stride, img_stride, d_feat, cap, d_n, d_lines, capL, d_nlines, d_junc, capJ, d_njunc, junction_images, d_found,
                            d_found ? d_found + B : nullptr, st);
-  c->force_nms_map = junction_images > 0;         // junction scores are read from the NMS'd maps
-  const int rc = detect_dev(c, d_gray, B, h, w, stride, img_stride, d_feat, cap, d_n, st);
-  c->force_nms_map = false;
-  if (rc) return 1;
+  if (detect_dev(c, d_gray, B, h, w, stride, img_stride, d_feat, cap, d_n, st)) return 1;      // (junction scores: the NMS keep plane over the raw scores, line_tail_dev)
   return plnet_lines_batch(c, B, h, w, d_lines, capL, d_nlines, d_junc, capJ, d_njunc, junction_images, d_found, st);
 } AIRFE_CATCH(c)
 
@@ -923,10 +918,7 @@ static int stereo_plnet_dev(airfe_ctx* c, const uint8_t* d_left, const uint8_t* 
   // (With stage timers on anything behind the encoder the chains run one after the other: a stage's event pair must not span the other chain.)
   const uint32_t enc_only = (1u << ST_PREPROCESS) | (1u << ST_CONV1_FUSED) | (1u << ST_CONV3X3_C64);
   const bool overlap = c->overlap_lines && (c->prof_mask & ~enc_only) == 0;
-  c->force_nms_map = d_juncL != nullptr;          // junction scores are read from the NMS'd maps
-  int rc = detect_dev2(c, d_left, d_right, B, h, w, stride, img_stride, d_featL, d_featR, cap, d_nL, d_nR, st);
-  c->force_nms_map = false;
-  if (rc) return 1;
+  if (detect_dev2(c, d_left, d_right, B, h, w, stride, img_stride, d_featL, d_featR, cap, d_nL, d_nR, st)) return 1;
   // lines of the 2 B images (left 0 .. B-1, right B .. 2B-1), junctions of the left ones (feature_detector.cc:100-101).
   // The line path and the matcher share nothing but the detector's results: the line path runs on the context's second stream beside
   // LightGlue on the caller's (+2 % from filled launch ramps and tails; fork behind the point branch, join behind both).  Round 2 kept this
@@ -947,6 +939,7 @@ static int stereo_plnet_dev(airfe_ctx* c, const uint8_t* d_left, const uint8_t* 
   }
   HIPCHK(c, hipEventRecord(c->ev_fork, st));                  // behind the point branch
   HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
+  int rc = 0;
   if (after_detect && (*after_detect)(c->stream2)) rc = 1;
   // The matcher is the longer chain: at small batches its launches are queued FIRST (the host needs ~4 us per launch; the ~20 launches of the line
   // path queued ahead of it kept the GPU's main queue idle for 80 us per batch-1 keyframe, tools/kf_timeline.py), at large ones the line path's

@@ -98,10 +98,6 @@ int detect_dev2(airfe_ctx* c, const uint8_t* d_gray, const uint8_t* d_gray1, int
   if (!c->has_sp) return fail(c, "detector weights were not loaded (cfg.superpoint_pack)");
   const int B = d_gray1 ? 2 * Bs : Bs;
   if (Bs < 1 || Bs > c->Bmax || B > c->Dmax) return fail(c, "batch exceeds cfg.max_batch");
-  // Two sources / two destinations that are in fact ONE array (the batch-1 keyframe entry lays left and right out back to back): the per-side
-  // launches below become one launch over the 2 Bs images — per image the same work, so the same bits.
-  const bool src_contig = d_gray1 && d_gray1 == d_gray + (size_t)Bs * img_stride;
-  const bool dst_contig = d_gray1 && d_feat1 == d_feat + (size_t)Bs * cap * AIRFE_FEAT_DIM && d_n1 == d_n + Bs;
   if (h < 1 || w < 1) return fail(c, "empty image");
   if (cap < c->cfg.max_keypoints) return fail(c, "feature capacity < max_keypoints");
   if (ensure_tables(c, h, w)) return 1;
@@ -113,14 +109,12 @@ int detect_dev2(airfe_ctx* c, const uint8_t* d_gray, const uint8_t* d_gray1, int
   } else {
     for (int c0 = 0, cb = 0; c0 < B; c0 += cb) {
       cb = std::min(c->chunk, B - c0);
-      {                                                                  // a chunk may straddle the two sources: one pre-process launch per source
+      {                                                                  // a chunk may straddle the two sources: still one pre-process launch
         ProfScope ps(c, ST_PREPROCESS, st, 0, (double)cb * ((double)h * w + (double)R * R * 4));
-        int n0 = std::min(std::max(Bs - c0, 0), cb);                    // images of this chunk that come from d_gray
-        if (src_contig) n0 = cb;                                        // (the second source lies right behind the first: one launch)
-        if (n0 > 0) launch_preprocess(d_gray + (size_t)c0 * img_stride, n0, h, w, stride, img_stride, c->xtab, c->ytab, c->lut, c->img32, R, R, st);
-        if (cb > n0)
-          launch_preprocess(d_gray1 + (size_t)(c0 + n0 - Bs) * img_stride, cb - n0, h, w, stride, img_stride, c->xtab, c->ytab, c->lut,
-                            c->img32 + (size_t)n0 * (R + 2) * (R + 2), R, R, st);
+        const int n0 = std::min(std::max(Bs - c0, 0), cb);              // images of this chunk that come from d_gray
+        const uint8_t* s0 = n0 > 0 ? d_gray + (size_t)c0 * img_stride : nullptr;
+        const uint8_t* s1 = cb > n0 ? d_gray1 + (size_t)(c0 + n0 - Bs) * img_stride : nullptr;
+        launch_preprocess(s0 ? s0 : s1, cb, h, w, stride, img_stride, c->xtab, c->ytab, c->lut, c->img32, R, R, st, s0 ? s1 : nullptr, n0);
       }
       {
         // conv1a (Cin = 1) fused into the persistent conv1b kernel: its 64-channel full-resolution output never
@@ -167,8 +161,8 @@ int detect_dev2(airfe_ctx* c, const uint8_t* d_gray, const uint8_t* d_gray1, int
     ProfScope ps(c, ST_NMS, st, 0, (double)B * R * R * 8);
     if (c->cfg.nms_radius == 4) {                        // the reference's radius: simple_nms in registers (kernels_nms512.hip; R = 512)
       // the dense NMS'd map is consumed only by the batch-1 line path (junction scores) and the inspection hook: large batches skip
-      // its 1 MB / image write (airfe_debug_detector_maps rebuilds it on demand)
-      c->nms_map_valid = B <= 2 || c->force_nms_map;
+      // its 1 MB / image write (airfe_debug_detector_maps rebuilds it on demand; the batched junction scores come from the keep plane, line_tail_dev)
+      c->nms_map_valid = B <= 2;
       launch_nms512_candidates(c->heat, c->nms_map_valid ? c->heat_nms : nullptr, c->nms_mask, B, c->cfg.keypoint_threshold,
                                c->cfg.remove_borders, c->cand, c->cand_cnt, ccap, st);
     } else if (c->cfg.nms_radius > 0) {
@@ -179,37 +173,45 @@ int detect_dev2(airfe_ctx* c, const uint8_t* d_gray, const uint8_t* d_gray1, int
       launch_candidates(c->heat, B, R, R, c->cfg.keypoint_threshold, c->cfg.remove_borders, c->cand, c->cand_cnt, ccap, st);
     }
   }
-  const int nhalf = (d_gray1 && !dst_contig) ? 2 : 1;
-  const int Bh = nhalf == 2 ? Bs : B;                                    // images per destination
-  for (int half = 0; half < nhalf; ++half) {                             // the two feature destinations: one launch each
-    const int b0 = half * Bs;
-    ProfScope ps(c, ST_SELECT, st, 0, (double)Bh * 8192 * 8);
-    launch_select_list(c->cand + (size_t)b0 * ccap, c->cand_cnt + b0, ccap, Bh, R, c->cfg.max_keypoints, cap, half ? d_feat1 : d_feat,
-                       half ? d_n1 : d_n, st);
+  // The two feature destinations of a stereo batch: ONE launch of every kernel below over the 2 Bs images, which pick their destination by image index
+  // (one-destination calls pass no second set).
+  const bool two = d_gray1 != nullptr;
+  const int M = B * cap * 4, Mp = (M + 255) / 256 * 256;
+  {
+    ProfScope ps(c, ST_SELECT, st, 0, (double)B * 8192 * 8);
+    SelectExtra ex;
+    if (two) { ex.feat1 = d_feat1; ex.n_out1 = d_n1; ex.Bs = Bs; }
+    // sparse descriptors: the top-K kernel also writes the four head rows each slot will sample (the gather GEMM's row list; zero for slots k >= n)
+    if (sparse_desc) { ex.desc_idx = c->desc_idx; ex.HC = R / 8; ex.WC = R / 8; }
+    launch_select_list(c->cand, c->cand_cnt, ccap, B, R, c->cfg.max_keypoints, cap, d_feat, d_n, st, &ex);
   }
+  bool sampled = false;
   if (sparse_desc) {
-    const int M = B * cap * 4, Mp = (M + 255) / 256 * 256;
-    for (int half = 0; half < nhalf; ++half)
-      launch_desc_cells(half ? d_feat1 : d_feat, half ? d_n1 : d_n, cap, Bh, half * Bs, R / 8, R / 8, c->desc_idx + (size_t)half * Bs * cap * 4, st);
     if (Mp > M) HIPCHK(c, hipMemsetAsync(c->desc_idx + M, 0, (size_t)(Mp - M) * 4, st));
     GemmArgs g;
     g.X1 = c->aDa; g.ld1 = 256; g.K1 = 256; g.Wp = c->cDb.w; g.bias = c->cDb.b; g.rowidx = c->desc_idx;
     g.M = Mp; g.N = 256; g.cb_total = c->cDb.cbt; g.epi = EPI_STORE_F32; g.out = c->desc; g.ldo = 256;
-    ProfScope ps(c, ST_HEAD_GEMM, st, 2.0 * Mp * 256 * 256, (double)Mp * (512 + 1024));
-    // large batches: the streaming kernel with gathered rows (kernels_gemmr.hip, GATHER) — the tiled 8-wave kernel ran this HBM-bound shape at 2.3 TB/s; the same bits
     g.gr_wgs = c->gemmr_wgs;
-    if (c->desc_gather_stream && Mp >= c->gemmr_min && gemmr_gather_applicable(256, g)) launch_gemmr_gather(c->prec, g, st);
-    else launch_gemm8(c->prec, 256, false, g, st);
+    // large batches: the streaming kernel with gathered rows (kernels_gemmr.hip, GATHER) — the tiled 8-wave kernel ran this HBM-bound shape at 2.3 TB/s; the same bits.
+    // Its SAMPLE form finishes the keypoints from the tile in LDS: no head rows written (1 KB per row) and read back, no sampling launch.
+    const bool stream = c->desc_gather_stream && Mp >= c->gemmr_min && gemmr_gather_applicable(256, g);
+    if (stream && gemmr_gather_sample_applicable(g)) {
+      ProfScope ps(c, ST_HEAD_GEMM, st, 2.0 * Mp * 256 * 256, (double)Mp * 512 + (double)B * c->cfg.max_keypoints * 1036);
+      DescSample ds;
+      ds.feat = d_feat; ds.n = d_n; ds.feat1 = two ? d_feat1 : nullptr; ds.n1 = two ? d_n1 : nullptr; ds.Bs = two ? Bs : B; ds.B = B; ds.cap = cap;
+      ds.HC = R / 8; ds.WC = R / 8; ds.w_scale = (float)w / (float)R; ds.h_scale = (float)h / (float)R; ds.flag = c->sat_flag;
+      launch_gemmr_gather_sample(c->prec, g, ds, st);
+      sampled = true;
+    } else {
+      ProfScope ps(c, ST_HEAD_GEMM, st, 2.0 * Mp * 256 * 256, (double)Mp * (512 + 1024));
+      if (stream) launch_gemmr_gather(c->prec, g, st);
+      else launch_gemm8(c->prec, 256, false, g, st);
+    }
   }
-  for (int half = 0; half < nhalf; ++half) {
-    const int b0 = half * Bs;
-    ProfScope ps(c, ST_SAMPLE, st, 0, (double)Bh * c->cfg.max_keypoints * (4096 + 1036));
-    if (sparse_desc)
-      launch_sample_desc(c->desc + (size_t)b0 * cap * 4 * 256, Bh, R / 8, R / 8, half ? d_feat1 : d_feat, half ? d_n1 : d_n, cap, (float)w / (float)R,
-                         (float)h / (float)R, 1, st, 1, c->sat_flag);
-    else
-      launch_sample_desc(c->desc + (size_t)b0 * (R / 8) * (R / 8) * 256, Bh, R / 8, R / 8, half ? d_feat1 : d_feat, half ? d_n1 : d_n, cap,
-                         (float)w / (float)R, (float)h / (float)R, c->desc_normalised ? 0 : 1, st, 0, c->sat_flag);
+  if (!sampled) {
+    ProfScope ps(c, ST_SAMPLE, st, 0, (double)B * c->cfg.max_keypoints * (4096 + 1036));
+    launch_sample_desc(c->desc, B, R / 8, R / 8, d_feat, d_n, cap, (float)w / (float)R, (float)h / (float)R,
+                       sparse_desc ? 1 : (c->desc_normalised ? 0 : 1), st, sparse_desc ? 1 : 0, c->sat_flag, two ? d_feat1 : nullptr, two ? d_n1 : nullptr, Bs);
   }
   return launch_status(c);
 }
@@ -336,9 +338,13 @@ int line_tail_dev(airfe_ctx* c, int i0, int nb, const float* loi_chw, int h, int
   }
   if ((phase & 2) && nj > 0) {
     ProfScope ps(c, ST_PL_FILTER, st, 0, (double)nj * R * R * 2);
-    if (c->cfg.nms_radius > 0 && !c->nms_map_valid) return fail(c, "line path: the NMS'd score maps of this batch were not kept");
-    const float* hsel = (c->cfg.nms_radius > 0 ? c->heat_nms : c->heat) + (size_t)i0 * R * R;
-    launch_junction_scan(c->jmap, hsel, R, c->cfg.remove_borders, d_junc, capJ, d_njunc, d_jfound, c->d_njunc + 2 * c->Lmax, nj, st);
+    // junction scores = the NMS'd map at the junction pixels.  Where the dense map was not written (radius 4, large batches) the same values come from
+    // the raw scores under the NMS's final keep plane: 32 KB per image instead of 1 MB written for < 1024 single-float reads.
+    const bool from_mask = c->cfg.nms_radius > 0 && !c->nms_map_valid;
+    if (from_mask && c->cfg.nms_radius != 4) return fail(c, "line path: the NMS'd score maps of this batch were not kept");
+    const float* hsel = (c->cfg.nms_radius > 0 && !from_mask ? c->heat_nms : c->heat) + (size_t)i0 * R * R;
+    const unsigned long long* mask = from_mask ? reinterpret_cast<const unsigned long long*>(c->nms_mask) + (size_t)i0 * (R / 8) * (R / 8) : nullptr;
+    launch_junction_scan(c->jmap, hsel, R, c->cfg.remove_borders, d_junc, capJ, d_njunc, d_jfound, c->d_njunc + 2 * c->Lmax, nj, st, mask);
     if (!c->desc_dense_valid) return fail(c, "line path: the dense descriptor map of this batch was not made");
     launch_sample_desc(c->desc + (size_t)i0 * (R / 8) * (R / 8) * 256, nj, R / 8, R / 8, d_junc, d_njunc, capJ, ws, hs,
                        c->desc_normalised ? 0 : 1, st);

@@ -149,7 +149,6 @@ struct airfe_ctx {
   DevBlock po_gather;            // airfe_track_pose_opt_batch_dev: PnP results, seeds and gathered constraints
   bool outlier_rejection = false;                                       // airfe_set_outlier_rejection: F-RANSAC behind the temporal match of track_frame / stereo_keyframe_tracked
   bool nms_map_valid = true;     // heat_nms holds the last batch's NMS'd maps (large batches skip writing them)
-  bool force_nms_map = false;    // the batched PLNet path reads junction scores from them: written at every batch size while set
   int Lmax = 1;                  // images the line-path arena holds (= Dmax)
   bool desc_normalised = false;  // dense descriptor map currently holds F.normalize'd rows (only after the inspection hook)
   int gemm_small_max = 4096, gemm8_min = 16000, gemmr_min = 8192, gemmr_wgs = 256;   // GemmArgs::small_max / g8_min / gr_min / gr_wgs (airfe_tuning::gemm_small_max_m, gemm8_min_m, gemmr_min_m, gemmr_wgs)

@@ -107,7 +107,7 @@ void launch_conv128r(int prec, const ConvArgs& a, hipStream_t st);
 // cv::resize(INTER_LINEAR, 8-bit fixed point) + /255 -> fp32 [B][RH+2][RW+2] interior
 void launch_preprocess(const uint8_t* src, int B, int h, int w, int stride, size_t img_stride,
                        const int* xtab /*[RW][4]: x0,x1,a0,a1*/, const int* ytab /*[RH][4]*/, const float* lut /*[256]*/,
-                       float* out, int RH, int RW, hipStream_t st);
+                       float* out, int RH, int RW, hipStream_t st, const uint8_t* src1 = nullptr, int n0 = 0);   // src1: images n0 .. B-1 of the launch are images 0 .. of src1
 
 // cv::remap(INTER_LINEAR, BORDER_CONSTANT 0) of B 8-bit images through one pair of CV_32FC1 maps [h][w] (Camera::UndistortImage, camera.cc:161-182)
 void launch_remap_linear(const uint8_t* src, int B, int h, int w, int stride, size_t img_stride, const float* mapx, const float* mapy,
@@ -122,7 +122,8 @@ void launch_l2norm256(float* d, int rows, hipStream_t st);
 void launch_simple_nms(const float* heat, float* out, float* tmp, int B, int H, int W, int radius, hipStream_t st);
 // simple_nms(4) on the 512 x 512 map as three register-resident launches (kernels_nms512.hip): out = NMS'd map (may be nullptr: no dense
 // map), and the detect_point candidates (score >= thr inside the border box) are appended to cand [B][cand_cap] (49-bit keys) /
-// cand_cnt [B]; planes = 2 x [B][64][64] 64-bit words
+// cand_cnt [B]; planes = 2 x [B][64][64] 64-bit words.  The FIRST plane ends up holding the final keep mask (bit set = the pixel survives; word
+// [image][band][lane], byte = row 8 band + r, bit = column 8 lane + j): what the dense map's non-zero pattern would be, at 32 KB per image
 void launch_nms512_candidates(const float* heat, float* out, void* planes, int B, float thr, int border, unsigned long long* cand,
                               int* cand_cnt, int cand_cap, hipStream_t st);
 // candidates from a finished map (NMS off, or radius != 4 through the multi-pass launch_simple_nms)
@@ -132,16 +133,32 @@ void launch_candidates(const float* heat, int B, int H, int W, float thr, int bo
 void launch_candidates_nms3(const float* heat, int B, int H, int W, float thr, unsigned long long* cand, int* cand_cnt, int cand_cap, hipStream_t st);
 // exact top-K (score desc, raster asc) / raster order when count <= K, on the candidate list
 //   feat [B][cap][259] rows: score,x,y written (x,y in 512-space, unscaled); n_out [B]
+// feat1 != nullptr: two destinations in one launch — images b >= Bs go to rows / counts b - Bs of feat1 / n_out1.
+// desc_idx != nullptr: also the descriptor head's gather rows of every slot, desc_idx[(b * cap + k) * 4 + tap] = b * HC * WC + cell (k >= n: 0); cap <= 1024
+struct SelectExtra {
+  float* feat1 = nullptr; int* n_out1 = nullptr; int Bs = 0;
+  int* desc_idx = nullptr; int HC = 0, WC = 0;
+};
 void launch_select_list(const unsigned long long* cand, const int* cand_cnt, int cand_cap, int B, int W, int topk, int cap,
-                        float* feat, int* n_out, hipStream_t st);
+                        float* feat, int* n_out, hipStream_t st, const SelectExtra* ex = nullptr);
 // bilinear descriptor sampling + L2 norm (plnet.cpp:369-417), then x,y *= (w_scale,h_scale)
 //   desc fp32 [B][HC][WC][256]
 // flag (may be NULL): flag[1] = 1 when a sampled descriptor is not finite (2-byte activations upstream left their range)
 void launch_sample_desc(const float* desc, int B, int HC, int WC, float* feat, const int* n, int cap,
-                        float w_scale, float h_scale, int normalise, hipStream_t st, int compact = 0, int* flag = nullptr);
-// idx[(b * cap + k) * 4 + tap] = row (b0 + b) * HC * WC + cell of the dense head input that keypoint k of image b samples (k >= n[b]: 0):
-// the row list of the descriptor head's gather GEMM; compact = 1 in launch_sample_desc reads that GEMM's output
-void launch_desc_cells(const float* feat, const int* n, int cap, int B, int b0, int HC, int WC, int* idx, hipStream_t st);
+                        float w_scale, float h_scale, int normalise, hipStream_t st, int compact = 0, int* flag = nullptr,
+                        float* feat1 = nullptr, const int* n1 = nullptr, int Bs = 0);       // feat1: images b >= Bs of the launch write feat1 / read n1 at b - Bs
+// Descriptor sampling inside the gather GEMM (launch_gemmr_gather): the rows are (b * cap + k) * 4 + tap, a 32-row tile is eight keypoints, and
+// the workgroup finishes them from the tile's fp32 values in LDS instead of storing the head rows (compact sample_desc's results, same bits)
+struct DescSample {
+  float* feat = nullptr; float* feat1 = nullptr;     // [Bs][cap][259] / [B - Bs][cap][259] (feat1 == nullptr: one destination, Bs = B)
+  const int* n = nullptr; const int* n1 = nullptr;
+  int Bs = 0, B = 0, cap = 0, HC = 0, WC = 0;
+  float w_scale = 1.f, h_scale = 1.f;
+  int* flag = nullptr;                               // flag[1] = 1 on a non-finite descriptor
+  float sx = 0.f, bx = 0.f, sy = 0.f, by = 0.f;      // (the launcher's: desc_grid_coeffs of HC, WC)
+};
+bool gemmr_gather_sample_applicable(const GemmArgs& a);      // (on top of gemmr_gather_applicable: the per-keypoint list fits behind the ring too)
+void launch_gemmr_gather_sample(int prec, const GemmArgs& a, const DescSample& ds, hipStream_t st);
 
 // ---- LightGlue ------------------------------------------------------------------------------
 struct LgPrepArgs {
@@ -229,8 +246,10 @@ void launch_line_filter(const float* la, const float* sc, const int* counts, int
                         int line_cap, int B, hipStream_t st);
 void launch_zero16(void* p, size_t bytes, hipStream_t st);        // bytes % 16 == 0, 16-byte aligned
 // jmap / heat [B][R*R], feat [B][cap][259], n_kept / n_found [B], wg_counts [B][64] scratch
+// mask != nullptr (R = 512): heat is the RAW score map and mask the final keep plane of launch_nms512_candidates ([image][band][lane] 64-bit words):
+// a junction's score is mask bit ? heat : 0 — the value of the dense NMS'd map
 void launch_junction_scan(const unsigned char* jmap, const float* heat, int R, int border, float* feat, int cap, int* n_kept, int* n_found,
-                          int* wg_counts, int B, hipStream_t st);
+                          int* wg_counts, int B, hipStream_t st, const unsigned long long* mask = nullptr);
 
 // ---- fp32 correctness path (kernels_f32.hip; cfg.precision = 2): fp32 storage, f32-input MFMA, plain kernels
 struct GemmF32Args {

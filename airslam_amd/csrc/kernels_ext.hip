@@ -1057,12 +1057,13 @@ __global__ __launch_bounds__(256) void junction_count_kernel(const unsigned char
 
 __global__ __launch_bounds__(256) void junction_emit_kernel(const unsigned char* __restrict__ jmap, const float* __restrict__ heat, int R, int border,
                                                             float* __restrict__ feat, int cap, int* __restrict__ n_kept, int* __restrict__ n_found,
-                                                            const int* __restrict__ wg_counts) {
+                                                            const int* __restrict__ wg_counts, const unsigned long long* __restrict__ mask) {
   __shared__ int wsum[4];
   const int N = R * R, per_wg = (N + JS_WGS - 1) / JS_WGS, per = (per_wg + 255) / 256;
   {
     const size_t img = blockIdx.y;
     jmap += img * N; heat += img * N; feat += img * cap * 259; wg_counts += img * JS_WGS;
+    if (mask) mask += img * (size_t)(R / 8) * (R / 8);
     n_kept += img; n_found += img;
   }
   border = max(border, 0);
@@ -1090,7 +1091,8 @@ __global__ __launch_bounds__(256) void junction_emit_kernel(const unsigned char*
       const int i = i0 + k, y = i / R, x = i - y * R;
       if (off < cap) {
         float* f = feat + (size_t)off * 259;
-        f[0] = heat[i];
+        // mask: the NMS keep plane (word = [row band y / 8][column group x / 8], bit = 8 (y % 8) + x % 8) over the raw scores = the dense NMS'd map's value
+        f[0] = (!mask || ((mask[(size_t)(y >> 3) * (R / 8) + (x >> 3)] >> (8 * (y & 7) + (x & 7))) & 1ull)) ? heat[i] : 0.f;
         f[1] = (float)x;
         f[2] = (float)y;
       }
@@ -1102,9 +1104,9 @@ __global__ __launch_bounds__(256) void junction_emit_kernel(const unsigned char*
 
 // jmap / heat [B][R * R], feat [B][cap][259], n_kept / n_found [B], wg_counts [B][64] scratch
 void launch_junction_scan(const unsigned char* jmap, const float* heat, int R, int border, float* feat, int cap, int* n_kept, int* n_found,
-                          int* wg_counts, int B, hipStream_t st) {
+                          int* wg_counts, int B, hipStream_t st, const unsigned long long* mask) {
   hipLaunchKernelGGL(junction_count_kernel, dim3(JS_WGS, B), dim3(256), 0, st, jmap, R, border, wg_counts);
-  hipLaunchKernelGGL(junction_emit_kernel, dim3(JS_WGS, B), dim3(256), 0, st, jmap, heat, R, border, feat, cap, n_kept, n_found, wg_counts);
+  hipLaunchKernelGGL(junction_emit_kernel, dim3(JS_WGS, B), dim3(256), 0, st, jmap, heat, R, border, feat, cap, n_kept, n_found, wg_counts, mask);
 }
 
 // =============================================================================== SuperGlue: keypoint encoder

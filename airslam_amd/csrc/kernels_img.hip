@@ -5,6 +5,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "desc_sample.h"
 
 namespace airfe {
 
@@ -71,13 +72,15 @@ __global__ __launch_bounds__(256) void preprocess_rows_kernel(const uint8_t* __r
 #define AIRFE_PRE_R 4
 #endif
 constexpr int PRE_R = AIRFE_PRE_R, PRE_R_MAX_W = 2048;
-__global__ __launch_bounds__(256) void preprocess_rows4_kernel(const uint8_t* __restrict__ src, int stride, size_t img_stride, int w,
+// src1 != nullptr: two sources in one launch — images b >= n0 of the launch are images b - n0 of src1 (a chunk that straddles the stereo sides)
+__global__ __launch_bounds__(256) void preprocess_rows4_kernel(const uint8_t* __restrict__ src, const uint8_t* __restrict__ src1, int n0, int stride,
+                                                               size_t img_stride, int w,
                                                                const int4* __restrict__ xtab, const int4* __restrict__ ytab,
                                                                const float* __restrict__ lut, float* __restrict__ out, int RH, int RW) {
   __shared__ uint32_t sm[PRE_R][2][PRE_R_MAX_W / 4];
   __shared__ float slut[256];
   const int y0 = blockIdx.x * PRE_R, b = blockIdx.y, t = threadIdx.x;
-  const uint8_t* s = src + (size_t)b * img_stride;
+  const uint8_t* s = (src1 && b >= n0) ? src1 + (size_t)(b - n0) * img_stride : src + (size_t)b * img_stride;
   int4 yt[PRE_R];
 #pragma unroll
   for (int r = 0; r < PRE_R; ++r) yt[r] = ytab[y0 + r];
@@ -146,12 +149,19 @@ void launch_remap_linear(const uint8_t* src, int B, int h, int w, int stride, si
 }
 
 void launch_preprocess(const uint8_t* src, int B, int h, int w, int stride, size_t img_stride, const int* xtab,
-                       const int* ytab, const float* lut, float* out, int RH, int RW, hipStream_t st) {
+                       const int* ytab, const float* lut, float* out, int RH, int RW, hipStream_t st, const uint8_t* src1, int n0) {
   (void)h;
-  const bool aligned = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride | (uintptr_t)img_stride) & 3) == 0;
+  if (src1 && n0 >= B) src1 = nullptr;
+  if (src1 && n0 <= 0) { src = src1; src1 = nullptr; }                 // (every image from the second source)
+  const bool aligned = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(src1) | (uintptr_t)stride | (uintptr_t)img_stride) & 3) == 0;
   if (aligned && w <= PRE_R_MAX_W && RH % PRE_R == 0) {
-    hipLaunchKernelGGL(preprocess_rows4_kernel, dim3(RH / PRE_R, B), dim3(256), 0, st, src, stride, img_stride, w,
+    hipLaunchKernelGGL(preprocess_rows4_kernel, dim3(RH / PRE_R, B), dim3(256), 0, st, src, src1, n0, stride, img_stride, w,
                        reinterpret_cast<const int4*>(xtab), reinterpret_cast<const int4*>(ytab), lut, out, RH, RW);
+    return;
+  }
+  if (src1) {        // the one-row and per-pixel forms take one source: a launch per source
+    launch_preprocess(src, n0, h, w, stride, img_stride, xtab, ytab, lut, out, RH, RW, st, nullptr, 0);
+    launch_preprocess(src1, B - n0, h, w, stride, img_stride, xtab, ytab, lut, out + (size_t)n0 * (RH + 2) * (RW + 2), RH, RW, st, nullptr, 0);
     return;
   }
   if (aligned && w <= PRE_MAX_W) {
@@ -199,13 +209,6 @@ __global__ void softmax_d2s_kernel(const float* __restrict__ logits, int ldl, fl
 void launch_softmax_d2s(const float* logits, int ldl, float* heat, int B, int HC, int WC, hipStream_t st) {
   const int ncell = B * HC * WC;
   hipLaunchKernelGGL(softmax_d2s_kernel, dim3((ncell + 127) / 128), dim3(128), 0, st, logits, ldl, heat, ncell, HC, WC);
-}
-
-// F.normalize(dim=channel) of one 256-channel row spread over a wave, 4 channels per lane
-__device__ __forceinline__ void l2norm_lane4(float4& v) {
-  const float ss = wave_sum(v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w);
-  const float inv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
-  v.x *= inv; v.y *= inv; v.z *= inv; v.w *= inv;
 }
 
 // dense form, one wave per row (inspection hook only; the product normalises lazily inside sample_desc_kernel)
@@ -284,57 +287,24 @@ void launch_simple_nms(const float* heat, float* out, float* tmp, int B, int H, 
 // extract_descriptors (src/plnet.cpp:369-417 == src/super_point.cpp:224-272) on a dense NHWC fp32 map,
 // one wave per keypoint (lane = 4 channels, 1 KiB coalesced row reads), then the final rescale
 // (plnet.cpp:574-575).  _rn intrinsics keep hipcc from contracting the reference's mul/add pairs.
-__device__ __forceinline__ int clipi(int v, int mx) { return v < 0 ? 0 : min(v, mx - 1); }
+// (the taps and the per-keypoint finish: desc_sample.h, shared with the top-K kernel and the fused gather GEMM)
 
-// the four taps of a keypoint (grid_sample bilinear, align_corners semantics of extract_descriptors) and their weights
-struct DescTaps { int c[4]; float w[4]; };       // cell = iy * WC + ix of nw, ne, sw, se
-__device__ __forceinline__ DescTaps desc_taps(float x, float y, float sx, float bx, float sy, float by, int HC, int WC) {
-  float kx = __fadd_rn(__fmul_rn(x, sx), bx), ky = __fadd_rn(__fmul_rn(y, sy), by);
-  kx = __fmul_rn(__fadd_rn(kx, 1.0f), 0.5f);
-  ky = __fmul_rn(__fadd_rn(ky, 1.0f), 0.5f);
-  const float ix = __fmul_rn(kx, (float)(WC - 1)), iy = __fmul_rn(ky, (float)(HC - 1));
-  const int ix_nw = clipi((int)floorf(ix), WC), iy_nw = clipi((int)floorf(iy), HC);
-  const int ix_ne = clipi(ix_nw + 1, WC), iy_ne = clipi(iy_nw, HC);
-  const int ix_sw = clipi(ix_nw, WC), iy_sw = clipi(iy_nw + 1, HC);
-  const int ix_se = clipi(ix_nw + 1, WC), iy_se = clipi(iy_nw + 1, HC);
-  DescTaps t;
-  t.w[0] = __fmul_rn(__fsub_rn((float)ix_se, ix), __fsub_rn((float)iy_se, iy));
-  t.w[1] = __fmul_rn(__fsub_rn(ix, (float)ix_sw), __fsub_rn((float)iy_sw, iy));
-  t.w[2] = __fmul_rn(__fsub_rn((float)ix_ne, ix), __fsub_rn(iy, (float)iy_ne));
-  t.w[3] = __fmul_rn(__fsub_rn(ix, (float)ix_nw), __fsub_rn(iy, (float)iy_nw));
-  t.c[0] = iy_nw * WC + ix_nw; t.c[1] = iy_ne * WC + ix_ne; t.c[2] = iy_sw * WC + ix_sw; t.c[3] = iy_se * WC + ix_se;
-  return t;
-}
-
-// rows of the dense head input that the keypoints of a batch will sample: idx[(b * cap + k) * 4 + tap] = (b0 + b) * HC * WC + cell
-// (slots k >= n[b]: row 0, computed and never read).  The descriptor head then runs as a GATHER GEMM over these rows only.
-__global__ void desc_cells_kernel(const float* __restrict__ feat, const int* __restrict__ n, int cap, int B, int b0, int HC, int WC,
-                                  float sx, float bx, float sy, float by, int* __restrict__ idx) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * cap) return;
-  const int b = i / cap, k = i - b * cap;
-  int4 o = make_int4(0, 0, 0, 0);
-  if (k < n[b]) {
-    const float* f = feat + (size_t)i * 259;
-    const DescTaps t = desc_taps(f[1], f[2], sx, bx, sy, by, HC, WC);
-    const int base = (b0 + b) * HC * WC;
-    o = make_int4(base + t.c[0], base + t.c[1], base + t.c[2], base + t.c[3]);
-  }
-  reinterpret_cast<int4*>(idx)[i] = o;
-}
 
 // compact != 0: `desc` holds the four head rows of keypoint (b, k) at rows (b * cap + k) * 4 + tap (the gather GEMM's output)
-// instead of the dense [B][HC][WC][256] map — same values, same operations from there on
+// instead of the dense [B][HC][WC][256] map — same values, same operations from there on.
+// feat1 != nullptr: two destinations in one launch — images b >= Bs write rows of feat1 / read counts n1 at image b - Bs.
 __global__ __launch_bounds__(256) void sample_desc_kernel(const float* __restrict__ desc, int HC, int WC,
-                                                          float* __restrict__ feat, const int* __restrict__ n, int cap,
+                                                          float* __restrict__ feat, const int* __restrict__ n, float* __restrict__ feat1,
+                                                          const int* __restrict__ n1, int Bs, int cap,
                                                           float sx, float bx, float sy, float by, float w_scale,
                                                           float h_scale, int normalise, int compact, int* __restrict__ flag) {
   const int b = blockIdx.y, k = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (k >= n[b]) return;
-  float* f = feat + ((size_t)b * cap + k) * 259;
+  int bl = b;
+  if (feat1 && b >= Bs) { feat = feat1; n = n1; bl = b - Bs; }
+  if (k >= n[bl]) return;
+  float* f = feat + ((size_t)bl * cap + k) * 259;
   const float x = f[1], y = f[2];
   const DescTaps tp = desc_taps(x, y, sx, bx, sy, by, HC, WC);
-  const float nw = tp.w[0], ne = tp.w[1], sw = tp.w[2], se = tp.w[3];
   float4 a0, a1, a2, a3;
   if (compact) {
     const float* d = desc + ((size_t)b * cap + k) * 4 * 256 + lane * 4;
@@ -349,55 +319,15 @@ __global__ __launch_bounds__(256) void sample_desc_kernel(const float* __restric
     a2 = *reinterpret_cast<const float4*>(d + (size_t)tp.c[2] * 256);
     a3 = *reinterpret_cast<const float4*>(d + (size_t)tp.c[3] * 256);
   }
-  if (normalise) {       // F.normalize(dim=channel) of the four cells, operation for operation as l2norm256_kernel does it
-    l2norm_lane4(a0);
-    l2norm_lane4(a1);
-    l2norm_lane4(a2);
-    l2norm_lane4(a3);
-  }
-  float v[4];
-  const float n0[4] = {a0.x, a0.y, a0.z, a0.w}, n1[4] = {a1.x, a1.y, a1.z, a1.w};
-  const float n2[4] = {a2.x, a2.y, a2.z, a2.w}, n3[4] = {a3.x, a3.y, a3.z, a3.w};
-  float ss = 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    float t = __fmul_rn(n0[j], nw);
-    t = __fadd_rn(t, __fmul_rn(n1[j], ne));
-    t = __fadd_rn(t, __fmul_rn(n2[j], sw));
-    t = __fadd_rn(t, __fmul_rn(n3[j], se));
-    v[j] = t;
-    ss = __fadd_rn(ss, __fmul_rn(t, t));
-  }
-  ss = wave_sum(ss);
-  const float nrm = sqrtf(ss);
-  if (flag && lane == 0 && !(ss <= FLT_MAX)) *reinterpret_cast<volatile int*>(flag + 1) = 1;      // inf / NaN descriptor: the detector's 2-byte activations overflowed (airfe.h, "activation range")
-  // Eigen (>= 3.3) colwise().normalize(): `if (squaredNorm() > 0) v /= sqrt(squaredNorm())` — a zero column stays zero, no NaN
-#pragma unroll
-  for (int j = 0; j < 4; ++j) f[3 + lane * 4 + j] = (ss > 0.f) ? v[j] / nrm : v[j];
-  if (lane == 0) {
-    f[1] = __fmul_rn(x, w_scale);
-    f[2] = __fmul_rn(y, h_scale);
-  }
-}
-
-static void desc_grid_coeffs(int HC, int WC, float& sx, float& bx, float& sy, float& by) {
-  const int s = 8;
-  sx = (float)(2.0 / (WC * s - s / 2 - 0.5)); bx = (float)((1 - s) / (WC * s - s / 2 - 0.5) - 1);
-  sy = (float)(2.0 / (HC * s - s / 2 - 0.5)); by = (float)((1 - s) / (HC * s - s / 2 - 0.5) - 1);
+  sample_desc_row(a0, a1, a2, a3, tp, x, y, f, lane, normalise, w_scale, h_scale, flag);
 }
 
 void launch_sample_desc(const float* desc, int B, int HC, int WC, float* feat, const int* n, int cap, float w_scale,
-                        float h_scale, int normalise, hipStream_t st, int compact, int* flag) {
+                        float h_scale, int normalise, hipStream_t st, int compact, int* flag, float* feat1, const int* n1, int Bs) {
   float sx, bx, sy, by;
   desc_grid_coeffs(HC, WC, sx, bx, sy, by);
-  hipLaunchKernelGGL(sample_desc_kernel, dim3((cap + 3) / 4, B), dim3(256), 0, st, desc, HC, WC, feat, n, cap, sx, bx,
+  hipLaunchKernelGGL(sample_desc_kernel, dim3((cap + 3) / 4, B), dim3(256), 0, st, desc, HC, WC, feat, n, feat1, n1, Bs, cap, sx, bx,
                      sy, by, w_scale, h_scale, normalise, compact, flag);
-}
-
-void launch_desc_cells(const float* feat, const int* n, int cap, int B, int b0, int HC, int WC, int* idx, hipStream_t st) {
-  float sx, bx, sy, by;
-  desc_grid_coeffs(HC, WC, sx, bx, sy, by);
-  hipLaunchKernelGGL(desc_cells_kernel, dim3((B * cap + 255) / 256), dim3(256), 0, st, feat, n, cap, B, b0, HC, WC, sx, bx, sy, by, idx);
 }
 
 }  // namespace airfe

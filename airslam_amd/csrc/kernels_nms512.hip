@@ -90,7 +90,7 @@ __device__ __forceinline__ U192 or3(U192 x, U192 y) { return U192{x.a | y.a, x.b
 
 //   MODE 0: Mout = (S == pool S)
 //   MODE 1: D = dilate(Min); ss = D ? 0 : S; Mout = Min | (!D && ss == pool ss)
-//   MODE 2: MODE 1, then the detect_point candidate list of M ? S : 0 (and, if out != nullptr, that dense map)
+//   MODE 2: MODE 1, then the detect_point candidate list of M ? S : 0 (and, if out != nullptr, that dense map; Mout = the final mask either way)
 template <int MODE>
 __global__ __launch_bounds__(64) void nms512_kernel(const float* __restrict__ heat, const u64* __restrict__ Min, u64* __restrict__ Mout,
                                                     float* __restrict__ out, int B, float thr, int border, u64* __restrict__ cand,
@@ -179,10 +179,8 @@ __global__ __launch_bounds__(64) void nms512_kernel(const float* __restrict__ he
   }
   u64 M = ((u64)eq[1] << 32) | eq[0];
   if (MODE >= 1) M = Mc | (M & ~(((u64)D[2] << 32) | D[1]));           // rows y0 .. y0+7 of D are its bytes 4 .. 11
-  if (MODE <= 1) {
-    Mout[((size_t)b * NBAND + band) * 64 + lane] = M;
-    return;
-  }
+  Mout[((size_t)b * NBAND + band) * 64 + lane] = M;                    // (MODE 2: the final keep mask — what a sparse reader needs of the dense map)
+  if (MODE <= 1) return;
 
   // ---- MODE 2: M ? S : 0 -> candidates (threshold + border box), one global atomic per wave and round
   const size_t img = (size_t)b * NR * NR;
@@ -237,7 +235,7 @@ __global__ __launch_bounds__(64) void nms512_kernel(const float* __restrict__ he
   }
 }
 
-// planes: 2 x [B][64][64] 64-bit words of scratch
+// planes: 2 x [B][64][64] 64-bit words of scratch; the last launch writes the final mask over the first plane (read only by the second launch, which is done)
 void launch_nms512_candidates(const float* heat, float* out, void* planes, int B, float thr, int border, u64* cand, int* cand_cnt,
                               int cand_cap, hipStream_t st) {
   u64* P0 = reinterpret_cast<u64*>(planes);
@@ -246,7 +244,7 @@ void launch_nms512_candidates(const float* heat, float* out, void* planes, int B
   const dim3 grid(B * NBAND), block(64);
   hipLaunchKernelGGL(nms512_kernel<0>, grid, block, 0, st, heat, (const u64*)nullptr, P0, (float*)nullptr, B, thr, border, cand, cand_cnt, cand_cap);
   hipLaunchKernelGGL(nms512_kernel<1>, grid, block, 0, st, heat, (const u64*)P0, P1, (float*)nullptr, B, thr, border, cand, cand_cnt, cand_cap);
-  hipLaunchKernelGGL(nms512_kernel<2>, grid, block, 0, st, heat, (const u64*)P1, (u64*)nullptr, out, B, thr, border, cand, cand_cnt, cand_cap);
+  hipLaunchKernelGGL(nms512_kernel<2>, grid, block, 0, st, heat, (const u64*)P1, P0, out, B, thr, border, cand, cand_cnt, cand_cap);
 }
 
 }  // namespace airfe

@@ -3,6 +3,7 @@
 // for the reference's radius 4, kernels_img.hip for any other radius.)
 #include "common.h"
 #include "kernels.h"
+#include "desc_sample.h"
 
 namespace airfe {
 
@@ -106,9 +107,11 @@ void launch_candidates(const float* heat, int B, int H, int W, float thr, int bo
 // count <= K : all candidates in RASTER order (unsorted by score)       (plnet.cpp:348-353)
 // count >  K : top K by key descending = score descending, ties by ascending raster index
 // One 1024-thread workgroup per image: MSB radix select on the 49-bit key, then a bitonic sort of <= 1024 survivors.
+// ex.feat1: the images b >= ex.Bs write the second destination (one launch over both sides of a stereo batch).  ex.desc_idx (cap <= 1024): the
+// descriptor head's gather rows of every slot too — desc_taps on the very x, y stored here, so the sampling kernels find the cells they compute themselves.
 __global__ __launch_bounds__(1024) void select_list_kernel(const u64* __restrict__ cand, const int* __restrict__ cand_cnt,
                                                            int cand_cap, int W, int topk, int cap, float* __restrict__ feat,
-                                                           int* __restrict__ n_out) {
+                                                           int* __restrict__ n_out, SelectExtra ex, float sx, float bx, float sy, float by) {
   __shared__ unsigned hist[2048];
   __shared__ u64 sk[1024];
   __shared__ unsigned wsum[16];
@@ -195,6 +198,9 @@ __global__ __launch_bounds__(1024) void select_list_kernel(const u64* __restrict
       __syncthreads();
     }
   }
+  int bl = b;                                                          // image index within its destination
+  if (ex.feat1 && b >= ex.Bs) { feat = ex.feat1; n_out = ex.n_out1; bl = b - ex.Bs; }
+  int4 rows = make_int4(0, 0, 0, 0);
   if (tid < n) {
     const u64 e = sk[tid];
     int idx;
@@ -202,17 +208,26 @@ __global__ __launch_bounds__(1024) void select_list_kernel(const u64* __restrict
     if (take_all) { idx = (int)(e >> 32); sb = (unsigned)(e & 0x7FFFFFFFull); }
     else { const u64 k = ~e; idx = 0x3FFFF - (int)(k & 0x3FFFFull); sb = (unsigned)((k >> 18) & 0x7FFFFFFFull); }
     const int y = idx / W, x = idx - y * W;
-    float* f = feat + ((size_t)b * cap + tid) * 259;
+    float* f = feat + ((size_t)bl * cap + tid) * 259;
     f[0] = __uint_as_float(sb);
     f[1] = (float)x;
     f[2] = (float)y;
+    if (ex.desc_idx) {
+      const DescTaps t = desc_taps((float)x, (float)y, sx, bx, sy, by, ex.HC, ex.WC);
+      const int base = b * ex.HC * ex.WC;
+      rows = make_int4(base + t.c[0], base + t.c[1], base + t.c[2], base + t.c[3]);
+    }
   }
-  if (tid == 0) n_out[b] = n;
+  if (ex.desc_idx && tid < cap) reinterpret_cast<int4*>(ex.desc_idx)[(size_t)b * cap + tid] = rows;      // (slots k >= n: row 0, computed and never read)
+  if (tid == 0) n_out[bl] = n;
 }
 
 void launch_select_list(const u64* cand, const int* cand_cnt, int cand_cap, int B, int W, int topk, int cap, float* feat,
-                        int* n_out, hipStream_t st) {
-  hipLaunchKernelGGL(select_list_kernel, dim3(B), dim3(1024), 0, st, cand, cand_cnt, cand_cap, W, topk, cap, feat, n_out);
+                        int* n_out, hipStream_t st, const SelectExtra* ex) {
+  const SelectExtra e = ex ? *ex : SelectExtra();
+  float sx = 0.f, bx = 0.f, sy = 0.f, by = 0.f;
+  if (e.desc_idx) desc_grid_coeffs(e.HC, e.WC, sx, bx, sy, by);
+  hipLaunchKernelGGL(select_list_kernel, dim3(B), dim3(1024), 0, st, cand, cand_cnt, cand_cap, W, topk, cap, feat, n_out, e, sx, bx, sy, by);
 }
 
 }  // namespace airfe
