@@ -82,6 +82,12 @@ class DebugLgBlockArgs(C.Structure):
                 + [("Np", C.c_int)] + [(n, C.c_void_p) for n in ("q", "k", "vt")] + [("rows_past", C.c_int * 5)])
 
 
+class DebugConvArgs(C.Structure):
+    """airfe_debug_conv_args (include/airfe_debug.h)"""
+    _fields_ = ([(n, C.c_void_p) for n in ("x", "img", "w1a", "b1a", "w", "b")] + [(n, C.c_int) for n in ("cin", "cout", "B", "H", "W", "pool", "out_pad", "relu", "wgs")]
+                + [("y_words", C.c_size_t), ("y_raw", C.c_void_p)])
+
+
 class DebugLgPrepareArgs(C.Structure):
     """airfe_debug_lg_prepare_args (include/airfe_debug.h)"""
     _fields_ = ([(n, C.c_int) for n in ("prec", "B", "cap", "ld", "kp_off", "normalize")] + [(n, C.c_float) for n in ("cx", "cy", "linv")]
@@ -246,6 +252,7 @@ SIGNATURES = {
     "airfe_debug_preprocess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "airfe_debug_conv3x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_int, C.c_int, C.c_void_p]),
+    "airfe_debug_conv": (C.c_int, [C.c_void_p, C.POINTER(DebugConvArgs)]),
     "airfe_debug_trace": (C.c_int, [C.c_void_p, C.c_int]),
     "airfe_debug_trace_stop": (C.c_int, [C.c_void_p, C.c_int]),
     "airfe_debug_trace_buffer": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),

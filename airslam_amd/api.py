@@ -493,6 +493,29 @@ class Context:
                                               int(pool), y.ctypes.data), "airfe_debug_conv3x3")
         return y
 
+    def debug_conv(self, w, b, prec, x=None, img=None, w1a=None, b1a=None, pool=False, out_pad=1, relu=True, wgs=256):
+        """airfe_debug_conv (include/airfe_debug.h): one 3x3 convolution launch on host tensors, x [B, cin, H, W] (plain form) or img [B, H, W] with w1a [64, 9] and
+        b1a [64] (fused conv1a -> conv1b).  prec names the context's 2-byte type (the words are converted with it).  Returns dict: raw = the device buffer's words
+        [B, Ho + 2 p, Wo + 2 p, cout] (uint16), guard_lo / guard_hi = the words before and behind it, y = its interior as float32 [B, cout, Ho, Wo]."""
+        f32 = lambda t: None if t is None else np.ascontiguousarray(t, np.float32)
+        x, img, w1a, b1a, w, b = map(f32, (x, img, w1a, b1a, w, b))
+        src = x if x is not None else img
+        bb, hh, ww = src.shape[0], src.shape[-2], src.shape[-1]
+        cout, cin = w.shape[0], w.shape[1]
+        p = int(out_pad)
+        ho, wo = (hh // 2, ww // 2) if pool else (hh, ww)
+        guard = (wo + 2 * p) * cout
+        words = bb * (ho + 2 * p) * guard
+        raw = np.zeros(words + 2 * guard, np.uint16)
+        ptr = lambda t: None if t is None else t.ctypes.data
+        a = _lib.DebugConvArgs(x=ptr(x), img=ptr(img), w1a=ptr(w1a), b1a=ptr(b1a), w=ptr(w), b=ptr(b), cin=cin, cout=cout, B=bb, H=hh, W=ww, pool=int(pool), out_pad=p,
+                               relu=int(relu), wgs=int(wgs), y_words=raw.size, y_raw=ptr(raw))
+        self._chk(self._l.airfe_debug_conv(self._h, C.byref(a)), "airfe_debug_conv")
+        buf = raw[guard:guard + words].reshape(bb, ho + 2 * p, wo + 2 * p, cout)
+        inner = np.ascontiguousarray(buf[:, p:p + ho, p:p + wo, :])
+        y = inner.view(np.float16).astype(np.float32) if prec == 1 else (inner.astype(np.uint32) << 16).view(np.float32)
+        return {"raw": buf, "guard_lo": raw[:guard], "guard_hi": raw[guard + words:], "y": np.ascontiguousarray(y.transpose(0, 3, 1, 2))}
+
     def debug_gemm(self, x, w, b, relu=False):
         x = np.ascontiguousarray(x, np.float32); w = np.ascontiguousarray(w, np.float32); b = np.ascontiguousarray(b, np.float32)
         m, k = x.shape

@@ -9,6 +9,24 @@ struct DbgTmp {                                  // device allocations of one ho
   ~DbgTmp() { for (void* p : h.allocs) (void)hipFree(p); }
 };
 
+// the conv hooks' staging: NCHW fp32 -> the arena's NHWC 2-byte layout with its zero border; [cout][cin][3][3] fp32 -> the packed slabs
+static std::vector<uint16_t> dbg_conv_x(const float* x, int B, int cin, int H, int W, int prec) {
+  std::vector<uint16_t> xin((size_t)B * (H + 2) * (W + 2) * cin, 0);
+  for (int bb = 0; bb < B; ++bb)
+    for (int ci = 0; ci < cin; ++ci)
+      for (int yy = 0; yy < H; ++yy)
+        for (int xx = 0; xx < W; ++xx)
+          xin[(((size_t)bb * (H + 2) + yy + 1) * (W + 2) + xx + 1) * cin + ci] = cvt2(x[(((size_t)bb * cin + ci) * H + yy) * W + xx], prec);
+  return xin;
+}
+static std::vector<uint16_t> dbg_conv_slabs(const float* w, int cin, int cout, int prec) {
+  const int nci = cin / 64;
+  return pack_slabs(cout / 64, 9 * nci, prec, [&](int feat, int s, int k) {
+    const int tap = s / nci, cc = s % nci, ci = cc * 64 + k;
+    return w[((size_t)feat * cin + ci) * 9 + tap];
+  });
+}
+
 extern "C" {
 
 // ---- kernel-level test hooks ------------------------------------------------------------------------------
@@ -29,42 +47,25 @@ int airfe_debug_conv3x3(airfe_ctx* c, const float* x, int B, int cin, int H, int
   AIRFE_ENTER(c);
   if ((cin != 64 && cin != 128) || cout % 64 || W % 16 || H % 16) return fail(c, "debug_conv3x3: unsupported shape");
   const int prec = c->prec;
-  std::vector<uint16_t> xin((size_t)B * (H + 2) * (W + 2) * cin, 0);
-  for (int bb = 0; bb < B; ++bb)
-    for (int ci = 0; ci < cin; ++ci)
-      for (int yy = 0; yy < H; ++yy)
-        for (int xx = 0; xx < W; ++xx)
-          xin[(((size_t)bb * (H + 2) + yy + 1) * (W + 2) + xx + 1) * cin + ci] = cvt2(x[(((size_t)bb * cin + ci) * H + yy) * W + xx], prec);
-  const int nci = cin / 64;
-  auto slabs = pack_slabs(cout / 64, 9 * nci, prec, [&](int feat, int s, int k) {
-    const int tap = s / nci, cc = s % nci, ci = cc * 64 + k;
-    return w[((size_t)feat * cin + ci) * 9 + tap];
-  });
   const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
-  uint16_t *dx = nullptr, *dw = nullptr, *dy = nullptr;
-  float* db = nullptr;
-  const size_t ybytes = (size_t)B * (Ho + 2) * (Wo + 2) * cout * 2;
-  HIPCHK(c, hipMalloc((void**)&dx, xin.size() * 2));
-  HIPCHK(c, hipMalloc((void**)&dw, slabs.size() * 2));
-  HIPCHK(c, hipMalloc((void**)&dy, ybytes));
-  HIPCHK(c, hipMalloc((void**)&db, (size_t)cout * 4));
-  HIPCHK(c, hipMemcpy(dx, xin.data(), xin.size() * 2, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(dw, slabs.data(), slabs.size() * 2, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(db, b, (size_t)cout * 4, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemset(dy, 0, ybytes));
+  const size_t ywords = (size_t)B * (Ho + 2) * (Wo + 2) * cout;
+  DbgTmp t(prec);
+  airfe_ctx& tmp = t.h;
   ConvArgs a;
-  a.X = dx; a.Wp = dw; a.bias = db; a.Y = dy; a.B = B; a.H = H; a.W = W; a.CIN = cin; a.COUT = cout;
+  a.X = dupload(&tmp, dbg_conv_x(x, B, cin, H, W, prec)); a.Wp = dupload(&tmp, dbg_conv_slabs(w, cin, cout, prec));
+  a.bias = dupload(&tmp, std::vector<float>(b, b + cout)); a.Y = dalloc<uint16_t>(&tmp, ywords);
+  if (!a.X || !a.Wp || !a.bias || !a.Y) return fail(c, "debug_conv3x3: allocation failed");
+  a.B = B; a.H = H; a.W = W; a.CIN = cin; a.COUT = cout;
   a.pool = pool; a.out_pad = 1; a.relu = 1;
   launch_conv3x3(prec, a, c->stream);
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  std::vector<uint16_t> yo(ybytes / 2);
-  HIPCHK(c, hipMemcpy(yo.data(), dy, ybytes, hipMemcpyDeviceToHost));
+  std::vector<uint16_t> yo(ywords);
+  HIPCHK(c, hipMemcpy(yo.data(), a.Y, ywords * 2, hipMemcpyDeviceToHost));
   for (int bb = 0; bb < B; ++bb)
     for (int co = 0; co < cout; ++co)
       for (int yy = 0; yy < Ho; ++yy)
         for (int xx = 0; xx < Wo; ++xx)
           y[(((size_t)bb * cout + co) * Ho + yy) * Wo + xx] = back2(yo[(((size_t)bb * (Ho + 2) + yy + 1) * (Wo + 2) + xx + 1) * cout + co], prec);
-  (void)hipFree(dx); (void)hipFree(dw); (void)hipFree(dy); (void)hipFree(db);
   return 0;
 } AIRFE_CATCH(c)
 
@@ -131,6 +132,50 @@ static void dbg_back2(const std::vector<uint16_t>& v, size_t n, int prec, float*
 }
 
 extern "C" {
+
+int airfe_debug_conv(airfe_ctx* c, airfe_debug_conv_args* a) try {
+  AIRFE_ENTER(c);
+  if (!a || !a->w || !a->b || !a->y_raw) return fail(c, "debug_conv: null argument");
+  const bool fused = a->img != nullptr;
+  if (fused == (a->x != nullptr)) return fail(c, "debug_conv: exactly one of x (plain form) and img (fused conv1a -> conv1b) must be given");
+  const int cin = a->cin, cout = a->cout, B = a->B, H = a->H, W = a->W, pool = a->pool, opad = a->out_pad, prec = c->prec;
+  if (prec != 0 && prec != 1) return fail(c, "debug_conv: the context's precision must be fp16 or bf16");
+  if (a->wgs < 1 || a->wgs > 256) return fail(c, "debug_conv: wgs must lie in 1 .. 256");
+  if (cin != 64 && cin != 128) return fail(c, "debug_conv: cin must be 64 or 128");
+  if (cout < 64 || cout % 64 || (cin == 128 && cout % 128)) return fail(c, "debug_conv: cout must be a multiple of 64 (of 128 when cin is 128)");
+  if (B < 1 || H < 16 || W < 16 || H % 16 || W % 16) return fail(c, "debug_conv: B >= 1, H and W multiples of 16");
+  if ((pool != 0 && pool != 1) || (opad != 0 && opad != 1) || (a->relu != 0 && a->relu != 1)) return fail(c, "debug_conv: pool, out_pad and relu are 0 or 1");
+  if (pool && !opad) return fail(c, "debug_conv: a pooled layer always feeds another conv (out_pad = 1); pool with out_pad = 0 is no form of the arena");
+  if (fused && (cin != 64 || cout != 64 || !pool || !opad || !a->relu || !a->w1a || !a->b1a))
+    return fail(c, "debug_conv: the fused form is conv1a -> conv1b: cin = cout = 64, pool = 1, out_pad = 1, relu = 1, w1a and b1a given");
+  const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
+  const size_t guard = (size_t)(Wo + 2 * opad) * cout, words = (size_t)B * (Ho + 2 * opad) * guard, total = words + 2 * guard;
+  if (a->y_words != total) return fail(c, "debug_conv: y_words must be (B (Ho + 2 out_pad) + 2) (Wo + 2 out_pad) cout");
+  DbgTmp t(prec);
+  airfe_ctx& tmp = t.h;
+  ConvArgs g;
+  if (fused) {
+    std::vector<float> im((size_t)B * (H + 2) * (W + 2), 0.f);
+    for (int bb = 0; bb < B; ++bb)
+      for (int yy = 0; yy < H; ++yy) memcpy(&im[((size_t)bb * (H + 2) + yy + 1) * (W + 2) + 1], a->img + ((size_t)bb * H + yy) * W, (size_t)W * sizeof(float));
+    g.img = dupload(&tmp, im);
+    g.w1a = dupload(&tmp, std::vector<float>(a->w1a, a->w1a + 64 * 9));
+    g.b1a = dupload(&tmp, std::vector<float>(a->b1a, a->b1a + 64));
+  } else {
+    g.X = dupload(&tmp, dbg_conv_x(a->x, B, cin, H, W, prec));
+  }
+  g.Wp = dupload(&tmp, dbg_conv_slabs(a->w, cin, cout, prec));
+  g.bias = dupload(&tmp, std::vector<float>(a->b, a->b + cout));
+  uint16_t* dy = dbg_canary<uint16_t>(&tmp, total);
+  if ((fused ? !g.img || !g.w1a || !g.b1a : !g.X) || !g.Wp || !g.bias || !dy) return fail(c, "debug_conv: allocation failed");
+  g.Y = dy + guard;
+  g.B = B; g.H = H; g.W = W; g.CIN = cin; g.COUT = cout; g.pool = pool; g.out_pad = opad; g.relu = a->relu; g.wgs = a->wgs;
+  if (fused) launch_conv64r(prec, g, c->stream);         // as detect_dev2 launches the first layer
+  else launch_conv3x3(prec, g, c->stream);               // production's dispatch: conv64r / conv128r, or conv3x3_kernel for relu = 0
+  if (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c)) return fail(c, "debug_conv: kernel failed");
+  HIPCHK(c, hipMemcpy(a->y_raw, dy, total * 2, hipMemcpyDeviceToHost));
+  return 0;
+} AIRFE_CATCH(c)
 
 int airfe_debug_linear(airfe_ctx* c, const airfe_debug_linear_args* a) try {
   AIRFE_ENTER(c);

@@ -93,16 +93,17 @@ struct ConvArgs {
   int pool = 0;                 // fused 2x2 max-pool
   int out_pad = 1;
   int relu = 1;
+  int wgs = 256;                // persistent workgroups of launch_conv64r / launch_conv128r (tests lower it so that a small input wraps the tile loop)
   // fused conv1a -> conv1b (launch_conv64r only): fp32 image [B][H+2][W+2], conv1a weights [64][9] and bias [64]
   const float* img = nullptr;
   const float* w1a = nullptr;
   const float* b1a = nullptr;
 };
 void launch_conv3x3(int prec, const ConvArgs& a, hipStream_t st);
-// persistent weight-stationary variant for CIN == COUT == 64 (launch_conv3x3 dispatches to it)
+// persistent weight-stationary variant for CIN == 64, COUT % 64 == 0 (launch_conv3x3 dispatches to it; a.img != nullptr: the fused conv1a -> conv1b form)
 void launch_conv64r(int prec, const ConvArgs& a, hipStream_t st);
+// persistent weight-stationary variant for CIN == 128, COUT % 128 == 0 (launch_conv3x3 dispatches to it)
 void launch_conv128r(int prec, const ConvArgs& a, hipStream_t st);
-// persistent tap-streamed variant for CIN == 128, COUT % 128 == 0 (launch_conv3x3 dispatches to it)
 
 // cv::resize(INTER_LINEAR, 8-bit fixed point) + /255 -> fp32 [B][RH+2][RW+2] interior
 void launch_preprocess(const uint8_t* src, int B, int h, int w, int stride, size_t img_stride,

@@ -175,7 +175,7 @@ static void conv128r_launch_t(const ConvArgs& a, hipStream_t st) {
   }
   const int tiles_x = a.W / 16, tiles_y = a.H / 8;
   const int ntiles = tiles_x * tiles_y * a.B;
-  const int grid = ntiles < 256 ? ntiles : 256;
+  const int grid = ntiles < a.wgs ? ntiles : a.wgs;
   for (int cb0 = 0; cb0 < a.COUT / 64; cb0 += 2)          // 128 output channels per pass
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), C128R_LDS, st, a, tiles_x, tiles_y, ntiles, cb0);
 }

@@ -460,7 +460,7 @@ static void conv64r_launch_t(const ConvArgs& a, hipStream_t st) {
   }
   const int tiles_x = a.W / 16, tiles_y = a.H / 16;
   const int ntiles = tiles_x * tiles_y * a.B;
-  const int grid = ntiles < 256 ? ntiles : 256;
+  const int grid = ntiles < a.wgs ? ntiles : a.wgs;
   for (int cb0 = 0; cb0 < a.COUT / 64; ++cb0)          // 64 output channels per pass
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(2048 / RW), LDS, st, a, tiles_x, tiles_y, ntiles, cb0);
 }

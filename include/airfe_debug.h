@@ -53,6 +53,30 @@ int airfe_debug_preprocess(airfe_ctx* ctx, const uint8_t* gray, int h, int w, in
 int airfe_debug_conv3x3(airfe_ctx* ctx, const float* x, int B, int cin, int H, int W, const float* w, const float* b,
                         int cout, int pool, float* y);
 int airfe_debug_gemm(airfe_ctx* ctx, const float* x, int M, int K, const float* w, const float* b, int N, int relu, float* y);
+/* ---- the encoder's 3x3 convolutions one launch at a time, every form the arena runs (tests/test_gpu_conv_kernels.py, tests/conv_ref.py).  HOST fp32 tensors in,
+ * rounded to the context's 2-byte type on the way in; the WHOLE device output buffer back as 2-byte words, so that the caller sees what the launch wrote and what it
+ * left alone.  Nothing here has a kernel of its own.
+ *   plain form (x given): launch_conv3x3, i.e. production's dispatch — conv64r_kernel (cin 64) / conv128r_kernel (cin 128) with relu = 1, conv3x3_kernel with relu = 0.
+ *   fused form (img given): launch_conv64r with ConvArgs::img set, as the detector launches conv1a -> conv1b -> 2x2 max-pool.  img [B][H][W] is staged as fp32
+ *     [B][H+2][W+2] with a zero border; w1a / b1a go to the device as fp32.  The kernel's contract: image, w1a and b1a are converted to fp16 in BOTH storage modes (conv1a
+ *     runs on the fp16 MFMA), conv1a's output is stored in the storage type, and it is exactly 0 at halo pixels outside the image.
+ * y_raw holds guard | buffer | guard: the buffer is [B][Ho + 2 out_pad][Wo + 2 out_pad][cout] (Ho, Wo = H, W halved by pool), a guard is one buffer row,
+ * (Wo + 2 out_pad) cout words; y_words = the three together.  Every byte of all three is 0xFF when the launch starts (0xFFFF is a NaN in both types).
+ * wgs = ConvArgs::wgs, the persistent kernels' workgroup cap (256 = production's grid; lower, and a small input wraps the tile loop).  conv3x3_kernel ignores it.
+ * Refused before any launch, with the context left usable: wgs outside 1 .. 256; cin other than 64 / 128; cout no multiple of 64 (of 128 when cin = 128); H or W no
+ * multiple of 16; pool with out_pad = 0 (every pooled layer of the arena feeds another conv, so that form exists nowhere and stays untested); the fused form with
+ * anything but cin = cout = 64, pool = 1, out_pad = 1, relu = 1; both or neither of x and img; a y_words that is not the size above. */
+typedef struct airfe_debug_conv_args {
+  const float* x;                 /* [B][cin][H][W], or NULL: the fused form */
+  const float* img;               /* [B][H][W] (the fused form), or NULL */
+  const float *w1a, *b1a;         /* [64][9], [64] (the fused form) */
+  const float *w, *b;             /* [cout][cin][3][3], [cout] */
+  int cin, cout, B, H, W;
+  int pool, out_pad, relu, wgs;
+  size_t y_words;
+  uint16_t* y_raw;                /* [y_words] out */
+} airfe_debug_conv_args;
+int airfe_debug_conv(airfe_ctx* ctx, airfe_debug_conv_args* a);
 /* ---- the matcher's / detector's GEMM family one form at a time (tests/test_gpu_linear_kernels.py, tests/test_gpu_lg_block.py).  HOST fp32 tensors in, rounded to the
  * 2-byte type `prec` (0 = bf16, 1 = fp16) on the way in; weights packed as the pipelines pack them (scale 1); HOST fp32 out in the kernel's own layout.  The kernels
  * are the production ones: nothing here has a kernel of its own. */
