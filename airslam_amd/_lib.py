@@ -186,6 +186,12 @@ SIGNATURES = {
     "airfe_bowdb_set_u_right_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "airfe_bowdb_set_u_right": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "airfe_bowdb_get_u_right": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "airfe_bowdb_attach_point_ids": (C.c_int, [C.c_void_p, C.c_int]),
+    "airfe_bowdb_set_point_ids_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "airfe_bowdb_set_point_ids": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "airfe_bowdb_get_point_ids": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "airfe_bowdb_build_covisibility_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "airfe_bowdb_build_covisibility": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "airfe_bowdb_query_stored_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] +
                                            [C.c_void_p] * 4),
     "airfe_loop_detect_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(LoopCfg), C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_int] +

@@ -1148,6 +1148,37 @@ class BowDatabase:
             nmatch_t.data_ptr(), ncons_t.data_ptr() if ncons_t is not None else None, self._ctx._stream(stream)), "airfe_loop_detect_batch_dev")
 
 
+    # ---- map-point ids and the covisibility build (include/airfe.h "Map-point ids and the covisibility build")
+    def attach_point_ids(self, max_points: int):
+        """the id table [max_frames][cap] int32 (-1 everywhere) and the build's work arrays for ids 0 .. max_points - 1; needs attach_map"""
+        self._ctx._chk(self._l.airfe_bowdb_attach_point_ids(self._h, int(max_points)), "airfe_bowdb_attach_point_ids")
+
+    def set_point_ids(self, first_frame: int, ids: np.ndarray):
+        """host buffer ids [B][cap] int32: the map point at each feature row, -1 where there is none (the rows that hold NaN in the point table)"""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1, self.cap)
+        self._ctx._chk(self._l.airfe_bowdb_set_point_ids(self._h, int(first_frame), ids.shape[0], ids.ctypes.data), "airfe_bowdb_set_point_ids")
+
+    def set_point_ids_dev(self, first_frame: int, ids_t, stream=None):
+        self._ctx._chk(self._l.airfe_bowdb_set_point_ids_dev(self._h, int(first_frame), ids_t.shape[0], ids_t.data_ptr(), self._ctx._stream(stream)),
+                       "airfe_bowdb_set_point_ids_dev")
+
+    def get_point_ids(self, first_frame: int, B: int) -> np.ndarray:
+        ids = np.empty((B, self.cap), np.int32)
+        self._ctx._chk(self._l.airfe_bowdb_get_point_ids(self._h, int(first_frame), B, ids.ctypes.data), "airfe_bowdb_get_point_ids")
+        return ids
+
+    def build_covisibility_dev(self, info_t, stream=None):
+        """Map::UpdateCovisibilityGraph from the id table, asynchronous on `stream`: replaces the whole graph; info i32 [4] (device) = status (1: more
+        entries than max_edges, the graph is empty), entries needed, valid (frame, row) entries, ids ignored as out of range"""
+        self._ctx._chk(self._l.airfe_bowdb_build_covisibility_dev(self._h, info_t.data_ptr(), self._ctx._stream(stream)), "airfe_bowdb_build_covisibility_dev")
+
+    def build_covisibility(self) -> int:
+        """the same on the context's stream, then a synchronisation -> the number of entries; more than max_edges raises (the graph is empty then)"""
+        e = C.c_int(0)
+        self._ctx._chk(self._l.airfe_bowdb_build_covisibility(self._h, C.byref(e)), "airfe_bowdb_build_covisibility")
+        return e.value
+
+
 # ------------------------------------------------------------------------------------ reference-shaped façade
 class FeatureDetector:
     """Mirror of FeatureDetector (include/feature_detector.h:8-31, src/feature_detector.cc)."""

@@ -1,5 +1,5 @@
 // airfe — the BoW side of libairfe.so (include/airfe.h): the BoW vector, the device-resident keyframe database with its queries, the grouping, and the
-// relocalisation and loop detection composites (kernels_bowdb.hip, kernels_bowgroup.hip, kernels_loopdet.hip).  The vocabulary itself (airfe_bow_load,
+// relocalisation and loop detection composites, and the covisibility build (kernels_bowdb.hip, kernels_bowgroup.hip, kernels_loopdet.hip, kernels_covis.hip).  The vocabulary itself (airfe_bow_load,
 // airfe_bow_transform*) is loaded in airfe.hip.
 #include "airfe_host.h"
 #include "fransac_core.h"
@@ -7,6 +7,7 @@
 #include "poseopt_core.h"
 #include "bowgroup_core.h"
 #include "loopdet_core.h"
+#include "covis_core.h"
 
 /* ---- BoW keyframe database (include/airfe.h "BoW keyframe database"; kernels_bowdb.hip): the database object is a C++ struct behind an opaque pointer */
 struct airfe_bowdb {
@@ -27,6 +28,10 @@ struct airfe_bowdb {
   double* pose = nullptr;                                                    // [max_frames][16], identity until set
   double* u_right = nullptr;                                                 // [max_frames][cap], -1 until set (> 0: stereo)
   DevBlock l_scratch;                                                        // stored queries / loop detection composite
+  // map-point ids (airfe_bowdb_attach_point_ids): what the covisibility build reads
+  int max_points = 0;
+  int32_t* point_id = nullptr;                                               // [max_frames][cap], -1 = no valid map point at this feature row
+  DevBlock c_scratch;                                                        // covisibility build: the per-point and per-row work arrays, sized at attach
 };
 
 namespace {
@@ -124,10 +129,10 @@ int airfe_bowdb_destroy(airfe_bowdb* db) try {
   if (!db) return 0;
   if (db->c) { (void)enter_device(db->c); (void)hipDeviceSynchronize(); }
   for (void* p : {(void*)db->ids, (void*)db->vals, (void*)db->nw, (void*)db->feat, (void*)db->n, (void*)db->xyz, (void*)db->cov_row, (void*)db->cov_nbr,
-                  (void*)db->cov_weight, (void*)db->pos, (void*)db->pose, (void*)db->u_right})      // the persistent tables
+                  (void*)db->cov_weight, (void*)db->pos, (void*)db->pose, (void*)db->u_right, (void*)db->point_id})      // the persistent tables
     if (p) (void)hipFree(p);
   if (db->c)
-    for (DevBlock* b : {&db->q_scratch, &db->m_scratch, &db->r_scratch, &db->l_scratch}) release(db->c, *b);
+    for (DevBlock* b : {&db->q_scratch, &db->m_scratch, &db->r_scratch, &db->l_scratch, &db->c_scratch}) release(db->c, *b);
   delete db;
   return 0;
 } AIRFE_CATCH(nullptr)
@@ -639,5 +644,114 @@ int airfe_loop_detect_batch_dev(airfe_ctx* c, airfe_bowdb* db, const airfe_loop_
   HIPCHK(c, hipGetLastError());
   return 0;
 } AIRFE_CATCH(c)
+
+/* ---- map-point ids and the covisibility build (include/airfe.h "Map-point ids and the covisibility build"; kernels_covis.hip, covis_core.h) ------- */
+// the build's work arrays inside c_scratch: sized by the database and max_points alone, so the block reserved at attach is never replaced by a build
+struct CovisWork {
+  Carve k;
+  size_t o_count, o_start, o_tile, o_packed, o_seg, o_rowcnt, o_info, zero_bytes;
+  CovisWork(const airfe_bowdb* db) {
+    const size_t rows = (size_t)db->max_frames * db->cap, pts = (size_t)db->max_points + 1;
+    zero_bytes = (pts + 4) * 4;                                                          // count [max_points + 1], then valid / ignored / status
+    o_count = k.take(zero_bytes); o_start = k.take(pts * 4); o_tile = k.take(((pts + CV_SCAN_TILE - 1) / CV_SCAN_TILE) * 4);
+    o_packed = k.take(rows * 4); o_seg = k.take(rows * 4); o_rowcnt = k.take((size_t)db->max_frames * 4); o_info = k.take(16);
+  }
+};
+
+static int covis_build_queue(airfe_bowdb* db, int32_t* d_info, hipStream_t st, const char* who, int32_t** own_info) {
+  airfe_ctx* c = db->c;
+  if (!db->point_id) return fail(c, std::string(who) + ": no id table (airfe_bowdb_attach_point_ids)");
+  if (db->size > CV_MAX_FRAMES) return fail(c, std::string(who) + ": more than 4096 frames in the database");
+  CovisWork w(db);
+  if (w.k.into(c, db->c_scratch, st)) return 1;
+  if (own_info) *own_info = d_info = w.k.at<int32_t>(w.o_info);
+  CovisArgs a;
+  a.point_id = db->point_id; a.n = db->n; a.size = db->size; a.max_frames = db->max_frames; a.cap = db->cap; a.max_points = db->max_points;
+  a.max_edges = db->max_edges;
+  a.count = w.k.i(w.o_count); a.acc = a.count + (size_t)db->max_points + 1; a.start = w.k.i(w.o_start); a.tile = w.k.i(w.o_tile);
+  a.packed = w.k.i(w.o_packed); a.seg = w.k.i(w.o_seg); a.rowcnt = w.k.i(w.o_rowcnt);
+  a.row_ptr = db->cov_row; a.nbr = db->cov_nbr; a.weight = db->cov_weight; a.info = d_info;
+  HIPCHK(c, hipMemsetAsync(a.count, 0, w.zero_bytes, st));
+  launch_covis_build(a, st);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+// rows first_frame .. first_frame + B - 1 of the id table
+static int point_ids_copy(airfe_bowdb* db, int first_frame, int B, const int32_t* src, int32_t* dst, hipMemcpyKind kind, hipStream_t st, const char* who) {
+  airfe_ctx* c = db->c;
+  if (!db->point_id) return fail(c, std::string(who) + ": no id table (airfe_bowdb_attach_point_ids)");
+  if (first_frame < 0 || B < 1 || B > db->max_frames - first_frame || (!src && !dst)) return fail(c, std::string(who) + ": bad argument (frames beyond max_frames)");
+  const size_t n = (size_t)B * db->cap;
+  if (src && kind == hipMemcpyHostToDevice)
+    for (size_t i = 0; i < n; ++i)
+      if (src[i] < -1 || src[i] >= db->max_points) return fail(c, std::string(who) + ": an id is < -1 or >= max_points (nothing was changed)");
+  int32_t* at = db->point_id + (size_t)first_frame * db->cap;
+  if (src) HIPCHK(c, hipMemcpyAsync(at, src, n * 4, kind, st));
+  else HIPCHK(c, hipMemcpyAsync(dst, at, n * 4, kind, st));
+  if (kind != hipMemcpyDeviceToDevice) HIPCHK(c, hipStreamSynchronize(st));
+  return 0;
+}
+int airfe_bowdb_attach_point_ids(airfe_bowdb* db, int max_points) try {
+  if (!db) return 1;
+  airfe_ctx* c = db->c;
+  AIRFE_ENTER(c);
+  if (!db->has_map) return fail(c, "bowdb_attach_point_ids: no map state (airfe_bowdb_attach_map)");
+  if (db->point_id) return fail(c, "bowdb_attach_point_ids: the id table is attached already");
+  if (max_points < 1 || max_points > CV_MAX_POINTS) return fail(c, "bowdb_attach_point_ids: max_points must be 1 .. 16777216");
+  const size_t rows = (size_t)db->max_frames * db->cap;
+  int32_t* ids = nullptr;
+  HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&ids), rows * 4));
+  db->max_points = max_points;
+  CovisWork w(db);
+  if (w.k.into(c, db->c_scratch, c->stream) || hipMemsetAsync(ids, 0xFF, rows * 4, c->stream) != hipSuccess ||      // every byte 0xFF: -1 in every slot
+      hipStreamSynchronize(c->stream) != hipSuccess) {
+    (void)hipFree(ids);
+    db->max_points = 0;
+    return fail(c, "bowdb_attach_point_ids: out of device memory");
+  }
+  db->point_id = ids;
+  return 0;
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_set_point_ids_dev(airfe_bowdb* db, int first_frame, int B, const int32_t* d_ids, void* stream) try {
+  if (!db) return 1;
+  AIRFE_ENTER(db->c);
+  return point_ids_copy(db, first_frame, B, d_ids, nullptr, hipMemcpyDeviceToDevice, stream ? (hipStream_t)stream : db->c->stream, "bowdb_set_point_ids_dev");
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_set_point_ids(airfe_bowdb* db, int first_frame, int B, const int32_t* ids) try {
+  if (!db) return 1;
+  AIRFE_ENTER(db->c);
+  return point_ids_copy(db, first_frame, B, ids, nullptr, hipMemcpyHostToDevice, db->c->stream, "bowdb_set_point_ids");
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_get_point_ids(airfe_bowdb* db, int first_frame, int B, int32_t* ids) try {
+  if (!db) return 1;
+  AIRFE_ENTER(db->c);
+  return point_ids_copy(db, first_frame, B, nullptr, ids, hipMemcpyDeviceToHost, db->c->stream, "bowdb_get_point_ids");
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_build_covisibility_dev(airfe_bowdb* db, int32_t* d_info, void* stream) try {
+  if (!db) return 1;
+  AIRFE_ENTER(db->c);
+  if (!d_info) return fail(db->c, "bowdb_build_covisibility_dev: bad argument");
+  return covis_build_queue(db, d_info, stream ? (hipStream_t)stream : db->c->stream, "bowdb_build_covisibility_dev", nullptr);
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_build_covisibility(airfe_bowdb* db, int* n_edges) try {
+  if (!db) return 1;
+  airfe_ctx* c = db->c;
+  AIRFE_ENTER(c);
+  if (!n_edges) return fail(c, "bowdb_build_covisibility: bad argument");
+  int32_t* d_info = nullptr;
+  int32_t info[4] = {0, 0, 0, 0};
+  if (covis_build_queue(db, nullptr, c->stream, "bowdb_build_covisibility", &d_info)) return 1;
+  HIPCHK(c, hipMemcpyAsync(info, d_info, 16, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *n_edges = info[1];
+  if (info[0]) return fail(c, "bowdb_build_covisibility: more entries than max_edges (the graph is empty now)");
+  return 0;
+} AIRFE_CATCH(db->c)
 
 }  // extern "C"

@@ -544,4 +544,15 @@ struct LoopFinishArgs {
 };
 void launch_loopdet_finish(const LoopFinishArgs& f, int Q, hipStream_t st);
 
+// The covisibility table from the stored map-point ids (map.cc:1385-1418; kernels_covis.hip, covis_core.h; contract: include/airfe.h)
+struct CovisArgs {
+  const int32_t* point_id = nullptr; const int* n = nullptr;                 // [max_frames][cap], [max_frames]: the id table, the stored feature counts
+  int size = 0, max_frames = 0, cap = 0, max_points = 0, max_edges = 0;
+  int *packed = nullptr, *seg = nullptr;                                     // [max_frames][cap] x 2: (id, first) per row; the (point -> frames) segments
+  int *count = nullptr, *start = nullptr, *tile = nullptr;                   // [max_points + 1] x 2, [tiles]: count is ZERO on entry
+  int *rowcnt = nullptr, *acc = nullptr;                                     // [max_frames]; [4]: valid, ignored, status — ZERO on entry
+  int32_t *row_ptr = nullptr, *nbr = nullptr, *weight = nullptr, *info = nullptr;      // the database's CSR, the caller's i32 [4]
+};
+void launch_covis_build(const CovisArgs& a, hipStream_t st);                 // size <= 4096
+
 }  // namespace airfe

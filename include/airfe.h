@@ -423,8 +423,8 @@ int airfe_bow_transform_dev(airfe_ctx* ctx, const float* d_feat, int N, uint32_t
  * RESTATED here, on the device, bit for bit (DBoW2 compiled unchanged is the test's reference for the vector; tests/bowdb_ref.py restates the rest):
  * FrameToBow to its end, AddFrame, Query, the two callers' filters, L1Scoring::score, the best-candidate rule — and, in the block "Grouping" below, the
  * GROUPING between the scores and the candidates (map_user.cc:177-264, map_refiner.cc:132-211) over a covisibility table the caller hands to the
- * database (airfe_bowdb_attach_map / airfe_bowdb_set_covisibility).  What stays the caller's: BUILDING that table from the map's observer lists, and
- * relocalisation's junction "sentences" (the junction database, FindJunctionConnections), whose result enters the grouping as one number per frame
+ * database (airfe_bowdb_attach_map / airfe_bowdb_set_covisibility) or builds there from the frames' map-point ids (the block "Map-point ids and the
+ * covisibility build" below).  What stays the caller's: relocalisation's junction "sentences" (the junction database, FindJunctionConnections), whose result enters the grouping as one number per frame
  * (d_extra).  The candidate list below IS the reference's frame_scores map.  airfe_bowdb_topk_dev is the PROJECT'S OWN ranking for callers without a
  * covisibility graph, not the reference's grouping.  Every floating-point sum is sequential in the order given; no fused multiply-adds.
  *   vector   Database::FrameToBow (src/bow/database.cc:57-89): per feature the descent of airfe_bow_transform (the same kernel); a feature counts iff its
@@ -502,7 +502,8 @@ int airfe_bowdb_match_candidates_batch_dev(airfe_ctx* ctx, airfe_bowdb* db, cons
  *                 whole graph (as Map::UpdateCovisibilityGraph does) from HOST arrays of n_frames rows (frames past n_frames get empty rows); every row
  *                 must be strictly ascending in nbr and row_ptr must start at 0 and not decrease, otherwise the call fails and changes nothing.  The
  *                 table is the reference's _covisibile_frames as it is: it INCLUDES each frame's entry for itself (UpdateFrameCovisibility counts a
- *                 frame among the observers of its own points); the library neither adds nor removes it.  Building it stays the caller's.
+ *                 frame among the observers of its own points); the library neither adds nor removes it.  airfe_bowdb_build_covisibility[_dev] ("Map-point ids and the covisibility build" below)
+ *                 builds the same table on the device.
  *   positions     [max_frames][3] f64, optional (airfe_bowdb_set_positions, host rows): the keyframes' twc, read by the loop form only.
  * The set_* / get_* entries on host buffers synchronise the context's stream; a grouping queued on ANOTHER stream must have completed before the graph
  * is replaced.  airfe_bowdb_set_points_dev is asynchronous on `stream`. */
@@ -636,7 +637,7 @@ int airfe_bowdb_query_stored_batch_dev(airfe_bowdb* db, const int32_t* d_qframe,
  * K outside 1 .. 5; Q > 4096.  A caller with a large map runs the stored query and airfe_bowdb_group_dev over all frames first (both are cheap) and hands
  * the composite only the frames that kept a group, in chunks of max_batch / K: d_qframe is an arbitrary list for that reason.
  * OUT OF SCOPE (the caller's, as in the reference): the "find more matches" search of :322-438, TriangulateMappoint, the mappoint merge, the pose graph,
- * building the covisibility table, junction sentences. */
+ * junction sentences. */
 typedef struct airfe_loop_cfg {
   float ratio;            /* 0.5f */
   int min_words;          /* 8 */
@@ -652,6 +653,42 @@ typedef struct airfe_loop_cfg {
 int airfe_loop_detect_batch_dev(airfe_ctx* ctx, airfe_bowdb* db, const airfe_loop_cfg* cfg, const int32_t* d_qframe, int Q, int* d_ok, int* d_stage,
                                 int32_t* d_loop, double* d_Twq, double* d_Rlq, double* d_tlq, int* d_num, uint8_t* d_mask, int32_t* d_idx, float* d_score,
                                 int mcap, int* d_nmatch, int* d_ncons, void* stream);
+
+/* ---- Map-point ids and the covisibility build: Map::UpdateCovisibilityGraph (src/map.cc:1385-1418) for a loaded map, on the device -------------------
+ * The table the grouping and the stored query read, from the IDENTITIES of the map points at the stored frames' feature rows.
+ * airfe_bowdb_attach_point_ids (needs airfe_bowdb_attach_map; a second attach is a return code) allocates
+ *   point_id   i32 [max_frames][cap], one per FEATURE ROW of the stored frame, initialised to -1.  id >= 0: the map point at that row; the caller writes -1
+ *              where mpt == nullptr || !mpt->IsValid() — the rows that hold NaN in the point table.
+ *   work       8 bytes per point (max_points + 1 entries) and 8 bytes per feature row, in one block that the build never replaces.  max_points is
+ *              1 .. 16777216 (2^24: 128 MiB of work memory at the limit); outside that: a return code.  Every build clears and scans the per-point
+ *              arrays, so its cost grows with max_points: size it by the map, not by the limit.
+ * airfe_bowdb_set_point_ids (host buffer [B][cap]) refuses an id < -1 or >= max_points and changes nothing then; _set_point_ids_dev copies blindly.  Stream
+ * and synchronisation rules are those of airfe_bowdb_set_points / _set_points_dev; frames beyond max_frames are a return code and change nothing.
+ * THE BUILD.  With size = the frames in the database and n[f] = the stored feature count of frame f (clamped to 0 .. cap):
+ *   valid(f, i)   f < size, i < n[f] and 0 <= point_id[f][i] < max_points
+ *   obs(m)        { f : some i with valid(f, i) and point_id[f][i] == m }
+ *   w[f][g]       #{ i : valid(f, i) and g in obs(point_id[f][i]) }
+ * Row f of the CSR holds the pairs (g, w[f][g]) with w > 0, strictly ascending in g; frames >= size get empty rows; row_ptr[max_frames] = E.  This is the
+ * reference's loop (per mappoint of the frame, one increment per observer), so: w[f][f] = the valid rows of f (the self entry is kept); a frame without
+ * a valid row has an EMPTY row, without a self entry; a point at two rows of f counts twice from f's side while f is ONE observer of it, so
+ * w[f][g] = 2 with w[g][f] = 1 — the table is not symmetric.  STATED DIFFERENCE: the observer lists are those the id table implies; the reference reads
+ * Mappoint::_obversers, which agrees with the frames' _mappoints in a map that passes CheckMap.
+ * Rows >= n[f] and frames >= size are never read as ids and may hold anything.  An id outside [0, max_points) other than -1 never indexes memory: it is
+ * counted in info[3] and treated as -1.
+ *   _dev    asynchronous on `stream`, no host synchronisation, no allocation.  REPLACES the whole graph (a grouping or stored query queued on ANOTHER
+ *           stream must have completed).  d_info i32 [4] (device): status (0 ok, 1 overflow), entries needed, valid (frame, row) entries, ids ignored as
+ *           out of range.  More entries needed than max_edges: the graph becomes EMPTY (every row_ptr 0) and status is 1.
+ *   host    the same on the context's stream, then a synchronisation; *n_edges = the entries needed; overflow is an error return (the graph is empty).
+ * Return codes: no id table; more than 4096 frames in the database.  Three statements that agree byte for byte: covis_build_host
+ * (airslam_amd/csrc/covis_core.h), the kernels (kernels_covis.hip) and tests/covis_ref.py.  Two builds of one table give the same bytes: the kernels'
+ * integer atomics only add to counters whose final value is read.  OUT OF SCOPE: UpdateFrameCovisibility for a single frame (a CSR row cannot be
+ * replaced in place). */
+int airfe_bowdb_attach_point_ids(airfe_bowdb* db, int max_points);
+int airfe_bowdb_set_point_ids_dev(airfe_bowdb* db, int first_frame, int B, const int32_t* d_ids, void* stream);   /* d_ids [B][cap] */
+int airfe_bowdb_set_point_ids(airfe_bowdb* db, int first_frame, int B, const int32_t* ids);                   /* host buffer [B][cap] */
+int airfe_bowdb_get_point_ids(airfe_bowdb* db, int first_frame, int B, int32_t* ids);                         /* host buffer [B][cap] */
+int airfe_bowdb_build_covisibility_dev(airfe_bowdb* db, int32_t* d_info, void* stream);
+int airfe_bowdb_build_covisibility(airfe_bowdb* db, int* n_edges);
 
 /* ---- the step BEFORE the path: rectification ------------------------------------------------------- */
 /* ≙ the maps Camera's constructor builds with cv::initUndistortRectifyMap (src/camera.cc:60-75; _mapl1/_mapl2 = side 0, _mapr1/_mapr2 =
