@@ -108,6 +108,18 @@ class DebugAttentionArgs(C.Structure):
                 + [("canary", C.c_int), ("raw", C.c_int), ("out", C.c_void_p), ("Np", C.c_int), ("rows_past", C.c_int)])
 
 
+class DebugDetectorTailArgs(C.Structure):
+    """airfe_debug_detector_tail_args (include/airfe_debug.h)"""
+    _fields_ = ([(n, C.c_int) for n in ("B", "Bs", "h", "w", "cap")] + [(n, C.c_void_p) for n in ("heat", "act", "feat", "feat1", "n", "n1", "nms_map", "keep", "cand_cnt")]
+                + [("nms_map_written", C.c_int)])
+
+
+class DebugLinePostArgs(C.Structure):
+    """airfe_debug_line_post_args (include/airfe_debug.h)"""
+    _fields_ = ([(n, C.c_int) for n in ("B", "nj", "ld", "h", "w", "capL", "capJ", "from_plane")]
+                + [(n, C.c_void_p) for n in ("la", "sc", "m2", "heat", "lines", "nlines", "nfound", "junc", "njunc", "jfound", "jmap")])
+
+
 # name -> (restype, argtypes); every symbol include/*.h declares
 SIGNATURES = {
     "airfe_copy_rows_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -250,6 +262,9 @@ SIGNATURES = {
     "airfe_debug_lg_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "airfe_debug_sg_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "airfe_debug_sg_sinkhorn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+    "airfe_debug_detector_tail": (C.c_int, [C.c_void_p, C.POINTER(DebugDetectorTailArgs)]),
+    "airfe_debug_line_post": (C.c_int, [C.c_void_p, C.POINTER(DebugLinePostArgs)]),
+    "airfe_debug_junctions_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "airfe_debug_lg_prepare": (C.c_int, [C.c_void_p, C.POINTER(DebugLgPrepareArgs)]),
     "airfe_debug_lg_assign": (C.c_int, [C.c_void_p, C.POINTER(DebugLgAssignArgs)]),
     "airfe_debug_plnet_stage0": (C.c_int, [C.c_void_p] + [C.c_void_p] * 10),

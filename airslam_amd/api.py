@@ -476,6 +476,59 @@ class Context:
                   "airfe_debug_detector_maps")
         return heat, nms, desc
 
+    def debug_detector_tail(self, heat, act, cap, Bs=0, h=512, w=512, sentinel=7.0, want_keep=True):
+        """airfe_debug_detector_tail (include/airfe_debug.h): everything the detector runs behind the score head on host score maps heat [B, 512, 512] and convDa
+        activations act [B, 64, 64, 256].  Bs = 0: one destination; else images b >= Bs go to the second.  The feature buffers start as `sentinel`, the counts as -1.
+        -> dict feat [B, cap, 259] and n [B] (both destinations concatenated in image order), cand_cnt [B], keep [B, 64, 64] uint64 (radius 4 and want_keep; else None),
+        nms_map [B, 512, 512] (None where the form wrote none)."""
+        heat, act = np.ascontiguousarray(heat, np.float32), np.ascontiguousarray(act, np.float32)
+        b = heat.shape[0]
+        assert heat.shape == (b, 512, 512) and act.shape == (b, 64, 64, 256)
+        b0 = Bs if Bs else b
+        feat, n = np.full((b0, cap, FEAT), sentinel, np.float32), np.full((b0,), -1, np.int32)
+        feat1, n1 = np.full((b - b0, cap, FEAT), sentinel, np.float32), np.full((b - b0,), -1, np.int32)
+        nms = np.full((b, 512, 512), np.nan, np.float32)
+        keep = np.zeros((b, 64, 64), np.uint64) if want_keep and self.cfg.nms_radius == 4 else None
+        cnt = np.full((b,), -1, np.int32)
+        a = _lib.DebugDetectorTailArgs(B=b, Bs=int(Bs), h=int(h), w=int(w), cap=int(cap), heat=heat.ctypes.data, act=act.ctypes.data, feat=feat.ctypes.data, n=n.ctypes.data,
+                                       nms_map=nms.ctypes.data, cand_cnt=cnt.ctypes.data)
+        if Bs:
+            a.feat1, a.n1 = feat1.ctypes.data, n1.ctypes.data
+        if keep is not None:
+            a.keep = keep.ctypes.data
+        self._chk(self._l.airfe_debug_detector_tail(self._h, C.byref(a)), "airfe_debug_detector_tail")
+        return {"feat": np.concatenate([feat, feat1]), "n": np.concatenate([n, n1]), "cand_cnt": cnt, "keep": keep, "nms_map": nms if a.nms_map_written else None}
+
+    def debug_line_post(self, la, sc, m2, heat, cap_lines, cap_junctions, nj=None, from_plane=False, h=512, w=512, sentinel=7.0, jmap=None):
+        """airfe_debug_line_post (include/airfe_debug.h): the line filter and the junction scan on host stage-1 outputs la [B, ld, 4], sc [B, ld] (m2 [B] lines each) and score
+        maps heat [B, 512, 512]; the junction scores come from the dense NMS'd map or (from_plane) from the raw scores under the keep plane.  The output buffers start as
+        `sentinel`.  jmap [nj, 512, 512] uint8 (optional) replaces the junction maps the filter wrote before the scan reads them.
+        -> dict lines [B, capL, 4] float64, nlines, nfound [B], junc [nj, capJ, 259], njunc, jfound [nj]."""
+        la, sc, heat = np.ascontiguousarray(la, np.float32), np.ascontiguousarray(sc, np.float32), np.ascontiguousarray(heat, np.float32)
+        m2 = np.ascontiguousarray(m2, np.int32).reshape(-1)
+        b, ld = sc.shape
+        nj = b if nj is None else int(nj)
+        assert la.shape == (b, ld, 4) and heat.shape == (b, 512, 512) and len(m2) == b
+        out = {"lines": np.full((b, cap_lines, 4), sentinel, np.float64), "nlines": np.full((b,), -1, np.int32), "nfound": np.full((b,), -1, np.int32),
+               "junc": np.full((nj, cap_junctions, FEAT), sentinel, np.float32), "njunc": np.full((nj,), -1, np.int32), "jfound": np.full((nj,), -1, np.int32)}
+        a = _lib.DebugLinePostArgs(B=b, nj=nj, ld=ld, h=int(h), w=int(w), capL=int(cap_lines), capJ=int(cap_junctions), from_plane=int(bool(from_plane)), la=la.ctypes.data,
+                                   sc=sc.ctypes.data, m2=m2.ctypes.data, heat=heat.ctypes.data, **{k: v.ctypes.data for k, v in out.items()})
+        if jmap is not None:
+            jmap = np.ascontiguousarray(jmap, np.uint8)
+            assert jmap.shape == (nj, 512, 512)
+            a.jmap = jmap.ctypes.data
+        self._chk(self._l.airfe_debug_line_post(self._h, C.byref(a)), "airfe_debug_line_post")
+        return out
+
+    def debug_junctions_topk(self, jloc, joff):
+        """airfe_debug_junctions_topk (include/airfe_debug.h): jloc [B, 128, 128], joff [B, 2, 128, 128] -> juncs_pred [B, 300, 2]"""
+        jloc, joff = np.ascontiguousarray(jloc, np.float32), np.ascontiguousarray(joff, np.float32)
+        b = jloc.shape[0]
+        assert jloc.shape == (b, 128, 128) and joff.shape == (b, 2, 128, 128)
+        out = np.full((b, 300, 2), np.nan, np.float32)
+        self._chk(self._l.airfe_debug_junctions_topk(self._h, jloc.ctypes.data, joff.ctypes.data, b, out.ctypes.data), "airfe_debug_junctions_topk")
+        return out
+
     def debug_preprocess(self, gray):
         gray = np.ascontiguousarray(gray, np.uint8)
         out = np.empty((512, 512), np.float32)

@@ -666,4 +666,130 @@ int airfe_debug_lg_assign(airfe_ctx* c, airfe_debug_lg_assign_args* a) try {
   return 0;
 } AIRFE_CATCH(c)
 
+/* ---- the detector's and the line path's index work on hand-built maps (include/airfe_debug.h; tests/test_gpu_detector_tail_pin.py, tests/detector_tail_ref.py).  HOST tensors
+ * staged into the context's own buffers, then the launchers production calls, in production's order and with production's arguments; nothing here has a kernel of its own. */
+int airfe_debug_detector_tail(airfe_ctx* c, airfe_debug_detector_tail_args* a) try {
+  AIRFE_ENTER(c);
+  if (!c->has_sp) return fail(c, "debug_detector_tail: detector not loaded");
+  if (c->prec != 0 && c->prec != 1) return fail(c, "debug_detector_tail drives the 2-byte detector (cfg.precision fp16 / bf16)");
+  if (!a || !a->heat || !a->act || !a->feat || !a->n) return fail(c, "debug_detector_tail: null argument");
+  const int B = a->B, Bs = a->Bs, cap = a->cap, R = AIRFE_INTERNAL_SIZE;
+  const bool two = Bs != 0;
+  if (B < 1 || B > c->Dmax || (two && (B != 2 * Bs || Bs > c->Bmax || !a->feat1 || !a->n1)) || (!two && B > c->Bmax))
+    return fail(c, "debug_detector_tail: 1 <= B <= max_batch, or B = 2 Bs with both destinations given");
+  if (a->h < 1 || a->w < 1 || cap < c->cfg.max_keypoints) return fail(c, "debug_detector_tail: empty image or feature capacity < max_keypoints");
+  if (a->keep && c->cfg.nms_radius != 4) return fail(c, "debug_detector_tail: the keep plane exists on the radius-4 path only");
+  const size_t px = (size_t)B * R * R, cells = (size_t)B * (R / 8) * (R / 8);
+  for (size_t i = 0; i < px; ++i)
+    if (!(a->heat[i] >= 0.f && a->heat[i] <= 1.f)) return fail(c, "debug_detector_tail: scores must lie in [0, 1]");
+  std::vector<uint16_t> act(cells * 256);
+  for (size_t i = 0; i < act.size(); ++i) act[i] = cvt2(a->act[i], c->prec);
+  const int B0 = two ? Bs : B, B1 = two ? B - Bs : 0;
+  DbgTmp t;
+  float* dfeat = dupload(&t.h, std::vector<float>(a->feat, a->feat + (size_t)B0 * cap * AIRFE_FEAT_DIM));
+  int* dn = dupload(&t.h, std::vector<int>(a->n, a->n + B0));
+  float* dfeat1 = two ? dupload(&t.h, std::vector<float>(a->feat1, a->feat1 + (size_t)B1 * cap * AIRFE_FEAT_DIM)) : nullptr;
+  int* dn1 = two ? dupload(&t.h, std::vector<int>(a->n1, a->n1 + B1)) : nullptr;
+  if (!dfeat || !dn || (two && (!dfeat1 || !dn1))) return fail(c, "debug_detector_tail: allocation failed");
+  hipStream_t st = c->stream;
+  clear_saturation(c);
+  HIPCHK(c, hipMemcpyAsync(c->heat, a->heat, px * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->aDa, act.data(), act.size() * 2, hipMemcpyHostToDevice, st));
+  // detect_dev2's descriptor-head rule (airfe_detect.hip), then its tail
+  const bool sparse_desc = B > 2 && cap * 4 <= (R / 8) * (R / 8) && cap <= 1024;
+  if (!sparse_desc && dense_desc_head(c, B, st)) { (void)hipStreamSynchronize(st); return 1; }
+  c->desc_dense_valid = !sparse_desc;
+  c->last_B = B;
+  const int rc = detect_tail_dev(c, B, Bs, two, sparse_desc, a->h, a->w, dfeat, dfeat1, cap, dn, dn1, st);
+  HIPCHK(c, hipStreamSynchronize(st));                       // (act goes out of scope)
+  if (rc) return 1;
+  if (saturation_status(c)) return 1;
+  HIPCHK(c, hipMemcpy(a->feat, dfeat, (size_t)B0 * cap * AIRFE_FEAT_DIM * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->n, dn, (size_t)B0 * 4, hipMemcpyDeviceToHost));
+  if (two) {
+    HIPCHK(c, hipMemcpy(a->feat1, dfeat1, (size_t)B1 * cap * AIRFE_FEAT_DIM * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(a->n1, dn1, (size_t)B1 * 4, hipMemcpyDeviceToHost));
+  }
+  a->nms_map_written = c->cfg.nms_radius > 0 && c->nms_map_valid;
+  if (a->nms_map && a->nms_map_written) HIPCHK(c, hipMemcpy(a->nms_map, c->heat_nms, px * 4, hipMemcpyDeviceToHost));
+  if (a->keep) HIPCHK(c, hipMemcpy(a->keep, c->nms_mask, cells * 8, hipMemcpyDeviceToHost));
+  if (a->cand_cnt) HIPCHK(c, hipMemcpy(a->cand_cnt, c->cand_cnt, (size_t)B * 4, hipMemcpyDeviceToHost));
+  return 0;
+} AIRFE_CATCH(c)
+
+int airfe_debug_line_post(airfe_ctx* c, airfe_debug_line_post_args* a) try {
+  AIRFE_ENTER(c);
+  if (!c->has_sp || !c->has_s1 || !c->s1_la || !c->jmap) return fail(c, "debug_line_post: the line path is not loaded (cfg.plnet_s1_pack)");
+  if (c->cfg.nms_radius != 4) return fail(c, "debug_line_post: both junction score sources exist on the radius-4 path only");
+  if (!a || !a->la || !a->sc || !a->m2 || !a->heat || !a->lines || !a->nlines || !a->nfound) return fail(c, "debug_line_post: null argument");
+  const int B = a->B, nj = a->nj, ld = a->ld, capL = a->capL, capJ = a->capJ, R = AIRFE_INTERNAL_SIZE;
+  if (B < 1 || B > c->Lmax || B > c->Dmax || nj < 0 || nj > B || ld < 1 || ld > LINE_CAP || capL < 1 || capJ < 1 || a->h < 1 || a->w < 1)
+    return fail(c, "debug_line_post: bad argument (1 <= B <= the arena's images, 0 <= nj <= B, 1 <= ld <= 45056, capL, capJ >= 1)");
+  if (nj > 0 && (!a->junc || !a->njunc || !a->jfound)) return fail(c, "debug_line_post: nj > 0 needs the junction outputs");
+  for (int b = 0; b < B; ++b)
+    if (a->m2[b] < 0 || a->m2[b] > ld) return fail(c, "debug_line_post: every m2 must lie in 0 .. ld");
+  DbgTmp t;
+  double* dlines = dupload(&t.h, std::vector<double>(a->lines, a->lines + (size_t)B * capL * 4));
+  float* djunc = nj > 0 ? dupload(&t.h, std::vector<float>(a->junc, a->junc + (size_t)nj * capJ * AIRFE_FEAT_DIM)) : nullptr;
+  int* dcnt = dbg_canary<int>(&t.h, (size_t)4 * B);          // nlines | nfound | njunc | jfound
+  if (!dlines || (nj > 0 && !djunc) || !dcnt) return fail(c, "debug_line_post: allocation failed");
+  hipStream_t st = c->stream;
+  clear_saturation(c);
+  std::vector<int> counts((size_t)B * LINE_CNT_LD, 0);
+  for (int b = 0; b < B; ++b) {
+    counts[(size_t)b * LINE_CNT_LD + 1] = a->m2[b];
+    HIPCHK(c, hipMemcpyAsync(c->s1_la + (size_t)b * LINE_CAP * 4, a->la + (size_t)b * ld * 4, (size_t)ld * 16, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->s1_sc + (size_t)b * LINE_CAP, a->sc + (size_t)b * ld, (size_t)ld * 4, hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(c, hipMemcpyAsync(c->wf_counts, counts.data(), counts.size() * 4, hipMemcpyHostToDevice, st));
+  c->wf_counted = false;                                     // (the per-workgroup counts of a previous line branch are gone)
+  HIPCHK(c, hipMemcpyAsync(c->heat, a->heat, (size_t)B * R * R * 4, hipMemcpyHostToDevice, st));
+  // the point branch's NMS as detect_tail_dev runs it: with the dense map (one- and two-image calls) or with the keep plane alone (larger batches)
+  c->nms_map_valid = !a->from_plane;
+  launch_nms512_candidates(c->heat, c->nms_map_valid ? c->heat_nms : nullptr, c->nms_mask, B, c->cfg.keypoint_threshold, c->cfg.remove_borders, c->cand, c->cand_cnt,
+                           R * R, st);
+  // line_tail_dev's filter and junction scan (airfe_detect.hip), images 0 .. B-1, junctions of the first nj
+  const float ws = (float)a->w / (float)R, hs = (float)a->h / (float)R;
+  if (nj > 0) launch_zero16(c->jmap, (size_t)nj * R * R, st);
+  launch_line_filter(c->s1_la, c->s1_sc, c->wf_counts, c->cfg.remove_borders, c->cfg.line_threshold, c->cfg.line_length_threshold, ws, hs, R, c->jmap, nj, dlines, capL,
+                     dcnt, dcnt + B, LINE_CAP, B, st);
+  // a caller's junction maps instead of the filter's, between the two launches: the scan's own bounds (the filter never marks a pixel the scan would reject)
+  if (nj > 0 && a->jmap) HIPCHK(c, hipMemcpyAsync(c->jmap, a->jmap, (size_t)nj * R * R, hipMemcpyHostToDevice, st));
+  if (nj > 0) {
+    const bool from_mask = c->cfg.nms_radius > 0 && !c->nms_map_valid;
+    const float* hsel = c->cfg.nms_radius > 0 && !from_mask ? c->heat_nms : c->heat;
+    const unsigned long long* mask = from_mask ? reinterpret_cast<const unsigned long long*>(c->nms_mask) : nullptr;
+    launch_junction_scan(c->jmap, hsel, R, c->cfg.remove_borders, djunc, capJ, dcnt + 2 * B, dcnt + 3 * B, c->d_njunc + 2 * c->Lmax, nj, st, mask);
+  }
+  HIPCHK(c, hipStreamSynchronize(st));                       // (counts goes out of scope)
+  if (launch_status(c)) return 1;
+  if (saturation_status(c)) return 1;
+  HIPCHK(c, hipMemcpy(a->lines, dlines, (size_t)B * capL * 32, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->nlines, dcnt, (size_t)B * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->nfound, dcnt + B, (size_t)B * 4, hipMemcpyDeviceToHost));
+  if (nj > 0) {
+    HIPCHK(c, hipMemcpy(a->junc, djunc, (size_t)nj * capJ * AIRFE_FEAT_DIM * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(a->njunc, dcnt + 2 * B, (size_t)nj * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(a->jfound, dcnt + 3 * B, (size_t)nj * 4, hipMemcpyDeviceToHost));
+  }
+  return 0;
+} AIRFE_CATCH(c)
+
+int airfe_debug_junctions_topk(airfe_ctx* c, const float* jloc, const float* joff, int B, float* juncs_pred) try {
+  AIRFE_ENTER(c);
+  if (!c->has_s0 || !c->s0_stage) return fail(c, "debug_junctions_topk: the line branch is not loaded (line.* tensors, cfg.plnet_s1_pack)");
+  if (!jloc || !joff || !juncs_pred || B < 1 || B > c->Lmax) return fail(c, "debug_junctions_topk: bad argument (1 <= B <= the arena's images)");
+  const size_t npx = 128 * 128;
+  hipStream_t st = c->stream;
+  clear_saturation(c);
+  HIPCHK(c, hipMemcpyAsync(c->l_jloc, jloc, (size_t)B * npx * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->l_joff, joff, (size_t)B * 2 * npx * 4, hipMemcpyHostToDevice, st));
+  junctions_topk_dev(c, B, st);
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (launch_status(c)) return 1;
+  if (saturation_status(c)) return 1;
+  HIPCHK(c, hipMemcpy2D(juncs_pred, 600 * 4, c->s0_stage + SG_JUNCS, SG_STRIDE * 4, 600 * 4, B, hipMemcpyDeviceToHost));
+  return 0;
+} AIRFE_CATCH(c)
+
 }  // extern "C"

@@ -90,6 +90,72 @@ int dense_desc_head(airfe_ctx* c, int B, hipStream_t st) {
   return c->cfg.check_launches ? launch_status(c) : 0;
 }
 
+// Everything of the detector behind the score head, over the B images whose score maps are in c->heat and whose convDa activations are in c->aDa: NMS, candidate
+// compaction, top-K, descriptor head over the sampled cells (sparse_desc; else the dense map is already in c->desc) and descriptor sampling.  two: images
+// b >= Bs write the second destination.  Shared by detect_dev2 and the test hook airfe_debug_detector_tail (airfe_debug.hip), so that hand-built score maps run
+// the very launches production runs.
+int detect_tail_dev(airfe_ctx* c, int B, int Bs, bool two, bool sparse_desc, int h, int w, float* d_feat, float* d_feat1, int cap, int* d_n, int* d_n1,
+                    hipStream_t st) {
+  const int R = AIRFE_INTERNAL_SIZE;
+  const int ccap = R * R;
+  {
+    ProfScope ps(c, ST_NMS, st, 0, (double)B * R * R * 8);
+    if (c->cfg.nms_radius == 4) {                        // the reference's radius: simple_nms in registers (kernels_nms512.hip; R = 512)
+      // the dense NMS'd map is consumed only by the batch-1 line path (junction scores) and the inspection hook: large batches skip
+      // its 1 MB / image write (airfe_debug_detector_maps rebuilds it on demand; the batched junction scores come from the keep plane, line_tail_dev)
+      c->nms_map_valid = B <= 2;
+      launch_nms512_candidates(c->heat, c->nms_map_valid ? c->heat_nms : nullptr, c->nms_mask, B, c->cfg.keypoint_threshold,
+                               c->cfg.remove_borders, c->cand, c->cand_cnt, ccap, st);
+    } else if (c->cfg.nms_radius > 0) {
+      c->nms_map_valid = true;
+      launch_simple_nms(c->heat, c->heat_nms, c->nms_tmp, B, R, R, c->cfg.nms_radius, st);
+      launch_candidates(c->heat_nms, B, R, R, c->cfg.keypoint_threshold, c->cfg.remove_borders, c->cand, c->cand_cnt, ccap, st);
+    } else {
+      launch_candidates(c->heat, B, R, R, c->cfg.keypoint_threshold, c->cfg.remove_borders, c->cand, c->cand_cnt, ccap, st);
+    }
+  }
+  // The two feature destinations of a stereo batch: ONE launch of every kernel below over the 2 Bs images, which pick their destination by image index
+  // (one-destination calls pass no second set).
+  const int M = B * cap * 4, Mp = (M + 255) / 256 * 256;
+  {
+    ProfScope ps(c, ST_SELECT, st, 0, (double)B * 8192 * 8);
+    SelectExtra ex;
+    if (two) { ex.feat1 = d_feat1; ex.n_out1 = d_n1; ex.Bs = Bs; }
+    // sparse descriptors: the top-K kernel also writes the four head rows each slot will sample (the gather GEMM's row list; zero for slots k >= n)
+    if (sparse_desc) { ex.desc_idx = c->desc_idx; ex.HC = R / 8; ex.WC = R / 8; }
+    launch_select_list(c->cand, c->cand_cnt, ccap, B, R, c->cfg.max_keypoints, cap, d_feat, d_n, st, &ex);
+  }
+  bool sampled = false;
+  if (sparse_desc) {
+    if (Mp > M) HIPCHK(c, hipMemsetAsync(c->desc_idx + M, 0, (size_t)(Mp - M) * 4, st));
+    GemmArgs g;
+    g.X1 = c->aDa; g.ld1 = 256; g.K1 = 256; g.Wp = c->cDb.w; g.bias = c->cDb.b; g.rowidx = c->desc_idx;
+    g.M = Mp; g.N = 256; g.cb_total = c->cDb.cbt; g.epi = EPI_STORE_F32; g.out = c->desc; g.ldo = 256;
+    g.gr_wgs = c->gemmr_wgs;
+    // large batches: the streaming kernel with gathered rows (kernels_gemmr.hip, GATHER) — the tiled 8-wave kernel ran this HBM-bound shape at 2.3 TB/s; the same bits.
+    // Its SAMPLE form finishes the keypoints from the tile in LDS: no head rows written (1 KB per row) and read back, no sampling launch.
+    const bool stream = c->desc_gather_stream && Mp >= c->gemmr_min && gemmr_gather_applicable(256, g);
+    if (stream && gemmr_gather_sample_applicable(g)) {
+      ProfScope ps(c, ST_HEAD_GEMM, st, 2.0 * Mp * 256 * 256, (double)Mp * 512 + (double)B * c->cfg.max_keypoints * 1036);
+      DescSample ds;
+      ds.feat = d_feat; ds.n = d_n; ds.feat1 = two ? d_feat1 : nullptr; ds.n1 = two ? d_n1 : nullptr; ds.Bs = two ? Bs : B; ds.B = B; ds.cap = cap;
+      ds.HC = R / 8; ds.WC = R / 8; ds.w_scale = (float)w / (float)R; ds.h_scale = (float)h / (float)R; ds.flag = c->sat_flag;
+      launch_gemmr_gather_sample(c->prec, g, ds, st);
+      sampled = true;
+    } else {
+      ProfScope ps(c, ST_HEAD_GEMM, st, 2.0 * Mp * 256 * 256, (double)Mp * (512 + 1024));
+      if (stream) launch_gemmr_gather(c->prec, g, st);
+      else launch_gemm8(c->prec, 256, false, g, st);
+    }
+  }
+  if (!sampled) {
+    ProfScope ps(c, ST_SAMPLE, st, 0, (double)B * c->cfg.max_keypoints * (4096 + 1036));
+    launch_sample_desc(c->desc, B, R / 8, R / 8, d_feat, d_n, cap, (float)w / (float)R, (float)h / (float)R,
+                       sparse_desc ? 1 : (c->desc_normalised ? 0 : 1), st, sparse_desc ? 1 : 0, c->sat_flag, two ? d_feat1 : nullptr, two ? d_n1 : nullptr, Bs);
+  }
+  return launch_status(c);
+}
+
 // Detector over ONE batch of B images, or — d_gray1 != nullptr — over the 2 B images of B stereo pairs in one pass (images 0 .. B-1 from
 // d_gray, B .. 2B-1 from d_gray1; features to d_feat / d_feat1): every whole-batch kernel then runs once over twice the tiles instead
 // of twice (half the launches, prologues and tails of the second half of the network; per-image results do not depend on the batch).
@@ -156,69 +222,23 @@ int detect_dev2(airfe_ctx* c, const uint8_t* d_gray, const uint8_t* d_gray1, int
     c->desc_dense_valid = !sparse_desc;
     c->last_B = B;
   }
-  const int ccap = R * R;
-  {
-    ProfScope ps(c, ST_NMS, st, 0, (double)B * R * R * 8);
-    if (c->cfg.nms_radius == 4) {                        // the reference's radius: simple_nms in registers (kernels_nms512.hip; R = 512)
-      // the dense NMS'd map is consumed only by the batch-1 line path (junction scores) and the inspection hook: large batches skip
-      // its 1 MB / image write (airfe_debug_detector_maps rebuilds it on demand; the batched junction scores come from the keep plane, line_tail_dev)
-      c->nms_map_valid = B <= 2;
-      launch_nms512_candidates(c->heat, c->nms_map_valid ? c->heat_nms : nullptr, c->nms_mask, B, c->cfg.keypoint_threshold,
-                               c->cfg.remove_borders, c->cand, c->cand_cnt, ccap, st);
-    } else if (c->cfg.nms_radius > 0) {
-      c->nms_map_valid = true;
-      launch_simple_nms(c->heat, c->heat_nms, c->nms_tmp, B, R, R, c->cfg.nms_radius, st);
-      launch_candidates(c->heat_nms, B, R, R, c->cfg.keypoint_threshold, c->cfg.remove_borders, c->cand, c->cand_cnt, ccap, st);
-    } else {
-      launch_candidates(c->heat, B, R, R, c->cfg.keypoint_threshold, c->cfg.remove_borders, c->cand, c->cand_cnt, ccap, st);
-    }
-  }
-  // The two feature destinations of a stereo batch: ONE launch of every kernel below over the 2 Bs images, which pick their destination by image index
-  // (one-destination calls pass no second set).
-  const bool two = d_gray1 != nullptr;
-  const int M = B * cap * 4, Mp = (M + 255) / 256 * 256;
-  {
-    ProfScope ps(c, ST_SELECT, st, 0, (double)B * 8192 * 8);
-    SelectExtra ex;
-    if (two) { ex.feat1 = d_feat1; ex.n_out1 = d_n1; ex.Bs = Bs; }
-    // sparse descriptors: the top-K kernel also writes the four head rows each slot will sample (the gather GEMM's row list; zero for slots k >= n)
-    if (sparse_desc) { ex.desc_idx = c->desc_idx; ex.HC = R / 8; ex.WC = R / 8; }
-    launch_select_list(c->cand, c->cand_cnt, ccap, B, R, c->cfg.max_keypoints, cap, d_feat, d_n, st, &ex);
-  }
-  bool sampled = false;
-  if (sparse_desc) {
-    if (Mp > M) HIPCHK(c, hipMemsetAsync(c->desc_idx + M, 0, (size_t)(Mp - M) * 4, st));
-    GemmArgs g;
-    g.X1 = c->aDa; g.ld1 = 256; g.K1 = 256; g.Wp = c->cDb.w; g.bias = c->cDb.b; g.rowidx = c->desc_idx;
-    g.M = Mp; g.N = 256; g.cb_total = c->cDb.cbt; g.epi = EPI_STORE_F32; g.out = c->desc; g.ldo = 256;
-    g.gr_wgs = c->gemmr_wgs;
-    // large batches: the streaming kernel with gathered rows (kernels_gemmr.hip, GATHER) — the tiled 8-wave kernel ran this HBM-bound shape at 2.3 TB/s; the same bits.
-    // Its SAMPLE form finishes the keypoints from the tile in LDS: no head rows written (1 KB per row) and read back, no sampling launch.
-    const bool stream = c->desc_gather_stream && Mp >= c->gemmr_min && gemmr_gather_applicable(256, g);
-    if (stream && gemmr_gather_sample_applicable(g)) {
-      ProfScope ps(c, ST_HEAD_GEMM, st, 2.0 * Mp * 256 * 256, (double)Mp * 512 + (double)B * c->cfg.max_keypoints * 1036);
-      DescSample ds;
-      ds.feat = d_feat; ds.n = d_n; ds.feat1 = two ? d_feat1 : nullptr; ds.n1 = two ? d_n1 : nullptr; ds.Bs = two ? Bs : B; ds.B = B; ds.cap = cap;
-      ds.HC = R / 8; ds.WC = R / 8; ds.w_scale = (float)w / (float)R; ds.h_scale = (float)h / (float)R; ds.flag = c->sat_flag;
-      launch_gemmr_gather_sample(c->prec, g, ds, st);
-      sampled = true;
-    } else {
-      ProfScope ps(c, ST_HEAD_GEMM, st, 2.0 * Mp * 256 * 256, (double)Mp * (512 + 1024));
-      if (stream) launch_gemmr_gather(c->prec, g, st);
-      else launch_gemm8(c->prec, 256, false, g, st);
-    }
-  }
-  if (!sampled) {
-    ProfScope ps(c, ST_SAMPLE, st, 0, (double)B * c->cfg.max_keypoints * (4096 + 1036));
-    launch_sample_desc(c->desc, B, R / 8, R / 8, d_feat, d_n, cap, (float)w / (float)R, (float)h / (float)R,
-                       sparse_desc ? 1 : (c->desc_normalised ? 0 : 1), st, sparse_desc ? 1 : 0, c->sat_flag, two ? d_feat1 : nullptr, two ? d_n1 : nullptr, Bs);
-  }
-  return launch_status(c);
+  return detect_tail_dev(c, B, Bs, d_gray1 != nullptr, sparse_desc, h, w, d_feat, d_feat1, cap, d_n, d_n1, st);
 }
 
 int detect_dev(airfe_ctx* c, const uint8_t* d_gray, int B, int h, int w, int stride, size_t img_stride, float* d_feat,
                int cap, int* d_n, hipStream_t st) {
   return detect_dev2(c, d_gray, nullptr, B, h, w, stride, img_stride, d_feat, nullptr, cap, d_n, nullptr, st);
+}
+
+// get_junctions over c->l_jloc / c->l_joff of stage slots 0 .. nb-1: top-300 of the 3x3-suppressed junction map (score descending, raster ascending on ties) -> juncs_pred
+// in the stage blocks.  Shared by line_branch_dev and the test hook airfe_debug_junctions_topk.
+void junctions_topk_dev(airfe_ctx* c, int nb, hipStream_t st) {
+  const int F = 128, ccap = F * F;
+  launch_candidates_nms3(c->l_jloc, nb, F, F, 1e-30f, c->l_cand, c->l_cand_cnt, ccap, st);      // non_maximum_suppression (3x3) inside the compaction
+  SelectExtra jx;
+  jx.sort_all = 1;                  // fewer than 300 maxima (a flat-topped or saturated jloc): still score order, as the contract's top-k — not detect_point's raster rule
+  launch_select_list(c->l_cand, c->l_cand_cnt, ccap, nb, F, 300, 320, c->l_sel, c->l_nsel, st, &jx);
+  launch_s0_juncs(c->l_sel, c->l_nsel, c->l_joff, c->s0_stage + SG_JUNCS, 300, 320, nb, SG_STRIDE, st);
 }
 
 // PLNet stage-0 LINE branch of images [i0, i0 + nb) of the batch the detector just ran on: fills stage slots 0 .. nb-1 with the Appendix
@@ -273,12 +293,8 @@ int line_branch_dev(airfe_ctx* c, hipStream_t st, int i0, int nb, bool chw) {
                      SG_STRIDE, st);
   else
     launch_s0_decode(c->l_dec, 32, 0, d + SG_LP, c->l_jloc, nullptr, c->l_joff, d + SG_THIN, d + SG_AUX, nullptr, c->l_ta8, nb, SG_STRIDE, st);
-  // get_junctions: top-300 of the 3x3-suppressed junction map (score descending, raster ascending on ties)
-  const int ccap = F * F;
   hipStream_t s3 = st;
-  launch_candidates_nms3(c->l_jloc, nb, F, F, 1e-30f, c->l_cand, c->l_cand_cnt, ccap, s3);      // non_maximum_suppression (3x3) inside the compaction
-  launch_select_list(c->l_cand, c->l_cand_cnt, ccap, nb, F, 300, 320, c->l_sel, c->l_nsel, s3);
-  launch_s0_juncs(c->l_sel, c->l_nsel, c->l_joff, d + SG_JUNCS, 300, 320, nb, SG_STRIDE, s3);
+  junctions_topk_dev(c, nb, s3);
   c->wf_counted = launch_s0_j2l(d + SG_LP, d + SG_JUNCS, 300, NP, 10.0f, d + SG_KEEP, d + SG_MIN, d + SG_MAX, c->wf_counts, nb, SG_STRIDE, chw ? 1 : 0, s3);
   }
   return launch_status(c);

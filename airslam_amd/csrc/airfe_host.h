@@ -388,9 +388,12 @@ bool make_linear(airfe_ctx* c, const float* W, const float* bias, int K, int N, 
 int ensure_tables(airfe_ctx* c, int h, int w);
 int run_conv(airfe_ctx* c, const ConvW& w, const uint16_t* x, uint16_t* y, int B, int H, int W, int pool, int out_pad, hipStream_t st);
 int dense_desc_head(airfe_ctx* c, int B, hipStream_t st);
+int detect_tail_dev(airfe_ctx* c, int B, int Bs, bool two, bool sparse_desc, int h, int w, float* d_feat, float* d_feat1, int cap, int* d_n, int* d_n1,
+                    hipStream_t st);
 int detect_dev2(airfe_ctx* c, const uint8_t* d_gray, const uint8_t* d_gray1, int Bs, int h, int w, int stride, size_t img_stride,
                 float* d_feat, float* d_feat1, int cap, int* d_n, int* d_n1, hipStream_t st);
 int detect_dev(airfe_ctx* c, const uint8_t* d_gray, int B, int h, int w, int stride, size_t img_stride, float* d_feat, int cap, int* d_n, hipStream_t st);
+void junctions_topk_dev(airfe_ctx* c, int nb, hipStream_t st);
 int line_branch_dev(airfe_ctx* c, hipStream_t st, int i0, int nb, bool chw);
 int line_tail_dev(airfe_ctx* c, int i0, int nb, const float* loi_chw, int h, int w, double* d_lines, int capL, int* d_nlines, int* d_lfound,
                   float* d_junc, int capJ, int* d_njunc, int* d_jfound, int nj, hipStream_t st, int phase = 3);

@@ -136,9 +136,11 @@ void launch_candidates_nms3(const float* heat, int B, int H, int W, float thr, u
 //   feat [B][cap][259] rows: score,x,y written (x,y in 512-space, unscaled); n_out [B]
 // feat1 != nullptr: two destinations in one launch — images b >= Bs go to rows / counts b - Bs of feat1 / n_out1.
 // desc_idx != nullptr: also the descriptor head's gather rows of every slot, desc_idx[(b * cap + k) * 4 + tap] = b * HC * WC + cell (k >= n: 0); cap <= 1024
+// sort_all: score order (raster ascending on ties) also when count <= K — get_junctions' top-k, which sorts whatever the count; detect_point's raster rule is the default
 struct SelectExtra {
   float* feat1 = nullptr; int* n_out1 = nullptr; int Bs = 0;
   int* desc_idx = nullptr; int HC = 0, WC = 0;
+  int sort_all = 0;
 };
 void launch_select_list(const unsigned long long* cand, const int* cand_cnt, int cand_cap, int B, int W, int topk, int cap,
                         float* feat, int* n_out, hipStream_t st, const SelectExtra* ex = nullptr);

@@ -104,7 +104,7 @@ void launch_candidates(const float* heat, int B, int H, int W, float thr, int bo
 }
 
 // =============================================================================== exact top-K on the candidate list
-// count <= K : all candidates in RASTER order (unsorted by score)       (plnet.cpp:348-353)
+// count <= K : all candidates in RASTER order (unsorted by score)       (plnet.cpp:348-353) — or, ex.sort_all, in key order like the rest (the junction top-k)
 // count >  K : top K by key descending = score descending, ties by ascending raster index
 // One 1024-thread workgroup per image: MSB radix select on the 49-bit key, then a bitonic sort of <= 1024 survivors.
 // ex.feat1: the images b >= ex.Bs write the second destination (one launch over both sides of a stereo batch).  ex.desc_idx (cap <= 1024): the
@@ -123,8 +123,8 @@ __global__ __launch_bounds__(1024) void select_list_kernel(const u64* __restrict
 
   u64 prefix = 0;
   unsigned remaining = (unsigned)topk;
-  const bool take_all = N <= topk;
-  if (!take_all) {
+  const bool take_all = N <= topk && !ex.sort_all;
+  if (N > topk) {
     const int shifts[5] = {38, 27, 16, 5, 0};
     const int nbits[5] = {11, 11, 11, 11, 5};
     for (int pass = 0; pass < 5; ++pass) {
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(1024) void select_list_kernel(const u64* __restrict
       if (done) break;       // every key under this prefix is selected; the lower threshold bits stay 0
     }
   }
-  const u64 T = prefix | (1ull << 49);
+  const u64 T = prefix | (1ull << 49);                                 // (no select pass ran: the valid bit alone, every key passes)
   if (tid == 0) s_cnt = 0;
   sk[tid] = ~0ull;
   __syncthreads();

@@ -212,6 +212,50 @@ typedef struct airfe_debug_lg_assign_args {
   int32_t* nmatch;                /* [B] */
 } airfe_debug_lg_assign_args;
 int airfe_debug_lg_assign(airfe_ctx* ctx, airfe_debug_lg_assign_args* a);
+/* ---- the index work behind the networks on hand-built maps (tests/test_gpu_detector_tail_pin.py, tests/detector_tail_ref.py): exact ties, plateaus, exact zeros, scores
+ * equal to the threshold, peaks on the border lines — inputs the soft-max maps of real images never hold.  HOST tensors are staged into the context's own buffers and the
+ * launchers production calls run in production's order with production's arguments; nothing here has a kernel of its own.  Each reports an activation-range overflow as the
+ * host entries do. */
+/* Everything airfe's detector runs behind the score head (detect_tail_dev, the function detect_dev2 ends in): NMS by cfg.nms_radius, candidate compaction, top-K
+ * (cfg.max_keypoints, cfg.keypoint_threshold, cfg.remove_borders), the descriptor head and descriptor sampling.  The forms are chosen as production chooses them: by B, cap and
+ * the context's tuning (B <= 2: dense NMS'd map, dense head, sample_desc; B > 2 and cap <= 1024: no dense map, the head as a gather GEMM over the sampled cells — tiled, or
+ * streaming with the sampling inside from airfe_tuning::gemmr_min_m rows on).  heat: finite, in [0, 1].  act: the convDa activations, rounded to the context's 2-byte type on
+ * the way in.  Bs = 0: one destination (feat / n, B images); else B = 2 Bs and images b >= Bs go to feat1 / n1, as in a stereo call.  feat / feat1 / n / n1 are uploaded as the
+ * caller filled them and come back whole, so a sentinel shows every write to a row k >= n[b].  nms_map comes back only where the form wrote it (nms_map_written = 1; the buffer is
+ * left alone otherwise); keep = the final keep plane (radius 4 only; word [image][band][lane], byte = row 8 band + r, bit = column 8 lane + j). */
+typedef struct airfe_debug_detector_tail_args {
+  int B, Bs, h, w, cap;           /* h, w: the image size the keypoints are scaled to */
+  const float* heat;              /* [B][512][512] */
+  const float* act;               /* [B][64][64][256] */
+  float *feat, *feat1;            /* [B or Bs][cap][259], [B - Bs][cap][259] or NULL; in / out */
+  int *n, *n1;                    /* [B or Bs], [B - Bs] or NULL; in / out */
+  float* nms_map;                 /* [B][512][512] or NULL */
+  unsigned long long* keep;       /* [B][64][64] or NULL */
+  int* cand_cnt;                  /* [B] or NULL */
+  int nms_map_written;            /* out */
+} airfe_debug_detector_tail_args;
+int airfe_debug_detector_tail(airfe_ctx* ctx, airfe_debug_detector_tail_args* a);
+/* The line path's filter and junction scan (line_tail_dev's launch_zero16, launch_line_filter, launch_junction_scan; no descriptor sampling) on hand-built stage-1 outputs:
+ * la [B][ld][4] / sc [B][ld] with m2[b] <= ld lines each go to the stage-1 buffers, heat to the score maps.  The point branch's radius-4 NMS runs first, from_plane = 0 with the
+ * dense NMS'd map (the junction scan reads it), 1 without (the scan reads raw scores under the keep plane).  lines / junc are uploaded as the caller filled them and come
+ * back whole: columns 3 .. 258 of every junction row and all rows past the counts keep the caller's sentinel.  nfound / jfound: the true counts (> cap = the overflow).
+ * jmap (optional): junction maps [nj][512][512] bytes that replace the filter's between the two launches — the filter marks no pixel outside the scan's box, so the scan's
+ * own bounds show only on a map that has such pixels. */
+typedef struct airfe_debug_line_post_args {
+  int B, nj, ld, h, w, capL, capJ, from_plane;
+  const float *la, *sc;           /* [B][ld][4], [B][ld] */
+  const int* m2;                  /* [B] */
+  const float* heat;              /* [B][512][512] */
+  double* lines;                  /* [B][capL][4] in / out */
+  int *nlines, *nfound;           /* [B] out */
+  float* junc;                    /* [nj][capJ][259] in / out */
+  int *njunc, *jfound;            /* [nj] out */
+  const unsigned char* jmap;      /* [nj][512][512] or NULL */
+} airfe_debug_line_post_args;
+int airfe_debug_line_post(airfe_ctx* ctx, airfe_debug_line_post_args* a);
+/* get_junctions alone (junctions_topk_dev, the function the line branch calls): jloc [B][128][128], joff [B][2][128][128] -> juncs_pred [B][300][2] (rows past the number of
+ * positive 3x3 maxima: 0, 0) */
+int airfe_debug_junctions_topk(airfe_ctx* ctx, const float* jloc, const float* joff, int B, float* juncs_pred);
 /* error-path test of cfg.check_launches: the NEXT group of launches of profiling stage `stage` (airfe_profile_stage_name's index) is preceded by one
  * deliberately invalid launch (4096 threads per workgroup), so that the entry that makes it must fail with "<stage name>: kernel launch failed: ..." —
  * with check_launches = 0 the same failure surfaces at the pipeline's end without the stage.  -1 disarms. */
