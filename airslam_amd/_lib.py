@@ -120,6 +120,13 @@ class DebugLinePostArgs(C.Structure):
                 + [(n, C.c_void_p) for n in ("la", "sc", "m2", "heat", "lines", "nlines", "nfound", "junc", "njunc", "jfound", "jmap")])
 
 
+class DebugLineMidArgs(C.Structure):
+    """airfe_debug_line_mid_args (include/airfe_debug.h)"""
+    _fields_ = ([(n, C.c_int) for n in ("B", "j2l", "s1_form", "wgs")]
+                + [(n, C.c_void_p) for n in ("juncs_pred", "lines_pred", "thin", "aux", "loi", "iskeep_in", "idx_min_in", "idx_max_in", "iskeep", "idx_min", "idx_max", "counts",
+                                             "keep", "pairs", "rep", "head4", "prop4", "ridx", "proj", "lines_adjusted", "scores_line", "table_dirty")])
+
+
 # name -> (restype, argtypes); every symbol include/*.h declares
 SIGNATURES = {
     "airfe_copy_rows_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -265,6 +272,7 @@ SIGNATURES = {
     "airfe_debug_detector_tail": (C.c_int, [C.c_void_p, C.POINTER(DebugDetectorTailArgs)]),
     "airfe_debug_line_post": (C.c_int, [C.c_void_p, C.POINTER(DebugLinePostArgs)]),
     "airfe_debug_junctions_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "airfe_debug_line_mid": (C.c_int, [C.c_void_p, C.POINTER(DebugLineMidArgs)]),
     "airfe_debug_lg_prepare": (C.c_int, [C.c_void_p, C.POINTER(DebugLgPrepareArgs)]),
     "airfe_debug_lg_assign": (C.c_int, [C.c_void_p, C.POINTER(DebugLgAssignArgs)]),
     "airfe_debug_plnet_stage0": (C.c_int, [C.c_void_p] + [C.c_void_p] * 10),

@@ -520,6 +520,30 @@ class Context:
         self._chk(self._l.airfe_debug_line_post(self._h, C.byref(a)), "airfe_debug_line_post")
         return out
 
+    def debug_line_mid(self, juncs_pred, lines_pred, thin, aux, loi, iskeep=None, idx_min=None, idx_max=None, j2l=0, s1_form=2, wgs=0):
+        """airfe_debug_line_mid (include/airfe_debug.h): the junction-to-line match, the kept list and unique pairs, the junction projections and stage 1 on host tensors
+        juncs_pred [B, 300, 2], lines_pred [B, 49152, 4], thin / aux [B, 4, 128, 128], loi [B, 16384, 128] (pixel-major), iskeep / idx_min / idx_max [B, 49152] (j2l = 0).
+        -> dict of whole device buffers, 0xFF bytes where the run wrote nothing: iskeep, idx_min, idx_max [B, 49152], counts [B, 2], keep [B, 49152], pairs [B, 45056, 2],
+        rep [B, 45056], head4, prop4, lines_adjusted [B, 45056, 4], scores_line [B, 45056], ridx [B, 300, 4], proj [B, 300, 256], table_dirty [B]."""
+        f = lambda x: np.ascontiguousarray(x, np.float32)
+        juncs_pred, lines_pred, thin, aux, loi = f(juncs_pred), f(lines_pred), f(thin), f(aux), f(loi)
+        b, n, cap = juncs_pred.shape[0], 3 * 128 * 128, 45056
+        assert juncs_pred.shape == (b, 300, 2) and lines_pred.shape == (b, n, 4) and thin.shape == aux.shape == (b, 4, 128, 128) and loi.shape == (b, 128 * 128, 128)
+        poison = lambda shape, dt: np.full(shape, -1, np.int32).view(dt) if dt == np.float32 else np.full(shape, -1, np.int32)
+        out = {"iskeep": poison((b, n), np.float32), "idx_min": poison((b, n), np.float32), "idx_max": poison((b, n), np.float32), "counts": poison((b, 2), np.int32),
+               "keep": poison((b, n), np.int32), "pairs": poison((b, cap, 2), np.int32), "rep": poison((b, cap), np.int32), "head4": poison((b, cap, 4), np.float32),
+               "prop4": poison((b, cap, 4), np.float32), "ridx": poison((b, 300, 4), np.int32), "proj": poison((b, 300, 256), np.float32),
+               "lines_adjusted": poison((b, cap, 4), np.float32), "scores_line": poison((b, cap), np.float32), "table_dirty": poison((b,), np.int32)}
+        a = _lib.DebugLineMidArgs(B=b, j2l=int(j2l), s1_form=int(s1_form), wgs=int(wgs), juncs_pred=juncs_pred.ctypes.data, lines_pred=lines_pred.ctypes.data,
+                                  thin=thin.ctypes.data, aux=aux.ctypes.data, loi=loi.ctypes.data, **{k: v.ctypes.data for k, v in out.items()})
+        ins = [None if x is None else f(x) for x in (iskeep, idx_min, idx_max)]
+        for name, x in zip(("iskeep_in", "idx_min_in", "idx_max_in"), ins):
+            if x is not None:
+                assert x.shape == (b, n)
+                setattr(a, name, x.ctypes.data)
+        self._chk(self._l.airfe_debug_line_mid(self._h, C.byref(a)), "airfe_debug_line_mid")
+        return out
+
     def debug_junctions_topk(self, jloc, joff):
         """airfe_debug_junctions_topk (include/airfe_debug.h): jloc [B, 128, 128], joff [B, 2, 128, 128] -> juncs_pred [B, 300, 2]"""
         jloc, joff = np.ascontiguousarray(jloc, np.float32), np.ascontiguousarray(joff, np.float32)

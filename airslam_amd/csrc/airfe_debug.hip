@@ -775,6 +775,142 @@ int airfe_debug_line_post(airfe_ctx* c, airfe_debug_line_post_args* a) try {
   return 0;
 } AIRFE_CATCH(c)
 
+/* the line path between the stage-0 tensors and the line filter (include/airfe_debug.h): line_branch_dev's launch_s0_j2l, then line_tail_dev's launch_wireframe, junction
+ * projections and stage 1 (airfe_detect.hip), on host tensors staged into the stage block and the line-path buffers */
+int airfe_debug_line_mid(airfe_ctx* c, airfe_debug_line_mid_args* a) try {
+  AIRFE_ENTER(c);
+  if (!c->has_sp || !c->has_s0 || !c->has_s1 || !c->s0_stage || !c->l_ta8) return fail(c, "debug_line_mid: the line path is not loaded (line.* tensors, cfg.plnet_s1_pack)");
+  if (!a || !a->juncs_pred || !a->lines_pred || !a->thin || !a->aux || !a->loi || !a->iskeep || !a->idx_min || !a->idx_max || !a->counts || !a->keep || !a->pairs || !a->rep ||
+      !a->head4 || !a->prop4 || !a->ridx || !a->proj || !a->lines_adjusted || !a->scores_line || !a->table_dirty)
+    return fail(c, "debug_line_mid: null argument");
+  const int B = a->B, form = a->s1_form, NP = KEEP_CAP, NPX = 128 * 128;
+  if (B < 1 || B > c->Lmax) return fail(c, "debug_line_mid: 1 <= B <= the arena's images");
+  if (a->j2l < 0 || a->j2l > 2 || form < 0 || form > 3) return fail(c, "debug_line_mid: j2l is 0 .. 2, s1_form 0 .. 3");
+  if (form <= 1 && B != 1) return fail(c, "debug_line_mid: forms 0 and 1 (CHW tensors, head rows) hold one image");
+  if (a->j2l == 0 && (!a->iskeep_in || !a->idx_min_in || !a->idx_max_in)) return fail(c, "debug_line_mid: j2l = 0 needs iskeep_in, idx_min_in and idx_max_in");
+  if (a->wgs < 0 || a->wgs > 512) return fail(c, "debug_line_mid: wgs must lie in 0 .. 512");
+  if (form == 3)
+    for (int i = 0; i < 6; ++i)
+      if (!c->s1_wsplit[i]) return fail(c, "debug_line_mid: form 3 needs the split stage-1 weights");
+  for (size_t i = 0; i < (size_t)B * 600; ++i)
+    if (!std::isfinite(a->juncs_pred[i])) return fail(c, "debug_line_mid: junction coordinates must be finite");
+  for (size_t i = 0; i < (size_t)B * NP * 4; ++i)
+    if (!std::isfinite(a->lines_pred[i])) return fail(c, "debug_line_mid: proposal coordinates must be finite");
+  hipStream_t st = c->stream;
+  float* d = c->s0_stage;
+  clear_saturation(c);
+  // ---- staging: the stage block (juncs | lines_pred | iskeep | min | max | thin | aux), the pixel-major thin | aux copy; 0xFF everywhere the device writes
+  std::vector<float> ta8((size_t)B * NPX * 8);
+  for (int b = 0; b < B; ++b)
+    for (int ch = 0; ch < 8; ++ch) {
+      const float* src = (ch < 4 ? a->thin : a->aux) + ((size_t)b * 4 + (ch & 3)) * NPX;
+      for (int p = 0; p < NPX; ++p) ta8[((size_t)b * NPX + p) * 8 + ch] = src[p];
+    }
+  HIPCHK(c, hipMemcpyAsync(c->l_ta8, ta8.data(), ta8.size() * 4, hipMemcpyHostToDevice, st));
+  for (int b = 0; b < B; ++b) {
+    float* s = d + (size_t)b * SG_STRIDE;
+    HIPCHK(c, hipMemcpyAsync(s + SG_JUNCS, a->juncs_pred + (size_t)b * 600, 600 * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(s + SG_LP, a->lines_pred + (size_t)b * NP * 4, (size_t)NP * 16, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(s + SG_THIN, a->thin + (size_t)b * 4 * NPX, (size_t)4 * NPX * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(s + SG_AUX, a->aux + (size_t)b * 4 * NPX, (size_t)4 * NPX * 4, hipMemcpyHostToDevice, st));
+    if (a->j2l == 0) {
+      HIPCHK(c, hipMemcpyAsync(s + SG_KEEP, a->iskeep_in + (size_t)b * NP, (size_t)NP * 4, hipMemcpyHostToDevice, st));
+      HIPCHK(c, hipMemcpyAsync(s + SG_MIN, a->idx_min_in + (size_t)b * NP, (size_t)NP * 4, hipMemcpyHostToDevice, st));
+      HIPCHK(c, hipMemcpyAsync(s + SG_MAX, a->idx_max_in + (size_t)b * NP, (size_t)NP * 4, hipMemcpyHostToDevice, st));
+    } else {
+      HIPCHK(c, hipMemsetAsync(s + SG_KEEP, 0xFF, (size_t)3 * NP * 4, st));          // (iskeep | min | max are one run of the block)
+    }
+  }
+  static_assert(SG_MIN == SG_KEEP + KEEP_CAP && SG_MAX == SG_MIN + KEEP_CAP, "iskeep | min | max are contiguous");
+  const size_t L = (size_t)B;
+  HIPCHK(c, hipMemsetAsync(c->wf_counts, 0xFF, L * LINE_CNT_LD * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->wf_keep, 0xFF, L * KEEP_CAP * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->wf_pairs, 0xFF, L * LINE_CAP * 8, st));
+  HIPCHK(c, hipMemsetAsync(c->wf_rep, 0xFF, L * LINE_CAP * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->wf_prop, 0xFF, L * LINE_CAP * 16, st));
+  HIPCHK(c, hipMemsetAsync(c->s1_la, 0xFF, L * LINE_CAP * 16, st));
+  HIPCHK(c, hipMemsetAsync(c->s1_sc, 0xFF, L * LINE_CAP * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->s1_jfeat, 0xFF, L * 300 * 256 * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->l_ridx, 0xFF, L * 1200 * 4, st));
+  // ---- line_branch_dev's match
+  bool counted = false;
+  if (a->j2l) counted = launch_s0_j2l(d + SG_LP, d + SG_JUNCS, 300, NP, 10.0f, d + SG_KEEP, d + SG_MIN, d + SG_MAX, c->wf_counts, B, SG_STRIDE, a->j2l == 1 ? 1 : 0, st);
+  if (a->j2l == 2 && !counted) { (void)hipStreamSynchronize(st); return fail(c, "debug_line_mid: the cell search did not leave the per-workgroup counts (the line path's form)"); }
+  // ---- line_tail_dev: the kept list and the unique pairs
+  launch_wireframe(d + SG_KEEP, d + SG_MIN, d + SG_MAX, NP, 300, c->wf_table, c->wf_keep, c->wf_pairs, c->wf_rep, KEEP_CAP, LINE_CAP, c->wf_counts, counted, d + SG_JUNCS,
+                   d + SG_LP, c->s1_la, c->wf_prop, B, SG_STRIDE, st);
+  c->wf_counted = false;
+  HIPCHK(c, hipStreamSynchronize(st));                       // (ta8 is on the device)
+  if (launch_status(c)) return 1;
+  HIPCHK(c, hipMemcpy(a->head4, c->s1_la, L * LINE_CAP * 16, hipMemcpyDeviceToHost));
+  if (form != 3) HIPCHK(c, hipMemsetAsync(c->s1_la, 0xFF, L * LINE_CAP * 16, st));      // stage 1 of forms 0 .. 2 writes lines_adjusted itself
+  // ---- the junction projections and stage 1
+  std::vector<float> chw, head, lrows;                       // (staged with the stream's copies: alive until the synchronisation behind stage 1)
+  if (form == 0) {
+    chw.resize((size_t)128 * NPX);
+    for (int p = 0; p < NPX; ++p)
+      for (int ch = 0; ch < 128; ++ch) chw[(size_t)ch * NPX + p] = a->loi[(size_t)p * 128 + ch];
+    HIPCHK(c, hipMemcpyAsync(c->s0_loi, chw.data(), chw.size() * 4, hipMemcpyHostToDevice, st));
+    launch_plnet_s1(d + SG_JUNCS, d + SG_LP, c->wf_keep, c->wf_pairs, c->wf_rep, c->wf_counts, c->s0_loi, 0, nullptr, nullptr, d + SG_THIN, d + SG_AUX, c->s1_w, c->s1_la,
+                    c->s1_sc, KEEP_CAP, LINE_CAP, B, SG_STRIDE, st, a->wgs);
+  } else {
+    if (form == 1) {
+      head.resize((size_t)NPX * 160);
+      memset(head.data(), 0xFF, head.size() * 4);            // (columns 128 .. 159: the 17 decoded channels, which nothing behind stage 0 reads)
+      for (int p = 0; p < NPX; ++p) memcpy(&head[(size_t)p * 160], a->loi + (size_t)p * 128, 128 * 4);
+      HIPCHK(c, hipMemcpyAsync(c->l_head, head.data(), head.size() * 4, hipMemcpyHostToDevice, st));
+      launch_s1_junc_proj(d + SG_JUNCS, c->l_head, (size_t)128 * 128 * 160, 160, nullptr, 300, c->s1_w[0], c->s1_jfeat, B, SG_STRIDE, st);
+    } else {
+      const int M = B * 1200, Mp = (M + 255) / 256 * 256;
+      launch_s1_junc_rows(d + SG_JUNCS, 300, c->l_ridx, B, SG_STRIDE, st);
+      if (Mp > M) HIPCHK(c, hipMemsetAsync(c->l_ridx + M, 0, (size_t)(Mp - M) * 4, st));
+      HIPCHK(c, hipStreamSynchronize(st));
+      if (launch_status(c)) return 1;
+      std::vector<int> ridx((size_t)M);
+      HIPCHK(c, hipMemcpy(ridx.data(), c->l_ridx, ridx.size() * 4, hipMemcpyDeviceToHost));
+      lrows.resize((size_t)M * 128);
+      for (int r = 0; r < M; ++r) {                          // what the gather GEMM hands on: row ridx[r] of the [B * 128*128][128] line-feature matrix
+        const int b = r / 1200;
+        if (ridx[r] < b * NPX || ridx[r] >= (b + 1) * NPX) return fail(c, "debug_line_mid: launch_s1_junc_rows listed a row outside its image");
+        memcpy(&lrows[(size_t)r * 128], a->loi + (size_t)ridx[r] * 128, 128 * 4);
+      }
+      HIPCHK(c, hipMemcpyAsync(c->l_lrows, lrows.data(), lrows.size() * 4, hipMemcpyHostToDevice, st));
+      if (form == 3) launch_s1h_junc_proj(d + SG_JUNCS, c->l_lrows, 300, c->s1_wsplit[4], c->s1_wsplit[5], c->s1_jfeat, B, SG_STRIDE, st);
+      else launch_s1_junc_proj(d + SG_JUNCS, nullptr, 0, 0, c->l_lrows, 300, c->s1_w[0], c->s1_jfeat, B, SG_STRIDE, st);
+    }
+    if (form == 3)
+      launch_plnet_s1h(c->wf_pairs, c->wf_counts, c->s1_jfeat, c->l_ta8, c->s1_wsplit, c->s1_w, c->s1_la, c->wf_prop, c->s1_sc, LINE_CAP, B, st, a->wgs);
+    else
+      launch_plnet_s1(d + SG_JUNCS, d + SG_LP, c->wf_keep, c->wf_pairs, c->wf_rep, c->wf_counts, nullptr, 0, c->s1_jfeat, c->l_ta8, d + SG_THIN, d + SG_AUX, c->s1_w,
+                      c->s1_la, c->s1_sc, KEEP_CAP, LINE_CAP, B, SG_STRIDE, st, a->wgs);
+  }
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (launch_status(c)) return 1;
+  if (saturation_status(c)) return 1;
+  // ---- everything back as the device left it
+  const size_t np4 = (size_t)NP * 4;
+  HIPCHK(c, hipMemcpy2D(a->iskeep, np4, d + SG_KEEP, SG_STRIDE * 4, np4, B, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy2D(a->idx_min, np4, d + SG_MIN, SG_STRIDE * 4, np4, B, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy2D(a->idx_max, np4, d + SG_MAX, SG_STRIDE * 4, np4, B, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy2D(a->counts, 8, c->wf_counts, LINE_CNT_LD * 4, 8, B, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->keep, c->wf_keep, L * KEEP_CAP * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->pairs, c->wf_pairs, L * LINE_CAP * 8, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->rep, c->wf_rep, L * LINE_CAP * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->prop4, c->wf_prop, L * LINE_CAP * 16, hipMemcpyDeviceToHost));
+  if (form >= 2) HIPCHK(c, hipMemcpy(a->ridx, c->l_ridx, L * 1200 * 4, hipMemcpyDeviceToHost));
+  if (form >= 1) HIPCHK(c, hipMemcpy(a->proj, c->s1_jfeat, L * 300 * 256 * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->lines_adjusted, c->s1_la, L * LINE_CAP * 16, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->scores_line, c->s1_sc, L * LINE_CAP * 4, hipMemcpyDeviceToHost));
+  std::vector<int> table(L * 300 * 300);
+  HIPCHK(c, hipMemcpy(table.data(), c->wf_table, table.size() * 4, hipMemcpyDeviceToHost));
+  for (int b = 0; b < B; ++b) {
+    int dirty = 0;
+    for (size_t i = 0; i < (size_t)300 * 300; ++i) dirty += table[(size_t)b * 300 * 300 + i] != 0x7FFFFFFF;
+    a->table_dirty[b] = dirty;
+  }
+  return 0;
+} AIRFE_CATCH(c)
+
 int airfe_debug_junctions_topk(airfe_ctx* c, const float* jloc, const float* joff, int B, float* juncs_pred) try {
   AIRFE_ENTER(c);
   if (!c->has_s0 || !c->s0_stage) return fail(c, "debug_junctions_topk: the line branch is not loaded (line.* tensors, cfg.plnet_s1_pack)");

@@ -233,12 +233,13 @@ void launch_s1_junc_proj(const float* juncs, const float* head, size_t head_img,
 void launch_plnet_s1(const float* juncs, const float* lines_pred, const int* keep, const int* pairs, const int* rep,
                      const int* counts, const float* loi, size_t loi_img, const float* proj, const float* ta8, const float* thin,
                      const float* aux, const float* const* w, float* lines_adjusted, float* scores_line, int keep_cap, int line_cap, int B,
-                     size_t stage_stride, hipStream_t st);
+                     size_t stage_stride, hipStream_t st, int wgs = 0);
 // the device path of launch_plnet_s1 (proj + ta8) with the dense layers on the 2-byte matrix pipe, operands as fp16 (hi, lo) pairs (cfg.line_precision = 3):
 // wsplit[4] = the fp16 (hi, lo) fragments of fc2.0's thin / aux columns, fc2_res.0, fc2.2, fc2.4 (airfe_load.hip); w = the fp32 set (biases, head, sample_t);
 // lines_adjusted / prop4 = launch_wireframe's head4 / prop4
+// wgs (both stage-1 launchers): workgroups per image instead of the rule by B (0: the rule; the kernel tests wrap the tile loop with it, as ConvArgs::wgs does)
 void launch_plnet_s1h(const int* pairs, const int* counts, const float* proj, const float* ta8, const uint16_t* const* wsplit, const float* const* w,
-                      const float* lines_adjusted, const float* prop4, float* scores_line, int line_cap, int B, hipStream_t st);
+                      const float* lines_adjusted, const float* prop4, float* scores_line, int line_cap, int B, hipStream_t st, int wgs = 0);
 // launch_s1_junc_proj's gather form (lrows) on the same pipe: wa / wb = the (hi, lo) planes [2][128][128] of fc2.0's columns 0..127 / 128..255
 void launch_s1h_junc_proj(const float* juncs, const float* lrows, int jn, const uint16_t* wa, const uint16_t* wb, float* proj, int B, size_t stage_stride,
                           hipStream_t st);

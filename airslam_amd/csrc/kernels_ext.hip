@@ -908,10 +908,10 @@ void launch_s1h_junc_proj(const float* juncs, const float* lrows, int jn, const 
 }
 
 void launch_plnet_s1h(const int* pairs, const int* counts, const float* proj, const float* ta8, const uint16_t* const* wsplit /*w0 wr w2 w4*/, const float* const* w,
-                      const float* lines_adjusted, const float* prop4, float* scores_line, int line_cap, int B, hipStream_t st) {
+                      const float* lines_adjusted, const float* prop4, float* scores_line, int line_cap, int B, hipStream_t st, int wgs) {
   S1WeightsH sw{wsplit[0], wsplit[1], wsplit[2], wsplit[3], w[1], w[7], w[3], w[5], w[8], w[9], w[10]};
   S1Loi sl{nullptr, 0, 128 * 128, 1, proj, 300, ta8};
-  const int gx = B == 1 ? 512 : (B <= 8 ? 128 : 64);
+  const int gx = wgs > 0 ? wgs : (B == 1 ? 512 : (B <= 8 ? 128 : 64));
   hipLaunchKernelGGL(plnet_s1h_kernel, dim3(gx, B), dim3(256), 0, st, pairs, counts, sl, sw, lines_adjusted, prop4, scores_line, line_cap);
 }
 
@@ -922,10 +922,10 @@ void launch_plnet_s1h(const int* pairs, const int* counts, const float* proj, co
 void launch_plnet_s1(const float* juncs, const float* lines_pred, const int* keep, const int* pairs, const int* rep,
                      const int* counts, const float* loi, size_t loi_img, const float* proj, const float* ta8, const float* thin,
                      const float* aux, const float* const* w, float* lines_adjusted, float* scores_line, int keep_cap, int line_cap, int B,
-                     size_t stage_stride, hipStream_t st) {
+                     size_t stage_stride, hipStream_t st, int wgs) {
   S1Weights sw{w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], w[9], w[10]};
   S1Loi sl{loi, loi_img, 128 * 128, 1, proj, 300, ta8};
-  const int gx = B == 1 ? 512 : (B <= 8 ? 128 : 64);
+  const int gx = wgs > 0 ? wgs : (B == 1 ? 512 : (B <= 8 ? 128 : 64));
   if (proj && ta8)
     hipLaunchKernelGGL(plnet_s1_kernel<true>, dim3(gx, B), dim3(256), 0, st, juncs, lines_pred, keep, pairs, rep, counts, sl, thin, aux, sw,
                        lines_adjusted, scores_line, keep_cap, line_cap, stage_stride);

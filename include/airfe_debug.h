@@ -256,6 +256,45 @@ int airfe_debug_line_post(airfe_ctx* ctx, airfe_debug_line_post_args* a);
 /* get_junctions alone (junctions_topk_dev, the function the line branch calls): jloc [B][128][128], joff [B][2][128][128] -> juncs_pred [B][300][2] (rows past the number of
  * positive 3x3 maxima: 0, 0) */
 int airfe_debug_junctions_topk(airfe_ctx* ctx, const float* jloc, const float* joff, int B, float* juncs_pred);
+/* ---- the line path between the stage-0 tensors and the line filter, one launcher at a time (tests/test_gpu_line_mid_pin.py, tests/line_mid_ref.py): the junction-to-line
+ * match (launch_s0_j2l), the kept list and the unique pairs (launch_wireframe), the junctions' tap rows and projections (launch_s1_junc_rows, launch_s1_junc_proj,
+ * launch_s1h_junc_proj) and stage 1 (launch_plnet_s1, launch_plnet_s1h) on hand-built HOST tensors: exact ties, threshold-exact distances, junctions on cell borders, (0, 0)
+ * padding junctions, more than 8192 kept proposals (wireframe_kernel's long path), more line tiles than workgroups (the stage-1 kernels' tile hand-over).  The tensors are
+ * staged into the context's own line-path buffers and the launchers production calls run in production's order with production's arguments (line_branch_dev / line_tail_dev);
+ * nothing here has a kernel of its own.  B <= the arena's images.
+ *   j2l: 0 = iskeep_in / idx_min_in / idx_max_in are staged as given (launch_wireframe counts the kept proposals itself: counted = false); 1 = launch_s0_j2l's brute-force
+ *     kernel (exact_all = 1); 2 = the line path's call (exact_all = 0, the cell search) with `counts` passed, its return value going to launch_wireframe as `counted`.
+ *   s1_form: 0 = launch_plnet_s1 on the contract's CHW tensors (loi transposed on the host; B = 1); 1 = launch_s1_junc_proj from head rows (loi staged at pitch 160, B = 1) +
+ *     plnet_s1_kernel<true>; 2 = launch_s1_junc_rows, tap rows, launch_s1_junc_proj(lrows), plnet_s1_kernel<true>; 3 = launch_s1_junc_rows, tap rows,
+ *     launch_s1h_junc_proj, launch_plnet_s1h.  Forms 2 and 3: the hook reads ridx back and gathers the four tap rows of every junction from the host loi ON THE HOST (the
+ *     gather GEMM is pinned by tests/test_gpu_linear_kernels.py), every index checked against the image's 16384 rows first.
+ *   wgs: workgroups per image of the stage-1 launch (0 = production's rule by B; lower, and a workgroup walks several 32-line tiles).
+ * EVERY output buffer is 0xFF bytes when the launches start (iskeep / idx_min / idx_max only where the device computes them), and all of it comes back as the device left
+ * it, capacity rows included: a finite or valid entry was written by this run.  head4 is read back between launch_wireframe and stage 1, and the buffer — production's
+ * lines_adjusted — is 0xFF again before forms 0 .. 2 run (their kernel writes lines_adjusted itself; form 3 reads what launch_wireframe left).  table_dirty[b] = entries of
+ * image b's pair table that are not 0x7FFFFFFF after the run (wireframe_kernel promises to leave it clean; the hook does not repair it).
+ * Refused before any launch, the context left usable: B outside the arena; forms 0 and 1 with B > 1; j2l = 0 without the three index tensors; wgs outside 0 .. 512; form 3
+ * without the split weights; a j2l or s1_form outside the lists above; a junction or proposal coordinate that is not finite.
+ * LINE_CAP (45056) exceeds the 44850 pairs 300 junctions can form and KEEP_CAP equals the proposal count, so the launchers' overflow branches (pos >= cap, pos >= line_cap,
+ * min(m1, cap)) cannot be reached through production's arguments and stay untested. */
+typedef struct airfe_debug_line_mid_args {
+  int B, j2l, s1_form, wgs;
+  const float* juncs_pred;                            /* [B][300][2] */
+  const float* lines_pred;                            /* [B][49152][4] */
+  const float *thin, *aux;                            /* [B][4][128][128]: staged as the CHW planes and as the pixel-major thin | aux copy */
+  const float* loi;                                   /* [B][128*128][128] pixel-major */
+  const float *iskeep_in, *idx_min_in, *idx_max_in;   /* [B][49152] (j2l = 0) or NULL */
+  float *iskeep, *idx_min, *idx_max;                  /* [B][49152] out */
+  int32_t* counts;                                    /* [B][2] out: M1, M2 */
+  int32_t* keep;                                      /* [B][49152] out */
+  int32_t *pairs, *rep;                               /* [B][45056][2], [B][45056] out */
+  float *head4, *prop4;                               /* [B][45056][4] out */
+  int32_t* ridx;                                      /* [B][300][4] out (forms 2, 3; else left alone) */
+  float* proj;                                        /* [B][300][256] out (forms 1 .. 3; else left alone) */
+  float *lines_adjusted, *scores_line;                /* [B][45056][4], [B][45056] out */
+  int32_t* table_dirty;                               /* [B] out */
+} airfe_debug_line_mid_args;
+int airfe_debug_line_mid(airfe_ctx* ctx, airfe_debug_line_mid_args* a);
 /* error-path test of cfg.check_launches: the NEXT group of launches of profiling stage `stage` (airfe_profile_stage_name's index) is preceded by one
  * deliberately invalid launch (4096 threads per workgroup), so that the entry that makes it must fail with "<stage name>: kernel launch failed: ..." —
  * with check_launches = 0 the same failure surfaces at the pipeline's end without the stage.  -1 disarms. */
