@@ -796,6 +796,54 @@ class Context:
                                                         u_right_t.data_ptr(), depth_t.data_ptr(), xyz_t.data_ptr(), good_t.data_ptr(), self._stream(stream)),
                   "airfe_stereo_points_batch_dev")
 
+    def stereo_lines(self, cam, lines_left: np.ndarray, lines_right: np.ndarray, line_matches: np.ndarray, Twc=None):
+        """The loop of Frame::AddRightFeatures over the line matches (src/frame.cc:185-191) + TriangulateByStereo + ComputeLine3DFromEndpoints on ONE
+        frame (airfe_stereo_lines, host only): cam as stereo_points, lines [n,4] float64, line_matches [nL] (match_lines' output), Twc [4,4] or None
+        -> dict(lines_right_sel [nL,4], right_valid [nL] uint8, status [nL] int32, endpoints [nL,6], plucker [nL,6] (NaN unset), count [3] int32)."""
+        cam = np.ascontiguousarray(cam, np.float64).reshape(8)
+        ll = np.ascontiguousarray(lines_left, np.float64).reshape(-1, 4)
+        lr = np.ascontiguousarray(lines_right, np.float64).reshape(-1, 4)
+        lm = np.ascontiguousarray(line_matches, np.int32).reshape(-1)
+        if len(lm) != len(ll):
+            raise ValueError("stereo_lines: one match per left line")
+        twc = None if Twc is None else np.ascontiguousarray(Twc, np.float64).reshape(16)
+        n = len(ll)
+        m = max(n, 1)
+        sel, valid, status = np.empty((m, 4)), np.empty(m, np.uint8), np.empty(m, np.int32)
+        ends, plk, count = np.empty((m, 6)), np.empty((m, 6)), np.empty(3, np.int32)
+        self._chk(self._l.airfe_stereo_lines(self._h, cam.ctypes.data, ll.ctypes.data, n, lr.ctypes.data if len(lr) else None, len(lr), lm.ctypes.data,
+                                             None if twc is None else twc.ctypes.data, sel.ctypes.data, valid.ctypes.data, status.ctypes.data,
+                                             ends.ctypes.data, plk.ctypes.data, count.ctypes.data), "airfe_stereo_lines")
+        return dict(lines_right_sel=sel[:n], right_valid=valid[:n], status=status[:n], endpoints=ends[:n], plucker=plk[:n], count=count)
+
+    def stereo_lines_batch_dev(self, cam, lines_left_t, nlines_left_t, lines_right_t, nlines_right_t, line_matches_t, Twc_t, lines_right_sel_t,
+                               right_valid_t, status_t, endpoints_t, plucker_t, count_t, stream=None):
+        """airfe_stereo_lines_batch_dev: lines [B,capL,4] float64 + nlines [B] per side (the halves of stereo_plnet_batch_dev's line buffer, in place),
+        line_matches_t [B,capL] int32, Twc_t [B,16] float64 or None -> lines_right_sel_t [B,capL,4], right_valid_t [B,capL] uint8, status_t [B,capL]
+        int32, endpoints_t / plucker_t [B,capL,6] float64, count_t [B,3] int32."""
+        cam = np.ascontiguousarray(cam, np.float64).reshape(8)
+        self._chk(self._l.airfe_stereo_lines_batch_dev(
+            self._h, cam.ctypes.data, lines_left_t.data_ptr(), nlines_left_t.data_ptr(), lines_right_t.data_ptr(), nlines_right_t.data_ptr(),
+            lines_left_t.shape[1], line_matches_t.data_ptr(), None if Twc_t is None else Twc_t.data_ptr(), lines_left_t.shape[0],
+            lines_right_sel_t.data_ptr(), right_valid_t.data_ptr(), status_t.data_ptr(), endpoints_t.data_ptr(), plucker_t.data_ptr(), count_t.data_ptr(),
+            self._stream(stream)), "airfe_stereo_lines_batch_dev")
+
+    def stereo_line_landmarks_batch_dev(self, cam, lines_left_t, nlines_left_t, lines_right_t, nlines_right_t, featL_t, nL_t, featR_t, nR_t, idx_t, nm_t,
+                                        Twc_t, relL, relR, line_matches_t, lines_right_sel_t, right_valid_t, status_t, endpoints_t, plucker_t, count_t,
+                                        stream=None):
+        """airfe_stereo_line_landmarks_batch_dev: the line half of a stereo keyframe on one stream (assign_points_to_lines_batch_dev on both sides,
+        match_lines_batch_dev with the band cam[0:3], stereo_lines_batch_dev).  relL / relR = (row_ptr [B,capL+1] i32, pt_idx [B,capE] i32, pt_dist
+        [B,capE] f64, total [B] i32 or None): the caller's relation buffers; line_matches_t [B,capL] i32; the rest as stereo_lines_batch_dev."""
+        cam = np.ascontiguousarray(cam, np.float64).reshape(8)
+        tot = [None if r[3] is None else r[3].data_ptr() for r in (relL, relR)]
+        self._chk(self._l.airfe_stereo_line_landmarks_batch_dev(
+            self._h, cam.ctypes.data, lines_left_t.data_ptr(), nlines_left_t.data_ptr(), lines_right_t.data_ptr(), nlines_right_t.data_ptr(),
+            lines_left_t.shape[1], featL_t.data_ptr(), nL_t.data_ptr(), featR_t.data_ptr(), nR_t.data_ptr(), featL_t.shape[1], idx_t.data_ptr(),
+            nm_t.data_ptr(), idx_t.shape[1], None if Twc_t is None else Twc_t.data_ptr(), lines_left_t.shape[0], relL[0].data_ptr(), relL[1].data_ptr(),
+            relL[2].data_ptr(), tot[0], relR[0].data_ptr(), relR[1].data_ptr(), relR[2].data_ptr(), tot[1], relL[1].shape[1],
+            line_matches_t.data_ptr(), lines_right_sel_t.data_ptr(), right_valid_t.data_ptr(), status_t.data_ptr(), endpoints_t.data_ptr(),
+            plucker_t.data_ptr(), count_t.data_ptr(), self._stream(stream)), "airfe_stereo_line_landmarks_batch_dev")
+
     def track_pose_batch_dev(self, K, xyz_t, feat_t, tidx_t, ntrack_t, Twc_t, mask_t, count_t, Rt_t=None, stream=None):
         """airfe_track_pose_batch_dev: keyframe points xyz_t [B,capK,3] float64, current rows feat_t [B,cap,259], temporal lists tidx_t [B,mcap,2]
         (keyframe, current) + ntrack_t [B] -> Twc_t [B,16], mask_t [B,mcap] uint8 (per list entry), count_t [B], Rt_t [B,12] (optional)."""

@@ -1,5 +1,5 @@
-// airfe — the geometry entries of libairfe.so (include/airfe.h): F-matrix RANSAC, PnP RANSAC, stereo back-projection, track pose and the pose-only frame
-// optimisation, each as a *_queue function on a stream (the composites of airfe_bowdb.hip and the keyframe / track entries of airfe.hip queue the same code)
+// airfe — the geometry entries of libairfe.so (include/airfe.h): F-matrix RANSAC, PnP RANSAC, stereo back-projection, track pose, the pose-only frame
+// optimisation and stereo line triangulation, each as a *_queue function on a stream (the composites of airfe_bowdb.hip and the keyframe / track entries of airfe.hip queue the same code)
 // and its host and batch entries.
 #include "airfe_host.h"
 #include "fransac_core.h"
@@ -286,6 +286,77 @@ int airfe_track_pose_opt_batch_dev(airfe_ctx* c, const double* cam, const double
   launch_poseopt_gather(q, B, st);
   HIPCHK(c, hipGetLastError());
   return poseopt_queue(c, q.X, q.obs, g.n, B, mcap, q.Twc0, cam, nullptr, thr, d_Twc, d_Rt, d_mask, mcap, g.map, d_num, lost_num_match, d_ok, st);
+} AIRFE_CATCH(c)
+
+}  // extern "C"
+
+// Stereo line triangulation (frame.cc:185-191, line_processor.cc:196-245, :312-326) over B device frames on `st` (kernels_stereoline.hip): the counts are
+// zeroed on the stream, then one launch.  No scratch, nothing allocated.
+int stereo_lines_queue(airfe_ctx* c, const double* cam, const double* d_left, const int* d_nl, const double* d_right, const int* d_nr, int capL,
+                       const int32_t* d_matches, const double* d_Twc, int B, double* d_sel, uint8_t* d_valid, int32_t* d_status, double* d_endpoints,
+                       double* d_plucker, int32_t* d_count, hipStream_t st) {
+  StereoLineArgs a;
+  a.left = d_left; a.right = d_right; a.nl = d_nl; a.nr = d_nr; a.capL = capL; a.matches = d_matches; a.Twc = d_Twc;
+  for (int k = 0; k < 8; ++k) a.cam[k] = cam[k];
+  a.sel = d_sel; a.valid = d_valid; a.status = d_status; a.endpoints = d_endpoints; a.plucker = d_plucker; a.count = d_count;
+  ProfScope ps(c, ST_LINE_ASSOC, st, 0, (double)B * (double)capL * 176);
+  HIPCHK(c, hipMemsetAsync(d_count, 0, (size_t)B * 12, st));
+  launch_stereo_lines(a, B, st);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+extern "C" {
+
+int airfe_stereo_lines(airfe_ctx* c, const double* cam, const double* lines_left, int nL, const double* lines_right, int nR, const int32_t* line_matches,
+                       const double* Twc, double* lines_right_sel, uint8_t* right_valid, int32_t* status, double* endpoints, double* plucker,
+                       int32_t* count) try {
+  if (!c) return 1;
+  if (!cam || !count || nL < 0 || nR < 0 || (nR > 0 && !lines_right) ||
+      (nL > 0 && (!lines_left || !line_matches || !lines_right_sel || !right_valid || !status || !endpoints || !plucker)))
+    return fail(c, "stereo_lines: bad argument");
+  stereo_lines_host(cam, lines_left, nL, lines_right, nR, line_matches, Twc, lines_right_sel, right_valid, status, endpoints, plucker, count);
+  return 0;
+} AIRFE_CATCH(c)
+
+int airfe_stereo_lines_batch_dev(airfe_ctx* c, const double* cam, const double* d_lines_left, const int* d_nlines_left, const double* d_lines_right,
+                                 const int* d_nlines_right, int capL, const int32_t* d_line_matches, const double* d_Twc, int B, double* d_lines_right_sel,
+                                 uint8_t* d_right_valid, int32_t* d_status, double* d_endpoints, double* d_plucker, int32_t* d_count, void* stream) try {
+  AIRFE_ENTER(c);
+  if (B < 1 || B > 65535 || capL < 1 || !cam || !d_lines_left || !d_nlines_left || !d_lines_right || !d_nlines_right || !d_line_matches)
+    return fail(c, "stereo_lines_batch_dev: bad argument");
+  if (!d_lines_right_sel || !d_right_valid || !d_status || !d_endpoints || !d_plucker || !d_count) return fail(c, "stereo_lines_batch_dev: null output");
+  return stereo_lines_queue(c, cam, d_lines_left, d_nlines_left, d_lines_right, d_nlines_right, capL, d_line_matches, d_Twc, B, d_lines_right_sel,
+                            d_right_valid, d_status, d_endpoints, d_plucker, d_count, stream ? (hipStream_t)stream : c->stream);
+} AIRFE_CATCH(c)
+
+int airfe_stereo_line_landmarks_batch_dev(airfe_ctx* c, const double* cam, const double* d_lines_left, const int* d_nlines_left, const double* d_lines_right,
+                                          const int* d_nlines_right, int capL, const float* d_featL, const int* d_nL, const float* d_featR, const int* d_nR,
+                                          int cap, const int32_t* d_idx, const int* d_nmatch, int mcap, const double* d_Twc, int B, int32_t* d_row_ptrL,
+                                          int32_t* d_pt_idxL, double* d_pt_distL, int* d_totalL, int32_t* d_row_ptrR, int32_t* d_pt_idxR, double* d_pt_distR,
+                                          int* d_totalR, int capE, int32_t* d_line_matches, double* d_lines_right_sel, uint8_t* d_right_valid,
+                                          int32_t* d_status, double* d_endpoints, double* d_plucker, int32_t* d_count, void* stream) try {
+  AIRFE_ENTER(c);
+  if (B < 1 || B > 65535 || capL < 1 || cap < 1 || mcap < 1 || capE < 1 || !cam || !d_lines_left || !d_nlines_left || !d_lines_right || !d_nlines_right ||
+      !d_featL || !d_nL || !d_featR || !d_nR || !d_idx || !d_nmatch)
+    return fail(c, "stereo_line_landmarks_batch_dev: bad argument");
+  if (!d_row_ptrL || !d_pt_idxL || !d_pt_distL || !d_row_ptrR || !d_pt_idxR || !d_pt_distR || !d_line_matches || !d_lines_right_sel || !d_right_valid ||
+      !d_status || !d_endpoints || !d_plucker || !d_count)
+    return fail(c, "stereo_line_landmarks_batch_dev: null output");
+  void* st = stream ? stream : (void*)c->stream;
+  // frame.cc:125, :177, :184 through the entries a caller would chain by hand, unchanged (association and match have no *_queue function: their public
+  // entries are called as they are, each with its own argument check, device check and catch, and its own scratch block in the context, which grows
+  // behind a stream synchronisation on the first call or a larger shape); then the loop of :185-191 and Map::InsertKeyframe's (map.cc:81-95)
+  if (airfe_assign_points_to_lines_batch_dev(c, d_lines_left, d_nlines_left, capL, d_featL, d_nL, cap, B, d_row_ptrL, d_pt_idxL, d_pt_distL, capE, d_totalL, st))
+    return 1;
+  if (airfe_assign_points_to_lines_batch_dev(c, d_lines_right, d_nlines_right, capL, d_featR, d_nR, cap, B, d_row_ptrR, d_pt_idxR, d_pt_distR, capE, d_totalR,
+                                             st))
+    return 1;
+  if (airfe_match_lines_batch_dev(c, d_row_ptrL, d_pt_idxL, d_nlines_left, d_nL, d_row_ptrR, d_pt_idxR, d_nlines_right, d_nR, capL, capE, d_idx, d_nmatch, mcap,
+                                  B, cam, d_featL, d_featR, cap, d_line_matches, st))
+    return 1;
+  return stereo_lines_queue(c, cam, d_lines_left, d_nlines_left, d_lines_right, d_nlines_right, capL, d_line_matches, d_Twc, B, d_lines_right_sel, d_right_valid,
+                            d_status, d_endpoints, d_plucker, d_count, (hipStream_t)st);
 } AIRFE_CATCH(c)
 
 }  // extern "C"

@@ -5,7 +5,7 @@
 //   airfe_match.hip   LightGlue / SuperGlue forwards and the fault-hunting trace
 //   airfe.hip         context life cycle, scratch blocks, profiling / trace entries and the C ABI of detection, rectification, matching, lines, PLNet and the
 //                     keyframe / track / promote entries (include/airfe.h), with the inspection hooks that share a body with one of them
-//   airfe_geom.hip    F-RANSAC, PnP, stereo points, track pose, frame optimisation
+//   airfe_geom.hip    F-RANSAC, PnP, stereo points, track pose, frame optimisation, stereo lines
 //   airfe_bowdb.hip   the BoW vector, the keyframe database, the relocalisation and loop detection composites
 //   airfe_debug.hip   the kernel-level test hooks (include/airfe_debug.h)
 #pragma once
@@ -452,3 +452,6 @@ int pnp_queue(airfe_ctx* c, const float* d_obj, const float* d_img, const int* d
               int mcap, const int* d_map, int* d_count, hipStream_t st);
 int poseopt_queue(airfe_ctx* c, const double* d_X, const double* d_obs, const int* d_n, int B, int ncap, const double* d_Twc0, const double* cam, const double* Tcb,
                   const double* thr, double* d_Twc, double* d_Rt, uint8_t* d_inlier, int mcap, const int* d_map, int* d_num, int lost, int* d_ok, hipStream_t st);
+int stereo_lines_queue(airfe_ctx* c, const double* cam, const double* d_left, const int* d_nl, const double* d_right, const int* d_nr, int capL,
+                       const int32_t* d_matches, const double* d_Twc, int B, double* d_sel, uint8_t* d_valid, int32_t* d_status, double* d_endpoints,
+                       double* d_plucker, int32_t* d_count, hipStream_t st);

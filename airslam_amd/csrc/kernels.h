@@ -398,6 +398,23 @@ struct StereoArgs {
   int* good = nullptr;                          // [B]
 };
 void launch_stereo_points(const StereoArgs& s, int B, hipStream_t st);
+// Stereo line triangulation (frame.cc:185-191, TriangulateByStereo, ComputeLine3DFromEndpoints) over B device frames (kernels_stereoline.hip;
+// contract: include/airfe.h "Stereo lines", one statement: stereoline_core.h)
+struct StereoLineArgs {
+  const double *left = nullptr, *right = nullptr;     // [B][capL][4] each
+  const int *nl = nullptr, *nr = nullptr;             // [B]
+  int capL = 0;
+  const int32_t* matches = nullptr;                   // [B][capL]
+  const double* Twc = nullptr;                        // [B][16] or nullptr
+  double cam[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double* sel = nullptr; uint8_t* valid = nullptr; int32_t* status = nullptr;   // [B][capL][4], [B][capL], [B][capL]
+  double *endpoints = nullptr, *plucker = nullptr;    // [B][capL][6] each
+  int32_t* count = nullptr;                           // [B][3], zero before the launch: the kernel adds
+};
+void launch_stereo_lines(const StereoLineArgs& a, int B, hipStream_t st);
+// the host side of the same statement over one frame, compiled in the kernel's translation unit (the same -ffp-contract=off)
+void stereo_lines_host(const double* cam, const double* lines_left, int nl, const double* lines_right, int nr, const int32_t* matches, const double* Twc,
+                       double* sel, uint8_t* valid, int32_t* status, double* endpoints, double* plucker, int32_t* count);
 
 // Pose-only frame optimisation (FrameOptimization of tracking, g2o_optimization.cc:446-898) over B device problems (kernels_poseopt.hip; contract: include/airfe.h)
 struct PoseoptArgs {

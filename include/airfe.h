@@ -315,6 +315,64 @@ int airfe_stereo_points(airfe_ctx* ctx, const double* cam, const float* featL, i
 int airfe_stereo_points_batch_dev(airfe_ctx* ctx, const double* cam, const float* d_featL, const int* d_nL, const float* d_featR, const int* d_nR, int B,
                                   int cap, const int32_t* d_idx, const int* d_nmatch, int mcap, double* d_u_right, double* d_depth, double* d_xyz,
                                   int* d_good, void* stream);
+/* ---- Stereo lines: the loop of Frame::AddRightFeatures over the line matches (src/frame.cc:185-191) and, per valid stereo pair, what
+ * Map::InsertKeyframe does with it (src/map.cc:81-95): Frame::TriangulateStereoLine -> TriangulateByStereo (src/line_processor.cc:196-245) with
+ * Camera::BackProjectStereo (src/camera.cc:268-280), then Mapline::SetEndpoints -> ComputeLine3DFromEndpoints (src/mapline.cc:74-83,
+ * src/line_processor.cc:312-326) ---------------------------------------------------------------------------------------------------------------------
+ * One statement for the host entry and the kernel: airslam_amd/csrc/stereoline_core.h (restated in tests/stereoline_ref.py).  Doubles only, no fused
+ * multiply-adds, sums in the order written; the only non-rational function is sqrt.  Inputs are finite; a non-finite coordinate never indexes memory and
+ * its outputs are unspecified.
+ *   input     cam [8] = min_x_diff, max_x_diff, max_y_diff, bf, fx, fy, cx, cy (HOST array, the layout of "Stereo points"; max_y_diff is unused here);
+ *             lines [.][4] doubles (x1, y1, x2, y2); line_matches [nL] = airfe_match_lines' output for the stereo pair; Twc [16] row-major, NULL = no
+ *             transform: the endpoints stay in the camera frame and nothing is multiplied (an explicit identity pose gives the same VALUES; the sign
+ *             of a zero may differ, since (+0 + -0) + t is not -0 + nothing: NULL promises the untouched camera-frame numbers).
+ *   select    for left line i: r = line_matches[i]; valid iff r > 0 && r < nR.  The `> 0` is the reference's (frame.cc:186): a match to right line 0
+ *             is DROPPED there, and here.  STATED DIFFERENCE: an index >= nR (stale, hostile) counts as invalid and never indexes memory; the
+ *             reference would read past its vector.  lines_right_sel[i] = the right line's four doubles, or four zeros when invalid (the reference
+ *             leaves the slot unspecified); right_valid[i] = 1 / 0.
+ *   gates     dx = x2 - x1, dy = y2 - y1; horizontal iff |dy| <= 3 || |dy / dx| < t, t = 0x1.6a1aa2e1bef6fp-3, first the left line, then the
+ *             right.  t is the smallest double whose atan is >= 0.175: the reference's |atan(dy / dx)| < 0.175 without an atan that two libms would
+ *             evaluate.  dx == 0 gives +-inf, which passes as atan(+-inf) = +-pi/2 does; dx == dy == 0 is already horizontal by |dy| <= 3.
+ *   disparity k = dx_right / dy_right; xr1 = x21 + k * (y11 - y21), xr2 = x21 + k * (y12 - y21); d1 = x11 - xr1, d2 = x12 - xr2; rejected iff
+ *             d < min_x_diff || d > max_x_diff on either end (strict: a disparity ON the band passes).
+ *   points    fx_inv = 1.0 / fx, fy_inv = 1.0 / fy; p = (((x - cx) * fx_inv) * d, ((y - cy) * fy_inv) * d, 1.0 * d), d = bf / (x - xr); with Twc each
+ *             row is ((r0 * px + r1 * py) + r2 * pz) + t.  endpoints = (p1, p2).
+ *   line      l = p2 - p1; |l| = sqrt((lx lx + ly ly) + lz lz); |l| < 0.01: no line.  Otherwise d = l / |l| per component, s = (dx p1x + dy p1y) +
+ *             dz p1z, p = p1 - d * s, q = p + d, w = p x q = (py qz - pz qy, pz qx - px qz, px qy - py qx); plucker = (w, d).  This is
+ *             g2o::Line3D::fromCartesian as published; g2o is not part of this project's build or tests, so nothing here is checked against g2o and
+ *             nothing claims equality with it: the formula written here is the contract, on every side.
+ *   status    0 map line: endpoints and plucker set | 1 no right line | 2 left line horizontal | 3 right line horizontal | 4 a disparity outside
+ *             the band | 5 triangulated but shorter than 0.01: endpoints set, plucker NaN (the reference's SetEndpoints then keeps NEITHER: it
+ *             returns before it stores the endpoints, mapline.cc:76).  endpoints / plucker are NaN wherever they are not set.
+ *   count [3] valid right lines, lines with status 0 or 5, lines with status 0 (integer sums: the same bytes in every run).
+ * Every slot of the first nL lines is written, nothing behind them is touched.  Per frame the batch and the host entry give the same bytes. */
+/* ONE frame through host buffers, no device work: lines_left [nL][4], lines_right [nR][4], line_matches [nL], Twc [16] or NULL ->
+ * lines_right_sel [nL][4], right_valid [nL], status [nL], endpoints [nL][6], plucker [nL][6], count [3]. */
+int airfe_stereo_lines(airfe_ctx* ctx, const double* cam, const double* lines_left, int nL, const double* lines_right, int nR, const int32_t* line_matches,
+                       const double* Twc, double* lines_right_sel, uint8_t* right_valid, int32_t* status, double* endpoints, double* plucker,
+                       int32_t* count);
+/* over B device frames, asynchronous on `stream`, nothing allocated: d_lines_left / d_lines_right [B][capL][4] + d_nlines_left / d_nlines_right [B]
+ * (clamped to 0..capL) — the two halves of airfe_stereo_plnet_batch_dev's d_lines [2B][capL][4] / d_nlines [2B], IN PLACE; d_line_matches [B][capL]
+ * (airfe_match_lines_batch_dev); d_Twc [B][16] or NULL; B <= 65535.  d_lines_right_sel [B][capL][4], d_right_valid [B][capL] u8, d_status [B][capL] i32,
+ * d_endpoints / d_plucker [B][capL][6], d_count [B][3] i32. */
+int airfe_stereo_lines_batch_dev(airfe_ctx* ctx, const double* cam, const double* d_lines_left, const int* d_nlines_left, const double* d_lines_right,
+                                 const int* d_nlines_right, int capL, const int32_t* d_line_matches, const double* d_Twc, int B, double* d_lines_right_sel,
+                                 uint8_t* d_right_valid, int32_t* d_status, double* d_endpoints, double* d_plucker, int32_t* d_count, void* stream);
+/* Composite: the line half of a stereo keyframe, from feature rows to map lines, on one stream: AssignPointsToLines on the left frame (frame.cc:125) and
+ * on the right (:177), MatchLines on the stereo list with the disparity band cam[0..2] (:147-160, :184) — the three through
+ * airfe_assign_points_to_lines_batch_dev / airfe_match_lines_batch_dev as they are — then airfe_stereo_lines_batch_dev.  The CSR relations
+ * (d_row_ptr* [B][capL + 1], d_pt_idx* / d_pt_dist* [B][capE], d_total* [B] or NULL) and d_line_matches [B][capL] are the CALLER's, with the shapes of
+ * those entries: the left relation stays for the temporal MatchLines of the next frame.  d_featL / d_featR [B][cap][259], d_nL / d_nR [B], d_idx
+ * [B][mcap][2] + d_nmatch [B].  Equal, byte for byte, to the four steps done one at a time.  The composite has no memory of its own and the
+ * triangulation allocates nothing; the two existing entries keep their own rule: their scratch blocks in the context (line counts [B][capL]; bit rows
+ * and row maxima [B][capL][(mcap + 31) / 32]) grow on the first call and on a larger shape, behind a synchronisation of the stream — a call at a shape
+ * already seen allocates and synchronises nothing. */
+int airfe_stereo_line_landmarks_batch_dev(airfe_ctx* ctx, const double* cam, const double* d_lines_left, const int* d_nlines_left, const double* d_lines_right,
+                                          const int* d_nlines_right, int capL, const float* d_featL, const int* d_nL, const float* d_featR, const int* d_nR,
+                                          int cap, const int32_t* d_idx, const int* d_nmatch, int mcap, const double* d_Twc, int B, int32_t* d_row_ptrL,
+                                          int32_t* d_pt_idxL, double* d_pt_distL, int* d_totalL, int32_t* d_row_ptrR, int32_t* d_pt_idxR, double* d_pt_distR,
+                                          int* d_totalR, int capE, int32_t* d_line_matches, double* d_lines_right_sel, uint8_t* d_right_valid,
+                                          int32_t* d_status, double* d_endpoints, double* d_plucker, int32_t* d_count, void* stream);
 /* Tracking composite: SolvePnPWithCV as tracking feeds it right after a keyframe (map_builder.cc:307-315), all on the device.  Per problem: the
  * keyframe's points d_xyz [B][capK][3] (airfe_stereo_points_batch_dev), the current rows d_feat [B][cap][259], the temporal list d_tidx [B][mcap][2]
  * = (keyframe index, current index) + d_ntrack [B] (airfe_track_frame / the batch matcher; mcap <= 1024).  Correspondences = the list entries whose
