@@ -127,6 +127,12 @@ class DebugLineMidArgs(C.Structure):
                                              "keep", "pairs", "rep", "head4", "prop4", "ridx", "proj", "lines_adjusted", "scores_line", "table_dirty")])
 
 
+class DebugS0DecodeArgs(C.Structure):
+    """airfe_debug_s0_decode_args (include/airfe_debug.h)"""
+    _fields_ = ([(n, C.c_int) for n in ("B", "mode", "ld", "off", "want_ta8", "want_loi", "want_jnms", "prec", "wgs")] + [(n, C.c_void_p) for n in ("rows", "x", "w", "b")]
+                + [("stage_floats", C.c_size_t)] + [(n, C.c_void_p) for n in ("stage", "jloc", "joff", "jnms", "ta8", "loi", "head_rows")])
+
+
 # name -> (restype, argtypes); every symbol include/*.h declares
 SIGNATURES = {
     "airfe_copy_rows_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -277,6 +283,7 @@ SIGNATURES = {
     "airfe_debug_line_post": (C.c_int, [C.c_void_p, C.POINTER(DebugLinePostArgs)]),
     "airfe_debug_junctions_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "airfe_debug_line_mid": (C.c_int, [C.c_void_p, C.POINTER(DebugLineMidArgs)]),
+    "airfe_debug_s0_decode": (C.c_int, [C.c_void_p, C.POINTER(DebugS0DecodeArgs)]),
     "airfe_debug_lg_prepare": (C.c_int, [C.c_void_p, C.POINTER(DebugLgPrepareArgs)]),
     "airfe_debug_lg_assign": (C.c_int, [C.c_void_p, C.POINTER(DebugLgAssignArgs)]),
     "airfe_debug_plnet_stage0": (C.c_int, [C.c_void_p] + [C.c_void_p] * 10),

@@ -544,6 +544,44 @@ class Context:
         self._chk(self._l.airfe_debug_line_mid(self._h, C.byref(a)), "airfe_debug_line_mid")
         return out
 
+    # stage-block offsets in floats (csrc/airfe_host.h, SG_*): juncs_pred | lines_pred | iskeep | idx_min | idx_max | thin | aux, the stride rounded up to 64
+    S0_STAGE = {"lines_pred": (600, 3 * 16384 * 4), "thin": (600 + 7 * 3 * 16384, 4 * 16384), "aux": (600 + 7 * 3 * 16384 + 4 * 16384, 4 * 16384)}
+    S0_STAGE_FLOATS = (600 + 7 * 3 * 16384 + 8 * 16384 + 63) // 64 * 64
+
+    def debug_s0_decode(self, rows=None, ld=160, off=128, ta8=True, loi=False, jnms=True, x=None, w=None, b=None, prec=1, wgs=0, two_pass=False):
+        """airfe_debug_s0_decode (include/airfe_debug.h): the stage-0 decode alone.  rows [B, 16384, ld] fp32 head rows (the 17 decoded channels from column off) through
+        launch_s0_decode; or x [B * 16384, 128] line features with a head w [17, 128], b [17] in the 2-byte type prec through launch_s0_head_decode(wgs), with two_pass
+        through launch_gemm + launch_s0_decode(32, 0).
+        -> dict of whole device buffers, 0xFF bytes where the run wrote nothing: stage [B, S0_STAGE_FLOATS] with its views lines_pred [B, 49152, 4] and thin / aux
+        [B, 4, 128, 128]; jloc, jnms [B, 128, 128]; joff [B, 2, 128, 128]; ta8 [B, 16384, 8]; loi [128, 128, 128] (CHW, image 0); head_rows [B, 16384, 32] (two_pass)."""
+        f = lambda t: np.ascontiguousarray(t, np.float32)
+        npx, sf = 128 * 128, self.S0_STAGE_FLOATS
+        a = _lib.DebugS0DecodeArgs(want_ta8=int(bool(ta8)), want_loi=int(bool(loi)), want_jnms=int(bool(jnms)), prec=int(prec), wgs=int(wgs), stage_floats=sf)
+        if rows is not None:
+            assert x is None and not two_pass
+            rows = f(rows)
+            bb = rows.shape[0]
+            assert rows.shape == (bb, npx, ld)
+            a.mode, a.ld, a.off, a.rows = 0, int(ld), int(off), rows.ctypes.data
+        else:
+            x, w, b = f(x), f(w), f(b)
+            bb = x.shape[0] // npx
+            assert x.shape == (bb * npx, 128) and w.shape == (17, 128) and b.shape == (17,)
+            a.mode, a.x, a.w, a.b = (2 if two_pass else 1), x.ctypes.data, w.ctypes.data, b.ctypes.data
+        poison = lambda *shape: np.full(shape, -1, np.int32).view(np.float32)
+        out = {"stage": poison(bb, sf), "jloc": poison(bb, 128, 128), "joff": poison(bb, 2, 128, 128), "jnms": poison(bb, 128, 128), "ta8": poison(bb, npx, 8),
+               "loi": poison(128, 128, 128)}
+        if two_pass:
+            out["head_rows"] = poison(bb, npx, 32)
+        a.B = bb
+        for k, v in out.items():
+            setattr(a, k, v.ctypes.data)
+        self._chk(self._l.airfe_debug_s0_decode(self._h, C.byref(a)), "airfe_debug_s0_decode")
+        for k, (o, n) in self.S0_STAGE.items():
+            v = out["stage"][:, o:o + n]
+            out[k] = v.reshape(bb, 3 * npx, 4) if k == "lines_pred" else v.reshape(bb, 4, 128, 128)
+        return out
+
     def debug_junctions_topk(self, jloc, joff):
         """airfe_debug_junctions_topk (include/airfe_debug.h): jloc [B, 128, 128], joff [B, 2, 128, 128] -> juncs_pred [B, 300, 2]"""
         jloc, joff = np.ascontiguousarray(jloc, np.float32), np.ascontiguousarray(joff, np.float32)

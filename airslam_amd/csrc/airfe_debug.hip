@@ -911,6 +911,84 @@ int airfe_debug_line_mid(airfe_ctx* c, airfe_debug_line_mid_args* a) try {
   return 0;
 } AIRFE_CATCH(c)
 
+/* the stage-0 decode (include/airfe_debug.h): line_branch_dev's launch_s0_decode, launch_s0_head_decode, or launch_gemm + launch_s0_decode (fuse_dec = 0), on host head rows /
+ * line features staged into the line branch's own buffers */
+int airfe_debug_s0_decode(airfe_ctx* c, airfe_debug_s0_decode_args* a) try {
+  AIRFE_ENTER(c);
+  if (!c->has_s0 || !c->s0_stage || !c->l_ta8 || !c->s0_loi) return fail(c, "debug_s0_decode: the line path is not loaded (line.* tensors, cfg.plnet_s1_pack)");
+  if (!a || !a->stage || !a->jloc || !a->joff || !a->jnms || !a->ta8 || !a->loi) return fail(c, "debug_s0_decode: null argument");
+  const int B = a->B, mode = a->mode;
+  const size_t NPX = 128 * 128;
+  if (B < 1 || B > c->Lmax) return fail(c, "debug_s0_decode: 1 <= B <= the arena's images");
+  if (mode < 0 || mode > 2) return fail(c, "debug_s0_decode: mode is 0 .. 2");
+  if (a->stage_floats != SG_STRIDE) return fail(c, "debug_s0_decode: stage_floats is not the library's stage stride");
+  if (mode == 0) {
+    if (!a->rows) return fail(c, "debug_s0_decode: mode 0 needs rows");
+    if (!((a->ld == 160 && a->off == 128) || (a->ld == 32 && a->off == 0))) return fail(c, "debug_s0_decode: the layouts are (ld 160, off 128) and (ld 32, off 0)");
+    if (a->want_loi && a->ld != 160) return fail(c, "debug_s0_decode: the CHW loi copy exists for the (ld 160, off 128) layout only");
+  } else {
+    if (!a->x || !a->w || !a->b || (mode == 2 && !a->head_rows)) return fail(c, "debug_s0_decode: modes 1 and 2 need x, w and b (mode 2: head_rows)");
+    if (a->prec != 0 && a->prec != 1) return fail(c, "debug_s0_decode: prec is 0 (bf16) or 1 (fp16)");
+    if (a->wgs < 0 || a->wgs > 4096) return fail(c, "debug_s0_decode: wgs must lie in 0 .. 4096");
+    if (a->want_loi) return fail(c, "debug_s0_decode: the CHW loi copy exists for the (ld 160, off 128) layout only");
+  }
+  hipStream_t st = c->stream;
+  float* d = c->s0_stage;
+  clear_saturation(c);
+  DbgTmp t(mode ? a->prec : 0);
+  float* djnms = dbg_canary<float>(&t.h, (size_t)B * NPX);
+  if (!djnms) return fail(c, "debug_s0_decode: allocation failed");
+  // ---- every output 0xFF
+  HIPCHK(c, hipMemsetAsync(d, 0xFF, (size_t)B * SG_STRIDE * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->l_jloc, 0xFF, (size_t)B * NPX * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->l_joff, 0xFF, (size_t)B * 2 * NPX * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->l_ta8, 0xFF, (size_t)B * 8 * NPX * 4, st));
+  HIPCHK(c, hipMemsetAsync(c->s0_loi, 0xFF, (size_t)128 * NPX * 4, st));
+  std::vector<uint16_t> xin;                                 // (staged with the stream's copies: alive until the synchronisation behind the launches)
+  if (mode == 0) {
+    const size_t n = (size_t)B * NPX * a->ld;
+    float* head = a->ld == 32 ? c->l_dec : c->l_head;
+    if (a->ld == 160 && B > 1) {                             // (l_head holds one image)
+      head = dalloc<float>(&t.h, n, false);
+      if (!head) return fail(c, "debug_s0_decode: allocation failed");
+    }
+    HIPCHK(c, hipMemcpyAsync(head, a->rows, n * 4, hipMemcpyHostToDevice, st));
+    launch_s0_decode(head, a->ld, a->off, d + SG_LP, c->l_jloc, a->want_jnms ? djnms : nullptr, c->l_joff, d + SG_THIN, d + SG_AUX, a->want_loi ? c->s0_loi : nullptr,
+                     a->want_ta8 ? c->l_ta8 : nullptr, B, SG_STRIDE, st);
+  } else {
+    const size_t n = (size_t)B * NPX * 128;
+    xin.resize(n);
+    for (size_t i = 0; i < n; ++i) xin[i] = cvt2(a->x[i], a->prec);
+    LinW lw;
+    if (!make_linear(&t.h, a->w, a->b, 128, 17, lw)) return fail(c, "debug_s0_decode: allocation failed");
+    HIPCHK(c, hipMemcpyAsync(c->l_feat, xin.data(), n * 2, hipMemcpyHostToDevice, st));
+    if (mode == 1) {
+      launch_s0_head_decode(a->prec, c->l_feat, lw.w, lw.b, d + SG_LP, c->l_jloc, a->want_jnms ? djnms : nullptr, c->l_joff, c->l_ta8, B, SG_STRIDE, st, a->wgs);
+    } else {
+      HIPCHK(c, hipMemsetAsync(c->l_dec, 0xFF, (size_t)B * NPX * 32 * 4, st));
+      GemmArgs g;
+      g.X1 = c->l_feat; g.ld1 = 128; g.K1 = 128; g.Wp = lw.w; g.bias = lw.b;
+      g.M = B * (int)NPX; g.N = lw.N; g.cb_total = lw.cbt; g.epi = EPI_STORE_F32; g.out = c->l_dec; g.ldo = 32;
+      g.small_max = 1 << 30; g.g8_min = c->gemm8_min; g.gr_min = c->gemmr_min; g.gr_wgs = c->gemmr_wgs;
+      launch_gemm(a->prec, 128, false, g, st);
+      launch_s0_decode(c->l_dec, 32, 0, d + SG_LP, c->l_jloc, a->want_jnms ? djnms : nullptr, c->l_joff, d + SG_THIN, d + SG_AUX, nullptr, c->l_ta8, B, SG_STRIDE, st);
+    }
+  }
+  HIPCHK(c, hipStreamSynchronize(st));                       // (xin goes out of scope)
+  if (launch_status(c)) return 1;
+  if (saturation_status(c)) return 1;
+  // ---- everything back as the device left it
+  HIPCHK(c, hipMemcpy(a->stage, d, (size_t)B * SG_STRIDE * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->jloc, c->l_jloc, (size_t)B * NPX * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->joff, c->l_joff, (size_t)B * 2 * NPX * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->jnms, djnms, (size_t)B * NPX * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->ta8, c->l_ta8, (size_t)B * 8 * NPX * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->loi, c->s0_loi, (size_t)128 * NPX * 4, hipMemcpyDeviceToHost));
+  if (mode == 2) HIPCHK(c, hipMemcpy(a->head_rows, c->l_dec, (size_t)B * NPX * 32 * 4, hipMemcpyDeviceToHost));
+  c->wf_counted = false;                                     // (the stage blocks no longer hold a line branch's match)
+  return 0;
+} AIRFE_CATCH(c)
+
 int airfe_debug_junctions_topk(airfe_ctx* c, const float* jloc, const float* joff, int B, float* juncs_pred) try {
   AIRFE_ENTER(c);
   if (!c->has_s0 || !c->s0_stage) return fail(c, "debug_junctions_topk: the line branch is not loaded (line.* tensors, cfg.plnet_s1_pack)");

@@ -349,9 +349,9 @@ void launch_s0_decode(const float* head, int ld, int off, float* lines_pred, flo
 }
 // X [B * 128*128][128] line features (2-byte), Wp / bias: the packed 17-channel head (its first 64-feature block); jnms = 3x3 NMS of jloc
 void launch_s0_head_decode(int prec, const uint16_t* X, const uint16_t* Wp, const float* bias, float* lines_pred, float* jloc, float* jnms,
-                           float* joff, float* ta8, int B, size_t stage_stride, hipStream_t st) {
+                           float* joff, float* ta8, int B, size_t stage_stride, hipStream_t st, int wgs) {
   const int ntiles = B * S0_NPX / 16;
-  const int wgs = std::min(ntiles / 4, 256 * 16);
+  if (wgs <= 0) wgs = std::min(ntiles / 4, 256 * 16);
   if (prec == 1)
     hipLaunchKernelGGL(s0_head_decode_kernel<PF16>, dim3(wgs), dim3(256), 0, st, X, Wp, bias, ntiles, lines_pred, jloc, joff, ta8, stage_stride);
   else

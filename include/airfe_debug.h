@@ -295,6 +295,39 @@ typedef struct airfe_debug_line_mid_args {
   int32_t* table_dirty;                               /* [B] out */
 } airfe_debug_line_mid_args;
 int airfe_debug_line_mid(airfe_ctx* ctx, airfe_debug_line_mid_args* a);
+/* ---- the stage-0 decode between the line head and the stage-0 tensors (kernels_s0.hip; tests/test_gpu_s0_decode_pin.py, tests/s0_decode_ref.py): s0_decode_kernel with
+ * s0_jnms_kernel and s0_loi_chw_kernel (launch_s0_decode), s0_head_decode_kernel (launch_s0_head_decode) and the two-pass form behind airfe_tuning::fuse_dec = 0, on hand-built
+ * HOST head rows or line features.  The input is staged into the context's own buffers and the launcher production calls runs with production's arguments (line_branch_dev);
+ * nothing here has a kernel of its own.
+ *   mode 0, rows: head rows [B][128*128][ld] with the 17 decoded channels (md0..2 dis res | jloc0 jloc1 | joffx joffy | thin0..3 | aux0..3) from column off, one of
+ *     production's two layouts (ld 160, off 128: the fused 145-channel head, staged in l_head — which holds one image, so B > 1 uses a buffer of the call; ld 32, off 0: the
+ *     17-channel head, staged in l_dec).  launch_s0_decode with ta8 / loi / jnms passed or NULL by want_ta8 / want_loi (ld 160 only: the CHW copy of image 0's columns
+ *     0 .. 127) / want_jnms.
+ *   mode 1, features: x [B*128*128][128] line features, rounded to the 2-byte type prec (0 = bf16, 1 = fp16) on the way in and staged in l_feat; head weight w [17][128] and
+ *     bias b [17], packed by make_linear as airfe_debug_linear packs.  launch_s0_head_decode(wgs): lines_pred, jloc, joff, the pixel-major thin | aux; want_jnms.
+ *   mode 2, features, two passes: the same input through launch_gemm (small_max = 1 << 30, EPI_STORE_F32, ldo 32) into l_dec, then launch_s0_decode(32, 0) with ta8 and the
+ *     CHW planes, as line_branch_dev runs it with fuse_dec = 0.  head_rows: l_dec as the GEMM left it.
+ * EVERY output buffer is 0xFF bytes when the launches start — the stage blocks of all B slots whole, jloc, joff, jnms, ta8, the CHW loi buffer, l_dec in mode 2 — and all of
+ * it comes back as the device left it: stage [B][stage_floats] holds juncs_pred | lines_pred | iskeep | min | max | thin | aux at the offsets of airfe_host.h (SG_*), so
+ * poison shows where the contract writes nothing.  jnms has no buffer in the context (the line path takes the candidates inside launch_candidates_nms3): a buffer of the call.
+ * Refused before any launch, the context left usable: B outside the arena; a mode outside 0 .. 2; a layout other than the two above; want_loi without ld 160; prec outside
+ * 0 / 1; wgs outside 0 .. 4096; a stage_floats that is not the library's stage stride; a missing pointer. */
+typedef struct airfe_debug_s0_decode_args {
+  int B, mode;
+  int ld, off;                    /* mode 0 */
+  int want_ta8, want_loi, want_jnms;
+  int prec, wgs;                  /* modes 1, 2 (wgs: mode 1) */
+  const float* rows;              /* [B][128*128][ld] (mode 0) */
+  const float* x;                 /* [B*128*128][128] (modes 1, 2) */
+  const float *w, *b;             /* [17][128], [17] (modes 1, 2) */
+  size_t stage_floats;            /* floats per stage block: must equal the library's stride */
+  float* stage;                   /* [B][stage_floats] out */
+  float *jloc, *joff, *jnms;      /* [B][128*128], [B][2][128*128], [B][128*128] out */
+  float* ta8;                     /* [B][128*128][8] out */
+  float* loi;                     /* [128][128*128] out: the context's one-image CHW buffer */
+  float* head_rows;               /* [B][128*128][32] out (mode 2; else left alone) */
+} airfe_debug_s0_decode_args;
+int airfe_debug_s0_decode(airfe_ctx* ctx, airfe_debug_s0_decode_args* a);
 /* error-path test of cfg.check_launches: the NEXT group of launches of profiling stage `stage` (airfe_profile_stage_name's index) is preceded by one
  * deliberately invalid launch (4096 threads per workgroup), so that the entry that makes it must fail with "<stage name>: kernel launch failed: ..." —
  * with check_launches = 0 the same failure surfaces at the pipeline's end without the stage.  -1 disarms. */

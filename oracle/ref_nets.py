@@ -75,6 +75,31 @@ def superpoint_forward(w: W, x: np.ndarray):
 
 
 # ------------------------------------------------------------------ PLNet stage-0 line branch
+def plnet_s0_decode(h: torch.Tensor, scale: float = 5.0):
+    """The per-pixel decode of the 17 head channels h [17,H,W] (md0..2 dis res | jloc0 jloc1 | joffx joffy | thin0..3 | aux0..3), float32 as plnet_s0_lines
+    runs it: hafm_decoding -> lines [3*H*W,4], jloc [H,W], joff [2,H,W], thin / aux [4,H,W] (torch tensors)."""
+    md, dis, res = torch.sigmoid(h[0:3]), torch.sigmoid(h[3:4]), torch.sigmoid(h[4:5])
+    jloc = torch.softmax(h[5:7], 0)[1]
+    joff = torch.sigmoid(h[7:9]) - 0.5
+    thin, aux = h[9:13], h[13:17]
+    hh, ww = jloc.shape
+    # hafm_decoding (residual sign pad -1, 0, +1)
+    y0, x0 = torch.meshgrid(torch.arange(hh, dtype=torch.float32), torch.arange(ww, dtype=torch.float32), indexing="ij")
+    sign = torch.tensor([-1.0, 0.0, 1.0]).reshape(3, 1, 1)
+    d = (dis + res * sign).clamp(0.0, 1.0)                               # [3,128,128]
+    pi = torch.tensor(np.float32(np.pi))
+    md_un = (md[0] - 0.5) * pi * 2.0
+    st_un = md[1] * pi / 2.0
+    ed_un = -md[2] * pi / 2.0
+    cs, ss, yst, yed = md_un.cos(), md_un.sin(), st_un.tan(), ed_un.tan()
+    xs = ((cs - ss * yst) * d * scale + x0).clamp(0, ww - 1)
+    ys = ((ss + cs * yst) * d * scale + y0).clamp(0, hh - 1)
+    xe = ((cs - ss * yed) * d * scale + x0).clamp(0, ww - 1)
+    ye = ((ss + cs * yed) * d * scale + y0).clamp(0, hh - 1)
+    lines = torch.stack([xs, ys, xe, ye], -1).reshape(-1, 4)             # [3*128*128, 4]
+    return lines, jloc, joff, thin, aux
+
+
 def plnet_s0_lines(w: W, x: np.ndarray, topk: int = 300, scale: float = 5.0, j2l: float = 10.0, f3a: torch.Tensor = None):
     """The stage-0 LINE branch: x [H,W] float32 in [0,1] (512x512) -> dict with the Appendix A.1 tensors
     (`juncs_pred` [300,2], `lines_pred` [3*128*128,4], `iskeep` / `idx_junc_to_end_min` / `idx_junc_to_end_max` [1,3,128,128],
@@ -95,25 +120,8 @@ def plnet_s0_lines(w: W, x: np.ndarray, topk: int = 300, scale: float = 5.0, j2l
         f = c("line.conv1", f)
         o = Fn.conv2d(f, _t(w["line.head.weight"])[:, :, None, None], _t(w["line.head.bias"]))[0]    # [145,128,128]
         loi, h = o[:128], o[128:]
-        md, dis, res = torch.sigmoid(h[0:3]), torch.sigmoid(h[3:4]), torch.sigmoid(h[4:5])
-        jloc = torch.softmax(h[5:7], 0)[1]
-        joff = torch.sigmoid(h[7:9]) - 0.5
-        thin, aux = h[9:13], h[13:17]
+        lines, jloc, joff, thin, aux = plnet_s0_decode(h, scale)
         hh, ww = jloc.shape
-        # hafm_decoding (residual sign pad -1, 0, +1)
-        y0, x0 = torch.meshgrid(torch.arange(hh, dtype=torch.float32), torch.arange(ww, dtype=torch.float32), indexing="ij")
-        sign = torch.tensor([-1.0, 0.0, 1.0]).reshape(3, 1, 1)
-        d = (dis + res * sign).clamp(0.0, 1.0)                               # [3,128,128]
-        pi = torch.tensor(np.float32(np.pi))
-        md_un = (md[0] - 0.5) * pi * 2.0
-        st_un = md[1] * pi / 2.0
-        ed_un = -md[2] * pi / 2.0
-        cs, ss, yst, yed = md_un.cos(), md_un.sin(), st_un.tan(), ed_un.tan()
-        xs = ((cs - ss * yst) * d * scale + x0).clamp(0, ww - 1)
-        ys = ((ss + cs * yst) * d * scale + y0).clamp(0, hh - 1)
-        xe = ((cs - ss * yed) * d * scale + x0).clamp(0, ww - 1)
-        ye = ((ss + cs * yed) * d * scale + y0).clamp(0, hh - 1)
-        lines = torch.stack([xs, ys, xe, ye], -1).reshape(-1, 4)             # [3*128*128, 4]
         juncs = junctions_topk(jloc.numpy(), joff.numpy(), topk)
         keep, imin, imax = j2l_match(lines.numpy(), juncs, j2l)
     return dict(juncs_pred=juncs, lines_pred=lines.numpy(), iskeep=keep.reshape(1, 3, hh, ww),

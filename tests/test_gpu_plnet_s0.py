@@ -1,6 +1,8 @@
 """PLNet stage-0 LINE branch on the device (SURVEY.md Appendix A.1 tensors) vs the oracle restatement (oracle/ref_nets.py::plnet_s0_lines).
 Index work (junction top-300, nearest-junction matching, min / max, iskeep) is checked EXACT by feeding the device's own dense maps
-to the numpy restatements; the network part within 2-byte tolerances; and the whole PLNet::infer path with no host tensors at all."""
+to the numpy restatements; the network part within 2-byte tolerances; and the whole PLNet::infer path with no host tensors at all.
+The decode itself (kernels_s0.hip: HAFM proposals, jloc, joff, the thin / aux / loi copies, the 3x3 suppression) is pinned per element on hand-built head rows in
+tests/test_gpu_s0_decode_pin.py: the gates here (2 % of a map's maximum, the proposals' 99th percentile) see whole images through an fp16 trunk and cannot."""
 import os
 
 import numpy as np
