@@ -120,6 +120,12 @@ class DebugLinePostArgs(C.Structure):
                 + [(n, C.c_void_p) for n in ("la", "sc", "m2", "heat", "lines", "nlines", "nfound", "junc", "njunc", "jfound", "jmap")])
 
 
+class DebugJunctionTailArgs(C.Structure):
+    """airfe_debug_junction_tail_args (include/airfe_debug.h)"""
+    _fields_ = ([(n, C.c_int) for n in ("B", "nj", "ld", "h", "w", "capL", "capJ")]
+                + [(n, C.c_void_p) for n in ("la", "sc", "m2", "heat", "act", "lines", "nlines", "nfound", "junc", "njunc", "jfound")] + [("fused", C.c_int)])
+
+
 class DebugLineMidArgs(C.Structure):
     """airfe_debug_line_mid_args (include/airfe_debug.h)"""
     _fields_ = ([(n, C.c_int) for n in ("B", "j2l", "s1_form", "wgs")]
@@ -281,6 +287,7 @@ SIGNATURES = {
     "airfe_debug_sg_sinkhorn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
     "airfe_debug_detector_tail": (C.c_int, [C.c_void_p, C.POINTER(DebugDetectorTailArgs)]),
     "airfe_debug_line_post": (C.c_int, [C.c_void_p, C.POINTER(DebugLinePostArgs)]),
+    "airfe_debug_junction_tail": (C.c_int, [C.c_void_p, C.POINTER(DebugJunctionTailArgs)]),
     "airfe_debug_junctions_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "airfe_debug_line_mid": (C.c_int, [C.c_void_p, C.POINTER(DebugLineMidArgs)]),
     "airfe_debug_s0_decode": (C.c_int, [C.c_void_p, C.POINTER(DebugS0DecodeArgs)]),

@@ -520,6 +520,25 @@ class Context:
         self._chk(self._l.airfe_debug_line_post(self._h, C.byref(a)), "airfe_debug_line_post")
         return out
 
+    def debug_junction_tail(self, la, sc, m2, heat, act, cap_lines, cap_junctions, nj=None, h=512, w=512, sentinel=7.0):
+        """airfe_debug_junction_tail (include/airfe_debug.h): line filter -> junction descriptors as the batched line path runs them, in the form production chooses
+        (B > 2 and the context's tuning: the junction list inside the filter and the sampling gather GEMM; else byte maps, scan, dense head, sample_desc), on host stage-1
+        outputs la [B, ld, 4], sc [B, ld], m2 [B], score maps heat [B, 512, 512] and convDa activations act [B, 64, 64, 256].  The output buffers start as `sentinel`.
+        -> dict lines [B, capL, 4] float64, nlines, nfound [B], junc [nj, capJ, 259], njunc, jfound [nj], fused (bool)."""
+        la, sc, heat = np.ascontiguousarray(la, np.float32), np.ascontiguousarray(sc, np.float32), np.ascontiguousarray(heat, np.float32)
+        act = np.ascontiguousarray(act, np.float32)
+        m2 = np.ascontiguousarray(m2, np.int32).reshape(-1)
+        b, ld = sc.shape
+        nj = b if nj is None else int(nj)
+        assert la.shape == (b, ld, 4) and heat.shape == (b, 512, 512) and act.shape == (b, 64, 64, 256) and len(m2) == b
+        out = {"lines": np.full((b, cap_lines, 4), sentinel, np.float64), "nlines": np.full((b,), -1, np.int32), "nfound": np.full((b,), -1, np.int32),
+               "junc": np.full((nj, cap_junctions, FEAT), sentinel, np.float32), "njunc": np.full((nj,), -1, np.int32), "jfound": np.full((nj,), -1, np.int32)}
+        a = _lib.DebugJunctionTailArgs(B=b, nj=nj, ld=ld, h=int(h), w=int(w), capL=int(cap_lines), capJ=int(cap_junctions), la=la.ctypes.data, sc=sc.ctypes.data,
+                                       m2=m2.ctypes.data, heat=heat.ctypes.data, act=act.ctypes.data, **{k: v.ctypes.data for k, v in out.items()})
+        self._chk(self._l.airfe_debug_junction_tail(self._h, C.byref(a)), "airfe_debug_junction_tail")
+        out["fused"] = bool(a.fused)
+        return out
+
     def debug_line_mid(self, juncs_pred, lines_pred, thin, aux, loi, iskeep=None, idx_min=None, idx_max=None, j2l=0, s1_form=2, wgs=0):
         """airfe_debug_line_mid (include/airfe_debug.h): the junction-to-line match, the kept list and unique pairs, the junction projections and stage 1 on host tensors
         juncs_pred [B, 300, 2], lines_pred [B, 49152, 4], thin / aux [B, 4, 128, 128], loi [B, 16384, 128] (pixel-major), iskeep / idx_min / idx_max [B, 49152] (j2l = 0).

@@ -851,8 +851,9 @@ static int plnet_lines_batch(airfe_ctx* c, int B, int h, int w, double* d_lines,
   if (nj < 0 || nj > B || (nj > 0 && (!d_junc || !d_njunc || capJ < 1))) return fail(c, "detect_plnet_batch: bad junction arguments");
   if ((phase & 1) && line_branch_dev(c, st, 0, B, false)) return 1;
   bool partial = false;
-  if ((phase & 2) && nj > 0 && !c->desc_dense_valid) {   // the point branch ran the descriptor head on the sampled cells only: the junction images'
-    dense_desc_head(c, nj, st);                   // dense maps now (the points have theirs already; c->desc is free to be rewritten)
+  // (junction_tail_fused: line_tail_dev runs the head at the junctions' tap rows only, inside the sampling gather GEMM — no dense map, desc_dense_valid stays false)
+  if ((phase & 2) && nj > 0 && !c->desc_dense_valid && !(phase == 3 && junction_tail_fused(c, nj, capJ))) {   // the point branch ran the descriptor head on the sampled
+    dense_desc_head(c, nj, st);                   // cells only: the junction images' dense maps now (the points have theirs already; c->desc is free to be rewritten)
     c->desc_dense_valid = true;
     partial = nj != c->last_B;
   }

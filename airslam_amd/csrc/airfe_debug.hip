@@ -124,7 +124,12 @@ static std::vector<float> dbg_rows4(const float* x, int rows, int cols, int rows
 template <class T>
 static T* dbg_canary(airfe_ctx* tmp, size_t n) {       // an output buffer whose every byte starts as 0xFF (NaN in fp32, fp16 and bf16)
   T* p = dalloc<T>(tmp, n, false);
-  if (p) (void)hipMemset(p, 0xFF, std::max<size_t>(n, 1) * sizeof(T));
+  if (p) {
+    (void)hipMemset(p, 0xFF, std::max<size_t>(n, 1) * sizeof(T));
+    // the fill of device memory runs on the null stream and may return before it is done; the hooks launch on the context's NON-BLOCKING stream, which does not
+    // wait for it: without this wait the fill could land on top of a fast kernel's rows (seen once as NaN rows in tests/test_gpu_linear_kernels.py)
+    (void)hipStreamSynchronize(nullptr);
+  }
   return p;
 }
 static void dbg_back2(const std::vector<uint16_t>& v, size_t n, int prec, float* out) {
@@ -764,6 +769,80 @@ int airfe_debug_line_post(airfe_ctx* c, airfe_debug_line_post_args* a) try {
   HIPCHK(c, hipStreamSynchronize(st));                       // (counts goes out of scope)
   if (launch_status(c)) return 1;
   if (saturation_status(c)) return 1;
+  HIPCHK(c, hipMemcpy(a->lines, dlines, (size_t)B * capL * 32, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->nlines, dcnt, (size_t)B * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(a->nfound, dcnt + B, (size_t)B * 4, hipMemcpyDeviceToHost));
+  if (nj > 0) {
+    HIPCHK(c, hipMemcpy(a->junc, djunc, (size_t)nj * capJ * AIRFE_FEAT_DIM * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(a->njunc, dcnt + 2 * B, (size_t)nj * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(a->jfound, dcnt + 3 * B, (size_t)nj * 4, hipMemcpyDeviceToHost));
+  }
+  return 0;
+} AIRFE_CATCH(c)
+
+/* the junction tail as the batched entries run it (include/airfe_debug.h): the point branch's state as detect_dev2 leaves it, plnet_lines_batch's rule for the junction
+ * images' dense descriptor map, then line_tail_dev's end (line_post_dev, airfe_detect.hip) — in either form, chosen as production chooses it */
+int airfe_debug_junction_tail(airfe_ctx* c, airfe_debug_junction_tail_args* a) try {
+  AIRFE_ENTER(c);
+  if (!c->has_sp || !c->has_s1 || !c->s1_la || !c->jmap) return fail(c, "debug_junction_tail: the line path is not loaded (cfg.plnet_s1_pack)");
+  if (c->prec != 0 && c->prec != 1) return fail(c, "debug_junction_tail drives the 2-byte detector (cfg.precision fp16 / bf16)");
+  if (c->cfg.nms_radius != 4) return fail(c, "debug_junction_tail: the keep plane exists on the radius-4 path only");
+  if (!a || !a->la || !a->sc || !a->m2 || !a->heat || !a->act || !a->lines || !a->nlines || !a->nfound) return fail(c, "debug_junction_tail: null argument");
+  const int B = a->B, nj = a->nj, ld = a->ld, capL = a->capL, capJ = a->capJ, R = AIRFE_INTERNAL_SIZE;
+  if (B < 1 || B > c->Lmax || B > c->Bmax || nj < 0 || nj > B || ld < 1 || ld > LINE_CAP || capL < 1 || capJ < 1 || a->h < 1 || a->w < 1)
+    return fail(c, "debug_junction_tail: bad argument (1 <= B <= max_batch, 0 <= nj <= B, 1 <= ld <= 45056, capL, capJ >= 1)");
+  if (nj > 0 && (!a->junc || !a->njunc || !a->jfound)) return fail(c, "debug_junction_tail: nj > 0 needs the junction outputs");
+  for (int b = 0; b < B; ++b)
+    if (a->m2[b] < 0 || a->m2[b] > ld) return fail(c, "debug_junction_tail: every m2 must lie in 0 .. ld");
+  const size_t px = (size_t)B * R * R, cells = (size_t)B * (R / 8) * (R / 8);
+  for (size_t i = 0; i < px; ++i)
+    if (!(a->heat[i] >= 0.f && a->heat[i] <= 1.f)) return fail(c, "debug_junction_tail: scores must lie in [0, 1]");
+  std::vector<uint16_t> act(cells * 256);
+  for (size_t i = 0; i < act.size(); ++i) act[i] = cvt2(a->act[i], c->prec);
+  DbgTmp t;
+  double* dlines = dupload(&t.h, std::vector<double>(a->lines, a->lines + (size_t)B * capL * 4));
+  float* djunc = nj > 0 ? dupload(&t.h, std::vector<float>(a->junc, a->junc + (size_t)nj * capJ * AIRFE_FEAT_DIM)) : nullptr;
+  int* dcnt = dbg_canary<int>(&t.h, (size_t)4 * B);          // nlines | nfound | njunc | jfound
+  if (!dlines || (nj > 0 && !djunc) || !dcnt) return fail(c, "debug_junction_tail: allocation failed");
+  hipStream_t st = c->stream;
+  clear_saturation(c);
+  std::vector<int> counts((size_t)B * LINE_CNT_LD, 0);
+  for (int b = 0; b < B; ++b) {
+    counts[(size_t)b * LINE_CNT_LD + 1] = a->m2[b];
+    HIPCHK(c, hipMemcpyAsync(c->s1_la + (size_t)b * LINE_CAP * 4, a->la + (size_t)b * ld * 4, (size_t)ld * 16, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->s1_sc + (size_t)b * LINE_CAP, a->sc + (size_t)b * ld, (size_t)ld * 4, hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(c, hipMemcpyAsync(c->wf_counts, counts.data(), counts.size() * 4, hipMemcpyHostToDevice, st));
+  c->wf_counted = false;
+  HIPCHK(c, hipMemcpyAsync(c->heat, a->heat, px * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->aDa, act.data(), act.size() * 2, hipMemcpyHostToDevice, st));
+  // the point branch as detect_dev2 / detect_tail_dev leave it: one- and two-image calls keep the dense NMS'd map and the dense descriptor map, larger batches the keep
+  // plane alone (their descriptor head ran over the sampled cells)
+  c->nms_map_valid = B <= 2;
+  launch_nms512_candidates(c->heat, c->nms_map_valid ? c->heat_nms : nullptr, c->nms_mask, B, c->cfg.keypoint_threshold, c->cfg.remove_borders, c->cand, c->cand_cnt,
+                           R * R, st);
+  c->desc_dense_valid = false;
+  c->last_B = B;
+  int rc = 0;
+  if (B <= 2) {
+    rc = dense_desc_head(c, B, st);
+    c->desc_dense_valid = true;
+  }
+  // plnet_lines_batch's rule (airfe.hip), then line_tail_dev's clear of the byte maps and its end
+  const bool fused = junction_tail_fused(c, nj, capJ);
+  bool partial = false;
+  if (!rc && nj > 0 && !c->desc_dense_valid && !fused) {
+    rc = dense_desc_head(c, nj, st);
+    c->desc_dense_valid = true;
+    partial = nj != B;
+  }
+  if (!rc && nj > 0 && !fused) launch_zero16(c->jmap, (size_t)nj * R * R, st);
+  if (!rc) rc = line_post_dev(c, 0, B, a->h, a->w, dlines, capL, dcnt, dcnt + B, djunc, capJ, dcnt + 2 * B, dcnt + 3 * B, nj, st, 3, fused);
+  if (partial) c->desc_dense_valid = false;
+  HIPCHK(c, hipStreamSynchronize(st));                       // (counts, act go out of scope)
+  if (rc || launch_status(c)) return 1;
+  if (saturation_status(c)) return 1;
+  a->fused = fused ? 1 : 0;
   HIPCHK(c, hipMemcpy(a->lines, dlines, (size_t)B * capL * 32, hipMemcpyDeviceToHost));
   HIPCHK(c, hipMemcpy(a->nlines, dcnt, (size_t)B * 4, hipMemcpyDeviceToHost));
   HIPCHK(c, hipMemcpy(a->nfound, dcnt + B, (size_t)B * 4, hipMemcpyDeviceToHost));

@@ -300,6 +300,27 @@ int line_branch_dev(airfe_ctx* c, hipStream_t st, int i0, int nb, bool chw) {
   return launch_status(c);
 }
 
+// The junction tail without the byte maps and without a dense descriptor map: the junction list inside the line filter (launch_line_filter_junc) and the descriptor
+// head at the junctions' tap rows with the sampling in its epilogue (launch_gemmr_gather_sample_junc).  It runs where the batched entries leave no dense maps — radius-4
+// NMS with the keep plane alone, no dense descriptor map — and the streaming gather GEMM applies at capJ * nj slots; everywhere else (B <= 2: the batch-1 keyframe path,
+// other radii, fp32 mode, the inspection hooks) the byte-map launches and sample_desc run as before.
+static void junction_gemm_args(airfe_ctx* c, int i0, int nj, float* d_junc, int capJ, const int* d_njunc, int h, int w, GemmArgs& g, DescSample& ds) {
+  const int R = AIRFE_INTERNAL_SIZE;
+  g.X1 = c->aDa + (size_t)i0 * (R / 8) * (R / 8) * 256; g.ld1 = 256; g.K1 = 256; g.Wp = c->cDb.w; g.bias = c->cDb.b;
+  g.M = (capJ + 7) / 8 * nj * 32; g.N = 256; g.cb_total = c->cDb.cbt; g.epi = EPI_STORE_F32; g.out = c->desc; g.ldo = 256;
+  g.gr_wgs = c->gemmr_wgs;
+  ds.feat = d_junc; ds.n = d_njunc; ds.Bs = nj; ds.B = nj; ds.cap = capJ; ds.HC = R / 8; ds.WC = R / 8;
+  ds.w_scale = (float)w / (float)R; ds.h_scale = (float)h / (float)R; ds.flag = nullptr;      // (the junction rows' sample_desc call passes no flag either)
+  ds.junc = 1;
+}
+bool junction_tail_fused(airfe_ctx* c, int nj, int capJ) {
+  if (nj < 1 || capJ < 1 || c->prec == 2 || c->cfg.nms_radius != 4 || c->nms_map_valid || c->desc_dense_valid || !c->desc_gather_stream) return false;
+  GemmArgs g;
+  DescSample ds;
+  junction_gemm_args(c, 0, nj, nullptr, capJ, nullptr, 1, 1, g, ds);
+  return g.M >= c->gemmr_min && gemmr_gather_sample_junc_applicable(g, ds);
+}
+
 // Everything behind the stage-0 tensors for stage slots 0 .. nb-1 (= images i0 .. i0+nb-1 of the detector batch): wireframe_matcher,
 // stage 1, the line / junction filter (plnet.cpp:272-307, 468-558) and, for the first nj of them, junction_detector + descriptors
 // (plnet.cpp:425-448).  LOI features: the head GEMM's rows (loi == nullptr) or a CHW block.  Results go to DEVICE buffers:
@@ -311,10 +332,10 @@ int line_tail_dev(airfe_ctx* c, int i0, int nb, const float* loi_chw, int h, int
   if (nb < 1 || nb > c->Lmax || nj < 0 || nj > nb) return fail(c, "line path: image range outside the arena");
   const int R = AIRFE_INTERNAL_SIZE, NP = KEEP_CAP;
   float* d = c->s0_stage;
-  const float ws = (float)w / (float)R, hs = (float)h / (float)R;
+  const bool fused = phase == 3 && junction_tail_fused(c, nj, capJ);
   if (phase & 1) {
   hipStream_t s4 = st;
-  if (nj > 0) launch_zero16(c->jmap, (size_t)nj * R * R, s4);
+  if (nj > 0 && !fused) launch_zero16(c->jmap, (size_t)nj * R * R, s4);
   {
   ProfScope ps(c, ST_PL_STAGE1, st, 0, (double)nb * 49152 * 12);
   launch_wireframe(d + SG_KEEP, d + SG_MIN, d + SG_MAX, NP, 300, c->wf_table, c->wf_keep, c->wf_pairs, c->wf_rep, KEEP_CAP, LINE_CAP,
@@ -348,18 +369,44 @@ int line_tail_dev(airfe_ctx* c, int i0, int nb, const float* loi_chw, int h, int
                       d + SG_AUX, c->s1_w, c->s1_la, c->s1_sc, KEEP_CAP, LINE_CAP, nb, SG_STRIDE, st);
   }
   }
-  ProfScope ps(c, ST_PL_FILTER, st, 0, (double)nb * R * R);
-  launch_line_filter(c->s1_la, c->s1_sc, c->wf_counts, c->cfg.remove_borders, c->cfg.line_threshold, c->cfg.line_length_threshold, ws, hs, R,
-                     c->jmap, nj, d_lines, capL, d_nlines, d_lfound, LINE_CAP, nb, st);
+  }
+  return line_post_dev(c, i0, nb, h, w, d_lines, capL, d_nlines, d_lfound, d_junc, capJ, d_njunc, d_jfound, nj, st, phase, fused);
+}
+
+// The end of line_tail_dev: the line filter over c->s1_la / c->s1_sc / c->wf_counts (phase & 1) and the junction rows of the first nj images (phase & 2).  fused
+// (junction_tail_fused, both phases in one call): two launches, no byte maps — else the caller has zeroed c->jmap and the dense descriptor map exists.  Shared with
+// the test hook airfe_debug_junction_tail (airfe_debug.hip).
+int line_post_dev(airfe_ctx* c, int i0, int nb, int h, int w, double* d_lines, int capL, int* d_nlines, int* d_lfound, float* d_junc, int capJ, int* d_njunc,
+                  int* d_jfound, int nj, hipStream_t st, int phase, bool fused) {
+  const int R = AIRFE_INTERNAL_SIZE;
+  const float ws = (float)w / (float)R, hs = (float)h / (float)R;
+  // junction scores = the NMS'd map at the junction pixels.  Where the dense map was not written (radius 4, large batches) the same values come from
+  // the raw scores under the NMS's final keep plane: 32 KB per image instead of 1 MB written for < 1024 single-float reads.
+  const bool from_mask = c->cfg.nms_radius > 0 && !c->nms_map_valid;
+  const float* hsel = (c->cfg.nms_radius > 0 && !from_mask ? c->heat_nms : c->heat) + (size_t)i0 * R * R;
+  const unsigned long long* mask = from_mask ? reinterpret_cast<const unsigned long long*>(c->nms_mask) + (size_t)i0 * (R / 8) * (R / 8) : nullptr;
+  if (fused) {
+    if (phase != 3 || nj < 1) return fail(c, "line path: the fused junction tail runs both phases in one call");
+    {
+      ProfScope ps(c, ST_PL_FILTER, st, 0, (double)nb * LINE_CAP * 20);
+      launch_line_filter_junc(c->s1_la, c->s1_sc, c->wf_counts, c->cfg.remove_borders, c->cfg.line_threshold, c->cfg.line_length_threshold, ws, hs, d_lines, capL,
+                              d_nlines, d_lfound, LINE_CAP, nb, nj, hsel, mask, d_junc, capJ, d_njunc, d_jfound, st);
+    }
+    GemmArgs g;
+    DescSample ds;
+    junction_gemm_args(c, i0, nj, d_junc, capJ, d_njunc, h, w, g, ds);
+    ProfScope ps(c, ST_HEAD_GEMM, st, 2.0 * g.M * 256 * 256, (double)g.M * 512);
+    launch_gemmr_gather_sample_junc(c->prec, g, ds, st);
+    return launch_status(c);
+  }
+  if (phase & 1) {
+    ProfScope ps(c, ST_PL_FILTER, st, 0, (double)nb * R * R);
+    launch_line_filter(c->s1_la, c->s1_sc, c->wf_counts, c->cfg.remove_borders, c->cfg.line_threshold, c->cfg.line_length_threshold, ws, hs, R,
+                       c->jmap, nj, d_lines, capL, d_nlines, d_lfound, LINE_CAP, nb, st);
   }
   if ((phase & 2) && nj > 0) {
     ProfScope ps(c, ST_PL_FILTER, st, 0, (double)nj * R * R * 2);
-    // junction scores = the NMS'd map at the junction pixels.  Where the dense map was not written (radius 4, large batches) the same values come from
-    // the raw scores under the NMS's final keep plane: 32 KB per image instead of 1 MB written for < 1024 single-float reads.
-    const bool from_mask = c->cfg.nms_radius > 0 && !c->nms_map_valid;
     if (from_mask && c->cfg.nms_radius != 4) return fail(c, "line path: the NMS'd score maps of this batch were not kept");
-    const float* hsel = (c->cfg.nms_radius > 0 && !from_mask ? c->heat_nms : c->heat) + (size_t)i0 * R * R;
-    const unsigned long long* mask = from_mask ? reinterpret_cast<const unsigned long long*>(c->nms_mask) + (size_t)i0 * (R / 8) * (R / 8) : nullptr;
     launch_junction_scan(c->jmap, hsel, R, c->cfg.remove_borders, d_junc, capJ, d_njunc, d_jfound, c->d_njunc + 2 * c->Lmax, nj, st, mask);
     if (!c->desc_dense_valid) return fail(c, "line path: the dense descriptor map of this batch was not made");
     launch_sample_desc(c->desc + (size_t)i0 * (R / 8) * (R / 8) * 256, nj, R / 8, R / 8, d_junc, d_njunc, capJ, ws, hs,

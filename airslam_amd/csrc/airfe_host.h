@@ -397,6 +397,9 @@ void junctions_topk_dev(airfe_ctx* c, int nb, hipStream_t st);
 int line_branch_dev(airfe_ctx* c, hipStream_t st, int i0, int nb, bool chw);
 int line_tail_dev(airfe_ctx* c, int i0, int nb, const float* loi_chw, int h, int w, double* d_lines, int capL, int* d_nlines, int* d_lfound,
                   float* d_junc, int capJ, int* d_njunc, int* d_jfound, int nj, hipStream_t st, int phase = 3);
+bool junction_tail_fused(airfe_ctx* c, int nj, int capJ);      // the junction list inside the line filter + the descriptors from the sampling gather GEMM (no dense maps)
+int line_post_dev(airfe_ctx* c, int i0, int nb, int h, int w, double* d_lines, int capL, int* d_nlines, int* d_lfound, float* d_junc, int capJ, int* d_njunc,
+                  int* d_jfound, int nj, hipStream_t st, int phase, bool fused);
 // ---- airfe_match.hip
 void trace(airfe_ctx* c, hipStream_t st, const char* what, size_t li, const char* blk, const void* p, size_t words, unsigned unit_words);
 int trace_finish(airfe_ctx* c, hipStream_t st);

@@ -30,10 +30,23 @@ constexpr int GR_STAGE_LD = 260;                  // SAMPLE: floats per staged r
 constexpr int GR_STAGE_BYTES = GR_TT * GR_STAGE_LD * 4;
 struct GrKeypoint { float x, y; int row, second; };   // SAMPLE: one keypoint slot of a tile: feature row of destination 0 / 1; row < 0: nothing to write (k >= n[b], or the padded tail)
 
-template <class P, bool TRANS, bool ROT, bool GATHER = false, bool SAMPLE = false>
+// JUNC (DescSample::junc): the tiles of the live prefix — every wave reads the B counts itself (no LDS, no barrier: the result is the same in every wave, so the
+// whole workgroup leaves or stays) and the tile count stops at ceil(max n[b] / 8) * B
+__device__ __forceinline__ int gr_junc_live_tiles(const DescSample& ds, int ntiles) {
+  int kmax = 0;
+  for (int b = threadIdx.x & 63; b < ds.B; b += 64) kmax = max(kmax, min(ds.n[b], ds.cap));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) kmax = max(kmax, __shfl_xor(kmax, o));
+  kmax = __builtin_amdgcn_readfirstlane(kmax);
+  return min(ntiles, ((kmax + 7) >> 3) * ds.B);
+}
+
+template <class P, bool TRANS, bool ROT, bool GATHER = false, bool SAMPLE = false, bool JUNC = false>
 __device__ __forceinline__ void gemmr_body(const GemmArgs& a, char* smem, int group, int first, int per_group, int ntiles, const DescSample* dsp = nullptr) {
   static_assert(!GATHER || (!TRANS && !ROT), "the gather form is the plain K = 256 linear with fp32 rows out");
   static_assert(!SAMPLE || GATHER, "sampling finishes the gather form's rows");
+  static_assert(!JUNC || SAMPLE, "the junction layout is a slot layout of the sampling form");
+  if constexpr (JUNC) ntiles = gr_junc_live_tiles(*dsp, ntiles);       // (before any DMA and any barrier; the ring's wait counts below depend on n only)
   constexpr int GR_SLOT = GR_XBYTES + (ROT ? GR_RBYTES : 0);
   constexpr int GR_SLOTS = ROT ? 6 : SAMPLE ? GR_SAMPLE_SLOTS : 8;
   constexpr int PER = ROT ? 3 : 2;                                    // DMA instructions per wave and tile
@@ -66,13 +79,32 @@ __device__ __forceinline__ void gemmr_body(const GemmArgs& a, char* smem, int gr
   [[maybe_unused]] float* stage = reinterpret_cast<float*>(smem + GR_SLOTS * GR_SLOT);      // SAMPLE: [32][GR_STAGE_LD] fp32, the tile's head rows
   [[maybe_unused]] int* idx_lds = reinterpret_cast<int*>(smem + GR_SLOTS * GR_SLOT + (SAMPLE ? GR_STAGE_BYTES : 0));
   [[maybe_unused]] GrKeypoint* kp_lds = reinterpret_cast<GrKeypoint*>(idx_lds + n * GR_TT);   // SAMPLE: [n][8] (16-byte entries behind the 128-byte index rows)
-  if constexpr (GATHER) {       // (a.rowidx == nullptr: the identity — every row in order, fp32 rows out: the DENSE descriptor head of the junction images)
+  if constexpr (GATHER && !JUNC) {       // (a.rowidx == nullptr: the identity — every row in order, fp32 rows out: the DENSE descriptor head of the junction images)
     for (int e = tid; e < n * GR_TT; e += 512) {
       const int r = (first + (e >> 5) * per_group) * GR_TT + (e & 31);
       idx_lds[e] = a.rowidx ? a.rowidx[r] : r;
     }
   }
-  if constexpr (SAMPLE) {       // keypoint slot s = row / 4 = b * cap + k over ALL images of the launch; the two destinations split at image Bs
+  if constexpr (JUNC) {         // tile T = slots 8 (T / B) .. + 7 of image T % B; the slot's four tap rows from its x, y (desc_taps, as the epilogue calls it): no row list in memory
+    const DescSample& ds = *dsp;
+    const int cells = ds.HC * ds.WC;
+    for (int e = tid; e < n * 8; e += 512) {
+      const int T = first + (e >> 3) * per_group;
+      const int b = T % ds.B, k = (T / ds.B) * 8 + (e & 7);
+      GrKeypoint kp{0.f, 0.f, -1, 0};
+      int r0 = 0, r1 = 0, r2 = 0, r3 = 0;                               // a dead slot gathers row 0 and writes nothing
+      if (k < ds.cap && k < ds.n[b]) {
+        const float* f = ds.feat + ((size_t)b * ds.cap + k) * 259;
+        kp.row = b * ds.cap + k;
+        kp.x = f[1];
+        kp.y = f[2];
+        const DescTaps t = desc_taps(kp.x, kp.y, ds.sx, ds.bx, ds.sy, ds.by, ds.HC, ds.WC);
+        r0 = b * cells + t.c[0]; r1 = b * cells + t.c[1]; r2 = b * cells + t.c[2]; r3 = b * cells + t.c[3];
+      }
+      kp_lds[e] = kp;
+      *reinterpret_cast<int4*>(idx_lds + e * 4) = make_int4(r0, r1, r2, r3);
+    }
+  } else if constexpr (SAMPLE) {       // keypoint slot s = row / 4 = b * cap + k over ALL images of the launch; the two destinations split at image Bs
     const DescSample& ds = *dsp;
     for (int e = tid; e < n * 8; e += 512) {
       const int s = (first + (e >> 3) * per_group) * 8 + (e & 7);

@@ -159,9 +159,17 @@ struct DescSample {
   float w_scale = 1.f, h_scale = 1.f;
   int* flag = nullptr;                               // flag[1] = 1 on a non-finite descriptor
   float sx = 0.f, bx = 0.f, sy = 0.f, by = 0.f;      // (the launcher's: desc_grid_coeffs of HC, WC)
+  // junc = 1, the JUNCTION slot layout (launch_gemmr_gather_sample_junc): no row list in memory — tile T holds slots k = 8 (T / B) .. + 7 of image b = T % B
+  // (one destination, feat [B][cap][259] with x, y unscaled in columns 1, 2 of the first n[b] rows), the four tap rows of a slot are computed from its x, y
+  // (b * HC * WC + desc_taps cell), and every workgroup stops at the stripes below ceil(max n[b] / 8) * B: with cap = 1024 for a few hundred junctions most
+  // tiles are dead, and interleaved over the images the live ones are a prefix of the tile order
+  int junc = 0;
 };
 bool gemmr_gather_sample_applicable(const GemmArgs& a);      // (on top of gemmr_gather_applicable: the per-keypoint list fits behind the ring too)
 void launch_gemmr_gather_sample(int prec, const GemmArgs& a, const DescSample& ds, hipStream_t st);
+// the junction layout: a.M = ceil(ds.cap / 8) * ds.B * 32 rows (the untrimmed bound), a.rowidx unused
+bool gemmr_gather_sample_junc_applicable(const GemmArgs& a, const DescSample& ds);
+void launch_gemmr_gather_sample_junc(int prec, const GemmArgs& a, const DescSample& ds, hipStream_t st);
 
 // ---- LightGlue ------------------------------------------------------------------------------
 struct LgPrepArgs {
@@ -254,6 +262,11 @@ void launch_zero16(void* p, size_t bytes, hipStream_t st);        // bytes % 16 
 // a junction's score is mask bit ? heat : 0 — the value of the dense NMS'd map
 void launch_junction_scan(const unsigned char* jmap, const float* heat, int R, int border, float* feat, int cap, int* n_kept, int* n_found,
                           int* wg_counts, int B, hipStream_t st, const unsigned long long* mask = nullptr);
+// launch_line_filter + launch_junction_scan as ONE launch without the byte maps (R = 512): the junction list of the first nj images from a bitmap in LDS.
+// heat [nj][512*512], mask [nj][64*64] keep-plane words or nullptr, feat [nj][capJ][259], n_kept / n_jfound [nj]; the same rows and counts
+void launch_line_filter_junc(const float* la, const float* sc, const int* counts, int border, float line_thr, float len_thr, float w_scale, float h_scale,
+                             double* lines_out, int capL, int* nlines, int* nfound, int line_cap, int B, int nj, const float* heat, const unsigned long long* mask,
+                             float* feat, int capJ, int* n_kept, int* n_jfound, hipStream_t st);
 
 // ---- fp32 correctness path (kernels_f32.hip; cfg.precision = 2): fp32 storage, f32-input MFMA, plain kernels
 struct GemmF32Args {

@@ -1002,6 +1002,116 @@ void launch_line_filter(const float* la, const float* sc, const int* counts, int
                      h_scale, R, jmap, lines_out, capL, nlines, nfound, line_cap, nj);
 }
 
+// The same filter with the junction list of the images b < nj built in the workgroup (no byte map, no scan launches): junction_map[y][x] = p_valid(x, y) is non-zero
+// exactly at the endpoint pixels with p true, all of them inside the scan's box, so the scan's output is the set of those pixels in raster order.  A 512 x 512-bit
+// map in LDS (32 KB): cleared, bits set by atomic OR in pass 0, then thread t owns pixels [256 t, 256 t + 256) — popcount, one block scan, ordered emit of
+// junction_emit_kernel's rows (score = heat under the keep plane `mask`, or heat itself where mask == nullptr: the dense NMS'd map).  R = 512.
+constexpr int LFJ_R = 512, LFJ_WORDS = LFJ_R * LFJ_R / 32;
+__global__ __launch_bounds__(1024) void line_filter_junc_kernel(const float* __restrict__ la, const float* __restrict__ sc, const int* __restrict__ counts, int border,
+                                                                float line_thr, float len_thr, float w_scale, float h_scale, double* __restrict__ lines_out, int capL,
+                                                                int* __restrict__ nlines, int* __restrict__ nfound, int line_cap, int nj,
+                                                                const float* __restrict__ heat, const unsigned long long* __restrict__ mask,
+                                                                float* __restrict__ feat, int capJ, int* __restrict__ n_kept, int* __restrict__ n_jfound) {
+  constexpr int R = LFJ_R;
+  __shared__ unsigned wsum[16];
+  __shared__ __attribute__((aligned(16))) unsigned bits[LFJ_WORDS];
+  const bool mark = (int)blockIdx.x < nj;          // (workgroup-uniform) only the images whose junctions are wanted build a list
+  {
+    const size_t img = blockIdx.x;
+    la += img * line_cap * 4; sc += img * line_cap; counts += img * LINE_CNT_LD;
+    lines_out += img * capL * 4; nlines += img;
+    if (nfound) nfound += img;
+    if (mark) {
+      heat += img * R * R; feat += img * capJ * 259; n_kept += img; n_jfound += img;
+      if (mask) mask += img * (size_t)(R / 8) * (R / 8);
+    }
+  }
+  const int tid = threadIdx.x, m2 = counts[1];
+  const int per = (m2 + 1023) / 1024, lo = tid * per, hi = min(lo + per, m2);
+  const float thr2 = __fmul_rn(len_thr, len_thr);
+  border = max(border, 0);
+  if (mark) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) reinterpret_cast<uint4*>(bits)[k * 1024 + tid] = make_uint4(0, 0, 0, 0);
+    __syncthreads();
+  }
+  unsigned cnt = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    unsigned off = 0, tot = 0;
+    if (pass == 1) off = block_excl_scan_1024(cnt, wsum, &tot);
+    for (int i = lo; i < hi; ++i) {
+      const float s = sc[i];
+      if (s < 0.5f) continue;
+      const float x1 = __fmul_rn(la[i * 4], 4.f), y1 = __fmul_rn(la[i * 4 + 1], 4.f);
+      const float x2 = __fmul_rn(la[i * 4 + 2], 4.f), y2 = __fmul_rn(la[i * 4 + 3], 4.f);
+      if (pass == 0 && mark) {
+        const int xi1 = (int)((double)x1 + 0.1), yi1 = (int)((double)y1 + 0.1);
+        const int xi2 = (int)((double)x2 + 0.1), yi2 = (int)((double)y2 + 0.1);
+        const bool p1 = xi1 > border && xi1 < R - border && yi1 > border && yi1 < R - border;      // (p implies 0 < xi, yi < R: inside the map)
+        const bool p2 = xi2 > border && xi2 < R - border && yi2 > border && yi2 < R - border;
+        if (p1) atomicOr(&bits[(yi1 * R + xi1) >> 5], 1u << (xi1 & 31));
+        if (p2) atomicOr(&bits[(yi2 * R + xi2) >> 5], 1u << (xi2 & 31));
+      }
+      if (s < line_thr) continue;
+      const float dx = __fsub_rn(x2, x1), dy = __fsub_rn(y2, y1);
+      const float l2 = __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
+      if (l2 < thr2) continue;
+      if (pass == 0) ++cnt;
+      else {
+        if (off < (unsigned)capL) {
+          lines_out[(size_t)off * 4 + 0] = (double)x1 * (double)w_scale;
+          lines_out[(size_t)off * 4 + 1] = (double)y1 * (double)h_scale;
+          lines_out[(size_t)off * 4 + 2] = (double)x2 * (double)w_scale;
+          lines_out[(size_t)off * 4 + 3] = (double)y2 * (double)h_scale;
+        }
+        ++off;
+      }
+    }
+    if (pass == 1 && tid == 0) {
+      *nlines = min((int)tot, capL);
+      if (nfound) *nfound = (int)tot;
+    }
+  }
+  if (!mark) return;
+  __syncthreads();                                 // every bit of pass 0 is set (the scan above has barriers of its own; this one does not depend on them)
+  unsigned w[8];
+  {
+    const uint4 q0 = reinterpret_cast<const uint4*>(bits)[tid * 2], q1 = reinterpret_cast<const uint4*>(bits)[tid * 2 + 1];
+    w[0] = q0.x; w[1] = q0.y; w[2] = q0.z; w[3] = q0.w; w[4] = q1.x; w[5] = q1.y; w[6] = q1.z; w[7] = q1.w;
+  }
+  unsigned jc = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) jc += __builtin_popcount(w[k]);
+  unsigned jtot = 0;
+  unsigned joff = block_excl_scan_1024(jc, wsum, &jtot);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    unsigned m = w[k];
+    while (m) {
+      const int bit = __builtin_ctz(m);
+      m &= m - 1;
+      const int i = (tid * 8 + k) * 32 + bit, y = i / R, x = i - y * R;
+      if (joff < (unsigned)capJ) {
+        float* f = feat + (size_t)joff * 259;
+        f[0] = (!mask || ((mask[(size_t)(y >> 3) * (R / 8) + (x >> 3)] >> (8 * (y & 7) + (x & 7))) & 1ull)) ? heat[i] : 0.f;
+        f[1] = (float)x;
+        f[2] = (float)y;
+      }
+      ++joff;
+    }
+  }
+  if (tid == 0) { *n_kept = min((int)jtot, capJ); *n_jfound = (int)jtot; }      // found > cap: the caller reports the overflow
+}
+
+// launch_line_filter + launch_junction_scan in one launch, without the byte maps (R = 512): feat [nj][capJ][259], n_kept / n_jfound [nj], heat [nj][R * R],
+// mask [nj][64 * 64] keep-plane words or nullptr (heat is the dense NMS'd map then)
+void launch_line_filter_junc(const float* la, const float* sc, const int* counts, int border, float line_thr, float len_thr, float w_scale, float h_scale,
+                             double* lines_out, int capL, int* nlines, int* nfound, int line_cap, int B, int nj, const float* heat, const unsigned long long* mask,
+                             float* feat, int capJ, int* n_kept, int* n_jfound, hipStream_t st) {
+  hipLaunchKernelGGL(line_filter_junc_kernel, dim3(B), dim3(1024), 0, st, la, sc, counts, border, line_thr, len_thr, w_scale, h_scale, lines_out, capL, nlines,
+                     nfound, line_cap, nj, heat, mask, feat, capJ, n_kept, n_jfound);
+}
+
 // hipMemsetAsync's byte fill ran at ~110 GB/s on 33 MB of junction maps (0.3 ms per step): 16-byte stores instead
 __global__ __launch_bounds__(256) void zero16_kernel(uint4* __restrict__ p, size_t n16) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) p[i] = make_uint4(0, 0, 0, 0);

@@ -253,6 +253,26 @@ typedef struct airfe_debug_line_post_args {
   const unsigned char* jmap;      /* [nj][512][512] or NULL */
 } airfe_debug_line_post_args;
 int airfe_debug_line_post(airfe_ctx* ctx, airfe_debug_line_post_args* a);
+/* The junction tail of the batched line path, line filter -> junction descriptors, in the form production chooses (line_post_dev, the function line_tail_dev ends in): with
+ * the dense maps gone (B > 2: radius-4 keep plane, no dense descriptor map) and the streaming gather GEMM applicable at ceil(capJ / 8) * nj * 32 rows (>=
+ * airfe_tuning::gemmr_min_m) the junction list is built inside the line filter from a bitmap in LDS and the descriptors come from the sampling gather GEMM at the junctions'
+ * tap rows (fused = 1); else the byte maps, the two scan launches, the dense descriptor head (of all B <= 2 images, as the detector leaves it, or of the nj junction images)
+ * and sample_desc run (fused = 0).  la / sc / m2 / heat as airfe_debug_line_post takes them; act: convDa activations, rounded to the context's 2-byte type on the way in.
+ * lines / junc are uploaded as the caller filled them and come back whole: rows past the counts keep the caller's sentinel, rows below them hold score, x, y (scaled to
+ * w, h) and the 256 descriptor columns.  nfound / jfound: the true counts (> cap = the overflow). */
+typedef struct airfe_debug_junction_tail_args {
+  int B, nj, ld, h, w, capL, capJ;
+  const float *la, *sc;           /* [B][ld][4], [B][ld] */
+  const int* m2;                  /* [B] */
+  const float* heat;              /* [B][512][512] */
+  const float* act;               /* [B][64][64][256] */
+  double* lines;                  /* [B][capL][4] in / out */
+  int *nlines, *nfound;           /* [B] out */
+  float* junc;                    /* [nj][capJ][259] in / out */
+  int *njunc, *jfound;            /* [nj] out */
+  int fused;                      /* out */
+} airfe_debug_junction_tail_args;
+int airfe_debug_junction_tail(airfe_ctx* ctx, airfe_debug_junction_tail_args* a);
 /* get_junctions alone (junctions_topk_dev, the function the line branch calls): jloc [B][128][128], joff [B][2][128][128] -> juncs_pred [B][300][2] (rows past the number of
  * positive 3x3 maxima: 0, 0) */
 int airfe_debug_junctions_topk(airfe_ctx* ctx, const float* jloc, const float* joff, int B, float* juncs_pred);
