@@ -1,5 +1,5 @@
 // airfe — context life cycle, scratch blocks, host staging and the C ABI of libairfe.so (include/airfe.h, include/airfe_debug.h); the pipelines behind it live in
-// airfe_load.hip / airfe_detect.hip / airfe_match.hip, the geometry, BoW and kernel-hook entries in airfe_geom.hip / airfe_bowdb.hip / airfe_debug.hip (see airfe_host.h).
+// airfe_load.hip / airfe_detect.hip / airfe_lines.hip / airfe_match.hip, the geometry, BoW and kernel-hook entries in airfe_geom.hip / airfe_bowdb.hip / airfe_debug.hip (see airfe_host.h).
 #include "airfe_host.h"
 
 namespace airfe_host {
@@ -803,7 +803,7 @@ int airfe_detect_plnet(airfe_ctx* c, const uint8_t* gray, int h, int w, int stri
   }
   int* nl_d = c->d_nlines;                            // [0] kept (<= LINE_CAP: the staging holds every candidate), [Lmax] found
   int *nj_d = c->d_njunc, *njf_d = c->d_njunc + c->Lmax;
-  if (line_tail_dev(c, 0, 1, s0 ? c->s0_loi : nullptr, h, w, c->d_lines, LINE_CAP, nl_d, nl_d + c->Lmax, c->junc_feat, JUNC_CAP, nj_d, njf_d,
+  if (line_tail_dev(c, 0, 1, s0 != nullptr, h, w, c->d_lines, LINE_CAP, nl_d, nl_d + c->Lmax, c->junc_feat, JUNC_CAP, nj_d, njf_d,
                     want_junctions ? 1 : 0, st))
     return 1;
   const size_t fbytes = 64 + (size_t)c->cfg.max_keypoints * AIRFE_FEAT_DIM * 4;
@@ -851,15 +851,10 @@ static int plnet_lines_batch(airfe_ctx* c, int B, int h, int w, double* d_lines,
   if (nj < 0 || nj > B || (nj > 0 && (!d_junc || !d_njunc || capJ < 1))) return fail(c, "detect_plnet_batch: bad junction arguments");
   if ((phase & 1) && line_branch_dev(c, st, 0, B, false)) return 1;
   bool partial = false;
-  // (junction_tail_fused: line_tail_dev runs the head at the junctions' tap rows only, inside the sampling gather GEMM — no dense map, desc_dense_valid stays false)
-  if ((phase & 2) && nj > 0 && !c->desc_dense_valid && !(phase == 3 && junction_tail_fused(c, nj, capJ))) {   // the point branch ran the descriptor head on the sampled
-    dense_desc_head(c, nj, st);                   // cells only: the junction images' dense maps now (the points have theirs already; c->desc is free to be rewritten)
-    c->desc_dense_valid = true;
-    partial = nj != c->last_B;
-  }
+  if (junction_dense_maps(c, nj, capJ, phase, st, partial)) return 1;
   int* lfound = d_found ? d_found : c->d_nlines + c->Lmax;
   int* jfound = d_found ? d_found + B : c->d_njunc + c->Lmax;
-  const int rc = line_tail_dev(c, 0, B, nullptr, h, w, d_lines, capL, d_nlines, lfound, d_junc, capJ, d_njunc, jfound, nj, st, phase);
+  const int rc = line_tail_dev(c, 0, B, false, h, w, d_lines, capL, d_nlines, lfound, d_junc, capJ, d_njunc, jfound, nj, st, phase);
   if (partial) c->desc_dense_valid = false;       // (only the first nj images' dense maps exist)
   return rc;
 }
@@ -876,7 +871,7 @@ static int plnet_batch_f32(airfe_ctx* c, const uint8_t* d_gray, int B, int h, in
     const bool jn = b < nj;
     const int rc = detect_dev(c, d_gray + (size_t)b * img_stride, 1, h, w, stride, img_stride, d_feat + (size_t)b * cap * AIRFE_FEAT_DIM, cap, d_n + b, st);      // (one image: the dense NMS'd map is written)
     if (rc || line_branch_dev(c, st, 0, 1, false)) return 1;
-    if (line_tail_dev(c, 0, 1, nullptr, h, w, d_lines + (size_t)b * capL * 4, capL, d_nlines + b, lfound ? lfound + b : c->d_nlines + c->Lmax,
+    if (line_tail_dev(c, 0, 1, false, h, w, d_lines + (size_t)b * capL * 4, capL, d_nlines + b, lfound ? lfound + b : c->d_nlines + c->Lmax,
                       jn ? d_junc + (size_t)b * capJ * AIRFE_FEAT_DIM : nullptr, capJ, jn ? d_njunc + b : nullptr, jn ? (jfound ? jfound + b : c->d_njunc + c->Lmax) : nullptr,
                       jn ? 1 : 0, st, 3))
       return 1;
@@ -1352,11 +1347,8 @@ int airfe_debug_plnet_s1(airfe_ctx* c, const airfe_plnet_stage0* s0, float* line
   if (!c || !c->has_s1 || !s0) return fail(c, "debug_plnet_s1: stage-1 not loaded");
   hipStream_t st = c->stream;
   if (upload_stage0(c, s0, st)) return 1;
-  float* d = c->s0_stage;
-  launch_wireframe(d + SG_KEEP, d + SG_MIN, d + SG_MAX, KEEP_CAP, 300, c->wf_table, c->wf_keep, c->wf_pairs, c->wf_rep, KEEP_CAP, LINE_CAP,
-                   c->wf_counts, false, d + SG_JUNCS, d + SG_LP, c->s1_la, c->wf_prop, 1, SG_STRIDE, st);
-  launch_plnet_s1(d + SG_JUNCS, d + SG_LP, c->wf_keep, c->wf_pairs, c->wf_rep, c->wf_counts, c->s0_loi, 0, nullptr, nullptr, d + SG_THIN, d + SG_AUX,
-                  c->s1_w, c->s1_la, c->s1_sc, KEEP_CAP, LINE_CAP, 1, SG_STRIDE, st);
+  line_dedup(c, 1, st);                        // (upload_stage0 left wf_counted false: host tensors, nothing has counted their kept proposals)
+  line_stage1(c, 1, S1_CHW, 0, st);
   int cnt[2] = {0, 0};
   HIPCHK(c, hipMemcpyAsync(cnt, c->wf_counts, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));

@@ -672,7 +672,8 @@ int airfe_debug_lg_assign(airfe_ctx* c, airfe_debug_lg_assign_args* a) try {
 } AIRFE_CATCH(c)
 
 /* ---- the detector's and the line path's index work on hand-built maps (include/airfe_debug.h; tests/test_gpu_detector_tail_pin.py, tests/detector_tail_ref.py).  HOST tensors
- * staged into the context's own buffers, then the launchers production calls, in production's order and with production's arguments; nothing here has a kernel of its own. */
+ * staged into the context's own buffers, then the steps production is composed of (airfe_detect.hip, airfe_lines.hip: each launch sequence is stated there once, the hooks call it;
+ * tests/test_line_path_one_statement_cpu.py); nothing here has a kernel or a line-path launch of its own. */
 int airfe_debug_detector_tail(airfe_ctx* c, airfe_debug_detector_tail_args* a) try {
   AIRFE_ENTER(c);
   if (!c->has_sp) return fail(c, "debug_detector_tail: detector not loaded");
@@ -700,11 +701,9 @@ int airfe_debug_detector_tail(airfe_ctx* c, airfe_debug_detector_tail_args* a) t
   clear_saturation(c);
   HIPCHK(c, hipMemcpyAsync(c->heat, a->heat, px * 4, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(c->aDa, act.data(), act.size() * 2, hipMemcpyHostToDevice, st));
-  // detect_dev2's descriptor-head rule (airfe_detect.hip), then its tail
-  const bool sparse_desc = B > 2 && cap * 4 <= (R / 8) * (R / 8) && cap <= 1024;
-  if (!sparse_desc && dense_desc_head(c, B, st)) { (void)hipStreamSynchronize(st); return 1; }
-  c->desc_dense_valid = !sparse_desc;
-  c->last_B = B;
+  // detect_dev2's descriptor-head rule (point_desc_head), then its tail
+  bool sparse_desc = false;
+  if (point_desc_head(c, B, cap, st, sparse_desc)) { (void)hipStreamSynchronize(st); return 1; }
   const int rc = detect_tail_dev(c, B, Bs, two, sparse_desc, a->h, a->w, dfeat, dfeat1, cap, dn, dn1, st);
   HIPCHK(c, hipStreamSynchronize(st));                       // (act goes out of scope)
   if (rc) return 1;
@@ -753,21 +752,14 @@ int airfe_debug_line_post(airfe_ctx* c, airfe_debug_line_post_args* a) try {
   c->nms_map_valid = !a->from_plane;
   launch_nms512_candidates(c->heat, c->nms_map_valid ? c->heat_nms : nullptr, c->nms_mask, B, c->cfg.keypoint_threshold, c->cfg.remove_borders, c->cand, c->cand_cnt,
                            R * R, st);
-  // line_tail_dev's filter and junction scan (airfe_detect.hip), images 0 .. B-1, junctions of the first nj
-  const float ws = (float)a->w / (float)R, hs = (float)a->h / (float)R;
-  if (nj > 0) launch_zero16(c->jmap, (size_t)nj * R * R, st);
-  launch_line_filter(c->s1_la, c->s1_sc, c->wf_counts, c->cfg.remove_borders, c->cfg.line_threshold, c->cfg.line_length_threshold, ws, hs, R, c->jmap, nj, dlines, capL,
-                     dcnt, dcnt + B, LINE_CAP, B, st);
+  // line_post_dev's steps without the descriptor sampling (line_filter_maps, junction_scan_maps), images 0 .. B-1, junctions of the first nj
+  junction_maps_clear(c, nj, st);
+  line_filter_maps(c, B, nj, a->h, a->w, dlines, capL, dcnt, dcnt + B, st);
   // a caller's junction maps instead of the filter's, between the two launches: the scan's own bounds (the filter never marks a pixel the scan would reject)
   if (nj > 0 && a->jmap) HIPCHK(c, hipMemcpyAsync(c->jmap, a->jmap, (size_t)nj * R * R, hipMemcpyHostToDevice, st));
-  if (nj > 0) {
-    const bool from_mask = c->cfg.nms_radius > 0 && !c->nms_map_valid;
-    const float* hsel = c->cfg.nms_radius > 0 && !from_mask ? c->heat_nms : c->heat;
-    const unsigned long long* mask = from_mask ? reinterpret_cast<const unsigned long long*>(c->nms_mask) : nullptr;
-    launch_junction_scan(c->jmap, hsel, R, c->cfg.remove_borders, djunc, capJ, dcnt + 2 * B, dcnt + 3 * B, c->d_njunc + 2 * c->Lmax, nj, st, mask);
-  }
+  const int rc = nj > 0 ? junction_scan_maps(c, 0, nj, djunc, capJ, dcnt + 2 * B, dcnt + 3 * B, st) : 0;
   HIPCHK(c, hipStreamSynchronize(st));                       // (counts goes out of scope)
-  if (launch_status(c)) return 1;
+  if (rc || launch_status(c)) return 1;
   if (saturation_status(c)) return 1;
   HIPCHK(c, hipMemcpy(a->lines, dlines, (size_t)B * capL * 32, hipMemcpyDeviceToHost));
   HIPCHK(c, hipMemcpy(a->nlines, dcnt, (size_t)B * 4, hipMemcpyDeviceToHost));
@@ -781,7 +773,7 @@ int airfe_debug_line_post(airfe_ctx* c, airfe_debug_line_post_args* a) try {
 } AIRFE_CATCH(c)
 
 /* the junction tail as the batched entries run it (include/airfe_debug.h): the point branch's state as detect_dev2 leaves it, plnet_lines_batch's rule for the junction
- * images' dense descriptor map, then line_tail_dev's end (line_post_dev, airfe_detect.hip) — in either form, chosen as production chooses it */
+ * images' dense descriptor map (junction_dense_maps), then line_tail_dev's end (line_post_dev, airfe_lines.hip) — in either form, chosen as production chooses it */
 int airfe_debug_junction_tail(airfe_ctx* c, airfe_debug_junction_tail_args* a) try {
   AIRFE_ENTER(c);
   if (!c->has_sp || !c->has_s1 || !c->s1_la || !c->jmap) return fail(c, "debug_junction_tail: the line path is not loaded (cfg.plnet_s1_pack)");
@@ -828,15 +820,11 @@ int airfe_debug_junction_tail(airfe_ctx* c, airfe_debug_junction_tail_args* a) t
     rc = dense_desc_head(c, B, st);
     c->desc_dense_valid = true;
   }
-  // plnet_lines_batch's rule (airfe.hip), then line_tail_dev's clear of the byte maps and its end
-  const bool fused = junction_tail_fused(c, nj, capJ);
+  // plnet_lines_batch's rule (junction_dense_maps), then line_tail_dev's clear of the byte maps and its end
   bool partial = false;
-  if (!rc && nj > 0 && !c->desc_dense_valid && !fused) {
-    rc = dense_desc_head(c, nj, st);
-    c->desc_dense_valid = true;
-    partial = nj != B;
-  }
-  if (!rc && nj > 0 && !fused) launch_zero16(c->jmap, (size_t)nj * R * R, st);
+  if (!rc) rc = junction_dense_maps(c, nj, capJ, 3, st, partial);
+  const bool fused = junction_tail_fused(c, nj, capJ);
+  if (!rc && !fused) junction_maps_clear(c, nj, st);
   if (!rc) rc = line_post_dev(c, 0, B, a->h, a->w, dlines, capL, dcnt, dcnt + B, djunc, capJ, dcnt + 2 * B, dcnt + 3 * B, nj, st, 3, fused);
   if (partial) c->desc_dense_valid = false;
   HIPCHK(c, hipStreamSynchronize(st));                       // (counts, act go out of scope)
@@ -854,8 +842,8 @@ int airfe_debug_junction_tail(airfe_ctx* c, airfe_debug_junction_tail_args* a) t
   return 0;
 } AIRFE_CATCH(c)
 
-/* the line path between the stage-0 tensors and the line filter (include/airfe_debug.h): line_branch_dev's launch_s0_j2l, then line_tail_dev's launch_wireframe, junction
- * projections and stage 1 (airfe_detect.hip), on host tensors staged into the stage block and the line-path buffers */
+/* the line path between the stage-0 tensors and the line filter (include/airfe_debug.h): line_branch_dev's line_match, then line_tail_dev's line_dedup, line_tap_rows and
+ * line_stage1 (airfe_lines.hip), on host tensors staged into the stage block and the line-path buffers */
 int airfe_debug_line_mid(airfe_ctx* c, airfe_debug_line_mid_args* a) try {
   AIRFE_ENTER(c);
   if (!c->has_sp || !c->has_s0 || !c->has_s1 || !c->s0_stage || !c->l_ta8) return fail(c, "debug_line_mid: the line path is not loaded (line.* tensors, cfg.plnet_s1_pack)");
@@ -911,14 +899,12 @@ int airfe_debug_line_mid(airfe_ctx* c, airfe_debug_line_mid_args* a) try {
   HIPCHK(c, hipMemsetAsync(c->s1_sc, 0xFF, L * LINE_CAP * 4, st));
   HIPCHK(c, hipMemsetAsync(c->s1_jfeat, 0xFF, L * 300 * 256 * 4, st));
   HIPCHK(c, hipMemsetAsync(c->l_ridx, 0xFF, L * 1200 * 4, st));
-  // ---- line_branch_dev's match
-  bool counted = false;
-  if (a->j2l) counted = launch_s0_j2l(d + SG_LP, d + SG_JUNCS, 300, NP, 10.0f, d + SG_KEEP, d + SG_MIN, d + SG_MAX, c->wf_counts, B, SG_STRIDE, a->j2l == 1 ? 1 : 0, st);
-  if (a->j2l == 2 && !counted) { (void)hipStreamSynchronize(st); return fail(c, "debug_line_mid: the cell search did not leave the per-workgroup counts (the line path's form)"); }
-  // ---- line_tail_dev: the kept list and the unique pairs
-  launch_wireframe(d + SG_KEEP, d + SG_MIN, d + SG_MAX, NP, 300, c->wf_table, c->wf_keep, c->wf_pairs, c->wf_rep, KEEP_CAP, LINE_CAP, c->wf_counts, counted, d + SG_JUNCS,
-                   d + SG_LP, c->s1_la, c->wf_prop, B, SG_STRIDE, st);
-  c->wf_counted = false;
+  // ---- line_branch_dev's match (line_match)
+  c->wf_counted = false;                                     // (j2l = 0: the caller's match, which nothing has counted)
+  if (a->j2l) line_match(c, B, a->j2l == 1, st);
+  if (a->j2l == 2 && !c->wf_counted) { (void)hipStreamSynchronize(st); return fail(c, "debug_line_mid: the cell search did not leave the per-workgroup counts (the line path's form)"); }
+  // ---- line_tail_dev: the kept list and the unique pairs (line_dedup)
+  line_dedup(c, B, st);
   HIPCHK(c, hipStreamSynchronize(st));                       // (ta8 is on the device)
   if (launch_status(c)) return 1;
   HIPCHK(c, hipMemcpy(a->head4, c->s1_la, L * LINE_CAP * 16, hipMemcpyDeviceToHost));
@@ -930,39 +916,28 @@ int airfe_debug_line_mid(airfe_ctx* c, airfe_debug_line_mid_args* a) try {
     for (int p = 0; p < NPX; ++p)
       for (int ch = 0; ch < 128; ++ch) chw[(size_t)ch * NPX + p] = a->loi[(size_t)p * 128 + ch];
     HIPCHK(c, hipMemcpyAsync(c->s0_loi, chw.data(), chw.size() * 4, hipMemcpyHostToDevice, st));
-    launch_plnet_s1(d + SG_JUNCS, d + SG_LP, c->wf_keep, c->wf_pairs, c->wf_rep, c->wf_counts, c->s0_loi, 0, nullptr, nullptr, d + SG_THIN, d + SG_AUX, c->s1_w, c->s1_la,
-                    c->s1_sc, KEEP_CAP, LINE_CAP, B, SG_STRIDE, st, a->wgs);
+  } else if (form == 1) {
+    head.resize((size_t)NPX * 160);
+    memset(head.data(), 0xFF, head.size() * 4);              // (columns 128 .. 159: the 17 decoded channels, which nothing behind stage 0 reads)
+    for (int p = 0; p < NPX; ++p) memcpy(&head[(size_t)p * 160], a->loi + (size_t)p * 128, 128 * 4);
+    HIPCHK(c, hipMemcpyAsync(c->l_head, head.data(), head.size() * 4, hipMemcpyHostToDevice, st));
   } else {
-    if (form == 1) {
-      head.resize((size_t)NPX * 160);
-      memset(head.data(), 0xFF, head.size() * 4);            // (columns 128 .. 159: the 17 decoded channels, which nothing behind stage 0 reads)
-      for (int p = 0; p < NPX; ++p) memcpy(&head[(size_t)p * 160], a->loi + (size_t)p * 128, 128 * 4);
-      HIPCHK(c, hipMemcpyAsync(c->l_head, head.data(), head.size() * 4, hipMemcpyHostToDevice, st));
-      launch_s1_junc_proj(d + SG_JUNCS, c->l_head, (size_t)128 * 128 * 160, 160, nullptr, 300, c->s1_w[0], c->s1_jfeat, B, SG_STRIDE, st);
-    } else {
-      const int M = B * 1200, Mp = (M + 255) / 256 * 256;
-      launch_s1_junc_rows(d + SG_JUNCS, 300, c->l_ridx, B, SG_STRIDE, st);
-      if (Mp > M) HIPCHK(c, hipMemsetAsync(c->l_ridx + M, 0, (size_t)(Mp - M) * 4, st));
-      HIPCHK(c, hipStreamSynchronize(st));
-      if (launch_status(c)) return 1;
-      std::vector<int> ridx((size_t)M);
-      HIPCHK(c, hipMemcpy(ridx.data(), c->l_ridx, ridx.size() * 4, hipMemcpyDeviceToHost));
-      lrows.resize((size_t)M * 128);
-      for (int r = 0; r < M; ++r) {                          // what the gather GEMM hands on: row ridx[r] of the [B * 128*128][128] line-feature matrix
-        const int b = r / 1200;
-        if (ridx[r] < b * NPX || ridx[r] >= (b + 1) * NPX) return fail(c, "debug_line_mid: launch_s1_junc_rows listed a row outside its image");
-        memcpy(&lrows[(size_t)r * 128], a->loi + (size_t)ridx[r] * 128, 128 * 4);
-      }
-      HIPCHK(c, hipMemcpyAsync(c->l_lrows, lrows.data(), lrows.size() * 4, hipMemcpyHostToDevice, st));
-      if (form == 3) launch_s1h_junc_proj(d + SG_JUNCS, c->l_lrows, 300, c->s1_wsplit[4], c->s1_wsplit[5], c->s1_jfeat, B, SG_STRIDE, st);
-      else launch_s1_junc_proj(d + SG_JUNCS, nullptr, 0, 0, c->l_lrows, 300, c->s1_w[0], c->s1_jfeat, B, SG_STRIDE, st);
+    const int M = B * 1200;
+    if (line_tap_rows(c, B, st)) return 1;
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (launch_status(c)) return 1;
+    std::vector<int> ridx((size_t)M);
+    HIPCHK(c, hipMemcpy(ridx.data(), c->l_ridx, ridx.size() * 4, hipMemcpyDeviceToHost));
+    lrows.resize((size_t)M * 128);
+    for (int r = 0; r < M; ++r) {                            // what the gather GEMM (line_loi_rows) hands on: row ridx[r] of the [B * 128*128][128] line-feature matrix
+      const int b = r / 1200;
+      if (ridx[r] < b * NPX || ridx[r] >= (b + 1) * NPX) return fail(c, "debug_line_mid: launch_s1_junc_rows listed a row outside its image");
+      memcpy(&lrows[(size_t)r * 128], a->loi + (size_t)ridx[r] * 128, 128 * 4);
     }
-    if (form == 3)
-      launch_plnet_s1h(c->wf_pairs, c->wf_counts, c->s1_jfeat, c->l_ta8, c->s1_wsplit, c->s1_w, c->s1_la, c->wf_prop, c->s1_sc, LINE_CAP, B, st, a->wgs);
-    else
-      launch_plnet_s1(d + SG_JUNCS, d + SG_LP, c->wf_keep, c->wf_pairs, c->wf_rep, c->wf_counts, nullptr, 0, c->s1_jfeat, c->l_ta8, d + SG_THIN, d + SG_AUX, c->s1_w,
-                      c->s1_la, c->s1_sc, KEEP_CAP, LINE_CAP, B, SG_STRIDE, st, a->wgs);
+    HIPCHK(c, hipMemcpyAsync(c->l_lrows, lrows.data(), lrows.size() * 4, hipMemcpyHostToDevice, st));
   }
+  static_assert(S1_CHW == 0 && S1_HEAD == 1 && S1_ROWS == 2 && S1_ROWS_H == 3, "s1_form (include/airfe_debug.h) is S1Form's first four");
+  line_stage1(c, B, form, a->wgs, st);
   HIPCHK(c, hipStreamSynchronize(st));
   if (launch_status(c)) return 1;
   if (saturation_status(c)) return 1;
@@ -990,8 +965,8 @@ int airfe_debug_line_mid(airfe_ctx* c, airfe_debug_line_mid_args* a) try {
   return 0;
 } AIRFE_CATCH(c)
 
-/* the stage-0 decode (include/airfe_debug.h): line_branch_dev's launch_s0_decode, launch_s0_head_decode, or launch_gemm + launch_s0_decode (fuse_dec = 0), on host head rows /
- * line features staged into the line branch's own buffers */
+/* the stage-0 decode (include/airfe_debug.h): line_branch_dev's steps line_decode_rows, line_head_decode, or line_head_gemm + line_decode_rows (fuse_dec = 0), on host head
+ * rows / line features staged into the line branch's own buffers */
 int airfe_debug_s0_decode(airfe_ctx* c, airfe_debug_s0_decode_args* a) try {
   AIRFE_ENTER(c);
   if (!c->has_s0 || !c->s0_stage || !c->l_ta8 || !c->s0_loi) return fail(c, "debug_s0_decode: the line path is not loaded (line.* tensors, cfg.plnet_s1_pack)");
@@ -1017,6 +992,7 @@ int airfe_debug_s0_decode(airfe_ctx* c, airfe_debug_s0_decode_args* a) try {
   DbgTmp t(mode ? a->prec : 0);
   float* djnms = dbg_canary<float>(&t.h, (size_t)B * NPX);
   if (!djnms) return fail(c, "debug_s0_decode: allocation failed");
+  float* jnms = a->want_jnms ? djnms : nullptr;
   // ---- every output 0xFF
   HIPCHK(c, hipMemsetAsync(d, 0xFF, (size_t)B * SG_STRIDE * 4, st));
   HIPCHK(c, hipMemsetAsync(c->l_jloc, 0xFF, (size_t)B * NPX * 4, st));
@@ -1032,8 +1008,7 @@ int airfe_debug_s0_decode(airfe_ctx* c, airfe_debug_s0_decode_args* a) try {
       if (!head) return fail(c, "debug_s0_decode: allocation failed");
     }
     HIPCHK(c, hipMemcpyAsync(head, a->rows, n * 4, hipMemcpyHostToDevice, st));
-    launch_s0_decode(head, a->ld, a->off, d + SG_LP, c->l_jloc, a->want_jnms ? djnms : nullptr, c->l_joff, d + SG_THIN, d + SG_AUX, a->want_loi ? c->s0_loi : nullptr,
-                     a->want_ta8 ? c->l_ta8 : nullptr, B, SG_STRIDE, st);
+    line_decode_rows(c, B, head, a->ld, a->off, jnms, a->want_ta8 != 0, a->want_loi != 0, st);
   } else {
     const size_t n = (size_t)B * NPX * 128;
     xin.resize(n);
@@ -1042,15 +1017,11 @@ int airfe_debug_s0_decode(airfe_ctx* c, airfe_debug_s0_decode_args* a) try {
     if (!make_linear(&t.h, a->w, a->b, 128, 17, lw)) return fail(c, "debug_s0_decode: allocation failed");
     HIPCHK(c, hipMemcpyAsync(c->l_feat, xin.data(), n * 2, hipMemcpyHostToDevice, st));
     if (mode == 1) {
-      launch_s0_head_decode(a->prec, c->l_feat, lw.w, lw.b, d + SG_LP, c->l_jloc, a->want_jnms ? djnms : nullptr, c->l_joff, c->l_ta8, B, SG_STRIDE, st, a->wgs);
-    } else {
+      line_head_decode(c, B, a->prec, lw, jnms, a->wgs, st);
+    } else {                                                 // (fuse_dec = 0: the 17-channel head as a GEMM, then the decode over its rows)
       HIPCHK(c, hipMemsetAsync(c->l_dec, 0xFF, (size_t)B * NPX * 32 * 4, st));
-      GemmArgs g;
-      g.X1 = c->l_feat; g.ld1 = 128; g.K1 = 128; g.Wp = lw.w; g.bias = lw.b;
-      g.M = B * (int)NPX; g.N = lw.N; g.cb_total = lw.cbt; g.epi = EPI_STORE_F32; g.out = c->l_dec; g.ldo = 32;
-      g.small_max = 1 << 30; g.g8_min = c->gemm8_min; g.gr_min = c->gemmr_min; g.gr_wgs = c->gemmr_wgs;
-      launch_gemm(a->prec, 128, false, g, st);
-      launch_s0_decode(c->l_dec, 32, 0, d + SG_LP, c->l_jloc, a->want_jnms ? djnms : nullptr, c->l_joff, d + SG_THIN, d + SG_AUX, nullptr, c->l_ta8, B, SG_STRIDE, st);
+      line_head_gemm(c, B, false, a->prec, lw, st);
+      line_decode_rows(c, B, c->l_dec, 32, 0, jnms, true, false, st);
     }
   }
   HIPCHK(c, hipStreamSynchronize(st));                       // (xin goes out of scope)

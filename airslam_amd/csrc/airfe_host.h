@@ -1,7 +1,8 @@
 // airfe — host side of libairfe.so, shared by its translation units: the context (persistent device arena, weights, staging blocks, stage timers),
 // error / allocation helpers and the internal entry points of the pipelines.
 //   airfe_load.hip    weight-pack loading and slab packing (≙ TensorRT engine build, src/plnet.cpp:24-196), the matcher arena
-//   airfe_detect.hip  the detector pipeline (encoder, heads, NMS, top-K, descriptors) and the PLNet line path
+//   airfe_detect.hip  the detector pipeline (encoder, heads, NMS, top-K, descriptors)
+//   airfe_lines.hip   the PLNet line path: its steps, and line_branch_dev / line_tail_dev / line_post_dev composed of them
 //   airfe_match.hip   LightGlue / SuperGlue forwards and the fault-hunting trace
 //   airfe.hip         context life cycle, scratch blocks, profiling / trace entries and the C ABI of detection, rectification, matching, lines, PLNet and the
 //                     keyframe / track / promote entries (include/airfe.h), with the inspection hooks that share a body with one of them
@@ -393,9 +394,26 @@ int detect_tail_dev(airfe_ctx* c, int B, int Bs, bool two, bool sparse_desc, int
 int detect_dev2(airfe_ctx* c, const uint8_t* d_gray, const uint8_t* d_gray1, int Bs, int h, int w, int stride, size_t img_stride,
                 float* d_feat, float* d_feat1, int cap, int* d_n, int* d_n1, hipStream_t st);
 int detect_dev(airfe_ctx* c, const uint8_t* d_gray, int B, int h, int w, int stride, size_t img_stride, float* d_feat, int cap, int* d_n, hipStream_t st);
+int point_desc_head(airfe_ctx* c, int B, int cap, hipStream_t st, bool& sparse);      // the sparse / dense descriptor-head decision, the dense head, desc_dense_valid and last_B
+// ---- airfe_lines.hip: the line path's steps (production's compositions below and the test hooks call the same ones)
 void junctions_topk_dev(airfe_ctx* c, int nb, hipStream_t st);
+void line_head_gemm(airfe_ctx* c, int nb, bool fused, int prec, const LinW& hw, hipStream_t st);
+void line_head_decode(airfe_ctx* c, int nb, int prec, const LinW& hw, float* jnms, int wgs, hipStream_t st);
+void line_decode_rows(airfe_ctx* c, int nb, const float* head, int ld, int off, float* jnms, bool ta8, bool loi_chw, hipStream_t st);
+void line_match(airfe_ctx* c, int nb, bool exact_all, hipStream_t st);
+void line_dedup(airfe_ctx* c, int nb, hipStream_t st);
+int line_tap_rows(airfe_ctx* c, int nb, hipStream_t st);
+void line_loi_rows(airfe_ctx* c, int nb, hipStream_t st);
+// stage 1's LOI source and operand form.  0 .. 3 are airfe_debug_line_mid's s1_form (include/airfe_debug.h); S1_HEAD_H is fp32 mode with cfg.line_precision = 3.
+enum S1Form { S1_CHW = 0, S1_HEAD = 1, S1_ROWS = 2, S1_ROWS_H = 3, S1_HEAD_H = 4 };      // CHW tensors | head rows | gathered rows, fp32 | gathered rows, fp16 pairs | head rows, fp16 pairs
+void line_stage1(airfe_ctx* c, int nb, int form, int wgs, hipStream_t st);
+void junction_maps_clear(airfe_ctx* c, int nj, hipStream_t st);
+void line_filter_maps(airfe_ctx* c, int nb, int nj, int h, int w, double* d_lines, int capL, int* d_nlines, int* d_lfound, hipStream_t st);
+int junction_scan_maps(airfe_ctx* c, int i0, int nj, float* d_junc, int capJ, int* d_njunc, int* d_jfound, hipStream_t st);
+int junction_desc_sample(airfe_ctx* c, int i0, int nj, int h, int w, float* d_junc, int capJ, const int* d_njunc, hipStream_t st);
+int junction_dense_maps(airfe_ctx* c, int nj, int capJ, int phase, hipStream_t st, bool& partial);
 int line_branch_dev(airfe_ctx* c, hipStream_t st, int i0, int nb, bool chw);
-int line_tail_dev(airfe_ctx* c, int i0, int nb, const float* loi_chw, int h, int w, double* d_lines, int capL, int* d_nlines, int* d_lfound,
+int line_tail_dev(airfe_ctx* c, int i0, int nb, bool host_s0, int h, int w, double* d_lines, int capL, int* d_nlines, int* d_lfound,
                   float* d_junc, int capJ, int* d_njunc, int* d_jfound, int nj, hipStream_t st, int phase = 3);
 bool junction_tail_fused(airfe_ctx* c, int nj, int capJ);      // the junction list inside the line filter + the descriptors from the sampling gather GEMM (no dense maps)
 int line_post_dev(airfe_ctx* c, int i0, int nb, int h, int w, double* d_lines, int capL, int* d_nlines, int* d_lfound, float* d_junc, int capJ, int* d_njunc,
