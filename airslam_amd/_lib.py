@@ -223,6 +223,17 @@ SIGNATURES = {
     "airfe_bowdb_get_point_ids": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "airfe_bowdb_build_covisibility_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "airfe_bowdb_build_covisibility": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "airfe_junction_connections_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int] +
+                                             [C.c_void_p] * 4),
+    "airfe_junction_connections": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int),
+                                             C.c_void_p]),
+    "airfe_bowdb_attach_junctions": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "airfe_bowdb_set_junctions_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6),
+    "airfe_bowdb_set_junctions": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5),
+    "airfe_bowdb_get_junctions": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 10),
+    "airfe_bowdb_junction_term_batch_dev": (C.c_int, [C.c_void_p] * 9 + [C.c_int] + [C.c_void_p] * 4),
+    "airfe_bowdb_junction_extra_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 4),
+    "airfe_bowdb_add_junction_frames_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
     "airfe_bowdb_query_stored_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] +
                                            [C.c_void_p] * 4),
     "airfe_loop_detect_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(LoopCfg), C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_int] +

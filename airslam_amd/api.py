@@ -1059,6 +1059,28 @@ class Context:
         self._chk(self._l.airfe_bow_vector_batch_dev(self._h, feat_t.data_ptr(), n_t.data_ptr(), b, cap, ids_t.data_ptr(), vals_t.data_ptr(), nw_t.data_ptr(),
                                                      word_t.data_ptr() if word_t is not None else None, self._stream(stream)), "airfe_bow_vector_batch_dev")
 
+    def junction_connections(self, lines: np.ndarray, junc: np.ndarray, W: int, H: int, ecap: int = 4096):
+        """≙ Frame::FindJunctionConnections (src/frame.cc:581-629), the host core on one frame: lines [nl, 4] f64, junction rows [nj, 259] ->
+        (edges int32 [ne, 2] distinct, ascending by (a, b); per line (a, b) or (-1, -1) int32 [nl, 2]; status 0 / 2 = more than ecap edges)."""
+        ln = np.ascontiguousarray(lines, np.float64).reshape(-1, 4)
+        jn = np.ascontiguousarray(junc, np.float32).reshape(-1, FEAT)
+        edge = np.zeros((max(int(ecap), 1), 2), np.int32)
+        pair = np.zeros((max(len(ln), 1), 2), np.int32)
+        ne = C.c_int(0)
+        rc = self._l.airfe_junction_connections(self._h, ln.ctypes.data, len(ln), jn.ctypes.data, len(jn), int(W), int(H), edge.ctypes.data, int(ecap),
+                                                C.byref(ne), pair.ctypes.data)
+        if rc not in (0, 2):
+            self._chk(rc, "airfe_junction_connections")
+        return edge[:ne.value].copy(), pair[:len(ln)].copy(), rc
+
+    def junction_connections_batch_dev(self, lines_t, nlines_t, junc_t, njunc_t, W, H, edge_t, nedge_t, status_t, line_pair_t=None, stream=None):
+        """FindJunctionConnections over B device frames in place on the PLNet outputs: lines [B][capL][4] f64, nlines [B], junc [B][capJ][259], njunc [B] ->
+        edge [B][ecap][2] i32, nedge [B], status [B], line_pair [B][capL][2] or None."""
+        self._chk(self._l.airfe_junction_connections_batch_dev(
+            self._h, lines_t.data_ptr(), nlines_t.data_ptr(), lines_t.shape[1], junc_t.data_ptr(), njunc_t.data_ptr(), junc_t.shape[1], junc_t.shape[0], int(W),
+            int(H), edge_t.data_ptr(), edge_t.shape[1], nedge_t.data_ptr(), status_t.data_ptr(), line_pair_t.data_ptr() if line_pair_t is not None else None,
+            self._stream(stream)), "airfe_junction_connections_batch_dev")
+
     def copy_rows_plan(self, jobs):
         """jobs: [(src tensor / pointer, dst tensor / pointer, count tensor (int32, one element) / pointer / None, row_bytes, cap rows)] -> a reusable plan for
         copy_rows_dev (the five host arrays of airfe_copy_rows_dev, built once: the buffers of a pipeline do not move)"""
@@ -1362,6 +1384,60 @@ class BowDatabase:
 
 
 # ------------------------------------------------------------------------------------ reference-shaped façade
+    # ---- the junction term (include/airfe.h "Junction term"): this database is the JUNCTION database, frame f = frame f of the point database
+    def attach_junctions(self, ecap: int, max_queries: int):
+        """allocates the stored frames' words and tables, the queries' tables and the composites' chain; nothing is allocated afterwards"""
+        self._ctx._chk(self._l.airfe_bowdb_attach_junctions(self._h, int(ecap), int(max_queries)), "airfe_bowdb_attach_junctions")
+        self._ecap = int(ecap)
+
+    def set_junctions_dev(self, first_frame: int, word_t, nj_t, edge_t, nedge_t, status_t=None, stream=None):
+        """word [B][cap] (uint32 in int32 storage), nj [B], edge [B][ecap][2], nedge [B], status [B] or None, on the device"""
+        self._ctx._chk(self._l.airfe_bowdb_set_junctions_dev(self._h, int(first_frame), word_t.shape[0], word_t.data_ptr(), nj_t.data_ptr(), edge_t.data_ptr(),
+                                                             nedge_t.data_ptr(), status_t.data_ptr() if status_t is not None else None,
+                                                             self._ctx._stream(stream)), "airfe_bowdb_set_junctions_dev")
+
+    def set_junctions(self, first_frame: int, word: np.ndarray, nj: np.ndarray, edge: np.ndarray, nedge: np.ndarray, status: np.ndarray = None):
+        """the same on host buffers; at most max_queries frames per call"""
+        word = np.ascontiguousarray(word, np.uint32); nj = np.ascontiguousarray(nj, np.int32)
+        edge = np.ascontiguousarray(edge, np.int32); nedge = np.ascontiguousarray(nedge, np.int32)
+        status = None if status is None else np.ascontiguousarray(status, np.int32)
+        self._ctx._chk(self._l.airfe_bowdb_set_junctions(self._h, int(first_frame), word.shape[0], word.ctypes.data, nj.ctypes.data, edge.ctypes.data,
+                                                         nedge.ctypes.data, status.ctypes.data if status is not None else None), "airfe_bowdb_set_junctions")
+
+    def get_junctions(self, first_frame: int, B: int, cap: int, ecap: int) -> dict:
+        """-> dict(word, nj, uword, wcnt, wconn, nuw, ukey, kcnt, nuk, status) of frames first_frame .. (entries past nuw / nuk are not meaningful)"""
+        o = dict(word=np.zeros((B, cap), np.uint32), nj=np.zeros(B, np.int32), uword=np.zeros((B, cap), np.uint32), wcnt=np.zeros((B, cap), np.int32),
+                 wconn=np.zeros((B, cap), np.int32), nuw=np.zeros(B, np.int32), ukey=np.zeros((B, ecap), np.uint64), kcnt=np.zeros((B, ecap), np.int32),
+                 nuk=np.zeros(B, np.int32), status=np.zeros(B, np.int32))
+        self._ctx._chk(self._l.airfe_bowdb_get_junctions(self._h, int(first_frame), int(B), *[o[k].ctypes.data for k in (
+            "word", "nj", "uword", "wcnt", "wconn", "nuw", "ukey", "kcnt", "nuk", "status")]), "airfe_bowdb_get_junctions")
+        return o
+
+    def junction_term_batch_dev(self, ids_t, vals_t, nw_t, word_t, nj_t, edge_t, nedge_t, extra_t, qstatus_t=None, match_num_t=None, line_match_num_t=None,
+                                stream=None):
+        """≙ map_user.cc:290-331 for Q queries against every stored frame: the queries' junction vectors and words (bow_vector_batch_dev on this database's
+        context), their connections -> extra f64 [Q][N], match_num / line_match_num i32 [Q][N] or None"""
+        p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self._ctx._chk(self._l.airfe_bowdb_junction_term_batch_dev(self._h, ids_t.data_ptr(), vals_t.data_ptr(), nw_t.data_ptr(), word_t.data_ptr(), nj_t.data_ptr(),
+                                                                   edge_t.data_ptr(), nedge_t.data_ptr(), p(qstatus_t), ids_t.shape[0], extra_t.data_ptr(),
+                                                                   p(match_num_t), p(line_match_num_t), self._ctx._stream(stream)),
+                       "airfe_bowdb_junction_term_batch_dev")
+
+    def junction_extra_batch_dev(self, junc_t, njunc_t, lines_t, nlines_t, W, H, extra_t, match_num_t=None, line_match_num_t=None, stream=None):
+        """the composite: the query frames' junction rows [Q][capJ][259] and lines [Q][capL][4] -> extra [Q][N] for relocalize_batch_dev, on one stream"""
+        p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self._ctx._chk(self._l.airfe_bowdb_junction_extra_batch_dev(self._h, junc_t.data_ptr(), njunc_t.data_ptr(), junc_t.shape[1], lines_t.data_ptr(),
+                                                                    nlines_t.data_ptr(), lines_t.shape[1], junc_t.shape[0], int(W), int(H), extra_t.data_ptr(),
+                                                                    p(match_num_t), p(line_match_num_t), self._ctx._stream(stream)),
+                       "airfe_bowdb_junction_extra_batch_dev")
+
+    def add_junction_frames_batch_dev(self, junc_t, njunc_t, lines_t, nlines_t, W, H, stream=None):
+        """≙ BuildJunctionDatabase's second loop + FindJunctionConnections (map_refiner.cc:977, 986-994) for B map frames: vector, add, connections, tables"""
+        self._ctx._chk(self._l.airfe_bowdb_add_junction_frames_batch_dev(self._h, junc_t.data_ptr(), njunc_t.data_ptr(), junc_t.shape[1], lines_t.data_ptr(),
+                                                                         nlines_t.data_ptr(), lines_t.shape[1], junc_t.shape[0], int(W), int(H),
+                                                                         self._ctx._stream(stream)), "airfe_bowdb_add_junction_frames_batch_dev")
+
+
 class FeatureDetector:
     """Mirror of FeatureDetector (include/feature_detector.h:8-31, src/feature_detector.cc)."""
 

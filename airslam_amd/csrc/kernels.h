@@ -589,4 +589,35 @@ struct CovisArgs {
 };
 void launch_covis_build(const CovisArgs& a, hipStream_t st);                 // size <= 4096
 
+// Relocalisation's junction term (frame.cc:581-629, map_user.cc:285-331; kernels_junction.hip, junction_core.h; contract: include/airfe.h)
+struct JunctionConnectArgs {
+  const double* lines = nullptr; const int* nlines = nullptr; int capL = 0;  // [B][capL][4], [B]
+  const float* junc = nullptr; const int* njunc = nullptr; int capJ = 0;     // [B][capJ][259], [B]; capJ <= 1024
+  int W = 0, H = 0, ecap = 0;                                                // ecap <= 4096
+  int32_t* edge = nullptr; int *nedge = nullptr, *status = nullptr;          // [B][ecap][2], [B], [B]
+  int32_t* line_pair = nullptr;                                              // [B][capL][2] or nullptr
+};
+void launch_junction_connect(const JunctionConnectArgs& a, int B, hipStream_t st);
+struct JunctionKeysArgs {                                                    // frame b of the inputs -> slot first + b of the tables
+  const unsigned* word = nullptr; const int* nj = nullptr; int cap = 0;      // [B][cap], [B]
+  const int32_t* edge = nullptr; const int* nedge = nullptr; int ecap = 0;   // [B][ecap][2], [B]
+  const int* status_in = nullptr;                                            // [B] or nullptr (all 0)
+  int first = 0;
+  unsigned* out_word = nullptr; int* out_nj = nullptr;                       // [..][cap], [..] or nullptr: the stored copy of the words
+  unsigned* uword = nullptr; int *wcnt = nullptr, *wconn = nullptr, *nuw = nullptr;      // [..][cap] x 3, [..]
+  unsigned long long* ukey = nullptr; int *kcnt = nullptr, *nuk = nullptr;   // [..][ecap] x 2, [..]
+  int* status = nullptr;                                                     // [..]
+};
+void launch_junction_keys(const JunctionKeysArgs& a, int B, hipStream_t st);
+struct JunctionTermArgs {
+  const unsigned* q_uword = nullptr; const int *q_wconn = nullptr, *q_nuw = nullptr;     // the queries' tables, [Q][cap] / [Q][ecap]
+  const unsigned long long* q_ukey = nullptr; const int *q_kcnt = nullptr, *q_nuk = nullptr, *q_status = nullptr;
+  const unsigned* f_uword = nullptr; const int *f_wcnt = nullptr, *f_nuw = nullptr;      // the stored frames' tables
+  const unsigned long long* f_ukey = nullptr; const int *f_kcnt = nullptr, *f_nuk = nullptr, *f_status = nullptr;
+  int N = 0, cap = 0, ecap = 0, frames_per_wg = 16;
+  const double* score = nullptr;                                             // [Q][N] of bowdb_query_kernel on the junction database
+  double* extra = nullptr; int *match_num = nullptr, *line_match_num = nullptr;          // [Q][N], [Q][N] or nullptr x 2
+};
+void launch_junction_term(const JunctionTermArgs& a, int Q, hipStream_t st);
+
 }  // namespace airfe

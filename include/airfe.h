@@ -482,8 +482,8 @@ int airfe_bow_transform_dev(airfe_ctx* ctx, const float* d_feat, int N, uint32_t
  * FrameToBow to its end, AddFrame, Query, the two callers' filters, L1Scoring::score, the best-candidate rule — and, in the block "Grouping" below, the
  * GROUPING between the scores and the candidates (map_user.cc:177-264, map_refiner.cc:132-211) over a covisibility table the caller hands to the
  * database (airfe_bowdb_attach_map / airfe_bowdb_set_covisibility) or builds there from the frames' map-point ids (the block "Map-point ids and the
- * covisibility build" below).  What stays the caller's: relocalisation's junction "sentences" (the junction database, FindJunctionConnections), whose result enters the grouping as one number per frame
- * (d_extra).  The candidate list below IS the reference's frame_scores map.  airfe_bowdb_topk_dev is the PROJECT'S OWN ranking for callers without a
+ * covisibility build" below).  Relocalisation's junction term, which enters the grouping as one number per frame (d_extra), is computed on the device by
+ * the block "Junction term" below.  The candidate list below IS the reference's frame_scores map.  airfe_bowdb_topk_dev is the PROJECT'S OWN ranking for callers without a
  * covisibility graph, not the reference's grouping.  Every floating-point sum is sequential in the order given; no fused multiply-adds.
  *   vector   Database::FrameToBow (src/bow/database.cc:57-89): per feature the descent of airfe_bow_transform (the same kernel); a feature counts iff its
  *            word's weight is > 0 (word_of_features = UINT_MAX otherwise).  The weights are the vocabulary's doubles (WordValue).  BowVector::addWeight:
@@ -747,6 +747,81 @@ int airfe_bowdb_set_point_ids(airfe_bowdb* db, int first_frame, int B, const int
 int airfe_bowdb_get_point_ids(airfe_bowdb* db, int first_frame, int B, int32_t* ids);                         /* host buffer [B][cap] */
 int airfe_bowdb_build_covisibility_dev(airfe_bowdb* db, int32_t* d_info, void* stream);
 int airfe_bowdb_build_covisibility(airfe_bowdb* db, int* n_edges);
+
+/* ---- Junction term: junction_frame_scores * (1 + rate) of MapUser::Relocalization (src/map_user.cc:285-331), on the device ---------------------------
+ * The number per stored frame that airfe_bowdb_group_dev / airfe_relocalize_batch_dev add to a group's score through d_extra [Q][N].  d_extra[q][deputy] is
+ * all the grouping reads, so the term is computed for every stored frame rather than for the group frames: the grouping is the same.
+ * WHERE THE JUNCTION DATABASE LIVES.  The reference's junction database has a vocabulary of its own (map_refiner.cc:956-999: k = 10, L = 3, TF-IDF, L1).
+ * Here: a second airfe_ctx with that vocabulary loaded (airfe_bow_load; a context needs no network pack) and on it a second airfe_bowdb, `jdb`
+ * (keep_features = 0 is enough).  Frame f of jdb IS frame f of the point database: same insertion order, the caller's responsibility.  At most 1024
+ * junctions per frame (the BoW kernels' limit).  Training the vocabulary (jun_voc->create) stays the caller's.
+ * RESTATED (junction_core.h: one statement the kernels and the host core both call; tests/junction_ref.py restates the reference literally):
+ *   connections   Frame::FindJunctionConnections (src/frame.cc:581-629).  Junction row i = (score, jx, jy, ...) sits at pixel
+ *                 ((int)((double)jx + 0.5), (int)((double)jy + 0.5)); of several junctions in one pixel the HIGHEST index owns it (:587-591 overwrites in
+ *                 index order).  An endpoint (ex, ey) has xi = int(ex + 0.5), yi = int(ey + 0.5) and matches the junction that owns the cell with the
+ *                 smallest key (|yi - r| + |xi - c|, r, c) over r in [max(yi - 2, 0), min(yi + 2, H - 1)], c in [max(xi - 2, 0), min(xi + 2, W - 1)]
+ *                 — the row-major scan of :600-614 with its strict < and its early return at distance 0 — or nothing (-1).  A line with both ends
+ *                 matched to a and b gives the directed edges (a, b) and (b, a) (a == b: the self loop (a, a), an edge like any other, :626-627); the
+ *                 second end is not looked at without the first (:621).  Output: the DISTINCT directed edges ascending by (a, b), i32 [ecap][2], their
+ *                 count, and optionally per line the pair (a, b) or (-1, -1).  The device keeps the junctions' pixels in LDS and every endpoint
+ *                 scans them: no H x W map.
+ *   tables        from word [nj] (u32, UINT_MAX = a word of weight 0: database.cc:70-75) and the edges.  WORD TABLE: the distinct valid words ascending,
+ *                 each with cnt = the junctions holding it (the inverted file's list, database.cc:98-106) and conn = those of them with at least one
+ *                 edge.  KEY TABLE: the distinct word[a] << 32 | word[b] over the edges whose two words are valid, ascending, each with its multiplicity.
+ *   term          :293-327 builds match_matrix[i][j] = (word_q[i] == word_f[j], the word valid) and counts over it.  With these tables
+ *                 match_num = sum over words w of conn_q(w) * cnt_f(w)  (:313-315) and line_match_num = sum over keys k of n_q(k) * n_f(k)  (:316-325),
+ *                 both i32 (ecap <= 4096 and 1024 junctions: <= 2^24 and <= 2^20).  rate = match_num > 0 ? (double)line_match_num / match_num : 0  (:329);
+ *                 extra = score * (1.0 + rate)  (:330-331) with score = L1Scoring::score(v1 = the stored frame's junction vector, v2 = the query's) as the
+ *                 unchanged query kernel computes it on jdb; one division, one add, one multiply, no fused multiply-add.  The counts are integer sums and
+ *                 do not depend on their order.
+ * THE QUIRK KEPT: invalid words never match each other (:300 skips them; they are in no inverted file).
+ * STATED DIFFERENCES: a junction whose pixel lies outside [0, W) x [0, H) owns no cell, where the reference writes out of bounds; an endpoint whose
+ * ex + 0.5 or ey + 0.5 is not finite or not inside (-2^31, 2^31) matches nothing, where the reference's conversion is undefined; more than ecap distinct
+ * edges sets the frame's STATUS to 2 (0 = ok), gives it no edges and a term of 0.0 with counts 0 — never a shorter list.  (nj > 1024 cannot reach the
+ * device entries: capJ > 1024 is a return code; the host core answers it with status 2.)
+ *   airfe_junction_connections_batch_dev   B frames in place on the batched PLNet outputs: d_lines [B][capL][4] f64, d_nlines [B], d_junc [B][capJ][259],
+ *       d_njunc [B]; counts are clamped to their capacities.  -> d_edge [B][ecap][2], d_nedge [B], d_status [B], d_line_pair [B][capL][2] or NULL (rows
+ *       below the frame's line count).  One workgroup per frame, sort and deduplication in LDS; a frame's bytes depend on neither B nor its position;
+ *       nothing is allocated; rows past the counts are neither read as data nor written.
+ *   airfe_junction_connections             the host core, one frame, no device work.  Returns 2 (and *nedge = 0) for status 2.
+ *   airfe_bowdb_attach_junctions(jdb, ecap, max_queries)   allocates, once: per stored frame its words [max_frames][cap], their count, the two tables and a
+ *       status (1 = no junction state yet: such a frame's term is 0.0); the same tables, the dense score and the composites' chain for max_queries
+ *       frames.  Nothing is allocated afterwards.  A second attach is a return code.
+ *   airfe_bowdb_set_junctions_dev / _set_junctions   store the words of frames first_frame .. first_frame + B - 1 and build their tables: d_word [B][cap]
+ *       (cap = the database's), d_nj [B], d_edge [B][ecap][2] (ecap = the attached one), d_nedge [B], d_status [B] or NULL (a non-zero entry: status 2).
+ *       An edge with an index outside [0, nj) is ignored.  The host form takes at most max_queries frames per call and synchronises.
+ *   airfe_bowdb_get_junctions              reads back (host buffers, any may be NULL): word [B][cap], nj [B], uword / wcnt / wconn [B][cap], nuw [B],
+ *       ukey u64 / kcnt [B][ecap], nuk [B], status [B].  Entries past nuw / nuk are whatever they were.
+ *   airfe_bowdb_junction_term_batch_dev    Q queries: d_ids / d_vals [Q][cap], d_nw [Q] and d_word [Q][cap] = airfe_bow_vector_batch_dev's outputs for the
+ *       query frames' junction rows on jdb's context; d_nj [Q]; d_edge [Q][ecap][2], d_nedge, d_qstatus [Q] (or NULL) = the connections' outputs.
+ *       -> d_extra f64 [Q][N], d_match_num / d_line_match_num i32 [Q][N] or NULL, N = jdb's size: EVERY one of the Q N entries is written.  A query or a
+ *       stored frame with a non-zero status gets extra = 0.0 and counts 0.  Grid: (query, slice of frames) as the query kernel's; the query's tables
+ *       in LDS; a wave per stored frame, integer partial sums reduced across the wave.
+ *   airfe_bowdb_junction_extra_batch_dev   the composite, from the query frames' raw junction rows and lines to d_extra on one stream:
+ *       airfe_bow_vector_batch_dev's code, the connections, the tables, the query, the term — byte for byte those steps done one at a time.  capJ must be
+ *       jdb's cap.  The caller passes d_extra to airfe_relocalize_batch_dev on the same stream.
+ *   airfe_bowdb_add_junction_frames_batch_dev   the same chain for B map frames: vector, add to jdb, connections, set_junctions — BuildJunctionDatabase's
+ *       second loop plus FindJunctionConnections (map_refiner.cc:977, 986-994).  B <= max_queries per call.
+ * Return codes that change nothing: capJ > 1024, ecap > 4096, Q (or B) > max_queries, a database without attach_junctions, frames beyond max_frames. */
+int airfe_junction_connections_batch_dev(airfe_ctx* ctx, const double* d_lines, const int* d_nlines, int capL, const float* d_junc, const int* d_njunc,
+                                         int capJ, int B, int W, int H, int32_t* d_edge, int ecap, int* d_nedge, int* d_status, int32_t* d_line_pair,
+                                         void* stream);
+int airfe_junction_connections(airfe_ctx* ctx, const double* lines, int nl, const float* junc, int nj, int W, int H, int32_t* edge, int ecap, int* nedge,
+                               int32_t* line_pair);
+int airfe_bowdb_attach_junctions(airfe_bowdb* jdb, int ecap, int max_queries);
+int airfe_bowdb_set_junctions_dev(airfe_bowdb* jdb, int first_frame, int B, const uint32_t* d_word, const int* d_nj, const int32_t* d_edge,
+                                  const int* d_nedge, const int* d_status, void* stream);
+int airfe_bowdb_set_junctions(airfe_bowdb* jdb, int first_frame, int B, const uint32_t* word, const int* nj, const int32_t* edge, const int* nedge,
+                              const int* status);
+int airfe_bowdb_get_junctions(airfe_bowdb* jdb, int first_frame, int B, uint32_t* word, int* nj, uint32_t* uword, int32_t* wcnt, int32_t* wconn, int* nuw,
+                              uint64_t* ukey, int32_t* kcnt, int* nuk, int* status);
+int airfe_bowdb_junction_term_batch_dev(airfe_bowdb* jdb, const uint32_t* d_ids, const double* d_vals, const int* d_nw, const uint32_t* d_word,
+                                        const int* d_nj, const int32_t* d_edge, const int* d_nedge, const int* d_qstatus, int Q, double* d_extra,
+                                        int32_t* d_match_num, int32_t* d_line_match_num, void* stream);
+int airfe_bowdb_junction_extra_batch_dev(airfe_bowdb* jdb, const float* d_junc, const int* d_njunc, int capJ, const double* d_lines, const int* d_nlines,
+                                         int capL, int Q, int W, int H, double* d_extra, int32_t* d_match_num, int32_t* d_line_match_num, void* stream);
+int airfe_bowdb_add_junction_frames_batch_dev(airfe_bowdb* jdb, const float* d_junc, const int* d_njunc, int capJ, const double* d_lines,
+                                              const int* d_nlines, int capL, int B, int W, int H, void* stream);
 
 /* ---- the step BEFORE the path: rectification ------------------------------------------------------- */
 /* ≙ the maps Camera's constructor builds with cv::initUndistortRectifyMap (src/camera.cc:60-75; _mapl1/_mapl2 = side 0, _mapr1/_mapr2 =
