@@ -223,6 +223,11 @@ SIGNATURES = {
     "airfe_bowdb_get_point_ids": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "airfe_bowdb_build_covisibility_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "airfe_bowdb_build_covisibility": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "airfe_bowdb_attach_triangulation": (C.c_int, [C.c_void_p]),
+    "airfe_bowdb_triangulate_points_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5),
+    "airfe_bowdb_triangulate_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "airfe_bowdb_fill_points_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "airfe_triangulate_point": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
     "airfe_junction_connections_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int] +
                                              [C.c_void_p] * 4),
     "airfe_junction_connections": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int),

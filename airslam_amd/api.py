@@ -1382,6 +1382,43 @@ class BowDatabase:
         self._ctx._chk(self._l.airfe_bowdb_build_covisibility(self._h, C.byref(e)), "airfe_bowdb_build_covisibility")
         return e.value
 
+    # ---- map-point triangulation (include/airfe.h "Map-point triangulation")
+    @staticmethod
+    def _cam4(cam):
+        return (C.c_double * 4)(*[float(x) for x in cam])
+
+    def attach_triangulation(self):
+        """the observation segments and the host form's outputs; needs attach_point_ids; nothing is allocated afterwards"""
+        self._ctx._chk(self._l.airfe_bowdb_attach_triangulation(self._h), "airfe_bowdb_attach_triangulation")
+
+    def triangulate_points_dev(self, cam, xyz_t, status_t, nobs_t, info_t, min_observers=2, stream=None):
+        """Map::TriangulateMappoint for every point of the id table from the stored rows and poses, asynchronous on `stream`: cam = (fx, fy, cx, cy);
+        xyz f64 [max_points][3] (NaN unless status is 0), status / nobs i32 [max_points], info i32 [4] = ok, observed, status 2, status 3"""
+        self._ctx._chk(self._l.airfe_bowdb_triangulate_points_dev(
+            self._h, None if cam is None else self._cam4(cam), int(min_observers), xyz_t.data_ptr() if xyz_t is not None else None,
+            status_t.data_ptr() if status_t is not None else None, nobs_t.data_ptr() if nobs_t is not None else None,
+            info_t.data_ptr() if info_t is not None else None, self._ctx._stream(stream)), "airfe_bowdb_triangulate_points_dev")
+
+    def triangulate_points(self, cam, max_points: int, min_observers=2):
+        """the same into host buffers on the context's stream, then a synchronisation -> (xyz [max_points][3], status, nobs, the points of status 0);
+        max_points: attach_point_ids'"""
+        xyz = np.empty((max_points, 3), np.float64); status = np.empty(max_points, np.int32); nobs = np.empty(max_points, np.int32)
+        ok = C.c_int(0)
+        self._ctx._chk(self._l.airfe_bowdb_triangulate_points(self._h, self._cam4(cam), int(min_observers), xyz.ctypes.data, status.ctypes.data,
+                                                              nobs.ctypes.data, C.byref(ok)), "airfe_bowdb_triangulate_points")
+        return xyz, status, nobs, ok.value
+
+    def fill_points_dev(self, xyz_t, status_t, written_t, only_missing=False, stream=None):
+        """points[f][i] = xyz[id] for every valid row whose point has status 0 (only_missing: only where the stored x is NaN); written i32 [1]"""
+        self._ctx._chk(self._l.airfe_bowdb_fill_points_dev(
+            self._h, xyz_t.data_ptr() if xyz_t is not None else None, status_t.data_ptr() if status_t is not None else None, 1 if only_missing else 0,
+            written_t.data_ptr() if written_t is not None else None, self._ctx._stream(stream)), "airfe_bowdb_fill_points_dev")
+
+    def retriangulate_dev(self, cam, xyz_t, status_t, nobs_t, info_t, written_t, min_observers=2, only_missing=False, stream=None):
+        """triangulate_points_dev, then fill_points_dev with its outputs, on one stream: the point table brought in line with the poses"""
+        self.triangulate_points_dev(cam, xyz_t, status_t, nobs_t, info_t, min_observers=min_observers, stream=stream)
+        self.fill_points_dev(xyz_t, status_t, written_t, only_missing=only_missing, stream=stream)
+
 
 # ------------------------------------------------------------------------------------ reference-shaped façade
     # ---- the junction term (include/airfe.h "Junction term"): this database is the JUNCTION database, frame f = frame f of the point database
@@ -1436,6 +1473,21 @@ class BowDatabase:
         self._ctx._chk(self._l.airfe_bowdb_add_junction_frames_batch_dev(self._h, junc_t.data_ptr(), njunc_t.data_ptr(), junc_t.shape[1], lines_t.data_ptr(),
                                                                          nlines_t.data_ptr(), lines_t.shape[1], junc_t.shape[0], int(W), int(H),
                                                                          self._ctx._stream(stream)), "airfe_bowdb_add_junction_frames_batch_dev")
+
+
+def triangulate_point(cam, Twc: np.ndarray, xy: np.ndarray):
+    """airfe_triangulate_point: Map::TriangulateMappoint for one point on the host, without a context.  cam = (fx, fy, cx, cy), Twc [n][16] (or [n][4][4])
+    float64, xy [n][2] float32 in observer order -> (xyz [3], status); at least two observers (include/airfe.h "Map-point triangulation")."""
+    l = _lib.lib()
+    Twc = np.ascontiguousarray(Twc, np.float64).reshape(-1, 16)
+    xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    if len(Twc) != len(xy):
+        raise AirfeError("triangulate_point: Twc and xy differ in length")
+    xyz = np.empty(3, np.float64)
+    status = C.c_int(0)
+    if l.airfe_triangulate_point((C.c_double * 4)(*[float(x) for x in cam]), Twc.ctypes.data, xy.ctypes.data, len(xy), xyz.ctypes.data, C.byref(status)) != 0:
+        raise AirfeError(f"airfe_triangulate_point: {(l.airfe_last_error(None) or b'').decode()}")
+    return xyz, status.value
 
 
 class FeatureDetector:

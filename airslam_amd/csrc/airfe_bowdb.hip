@@ -1,5 +1,6 @@
 // airfe — the BoW side of libairfe.so (include/airfe.h): the BoW vector, the device-resident keyframe database with its queries, the grouping, and the
-// relocalisation and loop detection composites, and the covisibility build (kernels_bowdb.hip, kernels_bowgroup.hip, kernels_loopdet.hip, kernels_covis.hip).  The vocabulary itself (airfe_bow_load,
+// relocalisation and loop detection composites, the covisibility build and the map-point triangulation (kernels_bowdb.hip, kernels_bowgroup.hip, kernels_loopdet.hip, kernels_covis.hip,
+// kernels_triangulate.hip).  The vocabulary itself (airfe_bow_load,
 // airfe_bow_transform*) is loaded in airfe.hip.
 #include "airfe_host.h"
 #include "fransac_core.h"
@@ -8,6 +9,7 @@
 #include "bowgroup_core.h"
 #include "loopdet_core.h"
 #include "covis_core.h"
+#include "triangulate_core.h"
 #include "junction_core.h"
 
 /* ---- BoW keyframe database (include/airfe.h "BoW keyframe database"; kernels_bowdb.hip): the database object is a C++ struct behind an opaque pointer */
@@ -33,6 +35,9 @@ struct airfe_bowdb {
   int max_points = 0;
   int32_t* point_id = nullptr;                                               // [max_frames][cap], -1 = no valid map point at this feature row
   DevBlock c_scratch;                                                        // covisibility build: the per-point and per-row work arrays, sized at attach
+  // map-point triangulation (airfe_bowdb_attach_triangulation): the observation segments and the host form's outputs, sized at attach
+  int has_tri = 0;
+  DevBlock t_scratch;
   // junction state (airfe_bowdb_attach_junctions): per stored frame its words and the two tables of junction_core.h; the same for max_queries queries
   struct JunctionTables {
     unsigned *uword = nullptr; int *wcnt = nullptr, *wconn = nullptr, *nuw = nullptr;          // [rows][cap] x 3, [rows]
@@ -145,7 +150,7 @@ int airfe_bowdb_destroy(airfe_bowdb* db) try {
                   (void*)db->cov_weight, (void*)db->pos, (void*)db->pose, (void*)db->u_right, (void*)db->point_id})      // the persistent tables
     if (p) (void)hipFree(p);
   if (db->c)
-    for (DevBlock* b : {&db->q_scratch, &db->m_scratch, &db->r_scratch, &db->l_scratch, &db->c_scratch, &db->j_block}) release(db->c, *b);
+    for (DevBlock* b : {&db->q_scratch, &db->m_scratch, &db->r_scratch, &db->l_scratch, &db->c_scratch, &db->t_scratch, &db->j_block}) release(db->c, *b);
   delete db;
   return 0;
 } AIRFE_CATCH(nullptr)
@@ -766,6 +771,117 @@ int airfe_bowdb_build_covisibility(airfe_bowdb* db, int* n_edges) try {
   if (info[0]) return fail(c, "bowdb_build_covisibility: more entries than max_edges (the graph is empty now)");
   return 0;
 } AIRFE_CATCH(db->c)
+
+/* ---- map-point triangulation (include/airfe.h "Map-point triangulation"; kernels_triangulate.hip, triangulate_core.h) ------------------------------ */
+// the triangulation's own arrays inside t_scratch, sized by the database and max_points alone: the segments as filled and sorted, and the host form's
+// device outputs.  The marks and the segment starts are the covisibility build's work arrays (c_scratch), rewritten by either build.
+struct TriWork {
+  Carve k;
+  size_t o_seg, o_sorted, o_xyz, o_status, o_nobs, o_info;
+  TriWork(const airfe_bowdb* db) {
+    const size_t rows = (size_t)db->max_frames * db->cap, pts = (size_t)db->max_points;
+    o_seg = k.take(rows * 4); o_sorted = k.take(rows * 4); o_xyz = k.take(pts * 24); o_status = k.take(pts * 4); o_nobs = k.take(pts * 4); o_info = k.take(16);
+  }
+};
+
+static int triangulate_queue(airfe_bowdb* db, const double* cam, int min_observers, double* d_xyz, int32_t* d_status, int32_t* d_nobs, int32_t* d_info,
+                             hipStream_t st, const char* who) {
+  airfe_ctx* c = db->c;
+  if (!db->has_tri) return fail(c, std::string(who) + ": no triangulation attached (airfe_bowdb_attach_triangulation)");
+  if (db->size > TR_MAX_FRAMES) return fail(c, std::string(who) + ": more than 4096 frames in the database");
+  if (!cam || !d_xyz || !d_status || !d_nobs || !d_info) return fail(c, std::string(who) + ": bad argument");
+  TriangulateArgs t;
+  if (!tr_cam(cam, t.cami)) return fail(c, std::string(who) + ": fx and fy must be finite and not zero");
+  CovisWork w(db);
+  TriWork tw(db);
+  if (w.k.into(c, db->c_scratch, st) || tw.k.into(c, db->t_scratch, st)) return 1;      // (reserved at attach: neither block is replaced here)
+  CovisArgs a;
+  a.point_id = db->point_id; a.n = db->n; a.size = db->size; a.max_frames = db->max_frames; a.cap = db->cap; a.max_points = db->max_points;
+  a.count = w.k.i(w.o_count); a.acc = a.count + (size_t)db->max_points + 1; a.start = w.k.i(w.o_start); a.tile = w.k.i(w.o_tile);
+  a.packed = w.k.i(w.o_packed);
+  t.feat = db->feat; t.n = db->n; t.pose = db->pose; t.size = db->size; t.cap = db->cap; t.feat_dim = AIRFE_FEAT_DIM; t.max_points = db->max_points;
+  t.min_observers = min_observers;
+  t.packed = a.packed; t.start = a.start; t.count = a.count; t.seg = tw.k.i(tw.o_seg); t.sorted = tw.k.i(tw.o_sorted);
+  t.xyz = d_xyz; t.status = d_status; t.nobs = d_nobs; t.info = d_info;
+  HIPCHK(c, hipMemsetAsync(a.count, 0, w.zero_bytes, st));
+  HIPCHK(c, hipMemsetAsync(d_info, 0, 16, st));
+  if (db->size > 0) launch_covis_segments(a, st);
+  launch_triangulate(t, st);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+static int fill_points_queue(airfe_bowdb* db, const double* d_xyz, const int32_t* d_status, int only_missing, int32_t* d_written, hipStream_t st,
+                             const char* who) {
+  airfe_ctx* c = db->c;
+  if (!db->has_tri) return fail(c, std::string(who) + ": no triangulation attached (airfe_bowdb_attach_triangulation)");
+  if (db->size > TR_MAX_FRAMES) return fail(c, std::string(who) + ": more than 4096 frames in the database");
+  if (!d_xyz || !d_status || !d_written) return fail(c, std::string(who) + ": bad argument");
+  FillPointsArgs f;
+  f.point_id = db->point_id; f.n = db->n; f.size = db->size; f.cap = db->cap; f.max_points = db->max_points; f.only_missing = only_missing != 0;
+  f.xyz = d_xyz; f.status = d_status; f.points = db->xyz; f.written = d_written;
+  HIPCHK(c, hipMemsetAsync(d_written, 0, 4, st));
+  launch_fill_points(f, st);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+int airfe_bowdb_attach_triangulation(airfe_bowdb* db) try {
+  if (!db) return 1;
+  airfe_ctx* c = db->c;
+  AIRFE_ENTER(c);
+  if (!db->point_id) return fail(c, "bowdb_attach_triangulation: no id table (airfe_bowdb_attach_point_ids)");
+  if (db->has_tri) return fail(c, "bowdb_attach_triangulation: the triangulation is attached already");
+  TriWork tw(db);
+  if (tw.k.into(c, db->t_scratch, c->stream)) return 1;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  db->has_tri = 1;
+  return 0;
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_triangulate_points_dev(airfe_bowdb* db, const double* cam, int min_observers, double* d_xyz, int32_t* d_status, int32_t* d_nobs,
+                                       int32_t* d_info, void* stream) try {
+  if (!db) return 1;
+  AIRFE_ENTER(db->c);
+  return triangulate_queue(db, cam, min_observers, d_xyz, d_status, d_nobs, d_info, stream ? (hipStream_t)stream : db->c->stream,
+                           "bowdb_triangulate_points_dev");
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_triangulate_points(airfe_bowdb* db, const double* cam, int min_observers, double* xyz, int32_t* status, int32_t* nobs, int* n_ok) try {
+  if (!db) return 1;
+  airfe_ctx* c = db->c;
+  AIRFE_ENTER(c);
+  if (!db->has_tri) return fail(c, "bowdb_triangulate_points: no triangulation attached (airfe_bowdb_attach_triangulation)");
+  if (!xyz || !status || !nobs || !n_ok) return fail(c, "bowdb_triangulate_points: bad argument");
+  TriWork tw(db);
+  if (tw.k.into(c, db->t_scratch, c->stream)) return 1;
+  int32_t info[4] = {0, 0, 0, 0};
+  if (triangulate_queue(db, cam, min_observers, tw.k.d(tw.o_xyz), tw.k.at<int32_t>(tw.o_status), tw.k.at<int32_t>(tw.o_nobs), tw.k.at<int32_t>(tw.o_info),
+                        c->stream, "bowdb_triangulate_points"))
+    return 1;
+  const size_t P = (size_t)db->max_points;
+  HIPCHK(c, hipMemcpyAsync(xyz, tw.k.d(tw.o_xyz), P * 24, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(status, tw.k.at<int32_t>(tw.o_status), P * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(nobs, tw.k.at<int32_t>(tw.o_nobs), P * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(info, tw.k.at<int32_t>(tw.o_info), 16, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *n_ok = info[0];
+  return 0;
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_fill_points_dev(airfe_bowdb* db, const double* d_xyz, const int32_t* d_status, int only_missing, int32_t* d_written, void* stream) try {
+  if (!db) return 1;
+  AIRFE_ENTER(db->c);
+  return fill_points_queue(db, d_xyz, d_status, only_missing, d_written, stream ? (hipStream_t)stream : db->c->stream, "bowdb_fill_points_dev");
+} AIRFE_CATCH(db->c)
+
+int airfe_triangulate_point(const double* cam, const double* Twc, const float* xy, int n, double* xyz, int* status) try {
+  double cami[4];
+  if (!cam || !xyz || !status || n < 0 || (n > 0 && (!Twc || !xy))) return fail(nullptr, "triangulate_point: bad argument");
+  if (!tr_cam(cam, cami)) return fail(nullptr, "triangulate_point: fx and fy must be finite and not zero");
+  *status = triangulate_point_core(cami, Twc, xy, n, 2, xyz);      // (compiled beside the kernels, without contraction)
+  return 0;
+} AIRFE_CATCH(nullptr)
 
 /* ---- relocalisation's junction term (include/airfe.h "Junction term"; kernels_junction.hip, junction_core.h) --------------------------------------- */
 static int junction_connect_queue(airfe_ctx* c, const double* d_lines, const int* d_nlines, int capL, const float* d_junc, const int* d_njunc, int capJ, int B,

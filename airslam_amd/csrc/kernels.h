@@ -588,6 +588,27 @@ struct CovisArgs {
   int32_t *row_ptr = nullptr, *nbr = nullptr, *weight = nullptr, *info = nullptr;      // the database's CSR, the caller's i32 [4]
 };
 void launch_covis_build(const CovisArgs& a, hipStream_t st);                 // size <= 4096
+// the build's first four launches alone: packed, start (count is ZERO again behind them); size >= 1
+void launch_covis_segments(const CovisArgs& a, hipStream_t st);
+
+// Map-point triangulation from the stored observations (map.cc:367-414; kernels_triangulate.hip, triangulate_core.h; contract: include/airfe.h)
+struct TriangulateArgs {
+  const float* feat = nullptr; const int* n = nullptr; const double* pose = nullptr;    // the database's [max_frames][cap][feat_dim], [max_frames], [max_frames][16]
+  int size = 0, cap = 0, feat_dim = 0, max_points = 0, min_observers = 2;
+  double cami[4] = {0, 0, 0, 0};                                             // tr_cam's: fxi, fyi, cx, cy
+  const int *packed = nullptr, *start = nullptr; int* count = nullptr;       // launch_covis_segments' outputs; count is the fill's cursor
+  int *seg = nullptr, *sorted = nullptr;                                     // [max_frames][cap] x 2: f * cap + i per observation, as filled / ascending
+  double* xyz = nullptr; int32_t *status = nullptr, *nobs = nullptr, *info = nullptr;   // [max_points][3], [max_points] x 2, [4]: info is ZERO on entry
+};
+void launch_triangulate(const TriangulateArgs& a, hipStream_t st);           // size <= 4096; behind launch_covis_segments when size >= 1
+struct FillPointsArgs {
+  const int32_t* point_id = nullptr; const int* n = nullptr; int size = 0, cap = 0, max_points = 0, only_missing = 0;
+  const double* xyz = nullptr; const int32_t* status = nullptr;              // [max_points][3], [max_points]
+  double* points = nullptr; int32_t* written = nullptr;                      // the database's point table; [1], ZERO on entry
+};
+void launch_fill_points(const FillPointsArgs& a, hipStream_t st);
+// triangulate_core.h's triangulate_point_host, compiled in the kernels' translation unit (no contraction); cami: tr_cam's
+int triangulate_point_core(const double* cami, const double* Twc, const float* xy, int n, int min_observers, double* xyz);
 
 // Relocalisation's junction term (frame.cc:581-629, map_user.cc:285-331; kernels_junction.hip, junction_core.h; contract: include/airfe.h)
 struct JunctionConnectArgs {

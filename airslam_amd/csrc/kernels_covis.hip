@@ -207,13 +207,17 @@ __global__ __launch_bounds__(256) void covis_emit_kernel(CovisArgs a) {
 
 }  // namespace
 
-void launch_covis_build(const CovisArgs& a, hipStream_t st) {
+void launch_covis_segments(const CovisArgs& a, hipStream_t st) {
   const int tiles = (a.max_points + 1 + CV_SCAN_TILE - 1) / CV_SCAN_TILE;
+  hipLaunchKernelGGL(covis_mark_kernel, dim3(a.size), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(covis_tile_sum_kernel, dim3(tiles), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(covis_tile_scan_kernel, dim3(1), dim3(256), 0, st, a, tiles);
+  hipLaunchKernelGGL(covis_start_kernel, dim3(tiles), dim3(256), 0, st, a);
+}
+
+void launch_covis_build(const CovisArgs& a, hipStream_t st) {
   if (a.size > 0) {
-    hipLaunchKernelGGL(covis_mark_kernel, dim3(a.size), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(covis_tile_sum_kernel, dim3(tiles), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(covis_tile_scan_kernel, dim3(1), dim3(256), 0, st, a, tiles);
-    hipLaunchKernelGGL(covis_start_kernel, dim3(tiles), dim3(256), 0, st, a);
+    launch_covis_segments(a, st);
     hipLaunchKernelGGL(covis_fill_kernel, dim3(a.size), dim3(256), 0, st, a);
     hipLaunchKernelGGL(covis_count_kernel, dim3(a.size), dim3(256), 0, st, a);
   }

@@ -748,6 +748,46 @@ int airfe_bowdb_get_point_ids(airfe_bowdb* db, int first_frame, int B, int32_t* 
 int airfe_bowdb_build_covisibility_dev(airfe_bowdb* db, int32_t* d_info, void* stream);
 int airfe_bowdb_build_covisibility(airfe_bowdb* db, int* n_edges);
 
+/* ---- Map-point triangulation: Map::TriangulateMappoint (src/map.cc:367-414) for every point of a loaded map, on the device ---------------------------
+ * The positions the point table holds, from what the database already stores: the frames' feature rows (x, y at columns 1 and 2), their poses
+ * (airfe_bowdb_set_poses) and the map-point id of every row (the id table above).  The reference calls the function for an UnTriangulated point with
+ * more than two observers at keyframe insertion (map.cc:64-66), from loop closure (map_refiner.cc:430) and from MergeMappointGroup (:702-704).
+ * airfe_bowdb_attach_triangulation (needs airfe_bowdb_attach_point_ids; a second attach is a return code) allocates 8 bytes per feature row for the
+ * observation segments and 32 bytes per point for the host form's outputs; nothing is allocated afterwards.  The marks and segment starts are the
+ * covisibility build's work arrays: a covisibility build, a grouping or a stored query queued on ANOTHER stream must have completed.
+ * THE STATEMENT (airslam_amd/csrc/triangulate_core.h; valid(f, i), size and n[f] as in the covisibility build):
+ *   observers   the observation of point m in frame f is the FIRST row i of f with valid(f, i) and point_id[f][i] == m.  STATED DIFFERENCE: the reference
+ *               keeps the last AddObverser per frame.  Observers are taken in ascending frame index (the reference's std::map order); nobs[m] = their number.
+ *   per observer, with fxi = 1.0 / fx, fyi = 1.0 / fy (Camera::BackProjectMono, camera.cc:268-273) and R, c the rotation and translation of the stored Twc:
+ *               b = (((double)x - cx) * fxi, ((double)y - cy) * fyi, 1);  v_r = (R[r][0] b0 + R[r][1] b1) + R[r][2] b2;  s = (v0 v0 + v1 v1) + v2 v2;
+ *               w_r = v_r * (1.0 / s);  d = (v0 c0 + v1 c1) + v2 c2;  in observer order M[r][q] += w_r v_q, g_r += w_r d, C_r += c_r.
+ *   system      A = n I - M, rhs = C - g (map.cc:398-403); a column-pivoted Householder QR of A by the rules of Eigen's ColPivHouseholderQR as far as they
+ *               decide anything (pivot = the remaining column of largest squared norm, the first wins a tie; Eigen's reflector and its application);
+ *               rank = #{ |R_kk| > 1e-5 max |R_kk| } (map.cc:405-409); with rank 3, x = P R^-1 Q^T rhs.  STATED DIFFERENCES: the remaining column norms
+ *               are recomputed at every step instead of down-dated; byte equality with Eigen is NOT claimed (triangulate_core.h says what is).
+ *   status      -1 no observer; 0 ok; 1 nobs < max(min_observers, 2); 2 rank < 3; 3 a non-finite keypoint, pose entry (rows 0 .. 2), s, system entry or
+ *               result, or s == 0, among the point's observers.  xyz = NaN unless status is 0.  A bad point never changes another point's bytes.
+ * Doubles, every sum sequential in the order written, no fused multiply-adds.  Three statements that agree byte for byte: triangulate_build_host
+ * (triangulate_core.h), the kernels (kernels_triangulate.hip) and tests/triangulate_ref.py.  Each point's observations are SORTED by frame before they are
+ * summed: no output byte depends on the order in which an atomic landed, and two calls give the same bytes.
+ *   _triangulate_points_dev   cam: HOST f64 [4] = fx, fy, cx, cy.  d_xyz f64 [max_points][3], d_status / d_nobs i32 [max_points], d_info i32 [4] = points ok,
+ *               points observed (status != -1), points of status 2, of status 3: every entry is written.  Asynchronous on `stream`, no host
+ *               synchronisation, no allocation.  The point table is not touched.
+ *   _triangulate_points       the same into host buffers on the context's stream, then a synchronisation; *n_ok = the points of status 0.
+ *   _fill_points_dev          for every valid row (f, i) with id m and d_status[m] == 0: points[f][i] = d_xyz[m] (a point at two rows of a frame fills both);
+ *               with only_missing only where the stored x is NaN (the reference's "only UnTriangulated points" rule).  Rows >= n[f], frames >= size and
+ *               rows of points with status != 0 are not touched.  d_written i32 [1] = the rows written.  Asynchronous on `stream`; a relocalisation or loop
+ *               detection reading the point table on ANOTHER stream must have completed.
+ *   airfe_triangulate_point   the host core for one point without a context: Twc [n][16], xy f32 [n][2] in observer order, min_observers = 2;
+ *               *status as above, xyz [3].
+ * Return codes (nothing is changed then): no triangulation attached; more than 4096 frames in the database; fx or fy zero or non-finite; a NULL argument. */
+int airfe_bowdb_attach_triangulation(airfe_bowdb* db);
+int airfe_bowdb_triangulate_points_dev(airfe_bowdb* db, const double* cam, int min_observers, double* d_xyz, int32_t* d_status, int32_t* d_nobs,
+                                       int32_t* d_info, void* stream);
+int airfe_bowdb_triangulate_points(airfe_bowdb* db, const double* cam, int min_observers, double* xyz, int32_t* status, int32_t* nobs, int* n_ok);
+int airfe_bowdb_fill_points_dev(airfe_bowdb* db, const double* d_xyz, const int32_t* d_status, int only_missing, int32_t* d_written, void* stream);
+int airfe_triangulate_point(const double* cam, const double* Twc, const float* xy, int n, double* xyz, int* status);
+
 /* ---- Junction term: junction_frame_scores * (1 + rate) of MapUser::Relocalization (src/map_user.cc:285-331), on the device ---------------------------
  * The number per stored frame that airfe_bowdb_group_dev / airfe_relocalize_batch_dev add to a group's score through d_extra [Q][N].  d_extra[q][deputy] is
  * all the grouping reads, so the term is computed for every stored frame rather than for the group frames: the grouping is the same.
