@@ -1,5 +1,5 @@
 // airfe — context life cycle, scratch blocks, host staging and the C ABI of libairfe.so (include/airfe.h, include/airfe_debug.h); the pipelines behind it live in
-// airfe_load.hip / airfe_detect.hip / airfe_lines.hip / airfe_match.hip, the geometry, BoW and kernel-hook entries in airfe_geom.hip / airfe_bowdb.hip / airfe_debug.hip (see airfe_host.h).
+// airfe_load.hip / airfe_detect.hip / airfe_lines.hip / airfe_match.hip, the geometry, BoW and kernel-hook entries in airfe_geom.hip / airfe_bowdb.hip, airfe_bowmap.hip, airfe_junction.hip / airfe_debug.hip (see airfe_host.h).
 #include "airfe_host.h"
 
 namespace airfe_host {
@@ -344,7 +344,7 @@ int airfe_debug_trace_slot(airfe_ctx* c, int i, char* name, int name_cap, unsign
 int airfe_debug_trace_read(airfe_ctx* c, void* stream, unsigned long long* digests, unsigned long long* table) try {
   if (c && enter_device(c)) return 1;
   if (!c || !c->trace_tab) return fail(c, "trace is off");
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t st = stream_of(c, stream);
   HIPCHK(c, hipStreamSynchronize(st));
   const size_t n = c->trace_slots.size();
   if (n == 0) return 0;
@@ -363,7 +363,7 @@ int airfe_sync(airfe_ctx* c) try {
 
 int airfe_superglue_status(airfe_ctx* c, void* stream) try {
   AIRFE_ENTER(c);
-  HIPCHK(c, hipStreamSynchronize(stream ? (hipStream_t)stream : c->stream));
+  HIPCHK(c, hipStreamSynchronize(stream_of(c, stream)));
   if (saturation_status(c)) return 1;
   return sinkhorn_failed(c);
 } AIRFE_CATCH(c)
@@ -371,7 +371,7 @@ int airfe_superglue_status(airfe_ctx* c, void* stream) try {
 int airfe_detect_points_batch_dev(airfe_ctx* c, const uint8_t* d_gray, int B, int h, int w, int stride, size_t img_stride,
                                   float* d_feat, int cap, int* d_n, void* stream) try {
   AIRFE_ENTER(c);
-  return detect_dev(c, d_gray, B, h, w, stride, img_stride, d_feat, cap, d_n, stream ? (hipStream_t)stream : c->stream);
+  return detect_dev(c, d_gray, B, h, w, stride, img_stride, d_feat, cap, d_n, stream_of(c, stream));
 } AIRFE_CATCH(c)
 
 int airfe_detect_points(airfe_ctx* c, const uint8_t* gray, int h, int w, int stride, float* feat, int cap, int* n) try {
@@ -423,7 +423,7 @@ int airfe_bow_transform_dev(airfe_ctx* c, const float* d_feat, int N, uint32_t* 
   AIRFE_ENTER(c);
   if (!c->bow_nodes) return fail(c, "bow_transform: no vocabulary loaded (airfe_bow_load)");
   if (N < 0 || (N > 0 && (!d_feat || !d_word || !d_weight))) return fail(c, "bow_transform: bad argument");
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t st = stream_of(c, stream);
   ProfScope ps(c, ST_BOW, st, 0, (double)N * 259 * 4);
   launch_bow_transform(d_feat, AIRFE_FEAT_DIM, 3, N, c->bow_desc, c->bow_first, c->bow_nch, c->bow_word, c->bow_weight, d_word, d_weight,
                        d_weight == c->bow_outw ? c->bow_outn : nullptr, st);
@@ -473,7 +473,7 @@ int airfe_rectify_batch_dev(airfe_ctx* c, int side, const uint8_t* d_raw, int B,
   if (side < 0 || side > 1 || !c->rmap[side][0]) return fail(c, "rectify: no maps set for this side (airfe_set_rectify_maps)");
   if (h != c->rmap_h[side] || w != c->rmap_w[side]) return fail(c, "rectify: image size differs from the maps'");
   if (stride < w || rstride < w) return fail(c, "rectify: stride smaller than the width");
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t st = stream_of(c, stream);
   ProfScope ps(c, ST_RECTIFY, st, 0, (double)B * h * w * (1 + 8 + 1));          // source pixels + two float maps + rectified pixels
   launch_remap_linear(d_raw, B, h, w, stride, img_stride, c->rmap[side][0], c->rmap[side][1], d_rect, rstride, rimg_stride, st);
   HIPCHK(c, hipGetLastError());
@@ -604,14 +604,14 @@ int airfe_match_lightglue_batch_dev(airfe_ctx* c, const float* d_f0, const int* 
                                     int B, int cap, int32_t* d_idx, float* d_score, int mcap, int* d_nmatch, void* stream) try {
   AIRFE_ENTER(c);
   return lightglue_dev(c, d_f0, d_n0, d_f1, d_n1, B, cap, AIRFE_FEAT_DIM, 1, 1, d_idx, d_score, mcap, d_nmatch, nullptr,
-                       stream ? (hipStream_t)stream : c->stream);
+                       stream_of(c, stream));
 } AIRFE_CATCH(c)
 
 int airfe_stereo_batch_dev(airfe_ctx* c, const uint8_t* d_left, const uint8_t* d_right, int B, int h, int w, int stride,
                            size_t img_stride, float* d_featL, float* d_featR, int cap, int* d_nL, int* d_nR, int32_t* d_idx,
                            float* d_score, int mcap, int* d_nmatch, void* stream) try {
   AIRFE_ENTER(c);
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t st = stream_of(c, stream);
   if (c->prec != 2 && 2 * B <= c->Dmax) {        // left and right images as ONE detector batch
     if (detect_dev2(c, d_left, d_right, B, h, w, stride, img_stride, d_featL, d_featR, cap, d_nL, d_nR, st)) return 1;
   } else {
@@ -665,7 +665,7 @@ int airfe_assign_points_to_lines_batch_dev(airfe_ctx* c, const double* d_lines, 
   AIRFE_ENTER(c);
   if (B < 1 || capL < 1 || cap < 1 || capE < 1 || !d_lines || !d_nlines || !d_feat || !d_n || !d_row_ptr || !d_pt_idx || !d_pt_dist)
     return fail(c, "assign_points_to_lines_batch_dev: bad argument");
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t st = stream_of(c, stream);
   // scratch of THIS entry (airfe_match_lines_batch_dev has its own: the two may be in flight on different streams); it grows only behind a
   // synchronisation of the stream it was last used on.  One stream at a time per entry and context — the contract of every *_dev entry (one ctx = one calling thread).
   if (reserve(c, c->pl_scratch, (size_t)B * capL * 4, st)) return 1;
@@ -744,7 +744,7 @@ int airfe_match_lines_batch_dev(airfe_ctx* c, const int32_t* d_row_ptr0, const i
       !d_n1 || !d_matches || !d_nmatch || !d_line_matches || (filter3 && (!d_feat0 || !d_feat1 || cap < 1)))
     return fail(c, "match_lines_batch_dev: bad argument");
   const int W = (mcap + 31) / 32;
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t st = stream_of(c, stream);
   // bit rows [2][B][capL][W] + row maxima [B][capL] (no vote matrix: the column pass recounts from the bit rows) — 7 MB at 64 frames x 1024 line slots
   Carve k;
   const size_t bits = (size_t)B * capL * W * 4, o_b0 = k.take(bits), o_b1 = k.take(bits), o_rloc = k.take((size_t)B * capL * 4);
@@ -883,7 +883,7 @@ int airfe_detect_plnet_batch_dev(airfe_ctx* c, const uint8_t* d_gray, int B, int
                                  int cap, int* d_n, double* d_lines, int capL, int* d_nlines, float* d_junc, int capJ, int* d_njunc,
                                  int junction_images, int* d_found, void* stream) try {
   AIRFE_ENTER(c);
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t st = stream_of(c, stream);
   if (c->prec == 2)
     return plnet_batch_f32(c, d_gray, B, h, w, stride, img_stride, d_feat, cap, d_n, d_lines, capL, d_nlines, d_junc, capJ, d_njunc, junction_images, d_found,
                            d_found ? d_found + B : nullptr, st);
@@ -957,7 +957,7 @@ int airfe_stereo_plnet_batch_dev(airfe_ctx* c, const uint8_t* d_left, const uint
   AIRFE_ENTER(c);
   if (!d_idx || !d_score || !d_nmatch) return fail(c, "stereo_plnet_batch: no match output");
   return stereo_plnet_dev(c, d_left, d_right, B, h, w, stride, img_stride, d_featL, d_featR, cap, d_nL, d_nR, d_lines, capL, d_nlines, d_juncL, capJ,
-                          d_njuncL, d_found, d_idx, d_score, mcap, d_nmatch, stream ? (hipStream_t)stream : c->stream);
+                          d_njuncL, d_found, d_idx, d_score, mcap, d_nmatch, stream_of(c, stream));
 } AIRFE_CATCH(c)
 
 // ONE stereo keyframe through host buffers (batch 1, the regime of AirSLAM's feature thread): what map_builder.cc:85-86 does in two façade calls —
@@ -1479,7 +1479,7 @@ int airfe_debug_sg_sinkhorn(airfe_ctx* c, const float* sim, const int* lens, int
 int airfe_match_superglue_batch_dev(airfe_ctx* c, const float* d_f0, const int* d_n0, const float* d_f1, const int* d_n1, int B, int cap,
                                     int32_t* d_idx0, int32_t* d_idx1, float* d_ms0, float* d_ms1, void* stream) try {
   AIRFE_ENTER(c);
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t st = stream_of(c, stream);
   if (superglue_dev(c, d_f0, d_n0, d_f1, d_n1, B, cap, 1, st)) return 1;
   const size_t sp = (size_t)c->Lz * 4, dp = (size_t)cap * 4, wb = (size_t)std::min(cap, c->Lz) * 4;
   HIPCHK(c, hipMemcpy2DAsync(d_idx0, dp, c->sg_out0, sp, wb, B, hipMemcpyDeviceToDevice, st));

@@ -1,5 +1,5 @@
 // airfe — the geometry entries of libairfe.so (include/airfe.h): F-matrix RANSAC, PnP RANSAC, stereo back-projection, track pose, the pose-only frame
-// optimisation and stereo line triangulation, each as a *_queue function on a stream (the composites of airfe_bowdb.hip and the keyframe / track entries of airfe.hip queue the same code)
+// optimisation and stereo line triangulation, each as a *_queue function on a stream (the composites of airfe_bowdb.hip / airfe_junction.hip and the keyframe / track entries of airfe.hip queue the same code)
 // and its host and batch entries.
 #include "airfe_host.h"
 #include "fransac_core.h"
@@ -30,7 +30,7 @@ int airfe_fundamental_ransac_batch_dev(airfe_ctx* c, const float* d_f0, const in
   (void)d_n0; (void)d_n1;
   if (B < 1 || cap < 1 || mcap < 1 || !d_f0 || !d_f1 || !d_idx || !d_score || !d_nmatch) return fail(c, "fundamental_ransac_batch_dev: bad argument");
   if (mcap > FR_MAX_MATCHES) return fail(c, "fundamental_ransac_batch_dev: mcap > 1024");
-  return fransac_queue(c, d_f0, d_f1, B, cap, d_idx, d_score, mcap, d_nmatch, d_F, stream ? (hipStream_t)stream : c->stream);
+  return fransac_queue(c, d_f0, d_f1, B, cap, d_idx, d_score, mcap, d_nmatch, d_F, stream_of(c, stream));
 } AIRFE_CATCH(c)
 
 int airfe_fundamental_ransac(airfe_ctx* c, const float* f0, int n0, const float* f1, int n1, int32_t* idx, float* score, int m, int* kept) try {
@@ -103,7 +103,7 @@ int airfe_pnp_ransac_batch_dev(airfe_ctx* c, const float* d_obj, const float* d_
   AIRFE_ENTER(c);
   if (B < 1 || ncap < 1 || !d_obj || !d_img || !d_n || !K || !d_Twc || !d_inlier || !d_count) return fail(c, "pnp_ransac_batch_dev: bad argument");
   if (ncap > PNP_MAX_POINTS) return fail(c, "pnp_ransac_batch_dev: ncap > 1024");
-  return pnp_queue(c, d_obj, d_img, d_n, B, ncap, K, d_Twc, d_Rt, d_inlier, ncap, nullptr, d_count, stream ? (hipStream_t)stream : c->stream);
+  return pnp_queue(c, d_obj, d_img, d_n, B, ncap, K, d_Twc, d_Rt, d_inlier, ncap, nullptr, d_count, stream_of(c, stream));
 } AIRFE_CATCH(c)
 
 int airfe_pnp_ransac(airfe_ctx* c, const double* obj, const double* img, int n, const double* K, double* Twc, double* Rt, uint8_t* inlier, int* count) try {
@@ -162,7 +162,7 @@ int airfe_stereo_points_batch_dev(airfe_ctx* c, const double* cam, const float* 
   s.fl = d_featL; s.fr = d_featR; s.nl = d_nL; s.nr = d_nR; s.cap = cap; s.idx = d_idx; s.nmatch = d_nmatch; s.mcap = mcap;
   s.min_x_diff = cam[0]; s.max_x_diff = cam[1]; s.max_y_diff = cam[2]; s.bf = cam[3]; s.fx = cam[4]; s.fy = cam[5]; s.cx = cam[6]; s.cy = cam[7];
   s.u_right = d_u_right; s.depth = d_depth; s.xyz = d_xyz; s.good = d_good;
-  launch_stereo_points(s, B, stream ? (hipStream_t)stream : c->stream);
+  launch_stereo_points(s, B, stream_of(c, stream));
   HIPCHK(c, hipGetLastError());
   return 0;
 } AIRFE_CATCH(c)
@@ -187,7 +187,7 @@ int airfe_track_pose_batch_dev(airfe_ctx* c, const double* K, const double* d_xy
   if (B < 1 || capK < 1 || cap < 1 || mcap < 1 || !K || !d_xyz || !d_feat || !d_tidx || !d_ntrack || !d_Twc || !d_mask || !d_count)
     return fail(c, "track_pose_batch_dev: bad argument");
   if (mcap > PNP_MAX_POINTS) return fail(c, "track_pose_batch_dev: mcap > 1024");
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t st = stream_of(c, stream);
   PnpGatherArgs g;
   if (pnp_gather_queue(c, d_xyz, capK, d_feat, cap, d_tidx, d_ntrack, mcap, B, g, st)) return 1;
   return pnp_queue(c, g.obj, g.img, g.n, B, mcap, K, d_Twc, d_Rt, d_mask, mcap, g.map, d_count, st);
@@ -222,7 +222,7 @@ int airfe_frame_optimize_batch_dev(airfe_ctx* c, const double* d_X, const double
     return fail(c, "frame_optimize_batch_dev: bad argument");
   if (ncap > PO_MAX_POINTS) return fail(c, "frame_optimize_batch_dev: ncap > 1024");
   return poseopt_queue(c, d_X, d_obs, d_n, B, ncap, d_Twc0, cam, Tcb, thr, d_Twc, d_Rt, d_inlier, ncap, nullptr, d_num, -1, nullptr,
-                       stream ? (hipStream_t)stream : c->stream);
+                       stream_of(c, stream));
 } AIRFE_CATCH(c)
 
 int airfe_frame_optimize(airfe_ctx* c, const double* X, const double* obs, int n, const double* cam, const double* Tcb, const double* thr,
@@ -268,7 +268,7 @@ int airfe_track_pose_opt_batch_dev(airfe_ctx* c, const double* cam, const double
       !d_num || !d_ok)
     return fail(c, "track_pose_opt_batch_dev: bad argument");
   if (mcap > PNP_MAX_POINTS) return fail(c, "track_pose_opt_batch_dev: mcap > 1024");
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t st = stream_of(c, stream);
   // this entry's block: X [B][mcap][3] | obs [B][mcap][3] | Twc_pnp [B][16] | Twc0 [B][16] f64 | pnp count [B] | pnp mask [B][mcap]
   Carve k;
   const size_t o_X = k.take((size_t)B * mcap * 24), o_obs = k.take((size_t)B * mcap * 24), o_pnp = k.take((size_t)B * 128), o_seed = k.take((size_t)B * 128),
@@ -327,7 +327,7 @@ int airfe_stereo_lines_batch_dev(airfe_ctx* c, const double* cam, const double* 
     return fail(c, "stereo_lines_batch_dev: bad argument");
   if (!d_lines_right_sel || !d_right_valid || !d_status || !d_endpoints || !d_plucker || !d_count) return fail(c, "stereo_lines_batch_dev: null output");
   return stereo_lines_queue(c, cam, d_lines_left, d_nlines_left, d_lines_right, d_nlines_right, capL, d_line_matches, d_Twc, B, d_lines_right_sel,
-                            d_right_valid, d_status, d_endpoints, d_plucker, d_count, stream ? (hipStream_t)stream : c->stream);
+                            d_right_valid, d_status, d_endpoints, d_plucker, d_count, stream_of(c, stream));
 } AIRFE_CATCH(c)
 
 int airfe_stereo_line_landmarks_batch_dev(airfe_ctx* c, const double* cam, const double* d_lines_left, const int* d_nlines_left, const double* d_lines_right,

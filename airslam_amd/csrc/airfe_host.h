@@ -7,7 +7,10 @@
 //   airfe.hip         context life cycle, scratch blocks, profiling / trace entries and the C ABI of detection, rectification, matching, lines, PLNet and the
 //                     keyframe / track / promote entries (include/airfe.h), with the inspection hooks that share a body with one of them
 //   airfe_geom.hip    F-RANSAC, PnP, stereo points, track pose, frame optimisation, stereo lines
-//   airfe_bowdb.hip   the BoW vector, the keyframe database, the relocalisation and loop detection composites
+//   airfe_bowdb.hip   the BoW vector, the keyframe database and its map tables, the relocalisation and loop detection composites (airfe_bowdb.h: the database
+//                     struct and the *_queue functions the next two files share with it)
+//   airfe_bowmap.hip  the database's map-point id table, the covisibility build and the map-point triangulation
+//   airfe_junction.hip  the junction connections, the database's junction tables, relocalisation's junction term and its composites
 //   airfe_debug.hip   the kernel-level test hooks (include/airfe_debug.h)
 #pragma once
 #include "../../include/airfe.h"
@@ -66,7 +69,8 @@ constexpr size_t SG_JUNCS = 0, SG_LP = 600, SG_KEEP = SG_LP + (size_t)KEEP_CAP *
 using namespace airfe_host;
 
 // One grow-on-demand device block.  Ownership, one rule: the memory is registered in its context's `allocs` by the reserve() that made it and freed with
-// everything else there by airfe_destroy; an owner that dies before its context (airfe_bowdb) hands its blocks back with release().
+// everything else there by airfe_destroy; an owner that dies before its context (airfe_bowdb: its scratch and its persistent tables alike, airfe_bowdb.h)
+// hands its blocks back with release().
 struct DevBlock {
   uint8_t* p = nullptr; size_t bytes = 0;
   hipStream_t last = nullptr;    // the stream the block was last handed out for (reserve): synchronised before the block is replaced
@@ -296,6 +300,9 @@ struct airfe_ctx {
   std::vector<Mark> marks;
   std::vector<hipEvent_t> ev_pool;
 };
+
+// the stream a *_dev entry queues on: the caller's, or the context's when the caller passes none
+inline hipStream_t stream_of(const airfe_ctx* c, void* stream) { return stream ? static_cast<hipStream_t>(stream) : c->stream; }
 
 enum Stage {
   ST_PREPROCESS = 0, ST_CONV1_FUSED /* conv1a + conv1b + pool: the dominant kernel, its own stage */, ST_CONV3X3_C64, ST_CONV3X3_C128, ST_HEAD_GEMM, ST_HEAD_ELTWISE, ST_NMS, ST_SELECT,

@@ -282,7 +282,7 @@ static int copy_rows_impl(airfe_ctx* c, int njobs, const void* const* src, void*
   }
   void* dp = nullptr;
   HIPCHK(c, hipHostGetDevicePointer(&dp, slot, 0));
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t st = stream_of(c, stream);
   if (!dst) hipLaunchKernelGGL(seq_offsets_kernel, dim3(1), dim3(256), 0, st, reinterpret_cast<const SeqJob*>(dp), njobs, d_off);
   const int chunks = (int)std::min<size_t>(16, std::max<size_t>(1, big / 32768));
   // a capped grid: copies into pinned memory wait on PCIe — a few dozen workgroups keep enough stores in flight (tools/microbench/pcie_kernel_write.hip: 64 reach the

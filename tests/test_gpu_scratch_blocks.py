@@ -149,6 +149,17 @@ def _query(ctx, state, B, stream):
     return (lambda: db.query_batch_dev(ids, vals, nw, cf, cs, sc, nc, ms, ratio=0.3, min_words=2, sharing_t=sh, stream=stream)), [cf, cs, sc, nc, ms, sh]
 
 
+def _query_stored(ctx, state, B, stream):
+    """stored frames 7, 6, .. against their predecessors: the one caller of the dense query that carves two blocks (the gathered vectors, then the dense cells)"""
+    import torch
+    db, _ = state
+    qframe, = _dev((7 - np.arange(B, dtype=np.int32)) % 8)
+    cf, cs = _full((B, 8), -7, torch.int32), _full((B, 8), -7, torch.int32)
+    sc = _full((B, 8), float("nan"), torch.float64)
+    nc, ms, sh = _full((B,), -1, torch.int32), _full((B,), -1, torch.int32), _full((B, 8), -1, torch.int32)
+    return (lambda: db.query_stored_batch_dev(qframe, cf, cs, sc, nc, ms, ratio=0.5, min_words=2, sharing_t=sh, stream=stream)), [cf, cs, sc, nc, ms, sh]
+
+
 CASES = {
     "fundamental_ransac": (None, _fransac),
     "pnp_ransac": (None, _pnp),
@@ -156,6 +167,7 @@ CASES = {
     "track_pose_opt": (None, _track_pose_opt),
     "bow_vector": (_bow_setup, _bow_vector),
     "bowdb_query": (_query_setup, _query),
+    "bowdb_query_stored": (_query_setup, _query_stored),
 }
 
 
@@ -198,5 +210,10 @@ def test_a_block_that_grows_under_queued_work_changes_no_result(name):
         assert sum(int(g[3].sum()) for g in got) > 0
     elif name == "bow_vector":
         assert all((g[2][::4] > 0).all() and (g[2] >= 0).all() for g in got)
+    elif name == "bowdb_query_stored":
+        # tests/loopdet_ref.py::stored_queries on these frames: 7, 6, 5, 3, 3, 2, 1 candidates for frames 7 .. 1, max_sharing 6 .. 9; frame 0 has no predecessor
+        for B, g in zip(BATCHES, got):
+            qf = (7 - np.arange(B)) % 8
+            assert (g[3][qf > 0] > 0).all() and (g[4][qf > 0] >= 2).all() and (g[3][qf == 0] == 0).all()
     else:
         assert all((g[3] > 0).all() and (g[4] >= 2).all() for g in got)
