@@ -92,16 +92,23 @@ class Context:
         if rc != 0:
             raise AirfeError(f"{what}: {(self._l.airfe_last_error(self._h) or b'').decode()}")
 
+    @staticmethod
+    def _image(img, wrong_type=None):
+        """The 2-D uint8 image check of every host entry -> the array the C entry reads: the caller's, or a contiguous copy where its strides cannot be handed over.
+        wrong_type: what a non-image raises (default: AirfeError("empty image"), as an empty one does)."""
+        img = np.asarray(img)
+        if img.ndim != 2 or img.dtype != np.uint8:
+            raise wrong_type if wrong_type is not None else AirfeError("empty image")
+        if img.size == 0:
+            raise AirfeError("empty image")
+        if img.strides[1] != 1 or img.strides[0] < img.shape[1]:      # negative / overlapping row strides: hand over a copy
+            img = np.ascontiguousarray(img)
+        return img
+
     # ---------------------------------------------------------------- host, batch-1 (≙ reference infer())
     def detect_points(self, gray: np.ndarray) -> np.ndarray:
         """-> [n, 259] float32 rows (score, x, y, desc).  Raises on an empty image."""
-        gray = np.asarray(gray)
-        if gray.ndim != 2 or gray.dtype != np.uint8:
-            raise TypeError("expected a 2-D uint8 image")
-        if gray.size == 0:
-            raise AirfeError("empty image")
-        if gray.strides[1] != 1 or gray.strides[0] < gray.shape[1]:      # negative / overlapping row strides: hand over a copy
-            gray = np.ascontiguousarray(gray)
+        gray = self._image(gray, TypeError("expected a 2-D uint8 image"))
         cap = self.np_rows
         feat = np.empty((cap, FEAT), dtype=np.float32)
         n = C.c_int(0)
@@ -133,11 +140,7 @@ class Context:
 
     def rectify_detect(self, side: int, raw: np.ndarray, detect: bool = True):
         """≙ Camera::UndistortImage + Detect: raw uint8 image -> (rectified uint8 [h, w], features [n, 259] or None)."""
-        raw = np.asarray(raw)
-        if raw.ndim != 2 or raw.dtype != np.uint8 or raw.size == 0:
-            raise AirfeError("empty image")
-        if raw.strides[1] != 1 or raw.strides[0] < raw.shape[1]:
-            raw = np.ascontiguousarray(raw)
+        raw = self._image(raw)
         rect = np.empty(raw.shape, np.uint8)
         cap = self.np_rows
         feat = np.empty((cap, FEAT), np.float32) if detect else None
@@ -181,11 +184,7 @@ class Context:
     def detect_plnet(self, gray: np.ndarray, stage0=None, want_junctions: bool = False, cap_lines: int = 45056,
                      cap_junc: int = 2048):
         """≙ PLNet::infer -> (feat [n,259], lines [L,4] float64, junctions [K,259])."""
-        gray = np.asarray(gray)
-        if gray.ndim != 2 or gray.dtype != np.uint8 or gray.size == 0:
-            raise AirfeError("empty image")
-        if gray.strides[1] != 1 or gray.strides[0] < gray.shape[1]:
-            gray = np.ascontiguousarray(gray)
+        gray = self._image(gray)
         cap = self.np_rows
         feat = np.empty((cap, FEAT), np.float32)
         lines = np.empty((cap_lines, 4), np.float64)
@@ -211,15 +210,10 @@ class Context:
             raise AirfeError("stereo_keyframe: ref_feat is the temporal match's reference: pass track=True")
         if track and not match:
             raise AirfeError("stereo_keyframe: track=True needs match=True (the temporal pair rides in the stereo match's forward)")
-        imgs = []
-        for g in (left, right):
-            g = np.asarray(g)
-            if g.ndim != 2 or g.dtype != np.uint8 or g.size == 0:
-                raise AirfeError("empty image")
-            imgs.append(g)
+        imgs = [self._image(g) for g in (left, right)]
         if imgs[0].shape != imgs[1].shape:
             raise AirfeError("stereo_keyframe: left and right images differ in size")
-        if any(g.strides[1] != 1 or g.strides[0] < g.shape[1] for g in imgs) or imgs[0].strides[0] != imgs[1].strides[0]:
+        if imgs[0].strides[0] != imgs[1].strides[0]:      # one row pitch for both: the C entry takes one stride
             imgs = [np.ascontiguousarray(g) for g in imgs]
         # fresh output arrays, filled by the library directly (like the reference's caller-owned Eigen matrices): the slices returned below own them
         cap = self.np_rows
@@ -254,11 +248,7 @@ class Context:
         """ONE tracked frame in one call (airfe_track_frame ≙ map_builder.cc:94-101): points of `gray` + LightGlue against the last keyframe's features
         (`ref_feat` [n,259]: uploaded when given, kept on the device when None) -> (feat [n,259], idx [m,2] (reference, new), score [m]).
         outlier_rejection=True: the list passes the F-matrix RANSAC on the device before it comes back (:101 passes `true`)."""
-        gray = np.asarray(gray)
-        if gray.ndim != 2 or gray.dtype != np.uint8 or gray.size == 0:
-            raise AirfeError("empty image")
-        if gray.strides[1] != 1 or gray.strides[0] < gray.shape[1]:
-            gray = np.ascontiguousarray(gray)
+        gray = self._image(gray)
         cap = self.np_rows
         feat, idx, sc = np.empty((cap, FEAT), np.float32), np.empty((cap, 2), np.int32), np.empty((cap,), np.float32)
         n, nm = C.c_int(0), C.c_int(0)
@@ -275,11 +265,7 @@ class Context:
     def promote_frame(self, right: np.ndarray):
         """The promotion of map_builder.cc:104-108 for the frame of the last track_frame call (airfe_promote_frame): Detect(right) + MatchingPoints(left, right)
         with the left rows still on the device -> (featR [n,259], idx [m,2] (left, right), score [m])."""
-        right = np.asarray(right)
-        if right.ndim != 2 or right.dtype != np.uint8 or right.size == 0:
-            raise AirfeError("empty image")
-        if right.strides[1] != 1 or right.strides[0] < right.shape[1]:
-            right = np.ascontiguousarray(right)
+        right = self._image(right)
         cap = self.np_rows
         feat, idx, sc = np.empty((cap, FEAT), np.float32), np.empty((cap, 2), np.int32), np.empty((cap,), np.float32)
         n, nm = C.c_int(0), C.c_int(0)

@@ -57,6 +57,7 @@ int airfe_debug_conv3x3(airfe_ctx* c, const float* x, int B, int cin, int H, int
   if (!a.X || !a.Wp || !a.bias || !a.Y) return fail(c, "debug_conv3x3: allocation failed");
   a.B = B; a.H = H; a.W = W; a.CIN = cin; a.COUT = cout;
   a.pool = pool; a.out_pad = 1; a.relu = 1;
+  (void)hipStreamSynchronize(nullptr);       // dalloc's zero fill of Y runs on the null stream, which the context's stream does not wait for (see dbg_canary)
   launch_conv3x3(prec, a, c->stream);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   std::vector<uint16_t> yo(ywords);
@@ -95,6 +96,7 @@ int airfe_debug_gemm(airfe_ctx* c, const float* x, int M, int K, const float* w,
     g.X1 = dx; g.ld1 = K; g.K1 = K; g.Wp = lw.w; g.bias = lw.b; g.M = Mp; g.N = N; g.cb_total = lw.cbt;
     g.epi = EPI_STORE_F32; g.act = relu ? ACT_RELU : ACT_NONE; g.out = dy; g.ldo = Np8;
     g.small_max = c->gemm_small_max; g.g8_min = c->gemm8_min; g.gr_min = c->gemmr_min; g.gr_wgs = c->gemmr_wgs;
+    (void)hipStreamSynchronize(nullptr);     // dy's zero fill (dalloc) must not land on top of the kernel's rows (see dbg_canary; seen once as zero rows in test_gemm)
     launch_gemm(prec, K, false, g, c->stream);
     if (hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, "debug_gemm: kernel failed");
   }
@@ -1053,6 +1055,104 @@ int airfe_debug_junctions_topk(airfe_ctx* c, const float* jloc, const float* jof
   if (launch_status(c)) return 1;
   if (saturation_status(c)) return 1;
   HIPCHK(c, hipMemcpy2D(juncs_pred, 600 * 4, c->s0_stage + SG_JUNCS, SG_STRIDE * 4, 600 * 4, B, hipMemcpyDeviceToHost));
+  return 0;
+} AIRFE_CATCH(c)
+
+int airfe_debug_detector_maps(airfe_ctx* c, int B, float* heat_raw, float* heat_nms, float* desc) try {
+  if (c && enter_device(c)) return 1;
+  if (!c || !c->has_sp || B > c->Dmax) return 1;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const size_t R = AIRFE_INTERNAL_SIZE;
+  if (heat_raw) HIPCHK(c, hipMemcpy(heat_raw, c->heat, (size_t)B * R * R * 4, hipMemcpyDeviceToHost));
+  if (heat_nms && c->cfg.nms_radius > 0 && !c->nms_map_valid) {      // the batch path skipped the dense map: rebuild it from the heat maps
+    launch_nms512_candidates(c->heat, c->heat_nms, c->nms_mask, (int)B, c->cfg.keypoint_threshold, c->cfg.remove_borders, c->cand, c->cand_cnt,
+                             R * R, c->stream);          // (the map is only ever skipped on the radius-4 path)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->nms_map_valid = true;
+  }
+  if (heat_nms) HIPCHK(c, hipMemcpy(heat_nms, c->cfg.nms_radius > 0 ? c->heat_nms : c->heat, (size_t)B * R * R * 4, hipMemcpyDeviceToHost));
+  if (desc) {
+    if (!c->desc_dense_valid) {     // the batch path ran the head on the sampled cells only: build the dense map from the kept activations
+      dense_desc_head(c, c->last_B, c->stream);
+      c->desc_dense_valid = true;
+    }
+    if (!c->desc_normalised) {      // the inspection hook returns the map the reference would hold: normalised
+      launch_l2norm256(c->desc, c->Dmax * 64 * 64, c->stream);
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      c->desc_normalised = true;
+    }
+    HIPCHK(c, hipMemcpy(desc, c->desc, (size_t)B * 64 * 64 * 256 * 4, hipMemcpyDeviceToHost));
+  }
+  return 0;
+} AIRFE_CATCH(c)
+
+/* the on-device stage-0 line branch of the LAST detected image, copied out in the Appendix A.1 layouts (NULL = skip) */
+int airfe_debug_plnet_stage0(airfe_ctx* c, float* juncs_pred, float* lines_pred, float* iskeep, float* idx_min, float* idx_max,
+                             float* loi, float* thin, float* aux, float* jloc, float* joff) try {
+  if (c && enter_device(c)) return 1;
+  if (!c || !c->has_s0 || !c->has_s1) return fail(c, "debug_plnet_stage0: line branch / stage 1 not loaded");
+  hipStream_t st = c->stream;
+  if (line_branch_dev(c, st, 0, 1, true)) return 1;
+  HIPCHK(c, hipStreamSynchronize(st));
+  const size_t NP = KEEP_CAP;
+  float* d = c->s0_stage;
+  struct { float* h; const float* dv; size_t n; } cp[10] = {
+      {juncs_pred, d + SG_JUNCS, 600}, {lines_pred, d + SG_LP, NP * 4}, {iskeep, d + SG_KEEP, NP}, {idx_min, d + SG_MIN, NP},
+      {idx_max, d + SG_MAX, NP}, {loi, c->s0_loi, (size_t)128 * 128 * 128}, {thin, d + SG_THIN, (size_t)4 * 128 * 128},
+      {aux, d + SG_AUX, (size_t)4 * 128 * 128}, {jloc, c->l_jloc, (size_t)128 * 128}, {joff, c->l_joff, (size_t)2 * 128 * 128}};
+  for (auto& e : cp)
+    if (e.h) HIPCHK(c, hipMemcpy(e.h, e.dv, e.n * 4, hipMemcpyDeviceToHost));
+  return 0;
+} AIRFE_CATCH(c)
+
+/* the junction-to-line match of the LAST detected image as the line path runs it (fast = 1: cell search, exact where it is consumed) or
+   as the inspection hook exports it (fast = 0: every proposal against every junction): iskeep, idx_junc_to_end_min / _max [3*128*128] */
+int airfe_debug_plnet_j2l(airfe_ctx* c, int fast, float* iskeep, float* idx_min, float* idx_max) try {
+  if (c && enter_device(c)) return 1;
+  if (!c || !c->has_s0 || !c->has_s1) return fail(c, "debug_plnet_j2l: line branch / stage 1 not loaded");
+  hipStream_t st = c->stream;
+  if (line_branch_dev(c, st, 0, 1, fast == 0)) return 1;
+  HIPCHK(c, hipStreamSynchronize(st));
+  const size_t NP = KEEP_CAP;
+  float* d = c->s0_stage;
+  if (iskeep) HIPCHK(c, hipMemcpy(iskeep, d + SG_KEEP, NP * 4, hipMemcpyDeviceToHost));
+  if (idx_min) HIPCHK(c, hipMemcpy(idx_min, d + SG_MIN, NP * 4, hipMemcpyDeviceToHost));
+  if (idx_max) HIPCHK(c, hipMemcpy(idx_max, d + SG_MAX, NP * 4, hipMemcpyDeviceToHost));
+  return 0;
+} AIRFE_CATCH(c)
+
+/* stage-1 alone on HOST stage-0 tensors: lines_adjusted [M2][4] + scores_line [M2] (parity vs the real plnet_s1.onnx) */
+int airfe_debug_plnet_s1(airfe_ctx* c, const airfe_plnet_stage0* s0, float* lines_adjusted, float* scores_line, int cap, int* m2) try {
+  if (c && enter_device(c)) return 1;
+  if (!c || !c->has_s1 || !s0) return fail(c, "debug_plnet_s1: stage-1 not loaded");
+  hipStream_t st = c->stream;
+  if (upload_stage0(c, s0, st)) return 1;
+  line_dedup(c, 1, st);                        // (upload_stage0 left wf_counted false: host tensors, nothing has counted their kept proposals)
+  line_stage1(c, 1, S1_CHW, 0, st);
+  int cnt[2] = {0, 0};
+  HIPCHK(c, hipMemcpyAsync(cnt, c->wf_counts, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  const int k = std::min(cnt[1], cap);
+  if (k > 0) {
+    HIPCHK(c, hipMemcpy(lines_adjusted, c->s1_la, (size_t)k * 16, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(scores_line, c->s1_sc, (size_t)k * 4, hipMemcpyDeviceToHost));
+  }
+  *m2 = k;
+  return 0;
+} AIRFE_CATCH(c)
+
+int airfe_debug_plnet_s1_last(airfe_ctx* c, float* lines_adjusted, float* scores_line, int cap, int* m2) try {
+  if (c && enter_device(c)) return 1;
+  if (!c || !c->has_s1 || !lines_adjusted || !scores_line || !m2) return fail(c, "debug_plnet_s1_last: stage-1 not loaded / bad argument");
+  HIPCHK(c, hipDeviceSynchronize());
+  int cnt[2] = {0, 0};
+  HIPCHK(c, hipMemcpy(cnt, c->wf_counts, 8, hipMemcpyDeviceToHost));
+  const int k = std::min(cnt[1], cap);
+  if (k > 0) {
+    HIPCHK(c, hipMemcpy(lines_adjusted, c->s1_la, (size_t)k * 16, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(scores_line, c->s1_sc, (size_t)k * 4, hipMemcpyDeviceToHost));
+  }
+  *m2 = k;
   return 0;
 } AIRFE_CATCH(c)
 

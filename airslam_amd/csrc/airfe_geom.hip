@@ -1,5 +1,5 @@
 // airfe — the geometry entries of libairfe.so (include/airfe.h): F-matrix RANSAC, PnP RANSAC, stereo back-projection, track pose, the pose-only frame
-// optimisation and stereo line triangulation, each as a *_queue function on a stream (the composites of airfe_bowdb.hip / airfe_junction.hip and the keyframe / track entries of airfe.hip queue the same code)
+// optimisation and stereo line triangulation, each as a *_queue function on a stream (the composites of airfe_bowdb.hip / airfe_junction.hip and the keyframe / track entries of airfe_frame.hip queue the same code)
 // and its host and batch entries.
 #include "airfe_host.h"
 #include "fransac_core.h"

@@ -3,9 +3,11 @@
 //   airfe_load.hip    weight-pack loading and slab packing (≙ TensorRT engine build, src/plnet.cpp:24-196), the matcher arena
 //   airfe_detect.hip  the detector pipeline (encoder, heads, NMS, top-K, descriptors)
 //   airfe_lines.hip   the PLNet line path: its steps, and line_branch_dev / line_tail_dev / line_post_dev composed of them
-//   airfe_match.hip   LightGlue / SuperGlue forwards and the fault-hunting trace
-//   airfe.hip         context life cycle, scratch blocks, profiling / trace entries and the C ABI of detection, rectification, matching, lines, PLNet and the
-//                     keyframe / track / promote entries (include/airfe.h), with the inspection hooks that share a body with one of them
+//   airfe_match.hip   LightGlue / SuperGlue forwards, the fault-hunting trace and the matchers' host / batch entries
+//   airfe.hip         context life cycle, scratch blocks, host staging, profiling / trace entries, sync and status, the BoW vocabulary and rectification entries
+//   airfe_frame.hip   the frame entries (include/airfe.h): detection, PLNet and stereo over host and device images, the stereo keyframe and track / promote /
+//                     adopt, with the pieces their queues and read-backs share
+//   airfe_assoc.hip   the point / line association entries: AssignPointsToLines, MatchLines
 //   airfe_geom.hip    F-RANSAC, PnP, stereo points, track pose, frame optimisation, stereo lines
 //   airfe_bowdb.hip   the BoW vector, the keyframe database and its map tables, the relocalisation and loop detection composites (airfe_bowdb.h: the database
 //                     struct and the *_queue functions the next two files share with it)
@@ -435,10 +437,11 @@ struct LgSecondPair { const float *f0, *f1; const int *n0, *n1; };      // a sec
 int lightglue_dev(airfe_ctx* c, const float* f0, const int* n0, const float* f1, const int* n1, int B, int cap, int ld, int kp_off, int normalize,
                   int32_t* d_idx, float* d_score, int mcap, int* d_nmatch, float* scores_out, hipStream_t st, const LgSecondPair* x2 = nullptr);
 int superglue_dev(airfe_ctx* c, const float* f0, const int* n0, const float* f1, const int* n1, int B, int cap, int normalize, hipStream_t st);
+int sinkhorn_failed(airfe_ctx* c);      // a Sinkhorn rendezvous of an earlier SuperGlue call timed out (read after a synchronisation, cleared once reported)
 
 }  // namespace airfe_host
 
-// ---- airfe.hip
+// ---- every file with C entries
 // Every extern "C" entry is a function-try-block ending in AIRFE_CATCH: std::bad_alloc from a std::vector / std::string of the host-side
 // bookkeeping (or anything else thrown below) becomes a non-zero return + airfe_last_error(), never an exception crossing the C ABI.
 #define AIRFE_CATCH(c)                                                                                                   \
@@ -453,6 +456,7 @@ inline int enter_device(airfe_ctx* c) {
   return 0;
 }
 #define AIRFE_ENTER(c) do { if (!(c)) return 1; if (enter_device(c)) return 1; } while (0)
+// ---- airfe.hip
 int ensure_pin(airfe_ctx* c, size_t bytes);
 int upload_image(airfe_ctx* c, const uint8_t* gray, int h, int w, int stride);
 // A host entry that returns with an error AFTER it queued work must not leave that work in flight: the next call memcpy's into the pinned block a
@@ -473,6 +477,30 @@ struct DrainOnError {
     if (ref_uploaded) c->ref_n = -1;
   }
 };
+// ---- the pinned block's read-backs, after the wait that brought them home (airfe_frame.hip, airfe_match.hip)
+// [counts | rows of image 0 | rows of image 1 ..] at the start of the pinned block, max_keypoints rows per image: image img's rows -> feat; returns how many
+inline int rows_out(const airfe_ctx* c, int img, float* feat) {
+  const int Np = c->cfg.max_keypoints, n = std::min(reinterpret_cast<const int*>(c->pin)[img], Np);
+  if (n > 0) memcpy(feat, c->pin + 64 + (size_t)img * Np * AIRFE_FEAT_DIM * 4, (size_t)n * AIRFE_FEAT_DIM * 4);
+  return n;
+}
+// [idx | score] at c->pin + off -> nm matches of the pair whose list starts at row `first`; stride = the bytes of the idx part (Np * 8 for one pair, Np * 16 for
+// the keyframe's two)
+inline void matches_out(const airfe_ctx* c, size_t off, size_t stride, int first, int nm, int32_t* idx, float* score) {
+  if (nm < 1) return;
+  memcpy(idx, c->pin + off + (size_t)first * 8, (size_t)nm * 8);
+  memcpy(score, c->pin + off + stride + (size_t)first * 4, (size_t)nm * 4);
+}
+// ---- airfe_frame.hip: what the batch-1 frame entries' queues share
+// [count | n_ref rows] through the pinned block at `off` into ref_blk, queued on st.  The stored count becomes valid with the queued upload; drain takes it back
+// if the call fails before the stream is idle.
+int upload_reference(airfe_ctx* c, DrainOnError& drain, size_t off, const float* ref_feat, int n_ref, hipStream_t st);
+// the first `bytes` of a frame entry's device block ([counts | feature rows]) go home to the start of the pinned block on s2; ev_feat marks their arrival
+int rows_home(airfe_ctx* c, const DevBlock& blk, size_t bytes, hipStream_t s2);
+// the second (and last) round trip of a PLNet host entry: line / junction rows, whose counts are known only after the first wait, through the pinned block
+struct RowsPart { const void* dev; void* host; size_t bytes; };
+int rows_second_trip(airfe_ctx* c, std::initializer_list<RowsPart> parts, hipStream_t st);
+int upload_stage0(airfe_ctx* c, const airfe_plnet_stage0* s0, hipStream_t st);      // caller-supplied stage-0 tensors -> stage slot 0 + the CHW LOI block
 // ---- airfe_geom.hip: the pipelines on a stream, queued by their own entries, by the keyframe / track entries and by the composites of airfe_bowdb.hip
 int fransac_queue(airfe_ctx* c, const float* d_f0, const float* d_f1, int B, int cap, int32_t* d_idx, float* d_score, int mcap, int* d_nmatch, double* d_F,
                   hipStream_t st);

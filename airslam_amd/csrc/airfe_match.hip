@@ -1,4 +1,4 @@
-// airfe — LightGlue / SuperGlue forwards on device-resident features and the fault-hunting trace (see airfe_host.h)
+// airfe — LightGlue / SuperGlue forwards on device-resident features, the fault-hunting trace and the matchers' host and batch entries (see airfe_host.h)
 #include "airfe_host.h"
 
 namespace airfe_host {
@@ -408,5 +408,201 @@ int superglue_dev(airfe_ctx* c, const float* f0, const int* n0, const float* f1,
   return launch_status(c);
 }
 
+// The register-resident Sinkhorn kernel raises a device word when one of its bounded rendezvous spins timed out (that pair's Z is NaN): read
+// after a synchronisation, cleared once reported.
+int sinkhorn_failed(airfe_ctx* c) {
+  if (!c->has_sg || !c->sg_cnt) return 0;
+  unsigned f = 0;
+  unsigned* flag = c->sg_cnt + (size_t)c->Pmax * 16;
+  if (hipMemcpy(&f, flag, 4, hipMemcpyDeviceToHost) != hipSuccess || f == 0) return 0;
+  (void)hipMemset(flag, 0, 4);
+  return fail(c, "SuperGlue: a Sinkhorn rendezvous timed out (workgroups of the cooperative launch not co-resident?): the scores of that call are NaN");
+}
 
 }  // namespace airfe_host
+
+extern "C" {
+
+static int lg_host(airfe_ctx* c, const float* f0, int n0, const float* f1, int n1, int32_t* idx, float* score, int cap,
+                   int* nmatch, float* scores_full) {
+  AIRFE_ENTER(c);
+  if (n0 < 1 || n1 < 1) { if (nmatch) *nmatch = 0; return 0; }   // point_matcher.cc:53-55
+  if (n0 > c->cfg.max_keypoints || n1 > c->cfg.max_keypoints) return fail(c, "keypoint count exceeds max_keypoints");
+  // ONE H2D: [n0 n1 | n0 rows of f0 | n1 rows of f1] assembled in the pinned block (f1 sits right behind f0's rows on the device too)
+  const size_t b0 = (size_t)n0 * 258 * 4, b1 = (size_t)n1 * 258 * 4;
+  if (ensure_pin(c, 64 + b0 + b1)) return 1;
+  reinterpret_cast<int*>(c->pin)[0] = n0;
+  reinterpret_cast<int*>(c->pin)[1] = n1;
+  memcpy(c->pin + 64, f0, b0);
+  memcpy(c->pin + 64 + b0, f1, b1);
+  HIPCHK(c, hipMemcpyAsync(c->io_in, c->pin, 64 + b0 + b1, hipMemcpyHostToDevice, c->stream));
+  const float* d_f1 = c->st_feat0 + (size_t)n0 * 258;
+  if (lightglue_dev(c, c->st_feat0, c->st_n0, d_f1, c->st_n1, 1, c->Np, 258, 0, 0, c->st_idx, c->st_score, c->Np,
+                    c->st_nm, scores_full ? c->st_scores_full : nullptr, c->stream))
+    return 1;
+  // ONE D2H: [nmatch | idx | score] (a few KB whatever the count), the rows copied out after the synchronisation
+  const size_t ob = 64 + (size_t)c->Np * 12;
+  HIPCHK(c, hipMemcpyAsync(c->pin, c->io_out, ob, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  int nm = *reinterpret_cast<const int*>(c->pin);
+  if (idx && score) {
+    nm = std::min(nm, cap);
+    matches_out(c, 64, (size_t)c->Np * 8, 0, nm, idx, score);
+  }
+  if (nmatch) *nmatch = nm;
+  if (scores_full)
+    for (int i = 0; i < n0; ++i)
+      HIPCHK(c, hipMemcpy(scores_full + (size_t)i * n1, c->st_scores_full + (size_t)i * c->Np, (size_t)n1 * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int airfe_match_lightglue(airfe_ctx* c, const float* f0, int n0, const float* f1, int n1, int32_t* idx, float* score,
+                          int cap, int* nmatch) try {
+  if (c && enter_device(c)) return 1;
+  return lg_host(c, f0, n0, f1, n1, idx, score, cap, nmatch, nullptr);
+} AIRFE_CATCH(c)
+
+int airfe_debug_lightglue_scores(airfe_ctx* c, const float* f0, int n0, const float* f1, int n1, float* scores) try {
+  if (c && enter_device(c)) return 1;
+  return lg_host(c, f0, n0, f1, n1, nullptr, nullptr, 0, nullptr, scores);
+} AIRFE_CATCH(c)
+
+/* filter_matches (src/light_glue.cpp:214-266) alone on one HOST score matrix [n0][n1] */
+int airfe_debug_lg_filter(airfe_ctx* c, const float* scores, int n0, int n1, int32_t* idx, float* score, int cap, int* nmatch) try {
+  if (c && enter_device(c)) return 1;
+  if (!c || !c->has_arena) return fail(c, "debug_lg_filter: no matcher loaded");
+  if (n0 < 1 || n1 < 1 || n0 > c->cfg.max_keypoints || n1 > c->cfg.max_keypoints || !scores || !idx || !score || !nmatch)
+    return fail(c, "debug_lg_filter: bad argument");
+  const int lens[2] = {n0, n1};
+  HIPCHK(c, hipMemcpyAsync(c->lens, lens, 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpy2DAsync(c->simbuf, (size_t)c->Np * 4, scores, (size_t)n1 * 4, (size_t)n1 * 4, n0, hipMemcpyHostToDevice, c->stream));
+  launch_lg_filter_scores(c->simbuf, c->lens, 1, c->Np, c->Np, 0.1f, c->rowarg, c->rowval, c->colarg, c->st_idx, c->st_score,
+                          c->st_nm, c->stream);
+  int nm = 0;
+  HIPCHK(c, hipMemcpyAsync(&nm, c->st_nm, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  nm = std::min(nm, cap);
+  if (nm > 0) {
+    HIPCHK(c, hipMemcpy(idx, c->st_idx, (size_t)nm * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(score, c->st_score, (size_t)nm * 4, hipMemcpyDeviceToHost));
+  }
+  *nmatch = nm;
+  return 0;
+} AIRFE_CATCH(c)
+
+int airfe_match_lightglue_batch_dev(airfe_ctx* c, const float* d_f0, const int* d_n0, const float* d_f1, const int* d_n1,
+                                    int B, int cap, int32_t* d_idx, float* d_score, int mcap, int* d_nmatch, void* stream) try {
+  AIRFE_ENTER(c);
+  return lightglue_dev(c, d_f0, d_n0, d_f1, d_n1, B, cap, AIRFE_FEAT_DIM, 1, 1, d_idx, d_score, mcap, d_nmatch, nullptr,
+                       stream_of(c, stream));
+} AIRFE_CATCH(c)
+
+static int sg_host(airfe_ctx* c, const float* f0, int n0, const float* f1, int n1, int32_t* idx0, int32_t* idx1, double* ms0,
+                   double* ms1, float* scores_full) {
+  AIRFE_ENTER(c);
+  if (n0 < 1 || n1 < 1) return fail(c, "airfe_match_superglue: empty input (MatchingPoints early-outs before calling infer)");
+  if (n0 > c->cfg.max_keypoints || n1 > c->cfg.max_keypoints) return fail(c, "keypoint count exceeds max_keypoints");
+  HIPCHK(c, hipMemcpyAsync(c->st_feat0, f0, (size_t)n0 * 259 * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->st_feat1, f1, (size_t)n1 * 259 * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->st_n0, &n0, 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->st_n1, &n1, 4, hipMemcpyHostToDevice, c->stream));
+  if (superglue_dev(c, c->st_feat0, c->st_n0, c->st_feat1, c->st_n1, 1, c->Np, 0, c->stream)) return 1;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (sinkhorn_failed(c)) return 1;
+  if (idx0) {
+    std::vector<float> m0(n0), m1(n1);
+    HIPCHK(c, hipMemcpy(idx0, c->sg_out0, (size_t)n0 * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(idx1, c->sg_out1, (size_t)n1 * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(m0.data(), c->sg_ms0, (size_t)n0 * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(m1.data(), c->sg_ms1, (size_t)n1 * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n0; ++i) ms0[i] = (double)m0[i];      // VectorXd filled from float vectors: super_glue.cpp:464-469
+    for (int j = 0; j < n1; ++j) ms1[j] = (double)m1[j];
+  }
+  if (scores_full)
+    HIPCHK(c, hipMemcpy2D(scores_full, (size_t)(n1 + 1) * 4, c->sg_Z, (size_t)c->Lz * 4, (size_t)(n1 + 1) * 4, n0 + 1, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int airfe_match_superglue(airfe_ctx* c, const float* f0, int n0, const float* f1, int n1, int32_t* idx0, int32_t* idx1,
+                          double* ms0, double* ms1) try {
+  if (c && enter_device(c)) return 1;
+  return sg_host(c, f0, n0, f1, n1, idx0, idx1, ms0, ms1, nullptr);
+} AIRFE_CATCH(c)
+
+/* decode (src/super_glue.cpp:339-367) alone on one HOST score matrix Z [n0+1][n1+1] */
+int airfe_debug_sg_decode(airfe_ctx* c, const float* Z, int n0, int n1, int32_t* idx0, int32_t* idx1, double* ms0, double* ms1) try {
+  if (c && enter_device(c)) return 1;
+  if (!c || !c->has_sg) return fail(c, "debug_sg_decode: SuperGlue not loaded");
+  if (n0 < 1 || n1 < 1 || n0 > c->cfg.max_keypoints || n1 > c->cfg.max_keypoints || !Z || !idx0 || !idx1 || !ms0 || !ms1)
+    return fail(c, "debug_sg_decode: bad argument");
+  const int lens[2] = {n0, n1};
+  HIPCHK(c, hipMemcpyAsync(c->lens, lens, 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpy2DAsync(c->sg_Z, (size_t)c->Lz * 4, Z, (size_t)(n1 + 1) * 4, (size_t)(n1 + 1) * 4, n0 + 1, hipMemcpyHostToDevice, c->stream));
+  launch_sg_decode(c->sg_Z, c->lens, 1, c->Np, c->Lz, 0.2f, c->sg_idx0, c->sg_max0, c->sg_idx1, c->sg_out0, c->sg_out1, c->sg_ms0,
+                   c->sg_ms1, c->stream);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<float> m0(n0), m1(n1);
+  HIPCHK(c, hipMemcpy(idx0, c->sg_out0, (size_t)n0 * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(idx1, c->sg_out1, (size_t)n1 * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(m0.data(), c->sg_ms0, (size_t)n0 * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(m1.data(), c->sg_ms1, (size_t)n1 * 4, hipMemcpyDeviceToHost));
+  for (int i = 0; i < n0; ++i) ms0[i] = (double)m0[i];
+  for (int j = 0; j < n1; ++j) ms1[j] = (double)m1[j];
+  return 0;
+} AIRFE_CATCH(c)
+
+/* launch_sg_sinkhorn alone on B HOST coupling matrices (include/airfe_debug.h).  Everything of the arena outside each pair's valid n0 x n1 block is NaN when
+   the launch starts, and so is the output: a finite Z [0..n0][0..n1] was written in full and came from inside `lens` alone. */
+int airfe_debug_sg_sinkhorn(airfe_ctx* c, const float* sim, const int* lens, int B, int ld, float alpha, int iters, int form, float* Z, int* form_ran) try {
+  if (c && enter_device(c)) return 1;
+  if (!c || !c->has_sg) return fail(c, "debug_sg_sinkhorn: SuperGlue not loaded");
+  if (!sim || !lens || !Z || !form_ran || B < 1 || B > c->Pmax || ld < 1 || iters < 0 || form < 0 || form > 2)
+    return fail(c, "debug_sg_sinkhorn: bad argument (1 <= B <= max_batch, iters >= 0, form 0 / 1 / 2)");
+  const int nmax = std::min(ld, c->cfg.max_keypoints);
+  for (int i = 0; i < 2 * B; ++i)
+    if (lens[i] < 1 || lens[i] > nmax) return fail(c, "debug_sg_sinkhorn: every n0, n1 must lie in 1 .. min(ld, max_keypoints)");
+  *form_ran = 0;
+  const int Np = c->Np, Lz = c->Lz;
+  const size_t blk = (size_t)Np * Np, zblk = (size_t)Lz * Lz;
+  HIPCHK(c, hipMemcpyAsync(c->lens, lens, (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->simbuf, 0xFF, (size_t)B * blk * 4, c->stream));          // 0xFFFFFFFF: a NaN
+  HIPCHK(c, hipMemsetAsync(c->sg_Z, 0xFF, (size_t)B * zblk * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->sg_xch, 0xFF, (size_t)B * Lz * 64 * 4, c->stream));      // [B][2][16][Lz] float2: a partial read before it was written is a NaN
+  for (int b = 0; b < B; ++b)
+    HIPCHK(c, hipMemcpy2DAsync(c->simbuf + b * blk, (size_t)Np * 4, sim + (size_t)b * ld * ld, (size_t)ld * 4, (size_t)lens[2 * b + 1] * 4, lens[2 * b],
+                               hipMemcpyHostToDevice, c->stream));
+  launch_sg_sinkhorn(c->simbuf, c->lens, B, Np, Lz, alpha, iters, c->sg_u, c->sg_v, c->sg_Z, c->sg_cnt, c->sg_cnt + (size_t)c->Pmax * 16, c->sg_xch, c->stream,
+                     form, form_ran);
+  if (*form_ran == 0)
+    return fail(c, "debug_sg_sinkhorn: form 2 asked for, but no register-resident instantiation applies to this context (max_keypoints, B against the co-resident "
+                   "workgroups) or the cooperative launch was refused");
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (launch_status(c) || sinkhorn_failed(c)) return 1;
+  for (int b = 0; b < B; ++b)
+    HIPCHK(c, hipMemcpy2D(Z + (size_t)b * (ld + 1) * (ld + 1), (size_t)(ld + 1) * 4, c->sg_Z + b * zblk, (size_t)Lz * 4, (size_t)(lens[2 * b + 1] + 1) * 4,
+                          lens[2 * b] + 1, hipMemcpyDeviceToHost));
+  return 0;
+} AIRFE_CATCH(c)
+
+/* SuperGlue on B pairs of DEVICE feature matrices (259-float rows, original pixel coordinates; NormalizeKeypoints with scale 0.7 on
+   the device): d_idx0 / d_idx1 [B][cap] (-1 = unmatched), d_ms0 / d_ms1 [B][cap] floats.  No reference counterpart (batch-1 there). */
+int airfe_match_superglue_batch_dev(airfe_ctx* c, const float* d_f0, const int* d_n0, const float* d_f1, const int* d_n1, int B, int cap,
+                                    int32_t* d_idx0, int32_t* d_idx1, float* d_ms0, float* d_ms1, void* stream) try {
+  AIRFE_ENTER(c);
+  hipStream_t st = stream_of(c, stream);
+  if (superglue_dev(c, d_f0, d_n0, d_f1, d_n1, B, cap, 1, st)) return 1;
+  const size_t sp = (size_t)c->Lz * 4, dp = (size_t)cap * 4, wb = (size_t)std::min(cap, c->Lz) * 4;
+  HIPCHK(c, hipMemcpy2DAsync(d_idx0, dp, c->sg_out0, sp, wb, B, hipMemcpyDeviceToDevice, st));
+  HIPCHK(c, hipMemcpy2DAsync(d_idx1, dp, c->sg_out1, sp, wb, B, hipMemcpyDeviceToDevice, st));
+  HIPCHK(c, hipMemcpy2DAsync(d_ms0, dp, c->sg_ms0, sp, wb, B, hipMemcpyDeviceToDevice, st));
+  HIPCHK(c, hipMemcpy2DAsync(d_ms1, dp, c->sg_ms1, sp, wb, B, hipMemcpyDeviceToDevice, st));
+  return 0;
+} AIRFE_CATCH(c)
+
+/* full SuperGlue output `scores` [n0+1][n1+1] (binding A.5) for one HOST pair */
+int airfe_debug_superglue_scores(airfe_ctx* c, const float* f0, int n0, const float* f1, int n1, float* scores) try {
+  if (c && enter_device(c)) return 1;
+  return sg_host(c, f0, n0, f1, n1, nullptr, nullptr, nullptr, nullptr, scores);
+} AIRFE_CATCH(c)
+
+}  // extern "C"

@@ -219,6 +219,60 @@ def test_promote_and_adopt_equal_detect_plus_match():
     kf.close(); nf.close()
 
 
+def _same_bytes(got, want):
+    assert len(got) == len(want)
+    for g, w in zip(got, want):
+        assert g.shape == w.shape and g.dtype == w.dtype and g.tobytes() == w.tobytes()
+
+
+def test_promote_is_never_outlier_rejected_and_keeps_the_reference():
+    """airfe_track_frame and airfe_promote_frame share one queue; map_builder.cc:101 passes `true` to MatchingPoints, :107 `false`: with the context's outlier
+    rejection ON, promote returns the bytes it returns with it off, and it touches neither the reference rows nor their count."""
+    kf, nf = _contexts(2)
+    det = api.FeatureDetector(nf)
+    (l0, _), (l1, r1), (l2, _) = _frames(3, 40, 40)
+    ok, f0 = det.Detect(l0)
+    nf.track_frame(l1, ref_feat=f0.T)
+    want = [a.copy() for a in nf.promote_frame(r1)]
+    assert len(want[1]) >= 60
+    nf._chk(nf._l.airfe_set_outlier_rejection(nf._h, 1), "airfe_set_outlier_rejection")
+    try:
+        got = [a.copy() for a in nf.promote_frame(r1)]
+    finally:
+        nf._l.airfe_set_outlier_rejection(nf._h, 0)
+    _same_bytes(got, want)
+    kept = [a.copy() for a in nf.track_frame(l2)]                                 # ref_feat=None: still frame 0's rows, as uploaded before the promotions
+    assert len(kept[1]) > 0                                                       # (the comparison below is not one of empty lists)
+    _same_bytes(kept, [a.copy() for a in nf.track_frame(l2, ref_feat=f0.T)])
+    kf.close(); nf.close()
+
+
+def test_a_rejected_promote_leaves_the_last_track_untouched():
+    """An airfe_promote_frame that is refused for its arguments (after an airfe_track_frame succeeded) changes nothing: the next valid promote returns the bytes
+    of one without the refused calls in between, and airfe_adopt_reference + airfe_track_frame still work on the tracked frame's rows."""
+    import ctypes as C
+    kf, nf = _contexts(2)
+    det, pm = api.FeatureDetector(nf), api.PointMatcher(nf, W, H, 0)
+    (l0, _), (l1, r1), (l2, _) = _frames(3, 40, 40)
+    ok, f0 = det.Detect(l0)
+    feat1 = nf.track_frame(l1, ref_feat=f0.T)[0].copy()
+    want = [a.copy() for a in nf.promote_frame(r1)]
+    cap = nf.np_rows
+    feat, idx, sc = np.empty((cap, api.FEAT), np.float32), np.empty((cap, 2), np.int32), np.empty((cap,), np.float32)
+    n, nm = C.c_int(0), C.c_int(0)
+    right = np.ascontiguousarray(r1)
+    for stride, fcap, text in ((W - 1, cap, "image stride smaller than its width"), (W, 8, "feature / match capacity < max_keypoints")):
+        rc = nf._l.airfe_promote_frame(nf._h, right.ctypes.data, H, W, stride, feat.ctypes.data, fcap, C.byref(n), idx.ctypes.data, sc.ctypes.data, cap, C.byref(nm))
+        assert rc != 0 and text in nf._l.airfe_last_error(nf._h).decode()
+    _same_bytes([a.copy() for a in nf.promote_frame(r1)], want)
+    nf.adopt_reference()
+    feat2, tidx, _ = nf.track_frame(l2)                                           # against frame 1's rows, adopted on the device
+    n2, m2 = pm.MatchingPoints(np.asfortranarray(feat1.T), np.asfortranarray(feat2.T))
+    assert n2 > 0
+    np.testing.assert_array_equal(tidx, np.array([(m[0], m[1]) for m in m2], np.int32))
+    kf.close(); nf.close()
+
+
 def test_sequence_against_the_oracle_chain():
     """>= 50 frames of one sequence (scenes of 14 frames) through SequenceFrontEnd against oracle/ref_seq.Chain FOLLOWING the device's schedule, frame by frame,
     under the gates the single-frame tests hold: keypoints <= 1 px (>= 99 % over the run), descriptors <= 1e-3 cosine, the oracle matcher fed with the device's own

@@ -1,5 +1,5 @@
-"""The PLNet line path's launch sequences are stated once (the steps in airslam_amd/csrc/airfe_lines.hip): the test hooks in airfe_debug.hip and airfe.hip
-call the steps production is composed of and hold no launcher call of their own, so a pin on a hook is a pin on production's arguments, buffers and order."""
+"""The PLNet line path's launch sequences are stated once (the steps in airslam_amd/csrc/airfe_lines.hip): the test hooks in airfe_debug.hip and the entries in
+airfe.hip, airfe_frame.hip and airfe_assoc.hip call the steps production is composed of and hold no launcher call of their own, so a pin on a hook is a pin on production's arguments, buffers and order."""
 import glob
 import os
 import re
@@ -17,7 +17,7 @@ def _calls(path):
 
 
 def test_hooks_hold_no_line_path_launch():
-    for src in ("airfe_debug.hip", "airfe.hip"):
+    for src in ("airfe_debug.hip", "airfe.hip", "airfe_frame.hip", "airfe_assoc.hip"):
         calls = _calls(os.path.join(CSRC, src))
         assert not any(calls.values()), (src, {n: k for n, k in calls.items() if k})
 
