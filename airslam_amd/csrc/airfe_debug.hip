@@ -1,13 +1,82 @@
-// airfe — the kernel-level test hooks of libairfe.so (include/airfe_debug.h): host tensors -> one production launcher -> host tensors.  Every device allocation
-// of a hook lives in a DbgTmp and is freed on every way out, an exception caught by AIRFE_CATCH included.
+// airfe — the kernel-level test hooks of libairfe.so (include/airfe_debug.h): host tensors -> one production launcher or line-path step -> host tensors.  Every hook has one
+// shape: argument checks, staging through a HookStage, the launches, the wait, read-backs through the HookStage.
 #include "airfe_host.h"
 
-struct DbgTmp {                                  // device allocations of one hook call, freed on every way out
-  airfe_ctx h;                                   // only as an allocation list holder (dalloc / dupload / make_linear)
-  DbgTmp() {}
-  explicit DbgTmp(int prec) { h.prec = h.pack_prec = prec; }      // the storage type make_linear packs for
-  ~DbgTmp() { for (void* p : h.allocs) (void)hipFree(p); }
+#include <memory>
+
+// One hook call's device work, bound to the context, the hook's name and the context's stream: every buffer the hook makes, every fill, upload and read-back, and the wait.
+//  * A device write made before the launches is complete when the call that made it returns (make_linear's blocking copies) or is queued on the stream the launches go to;
+//    nothing is queued on the null stream, which that (non-blocking) stream would not wait for, and nothing waits for it.
+//  * The host side of every queued copy is kept here until the holder dies.
+//  * After the first failure every later operation does nothing; the hook returns status().
+//  * The destructor waits for the stream when work was queued and not waited for, then frees: on every way out, an exception caught by AIRFE_CATCH included.
+struct HookStage {
+  enum { OWN_TEXT = 1, SATURATION = 2, DEVICE_WIDE = 4 };                  // wait(): "<hook>: kernel failed" for a failed wait or launch | saturation_status too | the whole device
+  HookStage(airfe_ctx* c_, const std::string& who_, int pack_prec = 0) : c(c_), who(who_), st(c_->stream) { mem.pack_prec = pack_prec; }
+  HookStage(const HookStage&) = delete;
+  ~HookStage() {
+    if (queued) (void)hipStreamSynchronize(st);
+    for (void* p : mem.allocs) (void)hipFree(p);
+  }
+  int status() const { return rc; }
+  hipStream_t stream() { queued = true; return st; }                       // for the hook's launches: whoever takes the stream queues on it
+  int refuse(const std::string& m) { return rc ? rc : rc = fail(c, who + ": " + m); }
+  void step(int r) { queued = true; if (r) rc = 1; }                       // a production step's own status (it has set the context's error)
+  template <class T> T* fresh(size_t n, int byte) {                        // a new buffer whose every byte is `byte` (0x00, or 0xFF: NaN in fp32, fp16 and bf16) when the launches start
+    T* p = raw<T>(n);
+    fill(p, byte, std::max<size_t>(n, 1) * sizeof(T));
+    return p;
+  }
+  template <class T> T* up(std::vector<T> v) { T* p = raw<T>(v.size()); put(p, std::move(v)); return p; }      // a new buffer holding v
+  template <class T> T* up(const T* src, size_t n) { return up(std::vector<T>(src, src + n)); }
+  bool linear(const float* W, const float* b, int K, int N, LinW& out) { if (!rc && !make_linear(&mem, W, b, K, N, out)) refuse("allocation failed"); return !rc; }
+  // the same two on memory the context owns (the arena and line-path buffers a hook stages into and restores)
+  void fill(void* p, int byte, size_t bytes) { if (!rc && bytes) hip(hipMemsetAsync(p, byte, bytes, stream()), "hipMemsetAsync"); }
+  template <class T> void put(void* dst, std::vector<T> v) {
+    auto h = std::make_shared<std::vector<T>>(std::move(v));
+    host.push_back(h);
+    if (!rc && !h->empty()) hip(hipMemcpyAsync(dst, h->data(), h->size() * sizeof(T), hipMemcpyHostToDevice, stream()), "hipMemcpyAsync");
+  }
+  void put(void* dst, const void* src, size_t bytes) { put2d(dst, bytes, src, bytes, bytes, 1); }
+  void put2d(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows) {      // the host rows are kept packed
+    std::vector<uint8_t> v(width * rows);
+    for (size_t r = 0; r < rows; ++r) memcpy(v.data() + r * width, static_cast<const uint8_t*>(src) + r * spitch, width);
+    if (rows == 1 || dpitch == width) return put(dst, std::move(v));
+    auto h = std::make_shared<std::vector<uint8_t>>(std::move(v));
+    host.push_back(h);
+    if (!rc && !h->empty()) hip(hipMemcpy2DAsync(dst, dpitch, h->data(), width, width, rows, hipMemcpyHostToDevice, stream()), "hipMemcpy2DAsync");
+  }
+  int wait(unsigned how = 0) {                                             // the stream idle, then launch_status, then (SATURATION) saturation_status
+    if (rc) return rc;
+    const hipError_t e = (how & DEVICE_WIDE) ? hipDeviceSynchronize() : hipStreamSynchronize(st);
+    queued = false;
+    if (how & OWN_TEXT) { if (e != hipSuccess || launch_status(c)) refuse("kernel failed"); }
+    else if (hip(e, (how & DEVICE_WIDE) ? "hipDeviceSynchronize" : "hipStreamSynchronize") && launch_status(c)) rc = 1;
+    if (!rc && (how & SATURATION) && saturation_status(c)) rc = 1;
+    return rc;
+  }
+  // read-backs, after the wait: blocking, checked
+  void get(void* dst, const void* src, size_t bytes) { if (!rc && bytes) hip(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost), "hipMemcpy"); }
+  template <class T> std::vector<T> get(const void* src, size_t n) { std::vector<T> v(n); get(v.data(), src, n * sizeof(T)); return v; }
+  void get2d(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows) {
+    if (!rc && width && rows) hip(hipMemcpy2D(dst, dpitch, src, spitch, width, rows, hipMemcpyDeviceToHost), "hipMemcpy2D");
+  }
+
+ private:
+  airfe_ctx* c; std::string who; hipStream_t st;
+  DevAllocs mem;                                                           // what dalloc / dupload / make_linear read of a context, owned here
+  std::vector<std::shared_ptr<void>> host;
+  int rc = 0; bool queued = false;
+  bool hip(hipError_t e, const char* call) { if (e != hipSuccess) refuse(std::string(call) + ": " + hipGetErrorString(e)); return e == hipSuccess; }
+  template <class T> T* raw(size_t n) {
+    void* p = nullptr;
+    if (rc) return nullptr;
+    if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) { refuse("allocation failed"); return nullptr; }
+    mem.allocs.push_back(p);
+    return static_cast<T*>(p);
+  }
 };
+struct DevSpan { void* p; size_t bytes; };                                 // for "every output 0xFF when the launch starts" / "zero again when the hook returns"
 
 // the conv hooks' staging: NCHW fp32 -> the arena's NHWC 2-byte layout with its zero border; [cout][cin][3][3] fp32 -> the packed slabs
 static std::vector<uint16_t> dbg_conv_x(const float* x, int B, int cin, int H, int W, int prec) {
@@ -26,6 +95,24 @@ static std::vector<uint16_t> dbg_conv_slabs(const float* w, int cin, int cout, i
     return w[((size_t)feat * cin + ci) * 9 + tap];
   });
 }
+// the GEMM family's staging: rows padded with zero rows to rows_cap
+static std::vector<uint16_t> dbg_rows2(const float* x, int rows, int cols, int rows_cap, int prec) {
+  std::vector<uint16_t> v((size_t)rows_cap * cols, 0);
+  if (x)
+    for (size_t i = 0; i < (size_t)rows * cols; ++i) v[i] = cvt2(x[i], prec);
+  return v;
+}
+static std::vector<float> dbg_rows4(const float* x, int rows, int cols, int rows_cap) {
+  std::vector<float> v((size_t)rows_cap * cols, 0.f);
+  if (x) memcpy(v.data(), x, (size_t)rows * cols * sizeof(float));
+  return v;
+}
+static void dbg_back2(const std::vector<uint16_t>& v, size_t n, int prec, float* out) {
+  for (size_t i = 0; i < n; ++i) out[i] = back2(v[i], prec);
+}
+static void dbg_gemm_dispatch(const airfe_ctx* c, GemmArgs& g, int gr_wgs) {      // the context's dispatch thresholds, as run_linear hands them on
+  g.small_max = c->gemm_small_max; g.g8_min = c->gemm8_min; g.gr_min = c->gemmr_min; g.gr_wgs = gr_wgs > 0 ? gr_wgs : c->gemmr_wgs;
+}
 
 extern "C" {
 
@@ -34,12 +121,14 @@ int airfe_debug_preprocess(airfe_ctx* c, const uint8_t* gray, int h, int w, int 
   if (c && enter_device(c)) return 1;
   if (!c || !c->has_sp) return fail(c, "debug_preprocess: detector not loaded");
   const size_t bytes = (size_t)h * stride;
-  if (upload_image(c, gray, h, w, stride) || ensure_tables(c, h, w)) return 1;
   const int R = AIRFE_INTERNAL_SIZE;
-  launch_preprocess(c->st_img.p, 1, h, w, stride, bytes, c->xtab, c->ytab, c->lut, c->img32, R, R, c->stream);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy2D(out, (size_t)R * 4, c->img32 + (R + 2) + 1, (size_t)(R + 2) * 4, (size_t)R * 4, R, hipMemcpyDeviceToHost));
-  return 0;
+  HookStage s(c, "debug_preprocess");
+  s.step(upload_image(c, gray, h, w, stride) || ensure_tables(c, h, w));
+  if (s.status()) return 1;
+  launch_preprocess(c->st_img.p, 1, h, w, stride, bytes, c->xtab, c->ytab, c->lut, c->img32, R, R, s.stream());
+  s.wait();
+  s.get2d(out, (size_t)R * 4, c->img32 + (R + 2) + 1, (size_t)(R + 2) * 4, (size_t)R * 4, R);
+  return s.status();
 } AIRFE_CATCH(c)
 
 int airfe_debug_conv3x3(airfe_ctx* c, const float* x, int B, int cin, int H, int W, const float* w, const float* b, int cout,
@@ -49,25 +138,22 @@ int airfe_debug_conv3x3(airfe_ctx* c, const float* x, int B, int cin, int H, int
   const int prec = c->prec;
   const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
   const size_t ywords = (size_t)B * (Ho + 2) * (Wo + 2) * cout;
-  DbgTmp t(prec);
-  airfe_ctx& tmp = t.h;
+  HookStage s(c, "debug_conv3x3");
   ConvArgs a;
-  a.X = dupload(&tmp, dbg_conv_x(x, B, cin, H, W, prec)); a.Wp = dupload(&tmp, dbg_conv_slabs(w, cin, cout, prec));
-  a.bias = dupload(&tmp, std::vector<float>(b, b + cout)); a.Y = dalloc<uint16_t>(&tmp, ywords);
-  if (!a.X || !a.Wp || !a.bias || !a.Y) return fail(c, "debug_conv3x3: allocation failed");
+  a.X = s.up(dbg_conv_x(x, B, cin, H, W, prec)); a.Wp = s.up(dbg_conv_slabs(w, cin, cout, prec));
+  a.bias = s.up(b, (size_t)cout); a.Y = s.fresh<uint16_t>(ywords, 0);
   a.B = B; a.H = H; a.W = W; a.CIN = cin; a.COUT = cout;
   a.pool = pool; a.out_pad = 1; a.relu = 1;
-  (void)hipStreamSynchronize(nullptr);       // dalloc's zero fill of Y runs on the null stream, which the context's stream does not wait for (see dbg_canary)
-  launch_conv3x3(prec, a, c->stream);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  std::vector<uint16_t> yo(ywords);
-  HIPCHK(c, hipMemcpy(yo.data(), a.Y, ywords * 2, hipMemcpyDeviceToHost));
+  if (s.status()) return 1;
+  launch_conv3x3(prec, a, s.stream());
+  s.wait();
+  const std::vector<uint16_t> yo = s.get<uint16_t>(a.Y, ywords);
   for (int bb = 0; bb < B; ++bb)
     for (int co = 0; co < cout; ++co)
       for (int yy = 0; yy < Ho; ++yy)
         for (int xx = 0; xx < Wo; ++xx)
           y[(((size_t)bb * cout + co) * Ho + yy) * Wo + xx] = back2(yo[(((size_t)bb * (Ho + 2) + yy + 1) * (Wo + 2) + xx + 1) * cout + co], prec);
-  return 0;
+  return s.status();
 } AIRFE_CATCH(c)
 
 int airfe_debug_fail_next_launch(airfe_ctx* c, int stage) try {
@@ -81,65 +167,23 @@ int airfe_debug_gemm(airfe_ctx* c, const float* x, int M, int K, const float* w,
   AIRFE_ENTER(c);
   if (K != 128 && K != 256 && K != 512) return fail(c, "debug_gemm: K must be 128, 256 or 512");
   const int prec = c->prec, Mp = (M + 127) / 128 * 128, Np8 = (N + 7) / 8 * 8;
-  std::vector<uint16_t> xin((size_t)Mp * K, 0);
-  for (size_t i = 0; i < (size_t)M * K; ++i) xin[i] = cvt2(x[i], prec);
-  DbgTmp t(prec);
-  airfe_ctx& tmp = t.h;
+  HookStage s(c, "debug_gemm", prec);
   LinW lw;
-  if (!make_linear(&tmp, w, b, K, N, lw)) return fail(c, "debug_gemm: allocation failed");
-  uint16_t* dx = dupload(&tmp, xin);
-  float* dy = dalloc<float>(&tmp, (size_t)Mp * Np8);
-  int rc = 0;
-  if (!dx || !dy) rc = fail(c, "debug_gemm: allocation failed");
-  if (!rc) {
-    GemmArgs g;
-    g.X1 = dx; g.ld1 = K; g.K1 = K; g.Wp = lw.w; g.bias = lw.b; g.M = Mp; g.N = N; g.cb_total = lw.cbt;
-    g.epi = EPI_STORE_F32; g.act = relu ? ACT_RELU : ACT_NONE; g.out = dy; g.ldo = Np8;
-    g.small_max = c->gemm_small_max; g.g8_min = c->gemm8_min; g.gr_min = c->gemmr_min; g.gr_wgs = c->gemmr_wgs;
-    (void)hipStreamSynchronize(nullptr);     // dy's zero fill (dalloc) must not land on top of the kernel's rows (see dbg_canary; seen once as zero rows in test_gemm)
-    launch_gemm(prec, K, false, g, c->stream);
-    if (hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, "debug_gemm: kernel failed");
-  }
-  if (!rc) {
-    std::vector<float> yo((size_t)Mp * Np8);
-    (void)hipMemcpy(yo.data(), dy, yo.size() * 4, hipMemcpyDeviceToHost);
-    for (int m = 0; m < M; ++m)
-      for (int n = 0; n < N; ++n) y[(size_t)m * N + n] = yo[(size_t)m * Np8 + n];
-  }
-  return rc;
+  s.linear(w, b, K, N, lw);
+  GemmArgs g;
+  g.X1 = s.up(dbg_rows2(x, M, K, Mp, prec)); g.ld1 = K; g.K1 = K; g.Wp = lw.w; g.bias = lw.b; g.M = Mp; g.N = N; g.cb_total = lw.cbt;
+  g.epi = EPI_STORE_F32; g.act = relu ? ACT_RELU : ACT_NONE; g.out = s.fresh<float>((size_t)Mp * Np8, 0); g.ldo = Np8;
+  dbg_gemm_dispatch(c, g, 0);
+  if (s.status()) return 1;
+  launch_gemm(prec, K, false, g, s.stream());
+  s.wait(HookStage::OWN_TEXT);
+  const std::vector<float> yo = s.get<float>(g.out, (size_t)Mp * Np8);
+  for (int m = 0; m < M; ++m)
+    for (int n = 0; n < N; ++n) y[(size_t)m * N + n] = yo[(size_t)m * Np8 + n];
+  return s.status();
 } AIRFE_CATCH(c)
 
-}  // extern "C"
-
 // ---- the GEMM family one form at a time (include/airfe_debug.h): host tensors -> the production launchers -> host tensors
-static std::vector<uint16_t> dbg_rows2(const float* x, int rows, int cols, int rows_cap, int prec) {
-  std::vector<uint16_t> v((size_t)rows_cap * cols, 0);
-  if (x)
-    for (size_t i = 0; i < (size_t)rows * cols; ++i) v[i] = cvt2(x[i], prec);
-  return v;
-}
-static std::vector<float> dbg_rows4(const float* x, int rows, int cols, int rows_cap) {
-  std::vector<float> v((size_t)rows_cap * cols, 0.f);
-  if (x) memcpy(v.data(), x, (size_t)rows * cols * sizeof(float));
-  return v;
-}
-template <class T>
-static T* dbg_canary(airfe_ctx* tmp, size_t n) {       // an output buffer whose every byte starts as 0xFF (NaN in fp32, fp16 and bf16)
-  T* p = dalloc<T>(tmp, n, false);
-  if (p) {
-    (void)hipMemset(p, 0xFF, std::max<size_t>(n, 1) * sizeof(T));
-    // the fill of device memory runs on the null stream and may return before it is done; the hooks launch on the context's NON-BLOCKING stream, which does not
-    // wait for it: without this wait the fill could land on top of a fast kernel's rows (seen once as NaN rows in tests/test_gpu_linear_kernels.py)
-    (void)hipStreamSynchronize(nullptr);
-  }
-  return p;
-}
-static void dbg_back2(const std::vector<uint16_t>& v, size_t n, int prec, float* out) {
-  for (size_t i = 0; i < n; ++i) out[i] = back2(v[i], prec);
-}
-
-extern "C" {
-
 int airfe_debug_conv(airfe_ctx* c, airfe_debug_conv_args* a) try {
   AIRFE_ENTER(c);
   if (!a || !a->w || !a->b || !a->y_raw) return fail(c, "debug_conv: null argument");
@@ -158,30 +202,29 @@ int airfe_debug_conv(airfe_ctx* c, airfe_debug_conv_args* a) try {
   const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
   const size_t guard = (size_t)(Wo + 2 * opad) * cout, words = (size_t)B * (Ho + 2 * opad) * guard, total = words + 2 * guard;
   if (a->y_words != total) return fail(c, "debug_conv: y_words must be (B (Ho + 2 out_pad) + 2) (Wo + 2 out_pad) cout");
-  DbgTmp t(prec);
-  airfe_ctx& tmp = t.h;
+  HookStage s(c, "debug_conv");
   ConvArgs g;
   if (fused) {
     std::vector<float> im((size_t)B * (H + 2) * (W + 2), 0.f);
     for (int bb = 0; bb < B; ++bb)
       for (int yy = 0; yy < H; ++yy) memcpy(&im[((size_t)bb * (H + 2) + yy + 1) * (W + 2) + 1], a->img + ((size_t)bb * H + yy) * W, (size_t)W * sizeof(float));
-    g.img = dupload(&tmp, im);
-    g.w1a = dupload(&tmp, std::vector<float>(a->w1a, a->w1a + 64 * 9));
-    g.b1a = dupload(&tmp, std::vector<float>(a->b1a, a->b1a + 64));
+    g.img = s.up(std::move(im));
+    g.w1a = s.up(a->w1a, (size_t)64 * 9);
+    g.b1a = s.up(a->b1a, (size_t)64);
   } else {
-    g.X = dupload(&tmp, dbg_conv_x(a->x, B, cin, H, W, prec));
+    g.X = s.up(dbg_conv_x(a->x, B, cin, H, W, prec));
   }
-  g.Wp = dupload(&tmp, dbg_conv_slabs(a->w, cin, cout, prec));
-  g.bias = dupload(&tmp, std::vector<float>(a->b, a->b + cout));
-  uint16_t* dy = dbg_canary<uint16_t>(&tmp, total);
-  if ((fused ? !g.img || !g.w1a || !g.b1a : !g.X) || !g.Wp || !g.bias || !dy) return fail(c, "debug_conv: allocation failed");
+  g.Wp = s.up(dbg_conv_slabs(a->w, cin, cout, prec));
+  g.bias = s.up(a->b, (size_t)cout);
+  uint16_t* dy = s.fresh<uint16_t>(total, 0xFF);
+  if (s.status()) return 1;
   g.Y = dy + guard;
   g.B = B; g.H = H; g.W = W; g.CIN = cin; g.COUT = cout; g.pool = pool; g.out_pad = opad; g.relu = a->relu; g.wgs = a->wgs;
-  if (fused) launch_conv64r(prec, g, c->stream);         // as detect_dev2 launches the first layer
-  else launch_conv3x3(prec, g, c->stream);               // production's dispatch: conv64r / conv128r, or conv3x3_kernel for relu = 0
-  if (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c)) return fail(c, "debug_conv: kernel failed");
-  HIPCHK(c, hipMemcpy(a->y_raw, dy, total * 2, hipMemcpyDeviceToHost));
-  return 0;
+  if (fused) launch_conv64r(prec, g, s.stream());        // as detect_dev2 launches the first layer
+  else launch_conv3x3(prec, g, s.stream());              // production's dispatch: conv64r / conv128r, or conv3x3_kernel for relu = 0
+  s.wait(HookStage::OWN_TEXT);
+  s.get(a->y_raw, dy, total * 2);
+  return s.status();
 } AIRFE_CATCH(c)
 
 int airfe_debug_linear(airfe_ctx* c, const airfe_debug_linear_args* a) try {
@@ -211,89 +254,73 @@ int airfe_debug_linear(airfe_ctx* c, const airfe_debug_linear_args* a) try {
   const int xrows = a->rowidx ? a->src_rows : Mp;
   const int ldo = (epi == EPI_STORE || epi == EPI_STORE_F32) ? (N + 7) / 8 * 8 : N;
   const int Sg = heads ? (Mp + a->Np - 1) / a->Np : 0, S = heads ? M / a->Np : 0;
-  DbgTmp t(prec);
-  airfe_ctx& tmp = t.h;
+  const bool f32 = epi == EPI_STORE_F32 || d2s, two = epi == EPI_HEADS && N == 512;
+  const size_t out_elems = d2s ? (size_t)M * 64 : heads ? (size_t)Sg * 4 * a->Np * 64 : (size_t)Mp * ldo, out_bytes = out_elems * (f32 ? 4 : 2);
+  HookStage s(c, "debug_linear", prec);
   LinW lw;
-  if (!make_linear(&tmp, a->w, a->b, K, N, lw)) return fail(c, "debug_linear: allocation failed");
+  s.linear(a->w, a->b, K, N, lw);
   GemmArgs g;
-  g.X1 = dupload(&tmp, dbg_rows2(a->x1, a->rowidx ? a->src_rows : M, K1, xrows, prec)); g.ld1 = K1; g.K1 = K1;
-  if (a->x2) { g.X2 = dupload(&tmp, dbg_rows2(a->x2, M, K - K1, Mp, prec)); g.ld2 = K - K1; }
+  g.X1 = s.up(dbg_rows2(a->x1, a->rowidx ? a->src_rows : M, K1, xrows, prec)); g.ld1 = K1; g.K1 = K1;
+  if (a->x2) { g.X2 = s.up(dbg_rows2(a->x2, M, K - K1, Mp, prec)); g.ld2 = K - K1; }
   g.Wp = lw.w; g.bias = lw.b; g.M = Mp; g.N = N; g.cb_total = lw.cbt; g.epi = epi; g.act = a->act; g.ldo = ldo; g.Np = a->Np; g.H = 4;
-  g.small_max = c->gemm_small_max; g.g8_min = c->gemm8_min; g.gr_min = c->gemmr_min; g.gr_wgs = a->gr_wgs > 0 ? a->gr_wgs : c->gemmr_wgs;
-  if (a->rot_cos) { g.rot_cos = dupload(&tmp, dbg_rows4(a->rot_cos, M, 32, Mp)); g.rot_sin = dupload(&tmp, dbg_rows4(a->rot_sin, M, 32, Mp)); }
-  if (a->rowidx) { std::vector<int> ri(Mp, 0); memcpy(ri.data(), a->rowidx, (size_t)M * sizeof(int)); g.rowidx = dupload(&tmp, ri); }
-  size_t out_elems = 0;
-  if (epi == EPI_STORE || epi == EPI_RESID) out_elems = (size_t)Mp * ldo;
-  else if (heads) out_elems = (size_t)Sg * 4 * a->Np * 64;
-  if (epi == EPI_STORE_F32) g.out = dbg_canary<float>(&tmp, (size_t)Mp * ldo);
-  else if (d2s) g.out = dbg_canary<float>(&tmp, (size_t)M * 64);
-  else g.out = dbg_canary<uint16_t>(&tmp, out_elems);
-  if (epi == EPI_HEADS && N == 512) g.out2 = dbg_canary<uint16_t>(&tmp, out_elems);
-  if (epi == EPI_RESID) g.x32 = dupload(&tmp, dbg_rows4(a->x32, M, N, Mp));
-  if (d2s) { g.d2s_hc = a->d2s_hc; g.d2s_wc = a->d2s_wc; g.flag = dalloc<int>(&tmp, 1); }
-  bool ok = g.X1 && (!a->x2 || g.X2) && g.out && (!(epi == EPI_HEADS && N == 512) || g.out2) && (epi != EPI_RESID || g.x32) && (!a->rot_cos || (g.rot_cos && g.rot_sin)) &&
-            (!a->rowidx || g.rowidx) && (!d2s || g.flag);
-  int rc = ok ? 0 : fail(c, "debug_linear: allocation failed");
+  dbg_gemm_dispatch(c, g, a->gr_wgs);
+  if (a->rot_cos) { g.rot_cos = s.up(dbg_rows4(a->rot_cos, M, 32, Mp)); g.rot_sin = s.up(dbg_rows4(a->rot_sin, M, 32, Mp)); }
+  if (a->rowidx) { std::vector<int> ri(Mp, 0); memcpy(ri.data(), a->rowidx, (size_t)M * sizeof(int)); g.rowidx = s.up(std::move(ri)); }
+  g.out = s.fresh<uint8_t>(out_bytes, 0xFF);
+  if (two) g.out2 = s.fresh<uint8_t>(out_bytes, 0xFF);
+  if (epi == EPI_RESID) g.x32 = s.up(dbg_rows4(a->x32, M, N, Mp));
+  if (d2s) { g.d2s_hc = a->d2s_hc; g.d2s_wc = a->d2s_wc; g.flag = s.fresh<int>(1, 0); }
+  if (s.status()) return 1;
   // a forced kernel runs only where its own applicability test says yes: never a silent fall-back to another kernel
   const char* refused = nullptr;
-  if (!rc) switch (kern) {
+  hipStream_t st = s.stream();
+  switch (kern) {
     case AIRFE_DEBUG_KERNEL_DISPATCH:
-      if (d2s) launch_gemm8(prec, K, false, g, c->stream);
-      else launch_gemm(prec, K, trans, g, c->stream);
+      if (d2s) launch_gemm8(prec, K, false, g, st);
+      else launch_gemm(prec, K, trans, g, st);
       break;
     case AIRFE_DEBUG_KERNEL_SMALL:                       // launch_gemm's own row test with every other path moved out of reach
       if (d2s || a->rowidx) refused = "gemm_small";
-      else { g.small_max = 1 << 30; g.g8_min = 1 << 30; g.gr_min = 1 << 30; launch_gemm(prec, K, trans, g, c->stream); }
+      else { g.small_max = 1 << 30; g.g8_min = 1 << 30; g.gr_min = 1 << 30; launch_gemm(prec, K, trans, g, st); }
       break;
     case AIRFE_DEBUG_KERNEL_TILED:
       if (d2s || a->rowidx || K1 % 64) refused = "gemm_kernel";
-      else { g.small_max = -1; g.g8_min = 1 << 30; g.gr_min = 1 << 30; launch_gemm(prec, K, trans, g, c->stream); }
+      else { g.small_max = -1; g.g8_min = 1 << 30; g.gr_min = 1 << 30; launch_gemm(prec, K, trans, g, st); }
       break;
     case AIRFE_DEBUG_KERNEL_GEMM8:
       if (K1 % 64) refused = "gemm8";
-      else launch_gemm8(prec, K, trans, g, c->stream);
+      else launch_gemm8(prec, K, trans, g, st);
       break;
     case AIRFE_DEBUG_KERNEL_GEMMR:
       if (a->rowidx || !gemmr_applicable(K, trans, g)) refused = "gemmr";
-      else launch_gemmr(prec, trans, g, c->stream);
+      else launch_gemmr(prec, trans, g, st);
       break;
     case AIRFE_DEBUG_KERNEL_GEMMR_GATHER:
       if (!gemmr_gather_applicable(K, g)) refused = "gemmr_gather";
-      else launch_gemmr_gather(prec, g, c->stream);
+      else launch_gemmr_gather(prec, g, st);
       break;
     default:
       if (!gemmr_gather128_applicable(g)) refused = "gemmr_gather128";
-      else launch_gemmr_gather128(prec, g, c->stream);
+      else launch_gemmr_gather128(prec, g, st);
       break;
   }
-  if (refused) rc = fail(c, std::string("debug_linear: ") + refused + " does not apply to this form");
-  if (!rc && (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c))) rc = fail(c, "debug_linear: kernel failed");
-  if (!rc) {
-    if (epi == EPI_STORE_F32 || d2s) {
-      std::vector<float> ho(d2s ? (size_t)M * 64 : (size_t)Mp * ldo);
-      (void)hipMemcpy(ho.data(), g.out, ho.size() * 4, hipMemcpyDeviceToHost);
-      if (d2s) memcpy(a->out, ho.data(), ho.size() * 4);
-      else
-        for (int m = 0; m < M; ++m) memcpy(a->out + (size_t)m * N, ho.data() + (size_t)m * ldo, (size_t)N * 4);
-      if (d2s && a->flag) (void)hipMemcpy(a->flag, g.flag, sizeof(int), hipMemcpyDeviceToHost);
-    } else if (heads) {
-      std::vector<uint16_t> ho(out_elems);
-      const size_t n = (size_t)S * 4 * a->Np * 64;
-      (void)hipMemcpy(ho.data(), g.out, ho.size() * 2, hipMemcpyDeviceToHost);
-      dbg_back2(ho, n, prec, a->out);
-      if (g.out2) {
-        (void)hipMemcpy(ho.data(), g.out2, ho.size() * 2, hipMemcpyDeviceToHost);
-        dbg_back2(ho, n, prec, a->out2);
-      }
-    } else {
-      std::vector<uint16_t> ho(out_elems);
-      (void)hipMemcpy(ho.data(), g.out, ho.size() * 2, hipMemcpyDeviceToHost);
-      for (int m = 0; m < M; ++m)
-        for (int n = 0; n < N; ++n) a->out[(size_t)m * N + n] = back2(ho[(size_t)m * ldo + n], prec);
-      if (epi == EPI_RESID) (void)hipMemcpy(a->x32, g.x32, (size_t)M * N * 4, hipMemcpyDeviceToHost);
-    }
+  if (refused) return s.refuse(std::string(refused) + " does not apply to this form");
+  s.wait(HookStage::OWN_TEXT);
+  if (f32) {
+    const std::vector<float> ho = s.get<float>(g.out, out_elems);
+    for (int m = 0; m < (d2s ? 1 : M); ++m) memcpy(a->out + (size_t)m * N, ho.data() + (size_t)m * ldo, (d2s ? out_elems : (size_t)N) * 4);
+    if (d2s && a->flag) s.get(a->flag, g.flag, sizeof(int));
+  } else if (heads) {
+    const size_t n = (size_t)S * 4 * a->Np * 64;
+    dbg_back2(s.get<uint16_t>(g.out, out_elems), n, prec, a->out);
+    if (two) dbg_back2(s.get<uint16_t>(g.out2, out_elems), n, prec, a->out2);
+  } else {
+    const std::vector<uint16_t> ho = s.get<uint16_t>(g.out, out_elems);
+    for (int m = 0; m < M; ++m)
+      for (int n = 0; n < N; ++n) a->out[(size_t)m * N + n] = back2(ho[(size_t)m * ldo + n], prec);
+    if (epi == EPI_RESID) s.get(a->x32, g.x32, (size_t)M * N * 4);
   }
-  return rc;
+  return s.status();
 } AIRFE_CATCH(c)
 
 int airfe_debug_qkv(airfe_ctx* c, int prec, int M, int Np, const float* x, const float* wqk, const float* bqk, int nqk, const float* wv, const float* bv,
@@ -304,45 +331,34 @@ int airfe_debug_qkv(airfe_ctx* c, int prec, int M, int Np, const float* x, const
     return fail(c, "debug_qkv: bad argument");
   const int Mp = (M + 127) / 128 * 128, Sg = (Mp + Np - 1) / Np, S = M / Np;
   const size_t elems = (size_t)Sg * 4 * Np * 64, n = (size_t)S * 4 * Np * 64;
-  DbgTmp t(prec);
-  airfe_ctx& tmp = t.h;
+  HookStage s(c, "debug_qkv", prec);
   LinW lqk, lv;
-  const bool packed = make_linear(&tmp, wqk, bqk, 256, nqk, lqk) && make_linear(&tmp, wv, bv, 256, 256, lv);
+  s.linear(wqk, bqk, 256, nqk, lqk);
+  s.linear(wv, bv, 256, 256, lv);
   GemmArgs ga, gb;
-  const uint16_t* dx = dupload(&tmp, dbg_rows2(x, M, 256, Mp, prec));
-  ga.X1 = gb.X1 = dx; ga.ld1 = gb.ld1 = 256; ga.K1 = gb.K1 = 256; ga.M = gb.M = Mp; ga.Np = gb.Np = Np; ga.H = gb.H = 4;
+  ga.X1 = gb.X1 = s.up(dbg_rows2(x, M, 256, Mp, prec));
+  ga.ld1 = gb.ld1 = 256; ga.K1 = gb.K1 = 256; ga.M = gb.M = Mp; ga.Np = gb.Np = Np; ga.H = gb.H = 4;
   ga.Wp = lqk.w; ga.bias = lqk.b; ga.N = nqk; ga.cb_total = lqk.cbt; ga.epi = EPI_HEADS; ga.ldo = nqk;
   gb.Wp = lv.w; gb.bias = lv.b; gb.N = 256; gb.cb_total = lv.cbt; gb.epi = EPI_HEADS_T; gb.ldo = 256;
-  ga.out = dbg_canary<uint16_t>(&tmp, elems);
-  if (nqk == 512) ga.out2 = dbg_canary<uint16_t>(&tmp, elems);
-  gb.out = dbg_canary<uint16_t>(&tmp, elems);
-  if (rot_cos) { ga.rot_cos = dupload(&tmp, dbg_rows4(rot_cos, M, 32, Mp)); ga.rot_sin = dupload(&tmp, dbg_rows4(rot_sin, M, 32, Mp)); }
-  for (GemmArgs* g : {&ga, &gb}) {
-    g->small_max = c->gemm_small_max; g->g8_min = c->gemm8_min; g->gr_min = c->gemmr_min; g->gr_wgs = gr_wgs > 0 ? gr_wgs : c->gemmr_wgs;
+  ga.out = s.fresh<uint16_t>(elems, 0xFF);
+  if (nqk == 512) ga.out2 = s.fresh<uint16_t>(elems, 0xFF);
+  gb.out = s.fresh<uint16_t>(elems, 0xFF);
+  if (rot_cos) { ga.rot_cos = s.up(dbg_rows4(rot_cos, M, 32, Mp)); ga.rot_sin = s.up(dbg_rows4(rot_sin, M, 32, Mp)); }
+  dbg_gemm_dispatch(c, ga, gr_wgs);
+  dbg_gemm_dispatch(c, gb, gr_wgs);
+  if (s.status()) return 1;
+  if (pair) {
+    if (!gemmr_pair_applicable(ga, gb)) return s.refuse("gemmr_pair does not apply to this form");
+    launch_gemmr_pair(prec, ga, gb, s.stream());
+  } else {
+    launch_gemm(prec, 256, false, ga, s.stream());
+    launch_gemm(prec, 256, true, gb, s.stream());
   }
-  int rc = (packed && dx && ga.out && gb.out && (nqk != 512 || ga.out2) && (!rot_cos || (ga.rot_cos && ga.rot_sin))) ? 0 : fail(c, "debug_qkv: allocation failed");
-  if (!rc) {
-    if (pair) {
-      if (!gemmr_pair_applicable(ga, gb)) rc = fail(c, "debug_qkv: gemmr_pair does not apply to this form");
-      else launch_gemmr_pair(prec, ga, gb, c->stream);
-    } else {
-      launch_gemm(prec, 256, false, ga, c->stream);
-      launch_gemm(prec, 256, true, gb, c->stream);
-    }
-  }
-  if (!rc && (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c))) rc = fail(c, "debug_qkv: kernel failed");
-  if (!rc) {
-    std::vector<uint16_t> ho(elems);
-    (void)hipMemcpy(ho.data(), ga.out, elems * 2, hipMemcpyDeviceToHost);
-    dbg_back2(ho, n, prec, q);
-    if (nqk == 512) {
-      (void)hipMemcpy(ho.data(), ga.out2, elems * 2, hipMemcpyDeviceToHost);
-      dbg_back2(ho, n, prec, k);
-    }
-    (void)hipMemcpy(ho.data(), gb.out, elems * 2, hipMemcpyDeviceToHost);
-    dbg_back2(ho, n, prec, vt);
-  }
-  return rc;
+  s.wait(HookStage::OWN_TEXT);
+  dbg_back2(s.get<uint16_t>(ga.out, elems), n, prec, q);
+  if (nqk == 512) dbg_back2(s.get<uint16_t>(ga.out2, elems), n, prec, k);
+  dbg_back2(s.get<uint16_t>(gb.out, elems), n, prec, vt);
+  return s.status();
 } AIRFE_CATCH(c)
 
 int airfe_debug_lg_block(airfe_ctx* c, airfe_debug_lg_block_args* a) try {
@@ -362,95 +378,79 @@ int airfe_debug_lg_block(airfe_ctx* c, airfe_debug_lg_block_args* a) try {
   const int cap = M + 256;                               // every pass form stays below M + 127 rows
   const int Sg = nq ? (cap + Np - 1) / Np : 0, S = nq ? M / Np : 0;
   const size_t helems = (size_t)Sg * 4 * Np * 64;
-  DbgTmp t(prec);
-  airfe_ctx& tmp = t.h;
+  HookStage s(c, "debug_lg_block", prec);
   LinW lo, l1, l2, lq, lv;
-  bool ok = (!a->wo || make_linear(&tmp, a->wo, a->bo, 256, 256, lo)) && make_linear(&tmp, a->w1, a->b1, 512, 512, l1) && make_linear(&tmp, a->w2, a->b2, 512, 256, l2) &&
-            (!nq || (make_linear(&tmp, a->nqk_w, a->nqk_b, 256, nq, lq) && make_linear(&tmp, a->nv_w, a->nv_b, 256, 256, lv)));
+  if (a->wo) s.linear(a->wo, a->bo, 256, 256, lo);
+  s.linear(a->w1, a->b1, 512, 512, l1);
+  s.linear(a->w2, a->b2, 512, 256, l2);
+  if (nq) { s.linear(a->nqk_w, a->nqk_b, 256, nq, lq); s.linear(a->nv_w, a->nv_b, 256, 256, lv); }
   const bool fr = lg_blockf_frag_weights();
-  std::vector<float> x32h = dbg_rows4(a->x32, M, 256, cap);
+  const std::vector<float> x32h = dbg_rows4(a->x32, M, 256, cap);
   std::vector<uint16_t> xbh((size_t)cap * 256);
   for (size_t i = 0; i < xbh.size(); ++i) xbh[i] = cvt2(x32h[i], prec);
   std::vector<float> gb(1024, 0.f);
   if (!a->relu) { memcpy(gb.data(), a->gamma, 512 * 4); memcpy(gb.data() + 512, a->beta, 512 * 4); }
   LgBlockFArgs g;
-  g.attn = dupload(&tmp, dbg_rows2(a->attn, M, 256, cap, prec));
-  g.xb = dupload(&tmp, xbh);
-  g.x32 = dupload(&tmp, x32h);
-  const float* dgb = dupload(&tmp, gb);
+  g.attn = s.up(dbg_rows2(a->attn, M, 256, cap, prec));
+  g.xb = s.up(xbh);
+  g.x32 = s.up(x32h);
+  const float* dgb = s.up(std::move(gb));
+  g.gamma = dgb; g.beta = dgb ? dgb + 512 : nullptr;
   g.wo = a->wo ? (fr ? lo.wf : lo.w) : nullptr; g.bo = a->wo ? lo.b : nullptr;
   g.w1 = fr ? l1.wf : l1.w; g.b1 = l1.b; g.w2 = fr ? l2.wf : l2.w; g.b2 = l2.b;
-  g.gamma = dgb; g.beta = dgb ? dgb + 512 : nullptr;
   g.M = M; g.tokens_per_wg = T; g.mixed = a->mixed; g.n_cu = c->n_cu; g.relu = a->relu;
   if (nq) {
     g.nqk_w = fr ? lq.wf : lq.w; g.nqk_b = lq.b; g.nqk_n = nq; g.nv_w = fr ? lv.wf : lv.w; g.nv_b = lv.b; g.Np = Np; g.H = 4;
-    if (nq == 512) { g.rot_cos = dupload(&tmp, dbg_rows4(a->rot_cos, M, 32, cap)); g.rot_sin = dupload(&tmp, dbg_rows4(a->rot_sin, M, 32, cap)); }
-    g.q_out = dbg_canary<uint16_t>(&tmp, helems);
-    if (nq == 512) g.k_out = dbg_canary<uint16_t>(&tmp, helems);
-    g.vt_out = dbg_canary<uint16_t>(&tmp, helems);
+    if (nq == 512) { g.rot_cos = s.up(dbg_rows4(a->rot_cos, M, 32, cap)); g.rot_sin = s.up(dbg_rows4(a->rot_sin, M, 32, cap)); }
+    g.q_out = s.fresh<uint16_t>(helems, 0xFF);
+    if (nq == 512) g.k_out = s.fresh<uint16_t>(helems, 0xFF);
+    g.vt_out = s.fresh<uint16_t>(helems, 0xFF);
   }
-  ok = ok && g.attn && g.xb && g.x32 && dgb && (!nq || (g.q_out && g.vt_out && (nq != 512 || (g.k_out && g.rot_cos && g.rot_sin))));
-  int rc = ok ? 0 : fail(c, "debug_lg_block: allocation failed");
-  if (!rc) {
-    launch_lg_blockf(prec, g, c->stream);
-    if (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c)) rc = fail(c, "debug_lg_block: kernel failed");
-  }
-  if (!rc) {
-    // rows past M that the launch changed: x32 / xb against their initial (zero) rows, q / k / v^T against the 0xFFFF fill
-    std::vector<float> x32o((size_t)cap * 256);
-    std::vector<uint16_t> xbo((size_t)cap * 256);
-    (void)hipMemcpy(x32o.data(), g.x32, x32o.size() * 4, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(xbo.data(), g.xb, xbo.size() * 2, hipMemcpyDeviceToHost);
-    memcpy(a->x32, x32o.data(), (size_t)M * 256 * 4);
-    dbg_back2(xbo, (size_t)M * 256, prec, a->xb);
-    for (int i = 0; i < 5; ++i) a->rows_past[i] = 0;
-    for (int r = M; r < cap; ++r)
-      for (int f = 0; f < 256; ++f) {
-        const size_t e = (size_t)r * 256 + f;
-        if (memcmp(&x32o[e], &x32h[e], 4)) a->rows_past[0] = r - M + 1;
-        if (xbo[e] != xbh[e]) a->rows_past[1] = r - M + 1;
-      }
-    if (nq) {
-      uint16_t* dev[3] = {g.q_out, g.k_out, g.vt_out};
-      float* host[3] = {a->q, a->k, a->vt};
-      std::vector<uint16_t> ho(helems);
-      for (int j = 0; j < 3; ++j) {
-        if (!dev[j]) continue;
-        (void)hipMemcpy(ho.data(), dev[j], helems * 2, hipMemcpyDeviceToHost);
-        dbg_back2(ho, (size_t)S * 4 * Np * 64, prec, host[j]);
-        for (size_t e = (size_t)S * 4 * Np * 64; e < helems; ++e) {
-          if (ho[e] == 0xFFFF) continue;
-          const size_t s = e / ((size_t)4 * Np * 64), w = e % ((size_t)Np * 64);
-          const int row = (int)(s * Np + (j == 2 ? w % Np : w / 64));          // q / k [s][h][n][64], v^T [s][h][d][n]
-          a->rows_past[2 + j] = std::max(a->rows_past[2 + j], row - M + 1);
-        }
-      }
+  if (s.status()) return 1;
+  launch_lg_blockf(prec, g, s.stream());
+  s.wait(HookStage::OWN_TEXT);
+  // rows past M that the launch changed: x32 / xb against their initial (zero) rows, q / k / v^T against the 0xFFFF fill
+  const std::vector<float> x32o = s.get<float>(g.x32, (size_t)cap * 256);
+  const std::vector<uint16_t> xbo = s.get<uint16_t>(g.xb, (size_t)cap * 256);
+  memcpy(a->x32, x32o.data(), (size_t)M * 256 * 4);
+  dbg_back2(xbo, (size_t)M * 256, prec, a->xb);
+  for (int i = 0; i < 5; ++i) a->rows_past[i] = 0;
+  for (int r = M; r < cap; ++r)
+    for (int f = 0; f < 256; ++f) {
+      const size_t e = (size_t)r * 256 + f;
+      if (memcmp(&x32o[e], &x32h[e], 4)) a->rows_past[0] = r - M + 1;
+      if (xbo[e] != xbh[e]) a->rows_past[1] = r - M + 1;
+    }
+  uint16_t* dev[3] = {g.q_out, g.k_out, g.vt_out};
+  float* host[3] = {a->q, a->k, a->vt};
+  for (int j = 0; j < 3 && nq; ++j) {
+    if (!dev[j]) continue;
+    const std::vector<uint16_t> ho = s.get<uint16_t>(dev[j], helems);
+    dbg_back2(ho, (size_t)S * 4 * Np * 64, prec, host[j]);
+    for (size_t e = (size_t)S * 4 * Np * 64; e < helems; ++e) {
+      if (ho[e] == 0xFFFF) continue;
+      const size_t sq = e / ((size_t)4 * Np * 64), w = e % ((size_t)Np * 64);
+      const int row = (int)(sq * Np + (j == 2 ? w % Np : w / 64));          // q / k [s][h][n][64], v^T [s][h][d][n]
+      a->rows_past[2 + j] = std::max(a->rows_past[2 + j], row - M + 1);
     }
   }
-  return rc;
+  return s.status();
 } AIRFE_CATCH(c)
 
 int airfe_debug_ln_gelu(airfe_ctx* c, int prec, float* h, const float* gamma, const float* beta, int M) try {
   AIRFE_ENTER(c);
   if ((prec != 0 && prec != 1) || M < 1 || !h || !gamma || !beta) return fail(c, "debug_ln_gelu: bad argument");
-  DbgTmp t;
-  airfe_ctx& tmp = t.h;
+  HookStage s(c, "debug_ln_gelu");
   std::vector<float> gb(1024);
   memcpy(gb.data(), gamma, 512 * 4);
   memcpy(gb.data() + 512, beta, 512 * 4);
-  uint16_t* dh = dupload(&tmp, dbg_rows2(h, M, 512, M, prec));
-  float* dgb = dupload(&tmp, gb);
-  int rc = dh && dgb ? 0 : fail(c, "debug_ln_gelu: allocation failed");
-  if (!rc) {
-    launch_ln_gelu(prec, dh, dgb, dgb + 512, M, c->stream);
-    if (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c)) rc = fail(c, "debug_ln_gelu: kernel failed");
-  }
-  if (!rc) {
-    std::vector<uint16_t> ho((size_t)M * 512);
-    (void)hipMemcpy(ho.data(), dh, ho.size() * 2, hipMemcpyDeviceToHost);
-    dbg_back2(ho, ho.size(), prec, h);
-  }
-  return rc;
+  uint16_t* dh = s.up(dbg_rows2(h, M, 512, M, prec));
+  const float* dgb = s.up(std::move(gb));
+  if (s.status()) return 1;
+  launch_ln_gelu(prec, dh, dgb, dgb + 512, M, s.stream());
+  s.wait(HookStage::OWN_TEXT);
+  dbg_back2(s.get<uint16_t>(dh, (size_t)M * 512), (size_t)M * 512, prec, h);
+  return s.status();
 } AIRFE_CATCH(c)
 }  // extern "C"
 
@@ -476,30 +476,25 @@ static int dbg_attention_run(airfe_ctx* c, airfe_debug_attn_args* a, const char*
           hk[(((size_t)s * H + h) * Np + i) * 64 + d] = cvt2(a->k[src], prec);
           hvt[(((size_t)s * H + h) * 64 + d) * Np + i] = cvt2(a->v[src], prec);       // V^T [S][H][64][Np]
         }
-  DbgTmp t;
-  airfe_ctx* tmp = &t.h;   // only as an allocation list holder
-  uint16_t *dq = dupload(tmp, hq), *dk = dupload(tmp, hk), *dv = dupload(tmp, hvt);
+  HookStage s(c, who);
+  const uint16_t *dq = s.up(std::move(hq)), *dk = s.up(std::move(hk)), *dv = s.up(std::move(hvt));
   const size_t out_n = (size_t)S * Np * H * 64, slack_n = (size_t)128 * H * 64;
-  uint16_t* dout = dalloc<uint16_t>(tmp, out_n + slack_n);
-  std::vector<int> hl(a->lens, a->lens + S);
-  int* dl = dupload(tmp, hl);
-  if (!dq || !dk || !dv || !dout || !dl) return fail(c, w + "allocation failed");
-  if (a->canary && hipMemsetAsync(dout, 0xFF, (out_n + slack_n) * 2, c->stream) != hipSuccess) return fail(c, w + "memset failed");
-  launch_attention32(prec, dq, dk, dv, dout, dl, S, H, Np, cross, c->stream);
-  if (hipStreamSynchronize(c->stream) != hipSuccess || launch_status(c)) return fail(c, w + "kernel failed");
-  std::vector<uint16_t> ho(out_n + slack_n);
-  if (hipMemcpy(ho.data(), dout, ho.size() * 2, hipMemcpyDeviceToHost) != hipSuccess) return fail(c, w + "copy failed");
+  uint16_t* dout = s.fresh<uint16_t>(out_n + slack_n, a->canary ? 0xFF : 0);
+  const int* dl = s.up(a->lens, (size_t)S);
+  if (s.status()) return 1;
+  launch_attention32(prec, dq, dk, dv, dout, dl, S, H, Np, cross, s.stream());
+  s.wait(HookStage::OWN_TEXT);
+  const std::vector<uint16_t> ho = s.get<uint16_t>(dout, out_n + slack_n);
   const int rows_out = a->raw ? Np : n;
-  for (int s = 0; s < S; ++s)
+  for (int q = 0; q < S; ++q)
     for (int i = 0; i < rows_out; ++i)
-      for (int f = 0; f < H * 64; ++f) a->out[((size_t)s * rows_out + i) * H * 64 + f] = back2(ho[((size_t)s * Np + i) * H * 64 + f], prec);
-  if (a->canary)
-    for (int r = 0; r < 128; ++r) {
-      bool changed = false;
-      for (int f = 0; f < H * 64 && !changed; ++f) changed = ho[out_n + (size_t)r * H * 64 + f] != 0xFFFFu;
-      a->rows_past += changed;
-    }
-  return 0;
+      for (int f = 0; f < H * 64; ++f) a->out[((size_t)q * rows_out + i) * H * 64 + f] = back2(ho[((size_t)q * Np + i) * H * 64 + f], prec);
+  for (int r = 0; r < 128 && a->canary; ++r) {
+    bool changed = false;
+    for (int f = 0; f < H * 64 && !changed; ++f) changed = ho[out_n + (size_t)r * H * 64 + f] != 0xFFFFu;
+    a->rows_past += changed;
+  }
+  return s.status();
 }
 
 extern "C" {
@@ -508,7 +503,7 @@ int airfe_debug_attention(airfe_ctx* c, const float* q, const float* k, const fl
   if (c->mprec == 2) return fail(c, "debug_attention drives the 2-byte kernel (matcher_precision fp16 / bf16)");
   airfe_debug_attn_args a = {};
   a.prec = c->mprec; a.S = S; a.H = H; a.n = n; a.cross = cross;
-  a.q = q; a.k = k; a.v = v; a.lens = lens; a.out = out;                 // canary = 0, raw = 0: the output buffer as the allocator left it, the first n rows back
+  a.q = q; a.k = k; a.v = v; a.lens = lens; a.out = out;                 // canary = 0, raw = 0: a zero-filled output buffer, the first n rows back
   return dbg_attention_run(c, &a, "debug_attention");
 } AIRFE_CATCH(c)
 
@@ -533,43 +528,36 @@ int airfe_debug_lg_prepare(airfe_ctx* c, airfe_debug_lg_prepare_args* a) try {
   if (a->f0x && (a->n0x < 0 || a->n0x > Np || a->n1x < 0 || a->n1x > Np)) return fail(c, "debug_lg_prepare: the second pair's lengths must lie in 0 .. Np");
   const size_t rows = (size_t)2 * Bt * Np + (size_t)a->slack_rows, R = c->arena_rows;
   if (rows > R || (size_t)a->rows != rows) return fail(c, "debug_lg_prepare: rows must be 2 Bt Np + slack_rows and fit the arena");
-  DbgTmp t;
+  HookStage s(c, "debug_lg_prepare");
   const size_t fl = (size_t)B * a->cap * a->ld;
-  std::vector<float> hf0(a->f0, a->f0 + fl), hf1(a->f1, a->f1 + fl), hwr(a->wr, a->wr + 64);
   std::vector<int> hn(2 * B + 2);
   for (int b = 0; b < B; ++b) { hn[b] = a->n0[b]; hn[B + b] = a->n1[b]; }
   hn[2 * B] = a->n0x; hn[2 * B + 1] = a->n1x;
-  float *df0 = dupload(&t.h, hf0), *df1 = dupload(&t.h, hf1), *dwr = dupload(&t.h, hwr), *df0x = nullptr, *df1x = nullptr;
-  int* dn = dupload(&t.h, hn);
+  const int* dn = s.up(std::move(hn));
+  LgPrepArgs pa;
+  pa.f0 = s.up(a->f0, fl); pa.f1 = s.up(a->f1, fl); pa.wr = s.up(a->wr, (size_t)64);
   if (a->f0x) {
     std::vector<float> x0(a->f0x, a->f0x + (size_t)a->n0x * a->ld), x1(a->f1x, a->f1x + (size_t)a->n1x * a->ld);
     x0.resize(x0.size() + a->ld, 0.f); x1.resize(x1.size() + a->ld, 0.f);          // (never empty)
-    df0x = dupload(&t.h, x0); df1x = dupload(&t.h, x1);
-    if (!df0x || !df1x) return fail(c, "debug_lg_prepare: allocation failed");
+    pa.f0x = s.up(std::move(x0)); pa.f1x = s.up(std::move(x1));
   }
-  if (!df0 || !df1 || !dwr || !dn) return fail(c, "debug_lg_prepare: allocation failed");
-  hipStream_t st = c->stream;
-  HIPCHK(c, hipMemsetAsync(c->x32, 0xFF, R * 256 * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->xb, 0xFF, R * 256 * 2, st));
-  HIPCHK(c, hipMemsetAsync(c->rot_cos, 0xFF, R * 32 * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->rot_sin, 0xFF, R * 32 * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->lens, 0xFF, (size_t)2 * c->Pmax * 4, st));
-  LgPrepArgs pa;
-  pa.f0 = df0; pa.f1 = df1; pa.n0 = dn; pa.n1 = dn + B; pa.ld = a->ld; pa.kp_off = a->kp_off; pa.normalize = a->normalize;
-  pa.cx = a->cx; pa.cy = a->cy; pa.linv = a->linv; pa.wr = dwr; pa.B = B; pa.cap = a->cap; pa.Np = Np;
+  const DevSpan arena[4] = {{c->x32, R * 256 * 4}, {c->xb, R * 256 * 2}, {c->rot_cos, R * 32 * 4}, {c->rot_sin, R * 32 * 4}};
+  for (const DevSpan& e : arena) s.fill(e.p, 0xFF, e.bytes);
+  s.fill(c->lens, 0xFF, (size_t)2 * c->Pmax * 4);
+  if (s.status()) return 1;
+  pa.n0 = dn; pa.n1 = dn + B; pa.ld = a->ld; pa.kp_off = a->kp_off; pa.normalize = a->normalize;
+  pa.cx = a->cx; pa.cy = a->cy; pa.linv = a->linv; pa.B = B; pa.cap = a->cap; pa.Np = Np;
   pa.x32 = c->x32; pa.xb = c->xb; pa.rot_cos = c->rot_cos; pa.rot_sin = c->rot_sin; pa.lens = c->lens;
-  if (a->f0x) { pa.f0x = df0x; pa.f1x = df1x; pa.n0x = dn + 2 * B; pa.n1x = dn + 2 * B + 1; }
+  if (a->f0x) { pa.n0x = dn + 2 * B; pa.n1x = dn + 2 * B + 1; }
   pa.slack_rows = a->slack_rows;
-  launch_lg_prepare(a->prec, pa, st);
-  HIPCHK(c, hipStreamSynchronize(st));
-  if (launch_status(c)) return 1;
-  std::vector<float> hx(R * 256);
-  std::vector<uint16_t> hb(R * 256);
-  HIPCHK(c, hipMemcpy(hx.data(), c->x32, hx.size() * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(hb.data(), c->xb, hb.size() * 2, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->rot_cos, c->rot_cos, rows * 32 * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->rot_sin, c->rot_sin, rows * 32 * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->lens, c->lens, (size_t)2 * Bt * 4, hipMemcpyDeviceToHost));
+  launch_lg_prepare(a->prec, pa, s.stream());
+  s.wait();
+  const std::vector<float> hx = s.get<float>(c->x32, R * 256);
+  const std::vector<uint16_t> hb = s.get<uint16_t>(c->xb, R * 256);
+  s.get(a->rot_cos, c->rot_cos, rows * 32 * 4);
+  s.get(a->rot_sin, c->rot_sin, rows * 32 * 4);
+  s.get(a->lens, c->lens, (size_t)2 * Bt * 4);
+  if (s.status()) return 1;
   memcpy(a->x32, hx.data(), rows * 256 * 4);
   dbg_back2(hb, rows * 256, a->prec, a->xb);
   int past = 0;
@@ -584,12 +572,8 @@ int airfe_debug_lg_prepare(airfe_ctx* c, airfe_debug_lg_prepare_args* a) try {
   }
   a->rows_past = past;
   // the arena as alloc_matcher_arena left it: the pipelines reset only the slack rows their own kernels can reach
-  HIPCHK(c, hipMemsetAsync(c->x32, 0, R * 256 * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->xb, 0, R * 256 * 2, st));
-  HIPCHK(c, hipMemsetAsync(c->rot_cos, 0, R * 32 * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->rot_sin, 0, R * 32 * 4, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  return 0;
+  for (const DevSpan& e : arena) s.fill(e.p, 0, e.bytes);
+  return s.wait();
 } AIRFE_CATCH(c)
 
 int airfe_debug_lg_assign(airfe_ctx* c, airfe_debug_lg_assign_args* a) try {
@@ -617,31 +601,22 @@ int airfe_debug_lg_assign(airfe_ctx* c, airfe_debug_lg_assign_args* a) try {
       for (int i = a->lens[s]; i < Np; ++i)
         for (int k = 0; k < 256; ++k) hmd[((size_t)s * Np + i) * 256 + k] = cvt2(a->pad[k], prec);
   }
-  DbgTmp t;
-  std::vector<float> hw(a->w, a->w + 256);
-  float* dw = dupload(&t.h, hw);
-  float* dscores = dalloc<float>(&t.h, (size_t)B * blk, false);
-  int32_t* didx = dalloc<int32_t>(&t.h, (size_t)B * cap * 2, false);
-  float* dscore = dalloc<float>(&t.h, (size_t)B * cap, false);
-  int* dnm = dalloc<int>(&t.h, (size_t)B, false);
-  if (!dw || !dscores || !didx || !dscore || !dnm) return fail(c, "debug_lg_assign: allocation failed");
-  hipStream_t st = c->stream;
-  HIPCHK(c, hipMemcpyAsync(c->mdb, hmd.data(), hmd.size() * 2, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->x32, hx.data(), hx.size() * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->lens, a->lens, (size_t)S * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemsetAsync(c->zbuf, 0xFF, M * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->simbuf, 0xFF, (size_t)B * blk * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->lg_part, 0xFF, pf * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->lg_argpart, 0xFF, pf * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->rowlse, 0xFF, (size_t)B * Np * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->collse, 0xFF, (size_t)B * Np * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->rowval, 0xFF, (size_t)B * Np * 4, st));
-  HIPCHK(c, hipMemsetAsync(dscores, 0xFF, (size_t)B * blk * 4, st));
-  HIPCHK(c, hipMemsetAsync(dscore, 0xFF, (size_t)B * cap * 4, st));
-  HIPCHK(c, hipMemsetAsync(dnm, 0xFF, (size_t)B * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->rowarg, 0, (size_t)B * Np * 4, st));          // zero, not -1: the value that passes for a valid index
-  HIPCHK(c, hipMemsetAsync(c->colarg, 0, (size_t)B * Np * 4, st));
-  HIPCHK(c, hipMemsetAsync(didx, 0, (size_t)B * cap * 8, st));
+  HookStage s(c, "debug_lg_assign");
+  const float* dw = s.up(a->w, (size_t)256);
+  float* dscores = s.fresh<float>((size_t)B * blk, 0xFF);
+  float* dscore = s.fresh<float>((size_t)B * cap, 0xFF);
+  int* dnm = s.fresh<int>((size_t)B, 0xFF);
+  int32_t* didx = s.fresh<int32_t>((size_t)B * cap * 2, 0);             // zero, not -1: the value that passes for a valid index
+  s.put(c->mdb, std::move(hmd));
+  s.put(c->x32, std::move(hx));
+  s.put(c->lens, a->lens, (size_t)S * 4);
+  const size_t bn = (size_t)B * Np * 4;
+  const DevSpan nan_out[7] = {{c->zbuf, M * 4}, {c->simbuf, (size_t)B * blk * 4}, {c->lg_part, pf * 4}, {c->lg_argpart, pf * 4}, {c->rowlse, bn}, {c->collse, bn}, {c->rowval, bn}};
+  for (const DevSpan& e : nan_out) s.fill(e.p, 0xFF, e.bytes);
+  s.fill(c->rowarg, 0, bn);
+  s.fill(c->colarg, 0, bn);
+  if (s.status()) return 1;
+  hipStream_t st = s.stream();
   launch_rowdot256(c->x32, dw, a->b, c->zbuf, (int)M, st);
   if (a->form == 1) {
     launch_lg_assign_fused(prec, c->mdb, c->zbuf, c->lens, B, Np, cap, a->thr, c->lg_part, c->lg_argpart, c->rowlse, c->collse, c->simbuf, dscores, c->rowarg,
@@ -650,27 +625,98 @@ int airfe_debug_lg_assign(airfe_ctx* c, airfe_debug_lg_assign_args* a) try {
     launch_sim(prec, c->mdb, c->simbuf, B, Np, st);
     launch_lg_assign(c->simbuf, c->zbuf, c->lens, B, Np, cap, a->thr, c->rowlse, c->collse, dscores, c->rowarg, c->rowval, c->colarg, didx, dscore, dnm, st);
   }
-  HIPCHK(c, hipStreamSynchronize(st));
-  if (launch_status(c)) return 1;
+  s.wait();
   const size_t nb = (size_t)n * 4, npb = (size_t)Np * 4;
-  HIPCHK(c, hipMemcpy2D(a->z, nb, c->zbuf, npb, nb, S, hipMemcpyDeviceToHost));
+  s.get2d(a->z, nb, c->zbuf, npb, nb, S);
   for (int b = 0; b < B; ++b) {
-    HIPCHK(c, hipMemcpy2D(a->sim + (size_t)b * n * n, nb, c->simbuf + b * blk, npb, nb, n, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy2D(a->scores + (size_t)b * n * n, nb, dscores + b * blk, npb, nb, n, hipMemcpyDeviceToHost));
+    s.get2d(a->sim + (size_t)b * n * n, nb, c->simbuf + b * blk, npb, nb, n);
+    s.get2d(a->scores + (size_t)b * n * n, nb, dscores + b * blk, npb, nb, n);
   }
-  HIPCHK(c, hipMemcpy2D(a->rowlse, nb, c->rowlse, npb, nb, B, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy2D(a->collse, nb, c->collse, npb, nb, B, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy2D(a->rowval, nb, c->rowval, npb, nb, B, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy2D(a->rowarg, nb, c->rowarg, npb, nb, B, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy2D(a->colarg, nb, c->colarg, npb, nb, B, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->idx, didx, (size_t)B * cap * 8, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->score, dscore, (size_t)B * cap * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->nmatch, dnm, (size_t)B * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemsetAsync(c->mdb, 0, M * 256 * 2, st));          // no NaN token rows stay behind
-  HIPCHK(c, hipMemsetAsync(c->x32, 0, M * 256 * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->zbuf, 0, M * 4, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  return 0;
+  const struct { void* h; const void* d; } rows[5] = {{a->rowlse, c->rowlse}, {a->collse, c->collse}, {a->rowval, c->rowval}, {a->rowarg, c->rowarg}, {a->colarg, c->colarg}};
+  for (const auto& e : rows) s.get2d(e.h, nb, e.d, npb, nb, B);
+  s.get(a->idx, didx, (size_t)B * cap * 8);
+  s.get(a->score, dscore, (size_t)B * cap * 4);
+  s.get(a->nmatch, dnm, (size_t)B * 4);
+  s.fill(c->mdb, 0, M * 256 * 2);          // no NaN token rows stay behind
+  s.fill(c->x32, 0, M * 256 * 4);
+  s.fill(c->zbuf, 0, M * 4);
+  return s.wait();
+} AIRFE_CATCH(c)
+
+/* ---- the matchers' tails alone on HOST score matrices, staged into the arena */
+/* filter_matches (src/light_glue.cpp:214-266) alone on one HOST score matrix [n0][n1] */
+int airfe_debug_lg_filter(airfe_ctx* c, const float* scores, int n0, int n1, int32_t* idx, float* score, int cap, int* nmatch) try {
+  if (c && enter_device(c)) return 1;
+  if (!c || !c->has_arena) return fail(c, "debug_lg_filter: no matcher loaded");
+  if (n0 < 1 || n1 < 1 || n0 > c->cfg.max_keypoints || n1 > c->cfg.max_keypoints || !scores || !idx || !score || !nmatch)
+    return fail(c, "debug_lg_filter: bad argument");
+  HookStage s(c, "debug_lg_filter");
+  const int lens[2] = {n0, n1};
+  s.put(c->lens, lens, 8);
+  s.put2d(c->simbuf, (size_t)c->Np * 4, scores, (size_t)n1 * 4, (size_t)n1 * 4, n0);
+  if (s.status()) return 1;
+  launch_lg_filter_scores(c->simbuf, c->lens, 1, c->Np, c->Np, 0.1f, c->rowarg, c->rowval, c->colarg, c->st_idx, c->st_score, c->st_nm, s.stream());
+  s.wait();
+  int nm = 0;
+  s.get(&nm, c->st_nm, 4);
+  nm = std::min(nm, cap);
+  s.get(idx, c->st_idx, (size_t)std::max(nm, 0) * 8);
+  s.get(score, c->st_score, (size_t)std::max(nm, 0) * 4);
+  *nmatch = nm;
+  return s.status();
+} AIRFE_CATCH(c)
+
+/* decode (src/super_glue.cpp:339-367) alone on one HOST score matrix Z [n0+1][n1+1] */
+int airfe_debug_sg_decode(airfe_ctx* c, const float* Z, int n0, int n1, int32_t* idx0, int32_t* idx1, double* ms0, double* ms1) try {
+  if (c && enter_device(c)) return 1;
+  if (!c || !c->has_sg) return fail(c, "debug_sg_decode: SuperGlue not loaded");
+  if (n0 < 1 || n1 < 1 || n0 > c->cfg.max_keypoints || n1 > c->cfg.max_keypoints || !Z || !idx0 || !idx1 || !ms0 || !ms1)
+    return fail(c, "debug_sg_decode: bad argument");
+  HookStage s(c, "debug_sg_decode");
+  const int lens[2] = {n0, n1};
+  s.put(c->lens, lens, 8);
+  s.put2d(c->sg_Z, (size_t)c->Lz * 4, Z, (size_t)(n1 + 1) * 4, (size_t)(n1 + 1) * 4, n0 + 1);
+  if (s.status()) return 1;
+  launch_sg_decode(c->sg_Z, c->lens, 1, c->Np, c->Lz, 0.2f, c->sg_idx0, c->sg_max0, c->sg_idx1, c->sg_out0, c->sg_out1, c->sg_ms0, c->sg_ms1, s.stream());
+  s.wait();
+  s.get(idx0, c->sg_out0, (size_t)n0 * 4);
+  s.get(idx1, c->sg_out1, (size_t)n1 * 4);
+  const std::vector<float> m0 = s.get<float>(c->sg_ms0, n0), m1 = s.get<float>(c->sg_ms1, n1);
+  for (int i = 0; i < n0; ++i) ms0[i] = (double)m0[i];
+  for (int j = 0; j < n1; ++j) ms1[j] = (double)m1[j];
+  return s.status();
+} AIRFE_CATCH(c)
+
+/* launch_sg_sinkhorn alone on B HOST coupling matrices (include/airfe_debug.h).  Everything of the arena outside each pair's valid n0 x n1 block is NaN when
+   the launch starts, and so is the output: a finite Z [0..n0][0..n1] was written in full and came from inside `lens` alone. */
+int airfe_debug_sg_sinkhorn(airfe_ctx* c, const float* sim, const int* lens, int B, int ld, float alpha, int iters, int form, float* Z, int* form_ran) try {
+  if (c && enter_device(c)) return 1;
+  if (!c || !c->has_sg) return fail(c, "debug_sg_sinkhorn: SuperGlue not loaded");
+  if (!sim || !lens || !Z || !form_ran || B < 1 || B > c->Pmax || ld < 1 || iters < 0 || form < 0 || form > 2)
+    return fail(c, "debug_sg_sinkhorn: bad argument (1 <= B <= max_batch, iters >= 0, form 0 / 1 / 2)");
+  const int nmax = std::min(ld, c->cfg.max_keypoints);
+  for (int i = 0; i < 2 * B; ++i)
+    if (lens[i] < 1 || lens[i] > nmax) return fail(c, "debug_sg_sinkhorn: every n0, n1 must lie in 1 .. min(ld, max_keypoints)");
+  *form_ran = 0;
+  const int Np = c->Np, Lz = c->Lz;
+  const size_t blk = (size_t)Np * Np, zblk = (size_t)Lz * Lz;
+  HookStage s(c, "debug_sg_sinkhorn");
+  s.put(c->lens, lens, (size_t)B * 8);
+  s.fill(c->simbuf, 0xFF, (size_t)B * blk * 4);          // 0xFFFFFFFF: a NaN
+  s.fill(c->sg_Z, 0xFF, (size_t)B * zblk * 4);
+  s.fill(c->sg_xch, 0xFF, (size_t)B * Lz * 64 * 4);      // [B][2][16][Lz] float2: a partial read before it was written is a NaN
+  for (int b = 0; b < B; ++b)
+    s.put2d(c->simbuf + b * blk, (size_t)Np * 4, sim + (size_t)b * ld * ld, (size_t)ld * 4, (size_t)lens[2 * b + 1] * 4, lens[2 * b]);
+  if (s.status()) return 1;
+  launch_sg_sinkhorn(c->simbuf, c->lens, B, Np, Lz, alpha, iters, c->sg_u, c->sg_v, c->sg_Z, c->sg_cnt, c->sg_cnt + (size_t)c->Pmax * 16, c->sg_xch, s.stream(),
+                     form, form_ran);
+  if (*form_ran == 0)
+    return s.refuse("form 2 asked for, but no register-resident instantiation applies to this context (max_keypoints, B against the co-resident "
+                    "workgroups) or the cooperative launch was refused");
+  if (!s.wait()) s.step(sinkhorn_failed(c));
+  for (int b = 0; b < B; ++b)
+    s.get2d(Z + (size_t)b * (ld + 1) * (ld + 1), (size_t)(ld + 1) * 4, c->sg_Z + b * zblk, (size_t)Lz * 4, (size_t)(lens[2 * b + 1] + 1) * 4, lens[2 * b] + 1);
+  return s.status();
 } AIRFE_CATCH(c)
 
 /* ---- the detector's and the line path's index work on hand-built maps (include/airfe_debug.h; tests/test_gpu_detector_tail_pin.py, tests/detector_tail_ref.py).  HOST tensors
@@ -693,35 +739,70 @@ int airfe_debug_detector_tail(airfe_ctx* c, airfe_debug_detector_tail_args* a) t
   std::vector<uint16_t> act(cells * 256);
   for (size_t i = 0; i < act.size(); ++i) act[i] = cvt2(a->act[i], c->prec);
   const int B0 = two ? Bs : B, B1 = two ? B - Bs : 0;
-  DbgTmp t;
-  float* dfeat = dupload(&t.h, std::vector<float>(a->feat, a->feat + (size_t)B0 * cap * AIRFE_FEAT_DIM));
-  int* dn = dupload(&t.h, std::vector<int>(a->n, a->n + B0));
-  float* dfeat1 = two ? dupload(&t.h, std::vector<float>(a->feat1, a->feat1 + (size_t)B1 * cap * AIRFE_FEAT_DIM)) : nullptr;
-  int* dn1 = two ? dupload(&t.h, std::vector<int>(a->n1, a->n1 + B1)) : nullptr;
-  if (!dfeat || !dn || (two && (!dfeat1 || !dn1))) return fail(c, "debug_detector_tail: allocation failed");
-  hipStream_t st = c->stream;
+  const size_t f0 = (size_t)B0 * cap * AIRFE_FEAT_DIM, f1 = (size_t)B1 * cap * AIRFE_FEAT_DIM;
+  HookStage s(c, "debug_detector_tail");
+  float* dfeat = s.up(a->feat, f0);
+  int* dn = s.up(a->n, (size_t)B0);
+  float* dfeat1 = two ? s.up(a->feat1, f1) : nullptr;
+  int* dn1 = two ? s.up(a->n1, (size_t)B1) : nullptr;
   clear_saturation(c);
-  HIPCHK(c, hipMemcpyAsync(c->heat, a->heat, px * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->aDa, act.data(), act.size() * 2, hipMemcpyHostToDevice, st));
+  s.put(c->heat, a->heat, px * 4);
+  s.put(c->aDa, std::move(act));
   // detect_dev2's descriptor-head rule (point_desc_head), then its tail
   bool sparse_desc = false;
-  if (point_desc_head(c, B, cap, st, sparse_desc)) { (void)hipStreamSynchronize(st); return 1; }
-  const int rc = detect_tail_dev(c, B, Bs, two, sparse_desc, a->h, a->w, dfeat, dfeat1, cap, dn, dn1, st);
-  HIPCHK(c, hipStreamSynchronize(st));                       // (act goes out of scope)
-  if (rc) return 1;
-  if (saturation_status(c)) return 1;
-  HIPCHK(c, hipMemcpy(a->feat, dfeat, (size_t)B0 * cap * AIRFE_FEAT_DIM * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->n, dn, (size_t)B0 * 4, hipMemcpyDeviceToHost));
+  if (!s.status()) s.step(point_desc_head(c, B, cap, s.stream(), sparse_desc));
+  if (!s.status()) s.step(detect_tail_dev(c, B, Bs, two, sparse_desc, a->h, a->w, dfeat, dfeat1, cap, dn, dn1, s.stream()));
+  s.wait(HookStage::SATURATION);
+  s.get(a->feat, dfeat, f0 * 4);
+  s.get(a->n, dn, (size_t)B0 * 4);
   if (two) {
-    HIPCHK(c, hipMemcpy(a->feat1, dfeat1, (size_t)B1 * cap * AIRFE_FEAT_DIM * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(a->n1, dn1, (size_t)B1 * 4, hipMemcpyDeviceToHost));
+    s.get(a->feat1, dfeat1, f1 * 4);
+    s.get(a->n1, dn1, (size_t)B1 * 4);
   }
   a->nms_map_written = c->cfg.nms_radius > 0 && c->nms_map_valid;
-  if (a->nms_map && a->nms_map_written) HIPCHK(c, hipMemcpy(a->nms_map, c->heat_nms, px * 4, hipMemcpyDeviceToHost));
-  if (a->keep) HIPCHK(c, hipMemcpy(a->keep, c->nms_mask, cells * 8, hipMemcpyDeviceToHost));
-  if (a->cand_cnt) HIPCHK(c, hipMemcpy(a->cand_cnt, c->cand_cnt, (size_t)B * 4, hipMemcpyDeviceToHost));
-  return 0;
+  if (a->nms_map && a->nms_map_written) s.get(a->nms_map, c->heat_nms, px * 4);
+  if (a->keep) s.get(a->keep, c->nms_mask, cells * 8);
+  if (a->cand_cnt) s.get(a->cand_cnt, c->cand_cnt, (size_t)B * 4);
+  return s.status();
 } AIRFE_CATCH(c)
+
+}  // extern "C"
+
+// what line_post and junction_tail share.  In: stage 1's lines_adjusted | scores rows and kept counts m2, the point branch's score map, the caller's line / junction rows and
+// the four count rows nlines | nfound | njunc | jfound as 0xFF.  Out: the same rows and counts.
+struct DbgLineIo { double* lines = nullptr; float* junc = nullptr; int* cnt = nullptr; };
+template <class A>
+static DbgLineIo dbg_line_stage(HookStage& s, airfe_ctx* c, const A* a) {
+  const int B = a->B, nj = a->nj, ld = a->ld, R = AIRFE_INTERNAL_SIZE;
+  DbgLineIo io;
+  io.lines = s.up(a->lines, (size_t)B * a->capL * 4);
+  if (nj > 0) io.junc = s.up(a->junc, (size_t)nj * a->capJ * AIRFE_FEAT_DIM);
+  io.cnt = s.fresh<int>((size_t)4 * B, 0xFF);
+  clear_saturation(c);
+  std::vector<int> counts((size_t)B * LINE_CNT_LD, 0);
+  for (int b = 0; b < B; ++b) counts[(size_t)b * LINE_CNT_LD + 1] = a->m2[b];
+  s.put2d(c->s1_la, (size_t)LINE_CAP * 16, a->la, (size_t)ld * 16, (size_t)ld * 16, B);
+  s.put2d(c->s1_sc, (size_t)LINE_CAP * 4, a->sc, (size_t)ld * 4, (size_t)ld * 4, B);
+  s.put(c->wf_counts, std::move(counts));
+  c->wf_counted = false;                                     // (the per-workgroup counts of a previous line branch are gone)
+  s.put(c->heat, a->heat, (size_t)B * R * R * 4);
+  return io;
+}
+template <class A>
+static int dbg_line_back(HookStage& s, A* a, const DbgLineIo& io) {
+  const size_t B = a->B, nj = a->nj;
+  s.get(a->lines, io.lines, B * a->capL * 32);
+  s.get(a->nlines, io.cnt, B * 4);
+  s.get(a->nfound, io.cnt + B, B * 4);
+  if (nj > 0) {
+    s.get(a->junc, io.junc, nj * a->capJ * AIRFE_FEAT_DIM * 4);
+    s.get(a->njunc, io.cnt + 2 * B, nj * 4);
+    s.get(a->jfound, io.cnt + 3 * B, nj * 4);
+  }
+  return s.status();
+}
+
+extern "C" {
 
 int airfe_debug_line_post(airfe_ctx* c, airfe_debug_line_post_args* a) try {
   AIRFE_ENTER(c);
@@ -734,44 +815,22 @@ int airfe_debug_line_post(airfe_ctx* c, airfe_debug_line_post_args* a) try {
   if (nj > 0 && (!a->junc || !a->njunc || !a->jfound)) return fail(c, "debug_line_post: nj > 0 needs the junction outputs");
   for (int b = 0; b < B; ++b)
     if (a->m2[b] < 0 || a->m2[b] > ld) return fail(c, "debug_line_post: every m2 must lie in 0 .. ld");
-  DbgTmp t;
-  double* dlines = dupload(&t.h, std::vector<double>(a->lines, a->lines + (size_t)B * capL * 4));
-  float* djunc = nj > 0 ? dupload(&t.h, std::vector<float>(a->junc, a->junc + (size_t)nj * capJ * AIRFE_FEAT_DIM)) : nullptr;
-  int* dcnt = dbg_canary<int>(&t.h, (size_t)4 * B);          // nlines | nfound | njunc | jfound
-  if (!dlines || (nj > 0 && !djunc) || !dcnt) return fail(c, "debug_line_post: allocation failed");
-  hipStream_t st = c->stream;
-  clear_saturation(c);
-  std::vector<int> counts((size_t)B * LINE_CNT_LD, 0);
-  for (int b = 0; b < B; ++b) {
-    counts[(size_t)b * LINE_CNT_LD + 1] = a->m2[b];
-    HIPCHK(c, hipMemcpyAsync(c->s1_la + (size_t)b * LINE_CAP * 4, a->la + (size_t)b * ld * 4, (size_t)ld * 16, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->s1_sc + (size_t)b * LINE_CAP, a->sc + (size_t)b * ld, (size_t)ld * 4, hipMemcpyHostToDevice, st));
-  }
-  HIPCHK(c, hipMemcpyAsync(c->wf_counts, counts.data(), counts.size() * 4, hipMemcpyHostToDevice, st));
-  c->wf_counted = false;                                     // (the per-workgroup counts of a previous line branch are gone)
-  HIPCHK(c, hipMemcpyAsync(c->heat, a->heat, (size_t)B * R * R * 4, hipMemcpyHostToDevice, st));
+  HookStage s(c, "debug_line_post");
+  const DbgLineIo io = dbg_line_stage(s, c, a);
+  if (s.status()) return 1;
+  hipStream_t st = s.stream();
   // the point branch's NMS as detect_tail_dev runs it: with the dense map (one- and two-image calls) or with the keep plane alone (larger batches)
   c->nms_map_valid = !a->from_plane;
   launch_nms512_candidates(c->heat, c->nms_map_valid ? c->heat_nms : nullptr, c->nms_mask, B, c->cfg.keypoint_threshold, c->cfg.remove_borders, c->cand, c->cand_cnt,
                            R * R, st);
   // line_post_dev's steps without the descriptor sampling (line_filter_maps, junction_scan_maps), images 0 .. B-1, junctions of the first nj
   junction_maps_clear(c, nj, st);
-  line_filter_maps(c, B, nj, a->h, a->w, dlines, capL, dcnt, dcnt + B, st);
+  line_filter_maps(c, B, nj, a->h, a->w, io.lines, capL, io.cnt, io.cnt + B, st);
   // a caller's junction maps instead of the filter's, between the two launches: the scan's own bounds (the filter never marks a pixel the scan would reject)
-  if (nj > 0 && a->jmap) HIPCHK(c, hipMemcpyAsync(c->jmap, a->jmap, (size_t)nj * R * R, hipMemcpyHostToDevice, st));
-  const int rc = nj > 0 ? junction_scan_maps(c, 0, nj, djunc, capJ, dcnt + 2 * B, dcnt + 3 * B, st) : 0;
-  HIPCHK(c, hipStreamSynchronize(st));                       // (counts goes out of scope)
-  if (rc || launch_status(c)) return 1;
-  if (saturation_status(c)) return 1;
-  HIPCHK(c, hipMemcpy(a->lines, dlines, (size_t)B * capL * 32, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->nlines, dcnt, (size_t)B * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->nfound, dcnt + B, (size_t)B * 4, hipMemcpyDeviceToHost));
-  if (nj > 0) {
-    HIPCHK(c, hipMemcpy(a->junc, djunc, (size_t)nj * capJ * AIRFE_FEAT_DIM * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(a->njunc, dcnt + 2 * B, (size_t)nj * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(a->jfound, dcnt + 3 * B, (size_t)nj * 4, hipMemcpyDeviceToHost));
-  }
-  return 0;
+  if (nj > 0 && a->jmap) s.put(c->jmap, a->jmap, (size_t)nj * R * R);
+  if (nj > 0 && !s.status()) s.step(junction_scan_maps(c, 0, nj, io.junc, capJ, io.cnt + 2 * B, io.cnt + 3 * B, st));
+  s.wait(HookStage::SATURATION);
+  return dbg_line_back(s, a, io);
 } AIRFE_CATCH(c)
 
 /* the junction tail as the batched entries run it (include/airfe_debug.h): the point branch's state as detect_dev2 leaves it, plnet_lines_batch's rule for the junction
@@ -793,23 +852,11 @@ int airfe_debug_junction_tail(airfe_ctx* c, airfe_debug_junction_tail_args* a) t
     if (!(a->heat[i] >= 0.f && a->heat[i] <= 1.f)) return fail(c, "debug_junction_tail: scores must lie in [0, 1]");
   std::vector<uint16_t> act(cells * 256);
   for (size_t i = 0; i < act.size(); ++i) act[i] = cvt2(a->act[i], c->prec);
-  DbgTmp t;
-  double* dlines = dupload(&t.h, std::vector<double>(a->lines, a->lines + (size_t)B * capL * 4));
-  float* djunc = nj > 0 ? dupload(&t.h, std::vector<float>(a->junc, a->junc + (size_t)nj * capJ * AIRFE_FEAT_DIM)) : nullptr;
-  int* dcnt = dbg_canary<int>(&t.h, (size_t)4 * B);          // nlines | nfound | njunc | jfound
-  if (!dlines || (nj > 0 && !djunc) || !dcnt) return fail(c, "debug_junction_tail: allocation failed");
-  hipStream_t st = c->stream;
-  clear_saturation(c);
-  std::vector<int> counts((size_t)B * LINE_CNT_LD, 0);
-  for (int b = 0; b < B; ++b) {
-    counts[(size_t)b * LINE_CNT_LD + 1] = a->m2[b];
-    HIPCHK(c, hipMemcpyAsync(c->s1_la + (size_t)b * LINE_CAP * 4, a->la + (size_t)b * ld * 4, (size_t)ld * 16, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->s1_sc + (size_t)b * LINE_CAP, a->sc + (size_t)b * ld, (size_t)ld * 4, hipMemcpyHostToDevice, st));
-  }
-  HIPCHK(c, hipMemcpyAsync(c->wf_counts, counts.data(), counts.size() * 4, hipMemcpyHostToDevice, st));
-  c->wf_counted = false;
-  HIPCHK(c, hipMemcpyAsync(c->heat, a->heat, px * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->aDa, act.data(), act.size() * 2, hipMemcpyHostToDevice, st));
+  HookStage s(c, "debug_junction_tail");
+  const DbgLineIo io = dbg_line_stage(s, c, a);
+  s.put(c->aDa, std::move(act));
+  if (s.status()) return 1;
+  hipStream_t st = s.stream();
   // the point branch as detect_dev2 / detect_tail_dev leave it: one- and two-image calls keep the dense NMS'd map and the dense descriptor map, larger batches the keep
   // plane alone (their descriptor head ran over the sampled cells)
   c->nms_map_valid = B <= 2;
@@ -817,31 +864,20 @@ int airfe_debug_junction_tail(airfe_ctx* c, airfe_debug_junction_tail_args* a) t
                            R * R, st);
   c->desc_dense_valid = false;
   c->last_B = B;
-  int rc = 0;
   if (B <= 2) {
-    rc = dense_desc_head(c, B, st);
+    s.step(dense_desc_head(c, B, st));
     c->desc_dense_valid = true;
   }
   // plnet_lines_batch's rule (junction_dense_maps), then line_tail_dev's clear of the byte maps and its end
   bool partial = false;
-  if (!rc) rc = junction_dense_maps(c, nj, capJ, 3, st, partial);
+  if (!s.status()) s.step(junction_dense_maps(c, nj, capJ, 3, st, partial));
   const bool fused = junction_tail_fused(c, nj, capJ);
-  if (!rc && !fused) junction_maps_clear(c, nj, st);
-  if (!rc) rc = line_post_dev(c, 0, B, a->h, a->w, dlines, capL, dcnt, dcnt + B, djunc, capJ, dcnt + 2 * B, dcnt + 3 * B, nj, st, 3, fused);
+  if (!s.status() && !fused) junction_maps_clear(c, nj, st);
+  if (!s.status()) s.step(line_post_dev(c, 0, B, a->h, a->w, io.lines, capL, io.cnt, io.cnt + B, io.junc, capJ, io.cnt + 2 * B, io.cnt + 3 * B, nj, st, 3, fused));
   if (partial) c->desc_dense_valid = false;
-  HIPCHK(c, hipStreamSynchronize(st));                       // (counts, act go out of scope)
-  if (rc || launch_status(c)) return 1;
-  if (saturation_status(c)) return 1;
+  if (s.wait(HookStage::SATURATION)) return 1;
   a->fused = fused ? 1 : 0;
-  HIPCHK(c, hipMemcpy(a->lines, dlines, (size_t)B * capL * 32, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->nlines, dcnt, (size_t)B * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->nfound, dcnt + B, (size_t)B * 4, hipMemcpyDeviceToHost));
-  if (nj > 0) {
-    HIPCHK(c, hipMemcpy(a->junc, djunc, (size_t)nj * capJ * AIRFE_FEAT_DIM * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(a->njunc, dcnt + 2 * B, (size_t)nj * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(a->jfound, dcnt + 3 * B, (size_t)nj * 4, hipMemcpyDeviceToHost));
-  }
-  return 0;
+  return dbg_line_back(s, a, io);
 } AIRFE_CATCH(c)
 
 /* the line path between the stage-0 tensors and the line filter (include/airfe_debug.h): line_branch_dev's line_match, then line_tail_dev's line_dedup, line_tap_rows and
@@ -865,7 +901,7 @@ int airfe_debug_line_mid(airfe_ctx* c, airfe_debug_line_mid_args* a) try {
     if (!std::isfinite(a->juncs_pred[i])) return fail(c, "debug_line_mid: junction coordinates must be finite");
   for (size_t i = 0; i < (size_t)B * NP * 4; ++i)
     if (!std::isfinite(a->lines_pred[i])) return fail(c, "debug_line_mid: proposal coordinates must be finite");
-  hipStream_t st = c->stream;
+  HookStage s(c, "debug_line_mid");
   float* d = c->s0_stage;
   clear_saturation(c);
   // ---- staging: the stage block (juncs | lines_pred | iskeep | min | max | thin | aux), the pixel-major thin | aux copy; 0xFF everywhere the device writes
@@ -875,96 +911,85 @@ int airfe_debug_line_mid(airfe_ctx* c, airfe_debug_line_mid_args* a) try {
       const float* src = (ch < 4 ? a->thin : a->aux) + ((size_t)b * 4 + (ch & 3)) * NPX;
       for (int p = 0; p < NPX; ++p) ta8[((size_t)b * NPX + p) * 8 + ch] = src[p];
     }
-  HIPCHK(c, hipMemcpyAsync(c->l_ta8, ta8.data(), ta8.size() * 4, hipMemcpyHostToDevice, st));
-  for (int b = 0; b < B; ++b) {
-    float* s = d + (size_t)b * SG_STRIDE;
-    HIPCHK(c, hipMemcpyAsync(s + SG_JUNCS, a->juncs_pred + (size_t)b * 600, 600 * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(s + SG_LP, a->lines_pred + (size_t)b * NP * 4, (size_t)NP * 16, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(s + SG_THIN, a->thin + (size_t)b * 4 * NPX, (size_t)4 * NPX * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(s + SG_AUX, a->aux + (size_t)b * 4 * NPX, (size_t)4 * NPX * 4, hipMemcpyHostToDevice, st));
-    if (a->j2l == 0) {
-      HIPCHK(c, hipMemcpyAsync(s + SG_KEEP, a->iskeep_in + (size_t)b * NP, (size_t)NP * 4, hipMemcpyHostToDevice, st));
-      HIPCHK(c, hipMemcpyAsync(s + SG_MIN, a->idx_min_in + (size_t)b * NP, (size_t)NP * 4, hipMemcpyHostToDevice, st));
-      HIPCHK(c, hipMemcpyAsync(s + SG_MAX, a->idx_max_in + (size_t)b * NP, (size_t)NP * 4, hipMemcpyHostToDevice, st));
-    } else {
-      HIPCHK(c, hipMemsetAsync(s + SG_KEEP, 0xFF, (size_t)3 * NP * 4, st));          // (iskeep | min | max are one run of the block)
-    }
-  }
+  s.put(c->l_ta8, std::move(ta8));
+  const size_t blk = SG_STRIDE * 4, np4 = (size_t)NP * 4, pl4 = (size_t)4 * NPX * 4;      // one image's stage block, a kept-proposal row, four planes: in bytes
+  s.put2d(d + SG_JUNCS, blk, a->juncs_pred, 600 * 4, 600 * 4, B);
+  s.put2d(d + SG_LP, blk, a->lines_pred, np4 * 4, np4 * 4, B);
+  s.put2d(d + SG_THIN, blk, a->thin, pl4, pl4, B);
+  s.put2d(d + SG_AUX, blk, a->aux, pl4, pl4, B);
   static_assert(SG_MIN == SG_KEEP + KEEP_CAP && SG_MAX == SG_MIN + KEEP_CAP, "iskeep | min | max are contiguous");
+  if (a->j2l == 0) {
+    s.put2d(d + SG_KEEP, blk, a->iskeep_in, np4, np4, B);
+    s.put2d(d + SG_MIN, blk, a->idx_min_in, np4, np4, B);
+    s.put2d(d + SG_MAX, blk, a->idx_max_in, np4, np4, B);
+  } else {
+    for (int b = 0; b < B; ++b) s.fill(d + (size_t)b * SG_STRIDE + SG_KEEP, 0xFF, 3 * np4);          // (iskeep | min | max are one run of the block)
+  }
   const size_t L = (size_t)B;
-  HIPCHK(c, hipMemsetAsync(c->wf_counts, 0xFF, L * LINE_CNT_LD * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->wf_keep, 0xFF, L * KEEP_CAP * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->wf_pairs, 0xFF, L * LINE_CAP * 8, st));
-  HIPCHK(c, hipMemsetAsync(c->wf_rep, 0xFF, L * LINE_CAP * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->wf_prop, 0xFF, L * LINE_CAP * 16, st));
-  HIPCHK(c, hipMemsetAsync(c->s1_la, 0xFF, L * LINE_CAP * 16, st));
-  HIPCHK(c, hipMemsetAsync(c->s1_sc, 0xFF, L * LINE_CAP * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->s1_jfeat, 0xFF, L * 300 * 256 * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->l_ridx, 0xFF, L * 1200 * 4, st));
+  const DevSpan outs[9] = {{c->wf_counts, L * LINE_CNT_LD * 4}, {c->wf_keep, L * KEEP_CAP * 4}, {c->wf_pairs, L * LINE_CAP * 8}, {c->wf_rep, L * LINE_CAP * 4},
+                           {c->wf_prop, L * LINE_CAP * 16}, {c->s1_la, L * LINE_CAP * 16}, {c->s1_sc, L * LINE_CAP * 4}, {c->s1_jfeat, L * 300 * 256 * 4},
+                           {c->l_ridx, L * 1200 * 4}};
+  for (const DevSpan& e : outs) s.fill(e.p, 0xFF, e.bytes);
+  if (s.status()) return 1;
+  hipStream_t st = s.stream();
   // ---- line_branch_dev's match (line_match)
   c->wf_counted = false;                                     // (j2l = 0: the caller's match, which nothing has counted)
   if (a->j2l) line_match(c, B, a->j2l == 1, st);
-  if (a->j2l == 2 && !c->wf_counted) { (void)hipStreamSynchronize(st); return fail(c, "debug_line_mid: the cell search did not leave the per-workgroup counts (the line path's form)"); }
+  if (a->j2l == 2 && !c->wf_counted) return s.refuse("the cell search did not leave the per-workgroup counts (the line path's form)");
   // ---- line_tail_dev: the kept list and the unique pairs (line_dedup)
   line_dedup(c, B, st);
-  HIPCHK(c, hipStreamSynchronize(st));                       // (ta8 is on the device)
-  if (launch_status(c)) return 1;
-  HIPCHK(c, hipMemcpy(a->head4, c->s1_la, L * LINE_CAP * 16, hipMemcpyDeviceToHost));
-  if (form != 3) HIPCHK(c, hipMemsetAsync(c->s1_la, 0xFF, L * LINE_CAP * 16, st));      // stage 1 of forms 0 .. 2 writes lines_adjusted itself
+  s.wait();
+  s.get(a->head4, c->s1_la, L * LINE_CAP * 16);
+  if (form != 3) s.fill(c->s1_la, 0xFF, L * LINE_CAP * 16);      // stage 1 of forms 0 .. 2 writes lines_adjusted itself
   // ---- the junction projections and stage 1
-  std::vector<float> chw, head, lrows;                       // (staged with the stream's copies: alive until the synchronisation behind stage 1)
   if (form == 0) {
-    chw.resize((size_t)128 * NPX);
+    std::vector<float> chw((size_t)128 * NPX);
     for (int p = 0; p < NPX; ++p)
       for (int ch = 0; ch < 128; ++ch) chw[(size_t)ch * NPX + p] = a->loi[(size_t)p * 128 + ch];
-    HIPCHK(c, hipMemcpyAsync(c->s0_loi, chw.data(), chw.size() * 4, hipMemcpyHostToDevice, st));
+    s.put(c->s0_loi, std::move(chw));
   } else if (form == 1) {
-    head.resize((size_t)NPX * 160);
+    std::vector<float> head((size_t)NPX * 160);
     memset(head.data(), 0xFF, head.size() * 4);              // (columns 128 .. 159: the 17 decoded channels, which nothing behind stage 0 reads)
     for (int p = 0; p < NPX; ++p) memcpy(&head[(size_t)p * 160], a->loi + (size_t)p * 128, 128 * 4);
-    HIPCHK(c, hipMemcpyAsync(c->l_head, head.data(), head.size() * 4, hipMemcpyHostToDevice, st));
+    s.put(c->l_head, std::move(head));
   } else {
     const int M = B * 1200;
-    if (line_tap_rows(c, B, st)) return 1;
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (launch_status(c)) return 1;
-    std::vector<int> ridx((size_t)M);
-    HIPCHK(c, hipMemcpy(ridx.data(), c->l_ridx, ridx.size() * 4, hipMemcpyDeviceToHost));
-    lrows.resize((size_t)M * 128);
+    if (!s.status()) s.step(line_tap_rows(c, B, s.stream()));
+    s.wait();
+    const std::vector<int> ridx = s.get<int>(c->l_ridx, (size_t)M);
+    if (s.status()) return 1;
+    std::vector<float> lrows((size_t)M * 128);
     for (int r = 0; r < M; ++r) {                            // what the gather GEMM (line_loi_rows) hands on: row ridx[r] of the [B * 128*128][128] line-feature matrix
       const int b = r / 1200;
-      if (ridx[r] < b * NPX || ridx[r] >= (b + 1) * NPX) return fail(c, "debug_line_mid: launch_s1_junc_rows listed a row outside its image");
+      if (ridx[r] < b * NPX || ridx[r] >= (b + 1) * NPX) return s.refuse("launch_s1_junc_rows listed a row outside its image");
       memcpy(&lrows[(size_t)r * 128], a->loi + (size_t)ridx[r] * 128, 128 * 4);
     }
-    HIPCHK(c, hipMemcpyAsync(c->l_lrows, lrows.data(), lrows.size() * 4, hipMemcpyHostToDevice, st));
+    s.put(c->l_lrows, std::move(lrows));
   }
   static_assert(S1_CHW == 0 && S1_HEAD == 1 && S1_ROWS == 2 && S1_ROWS_H == 3, "s1_form (include/airfe_debug.h) is S1Form's first four");
-  line_stage1(c, B, form, a->wgs, st);
-  HIPCHK(c, hipStreamSynchronize(st));
-  if (launch_status(c)) return 1;
-  if (saturation_status(c)) return 1;
+  if (s.status()) return 1;
+  line_stage1(c, B, form, a->wgs, s.stream());
+  s.wait(HookStage::SATURATION);
   // ---- everything back as the device left it
-  const size_t np4 = (size_t)NP * 4;
-  HIPCHK(c, hipMemcpy2D(a->iskeep, np4, d + SG_KEEP, SG_STRIDE * 4, np4, B, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy2D(a->idx_min, np4, d + SG_MIN, SG_STRIDE * 4, np4, B, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy2D(a->idx_max, np4, d + SG_MAX, SG_STRIDE * 4, np4, B, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy2D(a->counts, 8, c->wf_counts, LINE_CNT_LD * 4, 8, B, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->keep, c->wf_keep, L * KEEP_CAP * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->pairs, c->wf_pairs, L * LINE_CAP * 8, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->rep, c->wf_rep, L * LINE_CAP * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->prop4, c->wf_prop, L * LINE_CAP * 16, hipMemcpyDeviceToHost));
-  if (form >= 2) HIPCHK(c, hipMemcpy(a->ridx, c->l_ridx, L * 1200 * 4, hipMemcpyDeviceToHost));
-  if (form >= 1) HIPCHK(c, hipMemcpy(a->proj, c->s1_jfeat, L * 300 * 256 * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->lines_adjusted, c->s1_la, L * LINE_CAP * 16, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->scores_line, c->s1_sc, L * LINE_CAP * 4, hipMemcpyDeviceToHost));
-  std::vector<int> table(L * 300 * 300);
-  HIPCHK(c, hipMemcpy(table.data(), c->wf_table, table.size() * 4, hipMemcpyDeviceToHost));
+  s.get2d(a->iskeep, np4, d + SG_KEEP, blk, np4, B);
+  s.get2d(a->idx_min, np4, d + SG_MIN, blk, np4, B);
+  s.get2d(a->idx_max, np4, d + SG_MAX, blk, np4, B);
+  s.get2d(a->counts, 8, c->wf_counts, LINE_CNT_LD * 4, 8, B);
+  s.get(a->keep, c->wf_keep, L * KEEP_CAP * 4);
+  s.get(a->pairs, c->wf_pairs, L * LINE_CAP * 8);
+  s.get(a->rep, c->wf_rep, L * LINE_CAP * 4);
+  s.get(a->prop4, c->wf_prop, L * LINE_CAP * 16);
+  if (form >= 2) s.get(a->ridx, c->l_ridx, L * 1200 * 4);
+  if (form >= 1) s.get(a->proj, c->s1_jfeat, L * 300 * 256 * 4);
+  s.get(a->lines_adjusted, c->s1_la, L * LINE_CAP * 16);
+  s.get(a->scores_line, c->s1_sc, L * LINE_CAP * 4);
+  const std::vector<int> table = s.get<int>(c->wf_table, L * 300 * 300);
   for (int b = 0; b < B; ++b) {
     int dirty = 0;
     for (size_t i = 0; i < (size_t)300 * 300; ++i) dirty += table[(size_t)b * 300 * 300 + i] != 0x7FFFFFFF;
     a->table_dirty[b] = dirty;
   }
-  return 0;
+  return s.status();
 } AIRFE_CATCH(c)
 
 /* the stage-0 decode (include/airfe_debug.h): line_branch_dev's steps line_decode_rows, line_head_decode, or line_head_gemm + line_decode_rows (fuse_dec = 0), on host head
@@ -988,57 +1013,48 @@ int airfe_debug_s0_decode(airfe_ctx* c, airfe_debug_s0_decode_args* a) try {
     if (a->wgs < 0 || a->wgs > 4096) return fail(c, "debug_s0_decode: wgs must lie in 0 .. 4096");
     if (a->want_loi) return fail(c, "debug_s0_decode: the CHW loi copy exists for the (ld 160, off 128) layout only");
   }
-  hipStream_t st = c->stream;
   float* d = c->s0_stage;
   clear_saturation(c);
-  DbgTmp t(mode ? a->prec : 0);
-  float* djnms = dbg_canary<float>(&t.h, (size_t)B * NPX);
-  if (!djnms) return fail(c, "debug_s0_decode: allocation failed");
+  HookStage s(c, "debug_s0_decode", mode ? a->prec : 0);
+  float* djnms = s.fresh<float>((size_t)B * NPX, 0xFF);
   float* jnms = a->want_jnms ? djnms : nullptr;
   // ---- every output 0xFF
-  HIPCHK(c, hipMemsetAsync(d, 0xFF, (size_t)B * SG_STRIDE * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->l_jloc, 0xFF, (size_t)B * NPX * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->l_joff, 0xFF, (size_t)B * 2 * NPX * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->l_ta8, 0xFF, (size_t)B * 8 * NPX * 4, st));
-  HIPCHK(c, hipMemsetAsync(c->s0_loi, 0xFF, (size_t)128 * NPX * 4, st));
-  std::vector<uint16_t> xin;                                 // (staged with the stream's copies: alive until the synchronisation behind the launches)
+  const DevSpan outs[6] = {{d, (size_t)B * SG_STRIDE * 4}, {c->l_jloc, (size_t)B * NPX * 4}, {c->l_joff, (size_t)B * 2 * NPX * 4}, {c->l_ta8, (size_t)B * 8 * NPX * 4},
+                           {c->s0_loi, (size_t)128 * NPX * 4}, {c->l_dec, mode == 2 ? (size_t)B * NPX * 32 * 4 : 0}};
+  for (const DevSpan& e : outs) s.fill(e.p, 0xFF, e.bytes);
   if (mode == 0) {
     const size_t n = (size_t)B * NPX * a->ld;
     float* head = a->ld == 32 ? c->l_dec : c->l_head;
-    if (a->ld == 160 && B > 1) {                             // (l_head holds one image)
-      head = dalloc<float>(&t.h, n, false);
-      if (!head) return fail(c, "debug_s0_decode: allocation failed");
-    }
-    HIPCHK(c, hipMemcpyAsync(head, a->rows, n * 4, hipMemcpyHostToDevice, st));
-    line_decode_rows(c, B, head, a->ld, a->off, jnms, a->want_ta8 != 0, a->want_loi != 0, st);
+    if (a->ld == 160 && B > 1) head = s.up(a->rows, n);      // (l_head holds one image)
+    else s.put(head, a->rows, n * 4);
+    if (s.status()) return 1;
+    line_decode_rows(c, B, head, a->ld, a->off, jnms, a->want_ta8 != 0, a->want_loi != 0, s.stream());
   } else {
     const size_t n = (size_t)B * NPX * 128;
-    xin.resize(n);
+    std::vector<uint16_t> xin(n);
     for (size_t i = 0; i < n; ++i) xin[i] = cvt2(a->x[i], a->prec);
     LinW lw;
-    if (!make_linear(&t.h, a->w, a->b, 128, 17, lw)) return fail(c, "debug_s0_decode: allocation failed");
-    HIPCHK(c, hipMemcpyAsync(c->l_feat, xin.data(), n * 2, hipMemcpyHostToDevice, st));
+    s.linear(a->w, a->b, 128, 17, lw);
+    s.put(c->l_feat, std::move(xin));
+    if (s.status()) return 1;
     if (mode == 1) {
-      line_head_decode(c, B, a->prec, lw, jnms, a->wgs, st);
+      line_head_decode(c, B, a->prec, lw, jnms, a->wgs, s.stream());
     } else {                                                 // (fuse_dec = 0: the 17-channel head as a GEMM, then the decode over its rows)
-      HIPCHK(c, hipMemsetAsync(c->l_dec, 0xFF, (size_t)B * NPX * 32 * 4, st));
-      line_head_gemm(c, B, false, a->prec, lw, st);
-      line_decode_rows(c, B, c->l_dec, 32, 0, jnms, true, false, st);
+      line_head_gemm(c, B, false, a->prec, lw, s.stream());
+      line_decode_rows(c, B, c->l_dec, 32, 0, jnms, true, false, s.stream());
     }
   }
-  HIPCHK(c, hipStreamSynchronize(st));                       // (xin goes out of scope)
-  if (launch_status(c)) return 1;
-  if (saturation_status(c)) return 1;
+  s.wait(HookStage::SATURATION);
   // ---- everything back as the device left it
-  HIPCHK(c, hipMemcpy(a->stage, d, (size_t)B * SG_STRIDE * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->jloc, c->l_jloc, (size_t)B * NPX * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->joff, c->l_joff, (size_t)B * 2 * NPX * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->jnms, djnms, (size_t)B * NPX * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->ta8, c->l_ta8, (size_t)B * 8 * NPX * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(a->loi, c->s0_loi, (size_t)128 * NPX * 4, hipMemcpyDeviceToHost));
-  if (mode == 2) HIPCHK(c, hipMemcpy(a->head_rows, c->l_dec, (size_t)B * NPX * 32 * 4, hipMemcpyDeviceToHost));
-  c->wf_counted = false;                                     // (the stage blocks no longer hold a line branch's match)
-  return 0;
+  s.get(a->stage, d, (size_t)B * SG_STRIDE * 4);
+  s.get(a->jloc, c->l_jloc, (size_t)B * NPX * 4);
+  s.get(a->joff, c->l_joff, (size_t)B * 2 * NPX * 4);
+  s.get(a->jnms, djnms, (size_t)B * NPX * 4);
+  s.get(a->ta8, c->l_ta8, (size_t)B * 8 * NPX * 4);
+  s.get(a->loi, c->s0_loi, (size_t)128 * NPX * 4);
+  if (mode == 2) s.get(a->head_rows, c->l_dec, (size_t)B * NPX * 32 * 4);
+  if (!s.status()) c->wf_counted = false;                    // (the stage blocks no longer hold a line branch's match)
+  return s.status();
 } AIRFE_CATCH(c)
 
 int airfe_debug_junctions_topk(airfe_ctx* c, const float* jloc, const float* joff, int B, float* juncs_pred) try {
@@ -1046,44 +1062,44 @@ int airfe_debug_junctions_topk(airfe_ctx* c, const float* jloc, const float* jof
   if (!c->has_s0 || !c->s0_stage) return fail(c, "debug_junctions_topk: the line branch is not loaded (line.* tensors, cfg.plnet_s1_pack)");
   if (!jloc || !joff || !juncs_pred || B < 1 || B > c->Lmax) return fail(c, "debug_junctions_topk: bad argument (1 <= B <= the arena's images)");
   const size_t npx = 128 * 128;
-  hipStream_t st = c->stream;
+  HookStage s(c, "debug_junctions_topk");
   clear_saturation(c);
-  HIPCHK(c, hipMemcpyAsync(c->l_jloc, jloc, (size_t)B * npx * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->l_joff, joff, (size_t)B * 2 * npx * 4, hipMemcpyHostToDevice, st));
-  junctions_topk_dev(c, B, st);
-  HIPCHK(c, hipStreamSynchronize(st));
-  if (launch_status(c)) return 1;
-  if (saturation_status(c)) return 1;
-  HIPCHK(c, hipMemcpy2D(juncs_pred, 600 * 4, c->s0_stage + SG_JUNCS, SG_STRIDE * 4, 600 * 4, B, hipMemcpyDeviceToHost));
-  return 0;
+  s.put(c->l_jloc, jloc, (size_t)B * npx * 4);
+  s.put(c->l_joff, joff, (size_t)B * 2 * npx * 4);
+  if (s.status()) return 1;
+  junctions_topk_dev(c, B, s.stream());
+  s.wait(HookStage::SATURATION);
+  s.get2d(juncs_pred, 600 * 4, c->s0_stage + SG_JUNCS, SG_STRIDE * 4, 600 * 4, B);
+  return s.status();
 } AIRFE_CATCH(c)
 
 int airfe_debug_detector_maps(airfe_ctx* c, int B, float* heat_raw, float* heat_nms, float* desc) try {
   if (c && enter_device(c)) return 1;
   if (!c || !c->has_sp || B > c->Dmax) return 1;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HookStage s(c, "debug_detector_maps");
   const size_t R = AIRFE_INTERNAL_SIZE;
-  if (heat_raw) HIPCHK(c, hipMemcpy(heat_raw, c->heat, (size_t)B * R * R * 4, hipMemcpyDeviceToHost));
+  if (s.wait()) return 1;
+  if (heat_raw) s.get(heat_raw, c->heat, (size_t)B * R * R * 4);
   if (heat_nms && c->cfg.nms_radius > 0 && !c->nms_map_valid) {      // the batch path skipped the dense map: rebuild it from the heat maps
     launch_nms512_candidates(c->heat, c->heat_nms, c->nms_mask, (int)B, c->cfg.keypoint_threshold, c->cfg.remove_borders, c->cand, c->cand_cnt,
-                             R * R, c->stream);          // (the map is only ever skipped on the radius-4 path)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+                             R * R, s.stream());         // (the map is only ever skipped on the radius-4 path)
+    if (s.wait()) return 1;
     c->nms_map_valid = true;
   }
-  if (heat_nms) HIPCHK(c, hipMemcpy(heat_nms, c->cfg.nms_radius > 0 ? c->heat_nms : c->heat, (size_t)B * R * R * 4, hipMemcpyDeviceToHost));
+  if (heat_nms) s.get(heat_nms, c->cfg.nms_radius > 0 ? c->heat_nms : c->heat, (size_t)B * R * R * 4);
   if (desc) {
     if (!c->desc_dense_valid) {     // the batch path ran the head on the sampled cells only: build the dense map from the kept activations
-      dense_desc_head(c, c->last_B, c->stream);
+      s.step(dense_desc_head(c, c->last_B, s.stream()));
       c->desc_dense_valid = true;
     }
-    if (!c->desc_normalised) {      // the inspection hook returns the map the reference would hold: normalised
-      launch_l2norm256(c->desc, c->Dmax * 64 * 64, c->stream);
-      HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (!c->desc_normalised && !s.status()) {      // the inspection hook returns the map the reference would hold: normalised
+      launch_l2norm256(c->desc, c->Dmax * 64 * 64, s.stream());
+      if (s.wait()) return 1;
       c->desc_normalised = true;
     }
-    HIPCHK(c, hipMemcpy(desc, c->desc, (size_t)B * 64 * 64 * 256 * 4, hipMemcpyDeviceToHost));
+    s.get(desc, c->desc, (size_t)B * 64 * 64 * 256 * 4);
   }
-  return 0;
+  return s.status();
 } AIRFE_CATCH(c)
 
 /* the on-device stage-0 line branch of the LAST detected image, copied out in the Appendix A.1 layouts (NULL = skip) */
@@ -1091,9 +1107,9 @@ int airfe_debug_plnet_stage0(airfe_ctx* c, float* juncs_pred, float* lines_pred,
                              float* loi, float* thin, float* aux, float* jloc, float* joff) try {
   if (c && enter_device(c)) return 1;
   if (!c || !c->has_s0 || !c->has_s1) return fail(c, "debug_plnet_stage0: line branch / stage 1 not loaded");
-  hipStream_t st = c->stream;
-  if (line_branch_dev(c, st, 0, 1, true)) return 1;
-  HIPCHK(c, hipStreamSynchronize(st));
+  HookStage s(c, "debug_plnet_stage0");
+  s.step(line_branch_dev(c, s.stream(), 0, 1, true));
+  s.wait();
   const size_t NP = KEEP_CAP;
   float* d = c->s0_stage;
   struct { float* h; const float* dv; size_t n; } cp[10] = {
@@ -1101,8 +1117,8 @@ int airfe_debug_plnet_stage0(airfe_ctx* c, float* juncs_pred, float* lines_pred,
       {idx_max, d + SG_MAX, NP}, {loi, c->s0_loi, (size_t)128 * 128 * 128}, {thin, d + SG_THIN, (size_t)4 * 128 * 128},
       {aux, d + SG_AUX, (size_t)4 * 128 * 128}, {jloc, c->l_jloc, (size_t)128 * 128}, {joff, c->l_joff, (size_t)2 * 128 * 128}};
   for (auto& e : cp)
-    if (e.h) HIPCHK(c, hipMemcpy(e.h, e.dv, e.n * 4, hipMemcpyDeviceToHost));
-  return 0;
+    if (e.h) s.get(e.h, e.dv, e.n * 4);
+  return s.status();
 } AIRFE_CATCH(c)
 
 /* the junction-to-line match of the LAST detected image as the line path runs it (fast = 1: cell search, exact where it is consumed) or
@@ -1110,50 +1126,47 @@ int airfe_debug_plnet_stage0(airfe_ctx* c, float* juncs_pred, float* lines_pred,
 int airfe_debug_plnet_j2l(airfe_ctx* c, int fast, float* iskeep, float* idx_min, float* idx_max) try {
   if (c && enter_device(c)) return 1;
   if (!c || !c->has_s0 || !c->has_s1) return fail(c, "debug_plnet_j2l: line branch / stage 1 not loaded");
-  hipStream_t st = c->stream;
-  if (line_branch_dev(c, st, 0, 1, fast == 0)) return 1;
-  HIPCHK(c, hipStreamSynchronize(st));
+  HookStage s(c, "debug_plnet_j2l");
+  s.step(line_branch_dev(c, s.stream(), 0, 1, fast == 0));
+  s.wait();
   const size_t NP = KEEP_CAP;
   float* d = c->s0_stage;
-  if (iskeep) HIPCHK(c, hipMemcpy(iskeep, d + SG_KEEP, NP * 4, hipMemcpyDeviceToHost));
-  if (idx_min) HIPCHK(c, hipMemcpy(idx_min, d + SG_MIN, NP * 4, hipMemcpyDeviceToHost));
-  if (idx_max) HIPCHK(c, hipMemcpy(idx_max, d + SG_MAX, NP * 4, hipMemcpyDeviceToHost));
-  return 0;
+  if (iskeep) s.get(iskeep, d + SG_KEEP, NP * 4);
+  if (idx_min) s.get(idx_min, d + SG_MIN, NP * 4);
+  if (idx_max) s.get(idx_max, d + SG_MAX, NP * 4);
+  return s.status();
 } AIRFE_CATCH(c)
+
+// stage 1's kept count, then that many lines_adjusted [k][4] + scores_line [k] rows (at most cap), after the hook's wait
+static int dbg_s1_rows(HookStage& s, airfe_ctx* c, float* lines_adjusted, float* scores_line, int cap, int* m2) {
+  int cnt[2] = {0, 0};
+  s.get(cnt, c->wf_counts, 8);
+  const int k = std::max(std::min(cnt[1], cap), 0);
+  s.get(lines_adjusted, c->s1_la, (size_t)k * 16);
+  s.get(scores_line, c->s1_sc, (size_t)k * 4);
+  if (!s.status()) *m2 = std::min(cnt[1], cap);
+  return s.status();
+}
 
 /* stage-1 alone on HOST stage-0 tensors: lines_adjusted [M2][4] + scores_line [M2] (parity vs the real plnet_s1.onnx) */
 int airfe_debug_plnet_s1(airfe_ctx* c, const airfe_plnet_stage0* s0, float* lines_adjusted, float* scores_line, int cap, int* m2) try {
   if (c && enter_device(c)) return 1;
   if (!c || !c->has_s1 || !s0) return fail(c, "debug_plnet_s1: stage-1 not loaded");
-  hipStream_t st = c->stream;
-  if (upload_stage0(c, s0, st)) return 1;
-  line_dedup(c, 1, st);                        // (upload_stage0 left wf_counted false: host tensors, nothing has counted their kept proposals)
-  line_stage1(c, 1, S1_CHW, 0, st);
-  int cnt[2] = {0, 0};
-  HIPCHK(c, hipMemcpyAsync(cnt, c->wf_counts, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  const int k = std::min(cnt[1], cap);
-  if (k > 0) {
-    HIPCHK(c, hipMemcpy(lines_adjusted, c->s1_la, (size_t)k * 16, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(scores_line, c->s1_sc, (size_t)k * 4, hipMemcpyDeviceToHost));
-  }
-  *m2 = k;
-  return 0;
+  HookStage s(c, "debug_plnet_s1");
+  s.step(upload_stage0(c, s0, s.stream()));
+  if (s.status()) return 1;
+  line_dedup(c, 1, s.stream());                // (upload_stage0 left wf_counted false: host tensors, nothing has counted their kept proposals)
+  line_stage1(c, 1, S1_CHW, 0, s.stream());
+  s.wait();
+  return dbg_s1_rows(s, c, lines_adjusted, scores_line, cap, m2);
 } AIRFE_CATCH(c)
 
 int airfe_debug_plnet_s1_last(airfe_ctx* c, float* lines_adjusted, float* scores_line, int cap, int* m2) try {
   if (c && enter_device(c)) return 1;
   if (!c || !c->has_s1 || !lines_adjusted || !scores_line || !m2) return fail(c, "debug_plnet_s1_last: stage-1 not loaded / bad argument");
-  HIPCHK(c, hipDeviceSynchronize());
-  int cnt[2] = {0, 0};
-  HIPCHK(c, hipMemcpy(cnt, c->wf_counts, 8, hipMemcpyDeviceToHost));
-  const int k = std::min(cnt[1], cap);
-  if (k > 0) {
-    HIPCHK(c, hipMemcpy(lines_adjusted, c->s1_la, (size_t)k * 16, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(scores_line, c->s1_sc, (size_t)k * 4, hipMemcpyDeviceToHost));
-  }
-  *m2 = k;
-  return 0;
+  HookStage s(c, "debug_plnet_s1_last");
+  s.wait(HookStage::DEVICE_WIDE);              // the last entry may have run the line path on the second stream
+  return dbg_s1_rows(s, c, lines_adjusted, scores_line, cap, m2);
 } AIRFE_CATCH(c)
 
 }  // extern "C"

@@ -3,7 +3,7 @@
 //   airfe_load.hip    weight-pack loading and slab packing (≙ TensorRT engine build, src/plnet.cpp:24-196), the matcher arena
 //   airfe_detect.hip  the detector pipeline (encoder, heads, NMS, top-K, descriptors)
 //   airfe_lines.hip   the PLNet line path: its steps, and line_branch_dev / line_tail_dev / line_post_dev composed of them
-//   airfe_match.hip   LightGlue / SuperGlue forwards, the fault-hunting trace and the matchers' host / batch entries
+//   airfe_match.hip   LightGlue / SuperGlue forwards, the fault-hunting trace and the matchers' host / batch entries (with the two *_scores hooks that are those entries)
 //   airfe.hip         context life cycle, scratch blocks, host staging, profiling / trace entries, sync and status, the BoW vocabulary and rectification entries
 //   airfe_frame.hip   the frame entries (include/airfe.h): detection, PLNet and stereo over host and device images, the stereo keyframe and track / promote /
 //                     adopt, with the pieces their queues and read-backs share
@@ -13,7 +13,7 @@
 //                     struct and the *_queue functions the next two files share with it)
 //   airfe_bowmap.hip  the database's map-point id table, the covisibility build and the map-point triangulation
 //   airfe_junction.hip  the junction connections, the database's junction tables, relocalisation's junction term and its composites
-//   airfe_debug.hip   the kernel-level test hooks (include/airfe_debug.h)
+//   airfe_debug.hip   the kernel-level test hooks (include/airfe_debug.h): HookStage, the one stream-ordered holder they stage, wait and read back through
 #pragma once
 #include "../../include/airfe.h"
 #include "../../include/airfe_debug.h"
@@ -115,7 +115,13 @@ struct KfGraph {
   KfState state{};
   void reset() { if (exec) (void)hipGraphExecDestroy(exec); exec = nullptr; seen = 0; }
 };
-struct airfe_ctx {
+// What dalloc / dupload / make_linear read of a context: its allocation list and the storage type make_linear packs for (set by each load_* before it packs).  A context
+// is one; a test hook's HookStage (airfe_debug.hip) owns a small one of its own, so that no hook needs a whole context to hold its allocations.
+struct DevAllocs {
+  std::vector<void*> allocs;
+  int pack_prec = 0;
+};
+struct airfe_ctx : DevAllocs {
   airfe_cfg cfg;
   std::string err;
   std::string launch_err;        // cfg.check_launches: the first failed launch since the last report, with its stage's name (launch_status())
@@ -130,10 +136,8 @@ struct airfe_ctx {
   hipStream_t stream2 = nullptr;         // airfe_stereo_plnet_batch_dev: the line branch runs here while the matcher runs on the caller's stream
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_feat = nullptr;
   bool overlap_lines = true;             // line path on stream2 beside the matcher (airfe_stereo_plnet_batch_dev); airfe_tuning::overlap_lines = 0: one stream
-  std::vector<void*> allocs;
   int prec = 0;                  // detector storage type
   int mprec = 1;                 // matcher storage type (cfg.matcher_precision)
-  int pack_prec = 0;             // storage type make_linear packs for (set by each load_* before it packs)
   int Bmax = 1, chunk = 1, Np = 64, Pmax = 1;
   int lgb_tokens = 0;            // airfe_tuning::lgb_tokens: forces the fused block's tokens per workgroup (32 / 64 / 112 / 128)
   // batch-1 host entries: ONE pinned host block and contiguous device blocks, so that a call is one H2D and one D2H (the reference's
@@ -360,7 +364,7 @@ int launch_status(airfe_ctx* c);
 int saturation_status(airfe_ctx* c);
 
 template <class T>
-T* dalloc(airfe_ctx* c, size_t n, bool zero = true) {
+T* dalloc(DevAllocs* c, size_t n, bool zero = true) {
   void* p = nullptr;
   if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return nullptr;
   if (zero) (void)hipMemset(p, 0, std::max<size_t>(n, 1) * sizeof(T));
@@ -368,7 +372,7 @@ T* dalloc(airfe_ctx* c, size_t n, bool zero = true) {
   return reinterpret_cast<T*>(p);
 }
 template <class T>
-T* dupload(airfe_ctx* c, const std::vector<T>& v) {
+T* dupload(DevAllocs* c, const std::vector<T>& v) {
   T* p = dalloc<T>(c, v.size(), false);
   if (p && !v.empty()) (void)hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
   return p;
@@ -392,7 +396,7 @@ inline float back2(uint16_t v, int prec) {
   memcpy(&f, &u, 4);
   return f;
 }
-bool make_linear(airfe_ctx* c, const float* W, const float* bias, int K, int N, LinW& out, float scale = 1.f,
+bool make_linear(DevAllocs* c, const float* W, const float* bias, int K, int N, LinW& out, float scale = 1.f,
                  const std::function<int(int)>* src_row = nullptr, const std::function<int(int)>* src_col = nullptr);
 // ---- airfe_detect.hip
 int ensure_tables(airfe_ctx* c, int h, int w);

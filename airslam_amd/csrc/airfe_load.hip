@@ -131,7 +131,7 @@ bool make_conv(airfe_ctx* c, const Pack& p, const std::string& name, int cin, in
 }
 
 // Linear y = W x + b with W [N][K] row-major; `src_row(feature)` lets callers permute / select output rows
-bool make_linear(airfe_ctx* c, const float* W, const float* bias, int K, int N, LinW& out, float scale,
+bool make_linear(DevAllocs* c, const float* W, const float* bias, int K, int N, LinW& out, float scale,
                  const std::function<int(int)>* src_row, const std::function<int(int)>* src_col) {
   const int Kp = (K + 63) / 64 * 64, cbt = (N + 63) / 64;
   const int cbp = (cbt + 3) & ~3;        // the GEMMs consume feature blocks in pairs / quads (128- / 256-feature tiles): zero pad

@@ -467,29 +467,6 @@ int airfe_debug_lightglue_scores(airfe_ctx* c, const float* f0, int n0, const fl
   return lg_host(c, f0, n0, f1, n1, nullptr, nullptr, 0, nullptr, scores);
 } AIRFE_CATCH(c)
 
-/* filter_matches (src/light_glue.cpp:214-266) alone on one HOST score matrix [n0][n1] */
-int airfe_debug_lg_filter(airfe_ctx* c, const float* scores, int n0, int n1, int32_t* idx, float* score, int cap, int* nmatch) try {
-  if (c && enter_device(c)) return 1;
-  if (!c || !c->has_arena) return fail(c, "debug_lg_filter: no matcher loaded");
-  if (n0 < 1 || n1 < 1 || n0 > c->cfg.max_keypoints || n1 > c->cfg.max_keypoints || !scores || !idx || !score || !nmatch)
-    return fail(c, "debug_lg_filter: bad argument");
-  const int lens[2] = {n0, n1};
-  HIPCHK(c, hipMemcpyAsync(c->lens, lens, 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpy2DAsync(c->simbuf, (size_t)c->Np * 4, scores, (size_t)n1 * 4, (size_t)n1 * 4, n0, hipMemcpyHostToDevice, c->stream));
-  launch_lg_filter_scores(c->simbuf, c->lens, 1, c->Np, c->Np, 0.1f, c->rowarg, c->rowval, c->colarg, c->st_idx, c->st_score,
-                          c->st_nm, c->stream);
-  int nm = 0;
-  HIPCHK(c, hipMemcpyAsync(&nm, c->st_nm, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  nm = std::min(nm, cap);
-  if (nm > 0) {
-    HIPCHK(c, hipMemcpy(idx, c->st_idx, (size_t)nm * 8, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(score, c->st_score, (size_t)nm * 4, hipMemcpyDeviceToHost));
-  }
-  *nmatch = nm;
-  return 0;
-} AIRFE_CATCH(c)
-
 int airfe_match_lightglue_batch_dev(airfe_ctx* c, const float* d_f0, const int* d_n0, const float* d_f1, const int* d_n1,
                                     int B, int cap, int32_t* d_idx, float* d_score, int mcap, int* d_nmatch, void* stream) try {
   AIRFE_ENTER(c);
@@ -527,61 +504,6 @@ int airfe_match_superglue(airfe_ctx* c, const float* f0, int n0, const float* f1
                           double* ms0, double* ms1) try {
   if (c && enter_device(c)) return 1;
   return sg_host(c, f0, n0, f1, n1, idx0, idx1, ms0, ms1, nullptr);
-} AIRFE_CATCH(c)
-
-/* decode (src/super_glue.cpp:339-367) alone on one HOST score matrix Z [n0+1][n1+1] */
-int airfe_debug_sg_decode(airfe_ctx* c, const float* Z, int n0, int n1, int32_t* idx0, int32_t* idx1, double* ms0, double* ms1) try {
-  if (c && enter_device(c)) return 1;
-  if (!c || !c->has_sg) return fail(c, "debug_sg_decode: SuperGlue not loaded");
-  if (n0 < 1 || n1 < 1 || n0 > c->cfg.max_keypoints || n1 > c->cfg.max_keypoints || !Z || !idx0 || !idx1 || !ms0 || !ms1)
-    return fail(c, "debug_sg_decode: bad argument");
-  const int lens[2] = {n0, n1};
-  HIPCHK(c, hipMemcpyAsync(c->lens, lens, 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpy2DAsync(c->sg_Z, (size_t)c->Lz * 4, Z, (size_t)(n1 + 1) * 4, (size_t)(n1 + 1) * 4, n0 + 1, hipMemcpyHostToDevice, c->stream));
-  launch_sg_decode(c->sg_Z, c->lens, 1, c->Np, c->Lz, 0.2f, c->sg_idx0, c->sg_max0, c->sg_idx1, c->sg_out0, c->sg_out1, c->sg_ms0,
-                   c->sg_ms1, c->stream);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  std::vector<float> m0(n0), m1(n1);
-  HIPCHK(c, hipMemcpy(idx0, c->sg_out0, (size_t)n0 * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(idx1, c->sg_out1, (size_t)n1 * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(m0.data(), c->sg_ms0, (size_t)n0 * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(m1.data(), c->sg_ms1, (size_t)n1 * 4, hipMemcpyDeviceToHost));
-  for (int i = 0; i < n0; ++i) ms0[i] = (double)m0[i];
-  for (int j = 0; j < n1; ++j) ms1[j] = (double)m1[j];
-  return 0;
-} AIRFE_CATCH(c)
-
-/* launch_sg_sinkhorn alone on B HOST coupling matrices (include/airfe_debug.h).  Everything of the arena outside each pair's valid n0 x n1 block is NaN when
-   the launch starts, and so is the output: a finite Z [0..n0][0..n1] was written in full and came from inside `lens` alone. */
-int airfe_debug_sg_sinkhorn(airfe_ctx* c, const float* sim, const int* lens, int B, int ld, float alpha, int iters, int form, float* Z, int* form_ran) try {
-  if (c && enter_device(c)) return 1;
-  if (!c || !c->has_sg) return fail(c, "debug_sg_sinkhorn: SuperGlue not loaded");
-  if (!sim || !lens || !Z || !form_ran || B < 1 || B > c->Pmax || ld < 1 || iters < 0 || form < 0 || form > 2)
-    return fail(c, "debug_sg_sinkhorn: bad argument (1 <= B <= max_batch, iters >= 0, form 0 / 1 / 2)");
-  const int nmax = std::min(ld, c->cfg.max_keypoints);
-  for (int i = 0; i < 2 * B; ++i)
-    if (lens[i] < 1 || lens[i] > nmax) return fail(c, "debug_sg_sinkhorn: every n0, n1 must lie in 1 .. min(ld, max_keypoints)");
-  *form_ran = 0;
-  const int Np = c->Np, Lz = c->Lz;
-  const size_t blk = (size_t)Np * Np, zblk = (size_t)Lz * Lz;
-  HIPCHK(c, hipMemcpyAsync(c->lens, lens, (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->simbuf, 0xFF, (size_t)B * blk * 4, c->stream));          // 0xFFFFFFFF: a NaN
-  HIPCHK(c, hipMemsetAsync(c->sg_Z, 0xFF, (size_t)B * zblk * 4, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->sg_xch, 0xFF, (size_t)B * Lz * 64 * 4, c->stream));      // [B][2][16][Lz] float2: a partial read before it was written is a NaN
-  for (int b = 0; b < B; ++b)
-    HIPCHK(c, hipMemcpy2DAsync(c->simbuf + b * blk, (size_t)Np * 4, sim + (size_t)b * ld * ld, (size_t)ld * 4, (size_t)lens[2 * b + 1] * 4, lens[2 * b],
-                               hipMemcpyHostToDevice, c->stream));
-  launch_sg_sinkhorn(c->simbuf, c->lens, B, Np, Lz, alpha, iters, c->sg_u, c->sg_v, c->sg_Z, c->sg_cnt, c->sg_cnt + (size_t)c->Pmax * 16, c->sg_xch, c->stream,
-                     form, form_ran);
-  if (*form_ran == 0)
-    return fail(c, "debug_sg_sinkhorn: form 2 asked for, but no register-resident instantiation applies to this context (max_keypoints, B against the co-resident "
-                   "workgroups) or the cooperative launch was refused");
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (launch_status(c) || sinkhorn_failed(c)) return 1;
-  for (int b = 0; b < B; ++b)
-    HIPCHK(c, hipMemcpy2D(Z + (size_t)b * (ld + 1) * (ld + 1), (size_t)(ld + 1) * 4, c->sg_Z + b * zblk, (size_t)Lz * 4, (size_t)(lens[2 * b + 1] + 1) * 4,
-                          lens[2 * b] + 1, hipMemcpyDeviceToHost));
-  return 0;
 } AIRFE_CATCH(c)
 
 /* SuperGlue on B pairs of DEVICE feature matrices (259-float rows, original pixel coordinates; NormalizeKeypoints with scale 0.7 on

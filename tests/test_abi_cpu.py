@@ -94,9 +94,9 @@ def test_every_c_entry_catches_exceptions():
     trivial = {"airfe_profile_stages", "airfe_has_line_branch", "airfe_debug_trace_slots"}      # one expression on plain ints / pointers
     found = set()
     for fname, catch, least in (("airfe.hip", "} AIRFE_CATCH(", 18), ("airfe_frame.hip", "} AIRFE_CATCH(", 12), ("airfe_assoc.hip", "} AIRFE_CATCH(", 4),
-                                ("airfe_match.hip", "} AIRFE_CATCH(", 9), ("airfe_geom.hip", "} AIRFE_CATCH(", 10), ("airfe_bowdb.hip", "} AIRFE_CATCH(", 27),
+                                ("airfe_match.hip", "} AIRFE_CATCH(", 6), ("airfe_geom.hip", "} AIRFE_CATCH(", 10), ("airfe_bowdb.hip", "} AIRFE_CATCH(", 27),
                                 ("airfe_bowmap.hip", "} AIRFE_CATCH(", 11), ("airfe_junction.hip", "} AIRFE_CATCH(", 9),
-                                ("airfe_debug.hip", "} AIRFE_CATCH(", 15), ("airfe_seq.hip", "} SEQ_CATCH(", 5)):
+                                ("airfe_debug.hip", "} AIRFE_CATCH(", 18), ("airfe_seq.hip", "} SEQ_CATCH(", 5)):
         src = open(os.path.join(ROOT, "airslam_amd", "csrc", fname)).read()
         body = src[src.index('extern "C" {'):]
         defs = re.findall(r"^int (airfe_[a-z0-9_]+)\([^;{]*?\)\s*(try)?\s*\{", body, flags=re.M | re.S)

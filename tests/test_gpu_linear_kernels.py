@@ -220,3 +220,39 @@ def test_forced_kernel_is_refused_not_replaced(prec):
                dict(epi=STORE_F32, kernel="small", rowidx=np.zeros(1024, np.int32))):
         with pytest.raises(AirfeError):
             ctx.debug_linear(x1, w, b, prec=prec, **kw)
+
+
+@PRECS
+def test_a_refused_form_leaves_nothing_behind(prec):
+    """M = 160 rows (one 128-row tile plus a 32-row remainder), K = 128, N = 64, EPI_STORE: the dispatched form, then the same data through a forced kernel with a
+    row list that the hook refuses AFTER it staged every operand (its uploads and 0xFF fills are queued on the context's stream when it returns the error), then the
+    first form again: byte-equal.  The refusal that comes after the staging is the kernel's own applicability test — gemmr_gather wants K = 256; kernel = "small" with
+    a row list is turned away by the argument checks, before anything is staged, with another text."""
+    from airslam_amd.api import AirfeError
+    ctx = _ctx()
+    M = 160
+    rng, x1, _, w, b = _data(prec, M, 128, 64, 23)
+    first = ctx.debug_linear(x1, w, b, prec=prec, epi=STORE, kernel="dispatch")
+    with pytest.raises(AirfeError, match="does not apply"):
+        ctx.debug_linear(x1, w, b, prec=prec, epi=STORE, kernel="gemmr_gather", rowidx=np.arange(M, dtype=np.int32))
+    again = ctx.debug_linear(x1, w, b, prec=prec, epi=STORE, kernel="dispatch")
+    assert np.isfinite(first).all()
+    assert first.tobytes() == again.tobytes()
+
+
+@PRECS
+def test_softmax_flag_belongs_to_its_call(prec):
+    """M = 16 (one image of 4 x 4 cells), K = 256, N = 65, three calls on one context — clean input, one inf in one cell, clean again: flags 0, 1, 0 (the flag word
+    is zero when each launch starts), the third heat map byte-equal to the first, the second equal to the first outside the bad cell's 8 x 8 block"""
+    ctx = _ctx()
+    hc = wc = 4
+    rng, x1, _, w, b = _data(prec, hc * wc, 256, 65, 29)
+    bad = x1.copy()
+    cy, cx = 2, 1
+    bad[cy * wc + cx, 7] = np.inf
+    (h0, f0), (h1, f1), (h2, f2) = (ctx.debug_linear(x, w, b, prec=prec, epi=SOFTMAX_D2S, d2s=(hc, wc)) for x in (x1, bad, x1))
+    assert (f0, f1, f2) == (0, 1, 0)
+    assert h2.tobytes() == h0.tobytes()
+    keep = np.ones(h0.shape, bool)
+    keep[0, cy * 8:cy * 8 + 8, cx * 8:cx * 8 + 8] = False
+    assert np.array_equal(h1[keep], h0[keep])

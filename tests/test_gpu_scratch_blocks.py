@@ -7,7 +7,7 @@ Batch 1 and batch 3 are the pair to check.  Every part of a block starts on a 25
 one at which every block that exists grows again.  airfe_frame_optimize_batch_dev has no scratch of its own: it runs here as the other half of
 airfe_track_pose_opt_batch_dev, whose three blocks (gather, constraints, the PnP scratch) all grow.
 
-The debug hooks whose device allocations moved into the one RAII holder (csrc/airfe_debug.hip: DbgTmp) are covered by the tests that were there already, each
+The debug hooks whose device allocations moved into the one RAII holder (csrc/airfe_debug.hip: HookStage) are covered by the tests that were there already, each
 on its error returns and on its results: airfe_debug_linear and airfe_debug_qkv by tests/test_gpu_linear_kernels.py, airfe_debug_lg_block and
 airfe_debug_ln_gelu by tests/test_gpu_lg_block.py, airfe_debug_gemm by tests/test_gpu_kernels.py."""
 import numpy as np
