@@ -53,11 +53,10 @@ constexpr float ATT_QK_FOLD = 0.42466090014400953f;
 
 struct ConvW { uint16_t* w = nullptr; float* b = nullptr; int cin = 0, cout = 0; };
 struct LinW { uint16_t* w = nullptr; float* b = nullptr; int K = 0, N = 0, cbt = 0; uint16_t* wf = nullptr; /* the same weights in MFMA fragment order (make_linear) */ };
-struct LgLayer {
-  LinW qk, v, out, ffn0, ffn3, cqk, cv, cout, cffn0, cffn3;
-  float *ln_g = nullptr, *ln_b = nullptr, *cln_g = nullptr, *cln_b = nullptr;
-};
-struct SgLayer { LinW qk, v, merge, mlp0, mlp3; };
+// One residual block of either matcher: q | k and v projections, attention, out-projection, 512-wide MLP, residual.  LightGlue's cross half has ONE 256-row projection
+// for q and k (qk.N = 256: the two sides swap roles); ln_g = nullptr is the ReLU form (SuperGlue: merge, mlp.0 + ReLU, mlp.3), else LayerNorm + GELU.
+struct AttnBlock { LinW qk, v, out, ffn0, ffn3; float *ln_g = nullptr, *ln_b = nullptr; };
+struct LgLayer { AttnBlock self, cross; };
 constexpr int LINE_CAP = 45056;     // unique candidate lines per image: 300 junctions give at most 300 * 299 / 2 = 44850 (min, max) pairs
 constexpr int KEEP_CAP = 3 * 128 * 128;
 constexpr int JUNC_CAP = 2048;
@@ -238,7 +237,7 @@ struct airfe_ctx : DevAllocs {
 
   // SuperGlue
   bool has_sg = false;
-  std::vector<SgLayer> sg;
+  std::vector<AttnBlock> sg;
   LinW sg_final;
   float sg_alpha = 1.f;
   const float* sg_kenc[10] = {nullptr};
@@ -253,12 +252,14 @@ struct airfe_ctx : DevAllocs {
   // fp32 correctness path (cfg.precision = 2 / matcher_precision = 2): fp32 weights and activations, kernels_f32.hip
   struct F32Conv { float* w = nullptr; float* b = nullptr; int cin = 0, cout = 0; };
   struct F32Lin { float* w = nullptr; float* b = nullptr; int K = 0, N = 0; };
-  struct F32LgLayer { F32Lin qkv, out, ffn0, ffn3, cqk, cv, cout, cffn0, cffn3; float *ln_g, *ln_b, *cln_g, *cln_b; };
+  // AttnBlock in fp32.  An absent v (v.w = nullptr) means v's rows are in qk: ONE 768-row q | k | v matrix, rows head-major (LightGlue's self half, SuperGlue, whose
+  // out-projection also has its input columns head-major); LightGlue's cross half has its 256-row q = k matrix and v.
+  struct F32Block { F32Lin qk, v, out, ffn0, ffn3; float *ln_g = nullptr, *ln_b = nullptr; };
+  struct F32LgLayer { F32Block self, cross; };
   F32Conv f_c1b, f_c2a, f_c2b, f_c3a, f_c3b, f_c4a, f_c4b, f_cPa, f_cDa, f_cL1;
-  struct F32SgLayer { F32Lin qkv, merge, mlp0, mlp3; };      // SuperGlue GNN layer: q | k | v rows head-major, merge's input columns head-major
   F32Lin f_cPb, f_cDb, f_cLh, f_lgfinal, f_sgfinal;
   std::vector<F32LgLayer> f_lg;
-  std::vector<F32SgLayer> f_sg;
+  std::vector<F32Block> f_sg;
   int f_B = 0;                   // images per pass of the fp32 encoder (its activations are 4 bytes: 2 images at a time)
   float *f1a = nullptr, *f1b = nullptr, *fp1 = nullptr, *f2a = nullptr, *f2b = nullptr, *fp2 = nullptr, *f3a = nullptr, *f3b = nullptr,
         *fp3 = nullptr, *f4a = nullptr, *f4b = nullptr, *fPa = nullptr, *fDa = nullptr, *fL1 = nullptr;

@@ -111,6 +111,14 @@ const Tensor* need(const Pack& p, const std::string& name, std::string& err) {
   if (it == p.end()) { err = "weight pack is missing tensor " + name; return nullptr; }
   return &it->second;
 }
+// weight and bias of the Linear `name`, [N][K] and [N]
+static bool need_linear(const Pack& p, const std::string& name, int K, int N, const Tensor*& w, const Tensor*& b, std::string& err) {
+  w = need(p, name + ".weight", err);
+  b = need(p, name + ".bias", err);
+  if (!w || !b) return false;
+  if ((int)w->data.size() != N * K || (int)b->data.size() != N) { err = name + ": unexpected shape"; return false; }
+  return true;
+}
 
 bool make_conv(airfe_ctx* c, const Pack& p, const std::string& name, int cin, int cout, ConvW& out, std::string& err) {
   const Tensor* w = need(p, name + ".weight", err);
@@ -172,11 +180,8 @@ bool make_linear(DevAllocs* c, const float* W, const float* bias, int K, int N, 
 
 bool make_linear_named(airfe_ctx* c, const Pack& p, const std::string& name, int K, int N, LinW& out, std::string& err,
                        float scale = 1.f) {
-  const Tensor* w = need(p, name + ".weight", err);
-  const Tensor* b = need(p, name + ".bias", err);
-  if (!w || !b) return false;
-  if ((int)w->data.size() != N * K || (int)b->data.size() != N) { err = name + ": unexpected shape"; return false; }
-  return make_linear(c, w->data.data(), b->data.data(), K, N, out, scale);
+  const Tensor *w, *b;
+  return need_linear(p, name, K, N, w, b, err) && make_linear(c, w->data.data(), b->data.data(), K, N, out, scale);
 }
 
 // airfe_tuning::fold_out_proj.  A block computes  h = W1 cat(x, msg) + b1  with  msg = Wo a + bo  (a = the attention output) and nothing between the two
@@ -203,6 +208,40 @@ bool make_ffn0_folded(airfe_ctx* c, const Tensor& w1, const Tensor& b1, const Te
     B[n] = (float)bacc;
   }
   return make_linear(c, W.data(), B.data(), 512, 512, out, 1.f);
+}
+
+// ---- what the attention blocks of both matchers share, in either precision (AttnBlock / F32Block, airfe_host.h)
+// SuperGlue's MultiHeadedAttention views its channels as (dim, heads) — channel = d * 4 + h — while the attention kernels want a head's 64 features side by side:
+// head-major feature h * 64 + d -> the pack's channel (its q / k / v ROWS and merge's input COLUMNS go through this)
+static const std::function<int(int)> hm = [](int f) { return (f & 63) * 4 + (f >> 6); };
+// LightGlue's Wqkv output index = h * 192 + d * 3 + {q, k, v} (qkv.unflatten(-1, (H, -1, 3))): row of [q(h, d) | k(h, d) | v(h, d)] -> the pack's; v alone starts at 512
+static const std::function<int(int)> qkv_row = [](int f) { const int sel = f >> 8, hd = f & 255; return (hd >> 6) * 192 + (hd & 63) * 3 + sel; };
+static const std::function<int(int)> v_row = [](int f) { return qkv_row(512 + f); };
+// the tensors behind a block's attention: out-projection, the MLP's two linears and, LightGlue only, the LayerNorm between them
+struct BlockNames { std::string out, f0, f3, ln; };
+static BlockNames lg_names(int i, const char* half, const char* out) {
+  const std::string a = "transformers." + std::to_string(i) + half;
+  return {a + out, a + ".ffn.0", a + ".ffn.3", a + ".ffn.1"};
+}
+static BlockNames sg_names(const std::string& g) { return {g + ".attn.merge", g + ".mlp.0", g + ".mlp.3", ""}; }
+
+// out-projection (its input columns in the order `wo_col` gives: the order of the caller's attention output), ffn.0 — under fold_out multiplied with the
+// out-projection (make_ffn0_folded) —, ffn.3 and the LayerNorm pair of one block, uploaded in that order
+static bool load_block_tail(airfe_ctx* c, const Pack& p, const BlockNames& n, const std::function<int(int)>* wo_col, AttnBlock& b, std::string& err) {
+  const Tensor *wo, *bo;
+  bool ok = need_linear(p, n.out, 256, 256, wo, bo, err) && make_linear(c, wo->data.data(), bo->data.data(), 256, 256, b.out, 1.f, nullptr, wo_col);      // (stays packed under fold_out: nothing runs it in this context, airfe_debug hooks may)
+  if (c->fold_out) {
+    const Tensor *w1 = need(p, n.f0 + ".weight", err), *b1 = need(p, n.f0 + ".bias", err);
+    ok = ok && w1 && b1 && make_ffn0_folded(c, *w1, *b1, *wo, *bo, b.ffn0, err, wo_col);
+  } else {
+    ok = ok && make_linear_named(c, p, n.f0, 512, 512, b.ffn0, err);
+  }
+  ok = ok && make_linear_named(c, p, n.f3, 512, 256, b.ffn3, err);
+  if (!ok || n.ln.empty()) return ok;
+  const Tensor *g = need(p, n.ln + ".weight", err), *be = need(p, n.ln + ".bias", err);
+  if (!g || !be) return false;
+  b.ln_g = dupload(c, g->data); b.ln_b = dupload(c, be->data);
+  return true;
 }
 
 // OpenCV resize() INTER_LINEAR coefficient table (imgproc/src/resize.cpp) -> [d][4] = s0, s1, a0, a1
@@ -236,22 +275,33 @@ bool f32_conv(airfe_ctx* c, const Pack& p, const std::string& name, int cin, int
   out.w = dupload(c, t); out.b = dupload(c, b->data); out.cin = cin; out.cout = cout;
   return out.w && out.b;
 }
-bool f32_lin(airfe_ctx* c, const float* W, const float* bias, int K, int N, airfe_ctx::F32Lin& out, const std::function<int(int)>* src_row = nullptr) {
+bool f32_lin(airfe_ctx* c, const float* W, const float* bias, int K, int N, airfe_ctx::F32Lin& out, const std::function<int(int)>* src_row = nullptr,
+             const std::function<int(int)>* src_col = nullptr) {
   std::vector<float> w((size_t)N * K), b(N);
   for (int n = 0; n < N; ++n) {
     const int r = src_row ? (*src_row)(n) : n;
-    memcpy(&w[(size_t)n * K], W + (size_t)r * K, (size_t)K * 4);
+    if (!src_col) memcpy(&w[(size_t)n * K], W + (size_t)r * K, (size_t)K * 4);
+    else for (int k = 0; k < K; ++k) w[(size_t)n * K + k] = W[(size_t)r * K + (*src_col)(k)];
     b[n] = bias[r];
   }
   out.w = dupload(c, w); out.b = dupload(c, b); out.K = K; out.N = N;
   return out.w && out.b;
 }
-bool f32_lin_named(airfe_ctx* c, const Pack& p, const std::string& name, int K, int N, airfe_ctx::F32Lin& out, std::string& err) {
-  const Tensor* w = need(p, name + ".weight", err);
-  const Tensor* b = need(p, name + ".bias", err);
-  if (!w || !b) return false;
-  if ((int)w->data.size() != N * K || (int)b->data.size() != N) { err = name + ": unexpected shape"; return false; }
-  return f32_lin(c, w->data.data(), b->data.data(), K, N, out);
+bool f32_lin_named(airfe_ctx* c, const Pack& p, const std::string& name, int K, int N, airfe_ctx::F32Lin& out, std::string& err,
+                   const std::function<int(int)>* src_row = nullptr, const std::function<int(int)>* src_col = nullptr) {
+  const Tensor *w, *b;
+  return need_linear(p, name, K, N, w, b, err) && f32_lin(c, w->data.data(), b->data.data(), K, N, out, src_row, src_col);
+}
+// load_block_tail in fp32 (nothing is folded there)
+static bool f32_block_tail(airfe_ctx* c, const Pack& p, const BlockNames& n, const std::function<int(int)>* wo_col, airfe_ctx::F32Block& b, std::string& err) {
+  if (!f32_lin_named(c, p, n.out, 256, 256, b.out, err, nullptr, wo_col) || !f32_lin_named(c, p, n.f0, 512, 512, b.ffn0, err) ||
+      !f32_lin_named(c, p, n.f3, 512, 256, b.ffn3, err))
+    return false;
+  if (n.ln.empty()) return true;
+  const Tensor *g = need(p, n.ln + ".weight", err), *be = need(p, n.ln + ".bias", err);
+  if (!g || !be) return false;
+  b.ln_g = dupload(c, g->data); b.ln_b = dupload(c, be->data);
+  return true;
 }
 
 int load_superpoint_f32(airfe_ctx* c, const Pack& p) {
@@ -286,21 +336,12 @@ int load_lightglue_f32(airfe_ctx* c, const Pack& p, int L) {
   std::string err;
   c->f_lg.resize(L);
   bool ok = true;
-  // Wqkv output index = h*192 + d*3 + {q,k,v}  ->  rows [q(h,d) | k(h,d) | v(h,d)]
-  std::function<int(int)> qkv_row = [](int f) { const int sel = f >> 8, hd = f & 255; return (hd >> 6) * 192 + (hd & 63) * 3 + sel; };
   for (int i = 0; i < L && ok; ++i) {
     auto& l = c->f_lg[i];
     const std::string s = "transformers." + std::to_string(i) + ".self_attn", x = "transformers." + std::to_string(i) + ".cross_attn";
-    const Tensor *wq = need(p, s + ".Wqkv.weight", err), *bq = need(p, s + ".Wqkv.bias", err);
-    const Tensor *g1 = need(p, s + ".ffn.1.weight", err), *b1 = need(p, s + ".ffn.1.bias", err);
-    const Tensor *g2 = need(p, x + ".ffn.1.weight", err), *b2 = need(p, x + ".ffn.1.bias", err);
-    if (!wq || !bq || !g1 || !b1 || !g2 || !b2) { ok = false; break; }
-    ok = f32_lin(c, wq->data.data(), bq->data.data(), 256, 768, l.qkv, &qkv_row) && f32_lin_named(c, p, s + ".out_proj", 256, 256, l.out, err) &&
-         f32_lin_named(c, p, s + ".ffn.0", 512, 512, l.ffn0, err) && f32_lin_named(c, p, s + ".ffn.3", 512, 256, l.ffn3, err) &&
-         f32_lin_named(c, p, x + ".to_qk", 256, 256, l.cqk, err) && f32_lin_named(c, p, x + ".to_v", 256, 256, l.cv, err) &&
-         f32_lin_named(c, p, x + ".to_out", 256, 256, l.cout, err) && f32_lin_named(c, p, x + ".ffn.0", 512, 512, l.cffn0, err) &&
-         f32_lin_named(c, p, x + ".ffn.3", 512, 256, l.cffn3, err);
-    l.ln_g = dupload(c, g1->data); l.ln_b = dupload(c, b1->data); l.cln_g = dupload(c, g2->data); l.cln_b = dupload(c, b2->data);
+    ok = f32_lin_named(c, p, s + ".Wqkv", 256, 768, l.self.qk, err, &qkv_row) && f32_block_tail(c, p, lg_names(i, ".self_attn", ".out_proj"), nullptr, l.self, err) &&
+         f32_lin_named(c, p, x + ".to_qk", 256, 256, l.cross.qk, err) && f32_lin_named(c, p, x + ".to_v", 256, 256, l.cross.v, err) &&
+         f32_block_tail(c, p, lg_names(i, ".cross_attn", ".to_out"), nullptr, l.cross, err);
   }
   ok = ok && f32_lin_named(c, p, "log_assignment." + std::to_string(L - 1) + ".final_proj", 256, 256, c->f_lgfinal, err);
   if (!ok) return fail(c, err.empty() ? "device allocation failed while loading fp32 LightGlue weights" : err);
@@ -317,35 +358,25 @@ int alloc_matcher_arena_f32(airfe_ctx* c) {
   return 0;
 }
 
-// SuperGlue in fp32 (cfg.matcher_precision = 2): the GNN's linears as plain [N][K] fp32 matrices.  MultiHeadedAttention views its channels as
-// (dim, heads) — channel = d * 4 + h — while the attention kernel wants a head's 64 features side by side: the q / k / v ROWS and merge's input
-// COLUMNS are permuted to head-major here (the same permutation the 2-byte loader applies, load_superglue below), nothing else changes.
+// SuperGlue in fp32 (cfg.matcher_precision = 2): the GNN's linears as plain [N][K] fp32 matrices, q | k | v as one, their ROWS and merge's input COLUMNS head-major
+// (hm: the same permutation the 2-byte loader applies, load_superglue below), nothing else changes.
 int load_superglue_f32(airfe_ctx* c, const Pack& p, int L) {
   std::string err;
-  const auto hm = [](int f) { return (f & 63) * 4 + (f >> 6); };
   c->f_sg.resize(L);
   bool ok = true;
   for (int i = 0; i < L && ok; ++i) {
     auto& l = c->f_sg[i];
     const std::string g = "gnn.layers." + std::to_string(i);
-    const Tensor *w[3], *b[3];
-    for (int j = 0; j < 3; ++j) {
-      w[j] = need(p, g + ".attn.proj." + std::to_string(j) + ".weight", err);
-      b[j] = need(p, g + ".attn.proj." + std::to_string(j) + ".bias", err);
-      if (!w[j] || !b[j] || w[j]->data.size() != 256 * 256 || b[j]->data.size() != 256) { ok = false; break; }
-    }
-    const Tensor *wm = need(p, g + ".attn.merge.weight", err), *bm = need(p, g + ".attn.merge.bias", err);
-    if (!ok || !wm || !bm || wm->data.size() != 256 * 256 || bm->data.size() != 256) { ok = false; break; }
-    std::vector<float> wqkv((size_t)768 * 256), bqkv(768), wmp((size_t)256 * 256);
-    for (int j = 0; j < 3; ++j)
-      for (int f = 0; f < 256; ++f) {
-        memcpy(&wqkv[((size_t)j * 256 + f) * 256], &w[j]->data[(size_t)hm(f) * 256], 1024);
-        bqkv[j * 256 + f] = b[j]->data[hm(f)];
+    std::vector<float> wqkv((size_t)768 * 256), bqkv(768);
+    for (int j = 0; j < 3 && ok; ++j) {
+      const Tensor *w, *b;
+      ok = need_linear(p, g + ".attn.proj." + std::to_string(j), 256, 256, w, b, err);
+      for (int f = 0; ok && f < 256; ++f) {
+        memcpy(&wqkv[((size_t)j * 256 + f) * 256], &w->data[(size_t)hm(f) * 256], 1024);
+        bqkv[j * 256 + f] = b->data[hm(f)];
       }
-    for (int n = 0; n < 256; ++n)
-      for (int f = 0; f < 256; ++f) wmp[(size_t)n * 256 + f] = wm->data[(size_t)n * 256 + hm(f)];
-    ok = f32_lin(c, wqkv.data(), bqkv.data(), 256, 768, l.qkv) && f32_lin(c, wmp.data(), bm->data.data(), 256, 256, l.merge) &&
-         f32_lin_named(c, p, g + ".mlp.0", 512, 512, l.mlp0, err) && f32_lin_named(c, p, g + ".mlp.3", 512, 256, l.mlp3, err);
+    }
+    ok = ok && f32_lin(c, wqkv.data(), bqkv.data(), 256, 768, l.qk) && f32_block_tail(c, p, sg_names(g), &hm, l, err);
   }
   ok = ok && f32_lin_named(c, p, "final_proj", 256, 256, c->f_sgfinal, err);
   if (!ok) return fail(c, err.empty() ? "SuperGlue (fp32): unexpected shapes or device allocation failed" : err);
@@ -448,37 +479,14 @@ int load_lightglue(airfe_ctx* c, const char* path) {
   bool ok = true;
   for (int i = 0; i < L && ok; ++i) {
     LgLayer& l = c->lg[i];
-    const std::string s = "transformers." + std::to_string(i) + ".self_attn";
-    const std::string x = "transformers." + std::to_string(i) + ".cross_attn";
-    const Tensor* wqkv = need(p, s + ".Wqkv.weight", err);
-    const Tensor* bqkv = need(p, s + ".Wqkv.bias", err);
-    if (!wqkv || !bqkv || wqkv->data.size() != 768 * 256) { ok = false; break; }
-    // Wqkv output index = h*192 + d*3 + {q,k,v}  (qkv.unflatten(-1,(H,-1,3)))  ->  [q(h,d) | k(h,d)] and v(h,d)
-    std::function<int(int)> qk_row = [](int f) { const int sel = f >> 8, hd = f & 255; return (hd >> 6) * 192 + (hd & 63) * 3 + sel; };
-    std::function<int(int)> v_row = [](int f) { return (f >> 6) * 192 + (f & 63) * 3 + 2; };
-    ok = ok && make_linear(c, wqkv->data.data(), bqkv->data.data(), 256, 512, l.qk, ATT_QK_FOLD, &qk_row);
-    ok = ok && make_linear(c, wqkv->data.data(), bqkv->data.data(), 256, 256, l.v, 1.f, &v_row);
-    ok = ok && make_linear_named(c, p, s + ".out_proj", 256, 256, l.out, err);
-    if (c->fold_out) {         // (l.out / l.cout stay packed: nothing runs them in this context, airfe_debug hooks may)
-      const Tensor *w1 = need(p, s + ".ffn.0.weight", err), *b1f = need(p, s + ".ffn.0.bias", err), *wo = need(p, s + ".out_proj.weight", err), *bo = need(p, s + ".out_proj.bias", err);
-      ok = ok && w1 && b1f && wo && bo && make_ffn0_folded(c, *w1, *b1f, *wo, *bo, l.ffn0, err);
-    } else
-    ok = ok && make_linear_named(c, p, s + ".ffn.0", 512, 512, l.ffn0, err);
-    ok = ok && make_linear_named(c, p, s + ".ffn.3", 512, 256, l.ffn3, err);
-    ok = ok && make_linear_named(c, p, x + ".to_qk", 256, 256, l.cqk, err, ATT_QK_FOLD);
-    ok = ok && make_linear_named(c, p, x + ".to_v", 256, 256, l.cv, err);
-    ok = ok && make_linear_named(c, p, x + ".to_out", 256, 256, l.cout, err);
-    if (c->fold_out) {
-      const Tensor *w1 = need(p, x + ".ffn.0.weight", err), *b1f = need(p, x + ".ffn.0.bias", err), *wo = need(p, x + ".to_out.weight", err), *bo = need(p, x + ".to_out.bias", err);
-      ok = ok && w1 && b1f && wo && bo && make_ffn0_folded(c, *w1, *b1f, *wo, *bo, l.cffn0, err);
-    } else
-    ok = ok && make_linear_named(c, p, x + ".ffn.0", 512, 512, l.cffn0, err);
-    ok = ok && make_linear_named(c, p, x + ".ffn.3", 512, 256, l.cffn3, err);
-    const Tensor *g1 = need(p, s + ".ffn.1.weight", err), *b1 = need(p, s + ".ffn.1.bias", err);
-    const Tensor *g2 = need(p, x + ".ffn.1.weight", err), *b2 = need(p, x + ".ffn.1.bias", err);
-    if (!g1 || !b1 || !g2 || !b2) { ok = false; break; }
-    l.ln_g = dupload(c, g1->data); l.ln_b = dupload(c, b1->data);
-    l.cln_g = dupload(c, g2->data); l.cln_b = dupload(c, b2->data);
+    const std::string s = "transformers." + std::to_string(i) + ".self_attn", x = "transformers." + std::to_string(i) + ".cross_attn";
+    const Tensor *wqkv, *bqkv;
+    ok = need_linear(p, s + ".Wqkv", 256, 768, wqkv, bqkv, err) &&
+         make_linear(c, wqkv->data.data(), bqkv->data.data(), 256, 512, l.self.qk, ATT_QK_FOLD, &qkv_row) &&
+         make_linear(c, wqkv->data.data(), bqkv->data.data(), 256, 256, l.self.v, 1.f, &v_row) &&
+         load_block_tail(c, p, lg_names(i, ".self_attn", ".out_proj"), nullptr, l.self, err) &&
+         make_linear_named(c, p, x + ".to_qk", 256, 256, l.cross.qk, err, ATT_QK_FOLD) && make_linear_named(c, p, x + ".to_v", 256, 256, l.cross.v, err) &&
+         load_block_tail(c, p, lg_names(i, ".cross_attn", ".to_out"), nullptr, l.cross, err);
   }
   const std::string a = "log_assignment." + std::to_string(L - 1);
   ok = ok && make_linear_named(c, p, a + ".final_proj", 256, 256, c->lg_final, err, 0.25f /* d^-1/4, d = 256 */);
@@ -558,18 +566,14 @@ int load_superglue(airfe_ctx* c, const char* path) {
   // the two large layers also as packed MFMA operands (large batches: launch_sg_prepare with h128, then two GEMMs)
   if (!make_linear_named(c, p, "kenc.encoder.3", 128, 256, c->sg_k3, err) || !make_linear_named(c, p, "kenc.encoder.4", 256, 256, c->sg_k4, err))
     return fail(c, err.empty() ? "kenc: packing failed" : err);
-  // MultiHeadedAttention views channels as (dim, heads): channel = d*4 + h  ->  our head-major h*64 + d
-  std::function<int(int)> hm = [](int f) { return (f & 63) * 4 + (f >> 6); };
   c->sg.resize(L);
   bool ok = true;
   for (int i = 0; i < L && ok; ++i) {
-    SgLayer& l = c->sg[i];
+    AttnBlock& l = c->sg[i];
     const std::string g = "gnn.layers." + std::to_string(i);
-    const Tensor *wq = need(p, g + ".attn.proj.0.weight", err), *bq = need(p, g + ".attn.proj.0.bias", err);
-    const Tensor *wk = need(p, g + ".attn.proj.1.weight", err), *bk = need(p, g + ".attn.proj.1.bias", err);
-    const Tensor *wv = need(p, g + ".attn.proj.2.weight", err), *bv = need(p, g + ".attn.proj.2.bias", err);
-    const Tensor *wm = need(p, g + ".attn.merge.weight", err), *bm = need(p, g + ".attn.merge.bias", err);
-    if (!wq || !bq || !wk || !bk || !wv || !bv || !wm || !bm) { ok = false; break; }
+    const Tensor *wq, *bq, *wk, *bk, *wv, *bv;
+    if (!need_linear(p, g + ".attn.proj.0", 256, 256, wq, bq, err) || !need_linear(p, g + ".attn.proj.1", 256, 256, wk, bk, err) ||
+        !need_linear(p, g + ".attn.proj.2", 256, 256, wv, bv, err)) { ok = false; break; }
     std::vector<float> wqk(512 * 256), bqk(512);
     for (int f = 0; f < 256; ++f) {
       memcpy(&wqk[(size_t)f * 256], &wq->data[(size_t)hm(f) * 256], 1024);
@@ -577,15 +581,8 @@ int load_superglue(airfe_ctx* c, const char* path) {
       bqk[f] = bq->data[hm(f)];
       bqk[256 + f] = bk->data[hm(f)];
     }
-    ok = ok && make_linear(c, wqk.data(), bqk.data(), 256, 512, l.qk, ATT_QK_FOLD);
-    ok = ok && make_linear(c, wv->data.data(), bv->data.data(), 256, 256, l.v, 1.f, &hm);
-    ok = ok && make_linear(c, wm->data.data(), bm->data.data(), 256, 256, l.merge, 1.f, nullptr, &hm);
-    if (c->fold_out) {
-      const Tensor *w1 = need(p, g + ".mlp.0.weight", err), *b1f = need(p, g + ".mlp.0.bias", err);
-      ok = ok && w1 && b1f && make_ffn0_folded(c, *w1, *b1f, *wm, *bm, l.mlp0, err, &hm);
-    } else
-    ok = ok && make_linear_named(c, p, g + ".mlp.0", 512, 512, l.mlp0, err);
-    ok = ok && make_linear_named(c, p, g + ".mlp.3", 512, 256, l.mlp3, err);
+    ok = make_linear(c, wqk.data(), bqk.data(), 256, 512, l.qk, ATT_QK_FOLD) && make_linear(c, wv->data.data(), bv->data.data(), 256, 256, l.v, 1.f, &hm) &&
+         load_block_tail(c, p, sg_names(g), &hm, l, err);
   }
   ok = ok && make_linear_named(c, p, "final_proj", 256, 256, c->sg_final, err, 0.25f /* scores / 256^.5 split over both sides */);
   const Tensor* bs = need(p, "bin_score", err);

@@ -539,3 +539,75 @@ def test_empty_frames_in_a_batch_have_no_matches():
             assert k == len(want_idx) and k > 0, (fused, i, k, len(want_idx))
             np.testing.assert_array_equal(idx[i, :k].cpu().numpy(), want_idx)
             np.testing.assert_array_equal(sc[i, :k].cpu().numpy(), want_sc)
+
+
+# ---- the fault-hunting trace's slot names, their order and the groups a trace_stop cuts at (airfe_match.hip: lightglue_dev, attn_block_dev)
+def _trace_groups(L, fused, fold_qkv, fold_out):
+    """The slot names of one traced LightGlue call, in groups: a trace_stop inside a group takes effect at the group's end.  2 L half-steps, half-step h cross iff
+    h & 1, block of layer h // 2: it launches its own projections unless an earlier fused block carried them (fold and h > 0); its fused block carries the projections
+    of half-step h + 1 (k only for a self half); the separate launches trace the out-projection's message unless it is folded into ffn.0 (either half)."""
+    fold = fused and fold_qkv
+    groups = [["L0.prep.x32", "L0.prep.xb", "L0.prep.x32slack", "L0.prep.rc", "L0.prep.rs"]]
+    for h in range(2 * L):
+        cross = h & 1
+        p = f"L{h // 2}.{'cross' if cross else 'self'}"
+        if not fold or h == 0:
+            groups.append([p + ".qkv.q"] + ([] if cross else [p + ".qkv.k"]) + [p + ".qkv.vt"])
+        groups.append([p + ".attn.o"])
+        if fused:
+            groups.append([p + ".block.x32", p + ".block.xb"])
+            if fold and h + 1 < 2 * L:
+                groups.append([p + ".block.q"] + ([p + ".block.k"] if cross else []) + [p + ".block.vt"])
+        else:
+            if not fold_out:
+                groups.append([p + ".out.msg"])
+            groups.append([p + ".ffn.x32", p + ".ffn.xb"])
+    groups.append([f"L{L}.final.md", f"L{L}.final.x32slack"])
+    return groups + [[f"L{L}.{n}"] for n in ("final.z", "final.sim", "assign.rowlse", "assign.collse", "assign.rowval", "assign.rowarg", "assign.colarg")]
+
+
+def _traced_context(tuning):
+    from airslam_amd import api, weights
+    ctx = api.Context(lightglue=weights.synthetic_lightglue(1234, n_layers=2), max_batch=2, max_keypoints=400, tuning=tuning)
+    _, _, a, b = _pair(129, 63, 3232)
+    ctx.trace(True)
+    return ctx, a, b
+
+
+@pytest.mark.parametrize("tuning", [None, {"fuse_lg_block": 0}, {"fold_qkv": 0}, {"fuse_lg_block": 0, "fold_out_proj": 0}],
+                         ids=["default", "four_launches", "own_projections", "four_launches_out_proj"])
+def test_trace_slot_names_and_order(tuning):
+    t = tuning or {}
+    want = sum(_trace_groups(2, t.get("fuse_lg_block", 1) == 1, t.get("fold_qkv", 1) == 1, t.get("fold_out_proj", 1) == 1), [])
+    ctx, a, b = _traced_context(tuning)
+    try:
+        ctx.match_lightglue(a, b)
+        assert [s[0] for s in ctx.trace_slots()] == want
+        dig, _ = ctx.trace_read()
+        assert len(dig) == len(want)
+    finally:
+        ctx.trace(False)
+        ctx.close()
+
+
+def test_trace_stop_cuts_at_the_end_of_the_slot_group():
+    """trace_stop(k): the next call returns behind the GROUP of slots k lies in (the launches up to there have run, nothing after them), through trace_finish — the
+    digests of the slots it did record can be read.  One slot per group, the group's first: the rest of its group must still be recorded."""
+    groups = _trace_groups(2, True, True, True)
+    full = sum(groups, [])
+    ctx, a, b = _traced_context(None)
+    try:
+        ctx.match_lightglue(a, b)
+        assert [s[0] for s in ctx.trace_slots()] == full
+        end = 0
+        for g in groups:
+            k, end = end, end + len(g)
+            ctx.trace_stop(k)
+            ctx.match_lightglue(a, b)
+            assert [s[0] for s in ctx.trace_slots()] == full[:end], (k, full[k])
+            dig, _ = ctx.trace_read()
+            assert len(dig) == end
+    finally:
+        ctx.trace_stop(-1)
+        ctx.trace(False)
+        ctx.close()
