@@ -320,6 +320,7 @@ SIGNATURES = {
     "airfe_debug_trace_stop": (C.c_int, [C.c_void_p, C.c_int]),
     "airfe_debug_trace_buffer": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "airfe_debug_trace_slots": (C.c_int, [C.c_void_p]),
+    "airfe_debug_conv_order": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
     "airfe_debug_trace_slot": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
     "airfe_debug_trace_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "airfe_debug_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,

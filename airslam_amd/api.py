@@ -37,6 +37,15 @@ class AirfeError(RuntimeError):
     pass
 
 
+def conv_tile_order(order: int) -> int:
+    """Tile order of the persistent conv kernels, process-wide (airfe_debug_conv_order): bit 0 conv64r, bit 1 conv128r; set = XCD-blocked walk, cout passes in one
+    launch; 0 = raster walk, one launch per pass; -1 = the library's default.  Returns the value before the call.  The same output bytes either way."""
+    prev = C.c_int()
+    if _lib.lib().airfe_debug_conv_order(int(order), C.byref(prev)) != 0:
+        raise AirfeError((_lib.lib().airfe_last_error(None) or b"airfe_debug_conv_order failed").decode())
+    return prev.value
+
+
 class Context:
     """One airfe_ctx: one device, one stream, one calling thread."""
 
@@ -46,6 +55,10 @@ class Context:
         c = _lib.Cfg()
         self._l.airfe_default_cfg(C.byref(c))
         t = None
+        if tuning and "conv_order" in tuning:
+            # not an airfe_tuning field (the struct's size is pinned): the conv kernels' tile order is one process-wide switch (airfe_debug_conv_order)
+            tuning = dict(tuning)
+            conv_tile_order(int(tuning.pop("conv_order")))
         if tuning:
             t = _lib.Tuning()
             self._l.airfe_default_tuning(C.byref(t))

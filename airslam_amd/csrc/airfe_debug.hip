@@ -227,6 +227,13 @@ int airfe_debug_conv(airfe_ctx* c, airfe_debug_conv_args* a) try {
   return s.status();
 } AIRFE_CATCH(c)
 
+int airfe_debug_conv_order(int order, int* previous) try {
+  if (order < -1 || order > CONV_ORDER_DEFAULT) return fail(nullptr, "debug_conv_order: order must lie in -1 .. 3");
+  const int before = conv_tile_order_switch(order);
+  if (previous) *previous = before;
+  return 0;
+} AIRFE_CATCH(nullptr)
+
 int airfe_debug_linear(airfe_ctx* c, const airfe_debug_linear_args* a) try {
   AIRFE_ENTER(c);
   if (!a || !a->x1 || !a->w || !a->b || !a->out) return fail(c, "debug_linear: null argument");

@@ -257,22 +257,6 @@ __device__ __forceinline__ void rotate_pairs(float* v, const f32x4& c, const f32
   }
 }
 
-// tile -> (image, tile row, tile column): tiles per row / per image are powers of two at every size of this network (512 / 2^k
-// pixels, 16-pixel tiles): two shifts instead of the ~50 instructions of two scalar integer divisions, three times per tile
-__device__ __forceinline__ void tile_decode(int tile, int per_img, int tiles_x, int sh_img, int sh_x, int& b, int& ty, int& tx) {
-  if (sh_img >= 0) {
-    b = tile >> sh_img;
-    const int rem = tile & (per_img - 1);
-    ty = rem >> sh_x;
-    tx = rem & (tiles_x - 1);
-  } else {
-    b = tile / per_img;
-    const int rem = tile - b * per_img;
-    ty = rem / tiles_x;
-    tx = rem - ty * tiles_x;
-  }
-}
-
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);

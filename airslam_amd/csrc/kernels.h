@@ -104,6 +104,12 @@ void launch_conv3x3(int prec, const ConvArgs& a, hipStream_t st);
 void launch_conv64r(int prec, const ConvArgs& a, hipStream_t st);
 // persistent weight-stationary variant for CIN == 128, COUT % 128 == 0 (launch_conv3x3 dispatches to it)
 void launch_conv128r(int prec, const ConvArgs& a, hipStream_t st);
+// Tile order of the two persistent kernels (conv_tile_order.h), one bit per kernel: set = XCD-blocked walk with a layer's cout passes in one launch,
+// clear = raster walk, one launch per pass.  Process-wide, read once per launch (A/B runs and the byte comparison of the two orders:
+// airfe_debug_conv_order).  conv_tile_order_switch(v): v >= 0 sets it, v = -1 restores the default; returns the value before the call.
+constexpr int CONV_ORDER_64R = 1, CONV_ORDER_128R = 2, CONV_ORDER_DEFAULT = CONV_ORDER_64R | CONV_ORDER_128R;
+int conv_tile_order_switch();
+int conv_tile_order_switch(int v);
 
 // cv::resize(INTER_LINEAR, 8-bit fixed point) + /255 -> fp32 [B][RH+2][RW+2] interior
 void launch_preprocess(const uint8_t* src, int B, int h, int w, int stride, size_t img_stride,

@@ -10,6 +10,7 @@
 //   * LDS holds the double-buffered halo tile (2 x 45 KiB, LDS-DMA one tile ahead) and a 32 KiB output staging tile: a lane
 //     owns only 4 couts of a pixel, so results are transposed through LDS into whole 256-byte pixel rows before they leave.
 #include "common.h"
+#include "conv_tile_order.h"
 #include "kernels.h"
 
 namespace airfe {
@@ -29,16 +30,21 @@ constexpr int C128R_PIECES = 10 * 18 * 16;         // 2880 sixteen-byte pieces
 constexpr int C128R_OUT_OFF = 2 * C128R_TILE_BYTES;
 constexpr int C128R_LDS = C128R_OUT_OFF + 128 * 256;
 
-template <class P, bool POOL>
-__global__ __launch_bounds__(512, 1) void conv128r_kernel(ConvArgs a, int tiles_x, int tiles_y, int ntiles, int cb0) {
+// SHIFT: the tile grid is a power of two each way (every size of the network) and the tile decode is shifts; otherwise two divisions.  One
+// instantiation each: with both forms behind a branch the kernel (252 of 256 registers) spills around the staging of the next tile.
+template <class P, bool POOL, bool SHIFT>
+__global__ __launch_bounds__(512, 1) void conv128r_kernel(ConvArgs a, ConvTileOrder o) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, g = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // the workgroup's walk through the tiles and its cout pass (conv_tile_order.h): wave-uniform, one filter bank for its whole life
+  int tile, tstep, pass;
+  conv_tile_first(o, blockIdx.x, gridDim.x, tile, tstep, pass);
+  const int ntiles = o.ntiles, cb0 = 2 * pass;
   const int cb = cb0 + (wave >> 2), t = wave & 3;      // 64-cout block and 16-row tile inside its packed slabs
   const int H = a.H, W = a.W, COUT = a.COUT;
   const size_t in_row = (size_t)(W + 2) * 256;
   const size_t in_img = (size_t)(H + 2) * in_row;
-  const int per_img = tiles_x * tiles_y;
   const unsigned lds_base = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(las_ptr128r)smem);
 
   // ---- filters: slab (cb, tap, cin half cc), rows t*16 + l15, k-step ks -> MFMA A fragments
@@ -73,8 +79,8 @@ __global__ __launch_bounds__(512, 1) void conv128r_kernel(ConvArgs a, int tiles_
   }
   const bool last_piece = 5 * 512 + tid < C128R_PIECES;
   auto stage_tile = [&](int tile, int buf) {
-    const int b = tile / per_img, rem = tile - b * per_img;
-    const int ty = rem / tiles_x, tx = rem - ty * tiles_x;
+    int b, ty, tx;
+    if constexpr (SHIFT) conv_tile_decode_shift(o, tile, b, ty, tx); else conv_tile_decode_div(o, tile, b, ty, tx);
     const char* xin = reinterpret_cast<const char*>(a.X) + (size_t)b * in_img + (size_t)ty * 8 * in_row + (size_t)tx * 16 * 256;
     const unsigned dst = lds_base + buf * C128R_TILE_BYTES + wave * 1024;
 #pragma unroll
@@ -90,13 +96,12 @@ __global__ __launch_bounds__(512, 1) void conv128r_kernel(ConvArgs a, int tiles_
   const size_t orow = (size_t)(Wo + 2 * opad) * COUT;
   char* ost = smem + C128R_OUT_OFF;
 
-  int tile = blockIdx.x;
   if (tile < ntiles) stage_tile(tile, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
-  for (int i = 0; tile < ntiles; ++i, tile += gridDim.x) {
-    const int next = tile + gridDim.x;
+  for (int i = 0; tile < ntiles; ++i, tile += tstep) {
+    const int next = tile + tstep;
     if (next < ntiles) stage_tile(next, (i + 1) & 1);
     const int xoff = (i & 1) * C128R_TILE_BYTES;
     f32x4 acc[8];
@@ -120,8 +125,8 @@ __global__ __launch_bounds__(512, 1) void conv128r_kernel(ConvArgs a, int tiles_
     __syncthreads();
 
     // ---- epilogue: (bias is in the accumulators) round, ReLU / 2x2 max-pool on packed pairs, transpose through LDS
-    const int b = tile / per_img, rem = tile - b * per_img;
-    const int ty = rem / tiles_x, tx = rem - ty * tiles_x;
+    int b, ty, tx;
+    if constexpr (SHIFT) conv_tile_decode_shift(o, tile, b, ty, tx); else conv_tile_decode_div(o, tile, b, ty, tx);
     uint16_t* ybase = a.Y + (size_t)b * (Ho + 2 * opad) * orow + cb0 * 64;
     const int fch = (wave >> 2) * 8 + (f0 >> 3);        // 16-byte chunk of the 128-cout pass that holds this lane's 4 couts
     uint2 pk[8];
@@ -166,18 +171,26 @@ __global__ __launch_bounds__(512, 1) void conv128r_kernel(ConvArgs a, int tiles_
   }
 }
 
-template <class P, bool POOL>
-static void conv128r_launch_t(const ConvArgs& a, hipStream_t st) {
+template <class P, bool POOL, bool SHIFT>
+static void conv128r_launch_k(const ConvArgs& a, ConvTileOrder o, int grid, int launches, hipStream_t st) {
   static PerDeviceOnce attr_once;
-  auto kfn = conv128r_kernel<P, POOL>;
+  auto kfn = conv128r_kernel<P, POOL, SHIFT>;
   if (auto once_token = attr_once.first()) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, C128R_LDS);
   }
+  for (; o.pass0 < launches; ++o.pass0) hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), C128R_LDS, st, a, o);
+}
+
+template <class P, bool POOL>
+static void conv128r_launch_t(const ConvArgs& a, hipStream_t st) {
   const int tiles_x = a.W / 16, tiles_y = a.H / 8;
   const int ntiles = tiles_x * tiles_y * a.B;
   const int grid = ntiles < a.wgs ? ntiles : a.wgs;
-  for (int cb0 = 0; cb0 < a.COUT / 64; cb0 += 2)          // 128 output channels per pass
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), C128R_LDS, st, a, tiles_x, tiles_y, ntiles, cb0);
+  const int passes = a.COUT / 128;                        // 128 output channels per pass
+  const ConvTileOrder o = conv_tile_order(conv_tile_order_switch() & CONV_ORDER_128R, grid, tiles_x, tiles_y, a.B, passes, 16, 8);
+  const int launches = conv_tile_launches(o, passes);     // blocked: every pass in one launch
+  if (o.sh_img >= 0) conv128r_launch_k<P, POOL, true>(a, o, grid, launches, st);
+  else conv128r_launch_k<P, POOL, false>(a, o, grid, launches, st);
 }
 
 // requires CIN == 128, COUT % 128 == 0, H % 8 == 0, W % 16 == 0

@@ -16,6 +16,7 @@ __device__ long long c64_dbg[256 * 8 * 6];
 #else
 #define C64R_T(x)
 #endif
+#include "conv_tile_order.h"
 #include "kernels.h"
 
 namespace airfe {
@@ -62,7 +63,7 @@ constexpr int C64R_CONST_OFF = 2 * C64R_TILE_STRIDE + 3 * C64R_PATCH * 4;   // c
 
 // RW = pixel rows per wave: 8 -> 4 waves (one per SIMD, 512 registers each), 4 -> 8 waves (two per SIMD)
 template <class P, bool POOL, bool FUSE1A, int RW>
-__global__ __launch_bounds__(2048 / RW, 1) void conv64r_kernel(ConvArgs a, int tiles_x, int tiles_y, int ntiles, int cb0) {
+__global__ __launch_bounds__(2048 / RW, 1) void conv64r_kernel(ConvArgs a, ConvTileOrder o) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, g = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -74,9 +75,10 @@ __global__ __launch_bounds__(2048 / RW, 1) void conv64r_kernel(ConvArgs a, int t
   const int H = a.H, W = a.W, COUT = a.COUT;
   const size_t in_row = (size_t)(W + 2) * 128;
   const size_t in_img = (size_t)(H + 2) * in_row;
-  const int per_img = tiles_x * tiles_y;
-  const bool p2 = (tiles_x & (tiles_x - 1)) == 0 && (per_img & (per_img - 1)) == 0;
-  const int sh_x = p2 ? __builtin_ctz(tiles_x) : -1, sh_img = p2 ? __builtin_ctz(per_img) : -1;
+  // the workgroup's walk through the tiles and its cout pass (conv_tile_order.h): wave-uniform, one filter bank for its whole life
+  int tile, tstep, cb0;
+  conv_tile_first(o, blockIdx.x, gridDim.x, tile, tstep, cb0);
+  const int ntiles = o.ntiles;
 
   // ---- filters: slab rows (2*ch + tt)*16 + l15 of every tap, both channel halves, as MFMA A fragments
   typename P::vec8 wreg[9][2][2];
@@ -116,7 +118,7 @@ __global__ __launch_bounds__(2048 / RW, 1) void conv64r_kernel(ConvArgs a, int t
   const bool last_piece = (NPC - 1) * NT + tid < C64R_PIECES;
   auto stage = [&](int tile, int buf) {
     int b, ty, tx;
-    tile_decode(tile, per_img, tiles_x, sh_img, sh_x, b, ty, tx);
+    conv_tile_decode(o, tile, b, ty, tx);
     const char* xin = reinterpret_cast<const char*>(a.X) + (size_t)b * in_img + (size_t)ty * 16 * in_row + (size_t)tx * 16 * 128;
     const unsigned dst = lds_base + buf * C64R_TILE_STRIDE + wave * 1024;
 #pragma unroll
@@ -164,7 +166,7 @@ __global__ __launch_bounds__(2048 / RW, 1) void conv64r_kernel(ConvArgs a, int t
   // beyond even that are clamped: they only feed halo pixels outside the image, which are forced to 0 anyway.
   auto stage_patch = [&](int t, int buf) {
     int b, ty, tx;
-    tile_decode(t, per_img, tiles_x, sh_img, sh_x, b, ty, tx);
+    conv_tile_decode(o, t, b, ty, tx);
     const float* img = a.img + (size_t)b * (H + 2) * (W + 2);
 #pragma unroll
     for (int j = 0; j < (C64R_PATCH + NT - 1) / NT; ++j) {
@@ -228,10 +230,9 @@ __global__ __launch_bounds__(2048 / RW, 1) void conv64r_kernel(ConvArgs a, int t
   auto prod_finish = [&](int j, const Taps& tp3, int ty, int tx, int xbuf) { prod_finish_at(pwr[j], pyx[j], tp3, ty, tx, xbuf); };
   auto tile_xy = [&](int t, int& ty, int& tx) {
     int b_;
-    tile_decode(t, per_img, tiles_x, sh_img, sh_x, b_, ty, tx);
+    conv_tile_decode(o, t, b_, ty, tx);
   };
 
-  int tile = blockIdx.x;
   if constexpr (FUSE1A) {
     if (tile < ntiles) stage_patch(tile, 0);
   } else {
@@ -242,8 +243,8 @@ __global__ __launch_bounds__(2048 / RW, 1) void conv64r_kernel(ConvArgs a, int t
   if constexpr (FUSE1A) {
     // pipeline prologue: patch(1) in flight, conv1a of tile(0) produced, both visible before the loop
     if (tile < ntiles) {
-      if (tile + (int)gridDim.x < ntiles) stage_patch(tile + gridDim.x, 1);
-      if (tile + 2 * (int)gridDim.x < ntiles) stage_patch(tile + 2 * gridDim.x, 2);
+      if (tile + tstep < ntiles) stage_patch(tile + tstep, 1);
+      if (tile + 2 * tstep < ntiles) stage_patch(tile + 2 * tstep, 2);
       int ty0, tx0;
       tile_xy(tile, ty0, tx0);
 #pragma unroll
@@ -259,13 +260,13 @@ __global__ __launch_bounds__(2048 / RW, 1) void conv64r_kernel(ConvArgs a, int t
 #ifdef C64R_TIMING
   long long t_top = 0, t_mma = 0, t_wait = 0, t_bar = 0, t_epi = 0, tp_ = wall_clock64();
 #endif
-  for (int i = 0; tile < ntiles; ++i, tile += gridDim.x) {
-    const int next = tile + gridDim.x;
+  for (int i = 0; tile < ntiles; ++i, tile += tstep) {
+    const int next = tile + tstep;
     if constexpr (FUSE1A) {
       // patch(i+3) -> pbuf[i % 3] (consumed by the conv1a of one iteration ago).  Three patch buffers: the wait at the end
       // of this iteration only covers patch(i+2), issued a whole iteration earlier — with two buffers it also covered
       // the patch issued a few hundred cycles ago, i.e. an HBM round trip per tile (25 % of the kernel, measured).
-      if (tile + 3 * (int)gridDim.x < ntiles) stage_patch(tile + 3 * gridDim.x, pb3);
+      if (tile + 3 * tstep < ntiles) stage_patch(tile + 3 * tstep, pb3);
     } else {
       if (next < ntiles) stage(next, (i + 1) & 1);
     }
@@ -370,7 +371,7 @@ __global__ __launch_bounds__(2048 / RW, 1) void conv64r_kernel(ConvArgs a, int t
     // ---- epilogue (the bias is already in the accumulators): round to the 2-byte storage type FIRST, then ReLU and the
     // 2x2 max-pool on packed pairs (v_pk_max_i16; rounding is monotonic, so pooling after it gives the same bits)
     int b, ty, tx;
-    tile_decode(tile, per_img, tiles_x, sh_img, sh_x, b, ty, tx);
+    conv_tile_decode(o, tile, b, ty, tx);
     uint16_t* ybase = a.Y + (size_t)b * (Ho + 2 * opad) * orow + cb0 * 64 + ch * 32 + g * 8;
     uint4 pk[RW];
 #pragma unroll
@@ -416,7 +417,7 @@ __global__ __launch_bounds__(2048 / RW, 1) void conv64r_kernel(ConvArgs a, int t
       constexpr int NPP = (C64R_PATCH + NT - 1) / NT;
       // (an early epilogue has just issued NST stores: they are younger than patch(i+2) and may stay in flight too)
       constexpr int NST = POOL ? RW / 4 : RW;
-      if (tile + 3 * (int)gridDim.x < ntiles) {
+      if (tile + 3 * tstep < ntiles) {
         if (early_epi) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NPP + NST) : "memory");
         else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NPP) : "memory");
       } else {                                                              // tail: no patch(i+3) was issued
@@ -437,8 +438,8 @@ __global__ __launch_bounds__(2048 / RW, 1) void conv64r_kernel(ConvArgs a, int t
   }
 #ifdef C64R_TIMING
   if (lane == 0 && FUSE1A) {
-    long long* o = c64_dbg + (blockIdx.x * 8 + wave) * 6;
-    o[0] = t_top; o[1] = t_mma; o[2] = t_wait; o[3] = t_bar; o[4] = t_epi;
+    long long* dbg = c64_dbg + (blockIdx.x * 8 + wave) * 6;
+    dbg[0] = t_top; dbg[1] = t_mma; dbg[2] = t_wait; dbg[3] = t_bar; dbg[4] = t_epi;
   }
 #endif
 }
@@ -461,8 +462,10 @@ static void conv64r_launch_t(const ConvArgs& a, hipStream_t st) {
   const int tiles_x = a.W / 16, tiles_y = a.H / 16;
   const int ntiles = tiles_x * tiles_y * a.B;
   const int grid = ntiles < a.wgs ? ntiles : a.wgs;
-  for (int cb0 = 0; cb0 < a.COUT / 64; ++cb0)          // 64 output channels per pass
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(2048 / RW), LDS, st, a, tiles_x, tiles_y, ntiles, cb0);
+  const int passes = a.COUT / 64;                      // 64 output channels per pass
+  ConvTileOrder o = conv_tile_order(conv_tile_order_switch() & CONV_ORDER_64R, grid, tiles_x, tiles_y, a.B, passes, 16, 16);
+  for (const int n = conv_tile_launches(o, passes); o.pass0 < n; ++o.pass0)      // blocked: every pass in one launch
+    hipLaunchKernelGGL(kfn, dim3(grid), dim3(2048 / RW), LDS, st, a, o);
 }
 
 // requires CIN == 64, COUT % 64 == 0, relu, H % 16 == 0, W % 16 == 0.  a.img != nullptr selects the fused conv1a + conv1b

@@ -179,6 +179,10 @@ static void conv_launch_p(const ConvArgs& a, hipStream_t st) {
   }
 }
 
+static std::atomic<int> g_conv_order{CONV_ORDER_DEFAULT};
+int conv_tile_order_switch() { return g_conv_order.load(std::memory_order_relaxed); }
+int conv_tile_order_switch(int v) { return g_conv_order.exchange(v < 0 ? CONV_ORDER_DEFAULT : (v & CONV_ORDER_DEFAULT), std::memory_order_relaxed); }
+
 void launch_conv3x3(int prec, const ConvArgs& a, hipStream_t st) {
   if (a.CIN == 64 && (a.COUT % 64) == 0 && a.relu && (a.H % 16) == 0 && (a.W % 16) == 0) {
     launch_conv64r(prec, a, st);       // persistent kernel, filters resident in registers (kernels_conv64r.hip)

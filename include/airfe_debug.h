@@ -77,6 +77,11 @@ typedef struct airfe_debug_conv_args {
   uint16_t* y_raw;                /* [y_words] out */
 } airfe_debug_conv_args;
 int airfe_debug_conv(airfe_ctx* ctx, airfe_debug_conv_args* a);
+/* Tile order of conv64r_kernel (bit 0) and conv128r_kernel (bit 1), process-wide and read once per launch (csrc/conv_tile_order.h): bit set = workgroups placed by
+ * XCD over 2-D blocks of tiles with a layer's cout passes in one launch, bit clear = raster order, one launch per pass.  The per-tile arithmetic is the same: every
+ * output byte is (tests/test_gpu_conv_tile_order.py).  order 0 .. 3 sets it, -1 restores the library's default; *previous (may be NULL) receives the value before
+ * the call.  For A/B measurements (bench.py --tuning conv_order=0) and that test; not for use beside running work. */
+int airfe_debug_conv_order(int order, int* previous);
 /* ---- the matcher's / detector's GEMM family one form at a time (tests/test_gpu_linear_kernels.py, tests/test_gpu_lg_block.py).  HOST fp32 tensors in, rounded to the
  * 2-byte type `prec` (0 = bf16, 1 = fp16) on the way in; weights packed as the pipelines pack them (scale 1); HOST fp32 out in the kernel's own layout.  The kernels
  * are the production ones: nothing here has a kernel of its own. */
