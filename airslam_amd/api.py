@@ -1418,6 +1418,46 @@ class BowDatabase:
         self.triangulate_points_dev(cam, xyz_t, status_t, nobs_t, info_t, min_observers=min_observers, stream=stream)
         self.fill_points_dev(xyz_t, status_t, written_t, only_missing=only_missing, stream=stream)
 
+    # ---- map-point merge (include/airfe.h "Map-point merge")
+    def attach_merge(self):
+        """the merge's work arrays (24 bytes per point, 4 per feature row); needs attach_point_ids; nothing is allocated by a _dev call afterwards"""
+        self._ctx._chk(self._l.airfe_bowdb_attach_merge(self._h), "airfe_bowdb_attach_merge")
+
+    def merge_points_dev(self, pairs_t, map_t, info_t, stream=None):
+        """MergeMappoints on an explicit pair list pairs i32 [P][2] (device), asynchronous on `stream`: the id table and the point table are relabelled in
+        place; map i32 [max_points] = the best of an id's group or the id itself; info i32 [8] = pairs taken, pairs ignored, 0, 0, groups, ids removed,
+        rows relabelled, rows cleared"""
+        P = 0 if pairs_t is None else int(pairs_t.shape[0])
+        self._ctx._chk(self._l.airfe_bowdb_merge_points_dev(
+            self._h, pairs_t.data_ptr() if P else None, P, map_t.data_ptr() if map_t is not None else None,
+            info_t.data_ptr() if info_t is not None else None, self._ctx._stream(stream)), "airfe_bowdb_merge_points_dev")
+
+    def merge_points(self, pairs: np.ndarray, max_points: int):
+        """the same from a host pair list on the context's stream, then a synchronisation -> (map [max_points], info [8]); max_points: attach_point_ids'"""
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        mp, info = np.empty(max_points, np.int32), np.empty(8, np.int32)
+        self._ctx._chk(self._l.airfe_bowdb_merge_points(self._h, pairs.ctypes.data if len(pairs) else None, len(pairs), mp.ctypes.data, info.ctypes.data),
+                       "airfe_bowdb_merge_points")
+        return mp, info
+
+    def loop_merge_batch_dev(self, cam, qframe_t, stage_t, loop_t, Rlq_t, tlq_t, mask_t, idx_t, nmatch_t, map_t, info_t, stream=None):
+        """The tail of RelativatePoseEstimation and MergeMappoints straight from loop_detect_batch_dev's buffers, asynchronous on `stream`: cam = (fx, fy,
+        cx, cy); live entries adopt or pair, groups are merged into their best, the id table and the point table are relabelled in place; map i32
+        [max_points]; info i32 [8] = live, outliers, epipolar, rows adopted, groups, ids removed, rows relabelled, rows cleared"""
+        Q = int(qframe_t.shape[0])
+        p = lambda t: t.data_ptr() if (t is not None and Q) else None  # noqa: E731
+        self._ctx._chk(self._l.airfe_bowdb_loop_merge_batch_dev(
+            self._h, None if cam is None else self._cam4(cam), p(qframe_t), Q, p(stage_t), p(loop_t), p(Rlq_t), p(tlq_t), p(mask_t), p(idx_t),
+            int(idx_t.shape[1]), p(nmatch_t), map_t.data_ptr() if map_t is not None else None, info_t.data_ptr() if info_t is not None else None,
+            self._ctx._stream(stream)), "airfe_bowdb_loop_merge_batch_dev")
+
+    def loop_close_dev(self, cam, qframe_t, stage_t, loop_t, Rlq_t, tlq_t, mask_t, idx_t, nmatch_t, map_t, merge_info_t, xyz_t, status_t, nobs_t, tri_info_t,
+                       written_t, covis_info_t, min_observers=2, stream=None):
+        """loop_merge_batch_dev, then retriangulate_dev(only_missing=True), then build_covisibility_dev, on one stream: a detected loop taken into the map"""
+        self.loop_merge_batch_dev(cam, qframe_t, stage_t, loop_t, Rlq_t, tlq_t, mask_t, idx_t, nmatch_t, map_t, merge_info_t, stream=stream)
+        self.retriangulate_dev(cam, xyz_t, status_t, nobs_t, tri_info_t, written_t, min_observers=min_observers, only_missing=True, stream=stream)
+        self.build_covisibility_dev(covis_info_t, stream=stream)
+
 
 # ------------------------------------------------------------------------------------ reference-shaped façade
     # ---- the junction term (include/airfe.h "Junction term"): this database is the JUNCTION database, frame f = frame f of the point database

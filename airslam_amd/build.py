@@ -9,7 +9,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libairfe.so")
-SOURCES = ["airfe.hip", "airfe_frame.hip", "airfe_assoc.hip", "airfe_geom.hip", "airfe_bowdb.hip", "airfe_bowmap.hip", "airfe_junction.hip", "airfe_debug.hip", "airfe_seq.hip", "airfe_load.hip", "airfe_detect.hip", "airfe_lines.hip", "airfe_match.hip", "kernels_mm.hip", "kernels_conv64r.hip", "kernels_conv128r.hip", "kernels_gemm8.hip", "kernels_gemmr.hip", "kernels_gemmr_sample.hip", "kernels_img.hip", "kernels_sel.hip", "kernels_nms512.hip", "kernels_lg.hip", "kernels_attn.hip", "kernels_lgblockf.hip", "kernels_ext.hip", "kernels_s0.hip", "kernels_f32.hip", "kernels_fransac.hip", "kernels_pnp.hip", "kernels_poseopt.hip", "kernels_bowdb.hip", "kernels_bowgroup.hip", "kernels_loopdet.hip", "kernels_covis.hip", "kernels_stereoline.hip", "kernels_junction.hip", "kernels_triangulate.hip"]
+SOURCES = ["airfe.hip", "airfe_frame.hip", "airfe_assoc.hip", "airfe_geom.hip", "airfe_bowdb.hip", "airfe_bowmap.hip", "airfe_junction.hip", "airfe_debug.hip", "airfe_seq.hip", "airfe_load.hip", "airfe_detect.hip", "airfe_lines.hip", "airfe_match.hip", "kernels_mm.hip", "kernels_conv64r.hip", "kernels_conv128r.hip", "kernels_gemm8.hip", "kernels_gemmr.hip", "kernels_gemmr_sample.hip", "kernels_img.hip", "kernels_sel.hip", "kernels_nms512.hip", "kernels_lg.hip", "kernels_attn.hip", "kernels_lgblockf.hip", "kernels_ext.hip", "kernels_s0.hip", "kernels_f32.hip", "kernels_fransac.hip", "kernels_pnp.hip", "kernels_poseopt.hip", "kernels_bowdb.hip", "kernels_bowgroup.hip", "kernels_loopdet.hip", "kernels_covis.hip", "kernels_stereoline.hip", "kernels_junction.hip", "kernels_triangulate.hip", "kernels_merge.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # Per-file flags.  -fno-slp-vectorize: the SLP vectoriser packs incidental scalar fp32 arithmetic of these (latency- / HBM-bound) kernels into
 # v_pk_*_f32 with cross-half `op_sel` selections — the instruction form behind round 2's irreproducible rotary element (common.h, rotate_pairs;
@@ -22,6 +22,7 @@ EXTRA_FLAGS["kernels_loopdet.hip"] = ["-ffp-contract=off"]       # ... and loop 
 EXTRA_FLAGS["kernels_stereoline.hip"] = ["-ffp-contract=off"]    # ... and stereo line triangulation, kernel and host statement (stereoline_core.h)
 EXTRA_FLAGS["kernels_junction.hip"] = ["-ffp-contract=off"]      # ... and the junction term's rate and product (junction_core.h)
 EXTRA_FLAGS["kernels_triangulate.hip"] = ["-ffp-contract=off"]   # ... and map-point triangulation, kernels and host core (triangulate_core.h)
+EXTRA_FLAGS["kernels_merge.hip"] = ["-ffp-contract=off"]         # ... and the map-point merge's epipolar gate (merge_core.h)
 
 
 def csrc_sha() -> str:

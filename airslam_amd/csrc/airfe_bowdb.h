@@ -33,6 +33,10 @@ struct airfe_bowdb {
   // map-point triangulation (airfe_bowdb_attach_triangulation): the observation segments and the host form's outputs, sized at attach
   int has_tri = 0;
   DevBlock t_scratch;
+  // map-point merge (airfe_bowdb_attach_merge): per point the parent, flags, src, best and root, per feature row the adoption staging, sized at attach
+  int has_merge = 0;
+  DevBlock g_scratch;
+  DevBlock g_pairs;                                                          // airfe_bowdb_merge_points: the host pair list's device copy (grows with P)
   // junction state (airfe_bowdb_attach_junctions): per stored frame its words and the two tables of junction_core.h; the same for max_queries queries
   struct JunctionTables {
     unsigned *uword = nullptr; int *wcnt = nullptr, *wconn = nullptr, *nuw = nullptr;          // [rows][cap] x 3, [rows]

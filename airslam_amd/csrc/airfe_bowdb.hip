@@ -151,7 +151,7 @@ int airfe_bowdb_destroy(airfe_bowdb* db) try {
   if (db->c) { (void)enter_device(db->c); (void)hipDeviceSynchronize(); }
   if (db->c)
     for (DevBlock* b : {db->tables, db->tables + 1, db->tables + 2, db->tables + 3, db->tables + 4, &db->map_tables, &db->id_table, &db->q_scratch, &db->m_scratch,
-                        &db->r_scratch, &db->l_scratch, &db->c_scratch, &db->t_scratch, &db->j_block})
+                        &db->r_scratch, &db->l_scratch, &db->c_scratch, &db->t_scratch, &db->g_scratch, &db->g_pairs, &db->j_block})
       release(db->c, *b);
   delete db;
   return 0;

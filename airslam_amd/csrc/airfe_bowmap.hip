@@ -1,7 +1,9 @@
-// airfe — the database's map side beyond its tables (include/airfe.h "Map-point ids and the covisibility build", "Map-point triangulation"): the id table, the
-// covisibility build and the map-point triangulation with its host statement (kernels_covis.hip, kernels_triangulate.hip).
+// airfe — the database's map side beyond its tables (include/airfe.h "Map-point ids and the covisibility build", "Map-point triangulation", "Map-point merge"): the
+// id table, the covisibility build, the map-point triangulation with its host statement and the map-point merge (kernels_covis.hip, kernels_triangulate.hip,
+// kernels_merge.hip).
 #include "airfe_bowdb.h"
 #include "covis_core.h"
+#include "merge_core.h"
 #include "triangulate_core.h"
 
 extern "C" {
@@ -207,5 +209,86 @@ int airfe_triangulate_point(const double* cam, const double* Twc, const float* x
   *status = triangulate_point_core(cami, Twc, xy, n, 2, xyz);      // (compiled beside the kernels, without contraction)
   return 0;
 } AIRFE_CATCH(nullptr)
+
+/* ---- map-point merge (include/airfe.h "Map-point merge"; kernels_merge.hip, merge_core.h) ----------------------------------------------------------- */
+// the merge's arrays inside g_scratch, sized by the database and max_points alone: per point, the staging per feature row, the host form's device outputs
+struct MergeCarve {
+  Carve k;
+  size_t o_parent, o_flags, o_src, o_best, o_root, o_staged, o_map, o_info;
+  MergeCarve(const airfe_bowdb* db) {
+    const size_t rows = (size_t)db->max_frames * db->cap, pts = (size_t)db->max_points;
+    o_parent = k.take(pts * 4); o_flags = k.take(pts * 4); o_src = k.take(pts * 4); o_best = k.take(pts * 4); o_root = k.take(pts * 4);
+    o_staged = k.take(rows * 4); o_map = k.take(pts * 4); o_info = k.take(MG_INFO * 4);
+  }
+  MergeWork work(const airfe_bowdb* db, int32_t* d_map, int32_t* d_info) const {
+    return MergeWork{k.i(o_parent), k.i(o_flags), k.i(o_src), k.i(o_best), k.i(o_root), k.i(o_staged), db->max_frames, d_map, d_info};
+  }
+};
+
+// l == nullptr: the pair form on d_pairs [P][2]
+static int merge_queue(airfe_bowdb* db, const MergeLoop* l, const int32_t* d_pairs, int P, int32_t* d_map, int32_t* d_info, hipStream_t st, const char* who) {
+  airfe_ctx* c = db->c;
+  if (!db->has_merge) return fail(c, std::string(who) + ": no merge attached (airfe_bowdb_attach_merge)");
+  if (db->size > MG_MAX_FRAMES) return fail(c, std::string(who) + ": more than 4096 frames in the database");
+  if (!d_map || !d_info) return fail(c, std::string(who) + ": bad argument");
+  if (l) {
+    if (l->Q < 0 || l->Q > MG_MAX_QUERIES) return fail(c, std::string(who) + ": Q must be 0 .. 4096");
+    if (l->mcap < 1 || l->mcap > MG_MAX_MATCHES) return fail(c, std::string(who) + ": mcap must be 1 .. 1024");
+    if (l->Q > 0 && (!l->qframe || !l->stage || !l->loop || !l->Rlq || !l->tlq || !l->mask || !l->idx || !l->nmatch)) return fail(c, std::string(who) + ": bad argument");
+    if (!mg_cam_ok(l->cam)) return fail(c, std::string(who) + ": fx and fy must be finite and not zero");
+  }
+  if (!l && (P < 0 || (P > 0 && !d_pairs))) return fail(c, std::string(who) + ": bad argument");
+  MergeCarve m(db);
+  if (m.k.into(c, db->g_scratch, st)) return 1;                     // (reserved at attach: the block is not replaced here)
+  const MergeWork w = m.work(db, d_map, d_info);
+  const MergeTables t{db->point_id, db->xyz, db->feat, db->n, db->size, db->cap, AIRFE_FEAT_DIM, db->max_points};
+  HIPCHK(c, hipMemsetAsync(d_info, 0, MG_INFO * 4, st));
+  if (l) launch_merge_loop(t, *l, w, st);
+  else launch_merge_pairs(t, d_pairs, P, w, st);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+int airfe_bowdb_attach_merge(airfe_bowdb* db) try {
+  BOWDB_ENTER(db);
+  airfe_ctx* c = db->c;
+  if (!db->point_id) return fail(c, "bowdb_attach_merge: no id table (airfe_bowdb_attach_point_ids)");
+  if (db->has_merge) return fail(c, "bowdb_attach_merge: the merge is attached already");
+  MergeCarve m(db);
+  if (m.k.into(c, db->g_scratch, c->stream)) return 1;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  db->has_merge = 1;
+  return 0;
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_merge_points_dev(airfe_bowdb* db, const int32_t* d_pairs, int P, int32_t* d_map, int32_t* d_info, void* stream) try {
+  BOWDB_ENTER(db);
+  return merge_queue(db, nullptr, d_pairs, P, d_map, d_info, stream_of(db->c, stream), "bowdb_merge_points_dev");
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_merge_points(airfe_bowdb* db, const int32_t* pairs, int P, int32_t* map, int32_t* info) try {
+  BOWDB_ENTER(db);
+  airfe_ctx* c = db->c;
+  if (!db->has_merge) return fail(c, "bowdb_merge_points: no merge attached (airfe_bowdb_attach_merge)");
+  if (!map || !info || P < 0 || (P > 0 && !pairs)) return fail(c, "bowdb_merge_points: bad argument");
+  MergeCarve m(db);
+  if (m.k.into(c, db->g_scratch, c->stream)) return 1;
+  if (P > 0 && reserve(c, db->g_pairs, (size_t)P * 8, c->stream)) return 1;      // the pair list's device copy: the one block of the merge that grows with a call
+  if (P > 0) HIPCHK(c, hipMemcpyAsync(db->g_pairs.p, pairs, (size_t)P * 8, hipMemcpyHostToDevice, c->stream));
+  if (merge_queue(db, nullptr, db->g_pairs.at<int32_t>(0), P, m.k.at<int32_t>(m.o_map), m.k.at<int32_t>(m.o_info), c->stream, "bowdb_merge_points")) return 1;
+  HIPCHK(c, hipMemcpyAsync(map, m.k.at<int32_t>(m.o_map), (size_t)db->max_points * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(info, m.k.at<int32_t>(m.o_info), MG_INFO * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+} AIRFE_CATCH(db->c)
+
+int airfe_bowdb_loop_merge_batch_dev(airfe_bowdb* db, const double* cam, const int32_t* d_qframe, int Q, const int* d_stage, const int32_t* d_loop,
+                                     const double* d_Rlq, const double* d_tlq, const uint8_t* d_mask, const int32_t* d_idx, int mcap, const int* d_nmatch,
+                                     int32_t* d_map, int32_t* d_info, void* stream) try {
+  BOWDB_ENTER(db);
+  if (!cam) return fail(db->c, "bowdb_loop_merge_batch_dev: bad argument");
+  const MergeLoop l{d_qframe, Q, d_stage, d_loop, d_Rlq, d_tlq, d_mask, d_idx, mcap, d_nmatch, {cam[0], cam[1], cam[2], cam[3]}};
+  return merge_queue(db, &l, nullptr, 0, d_map, d_info, stream_of(db->c, stream), "bowdb_loop_merge_batch_dev");
+} AIRFE_CATCH(db->c)
 
 }  // extern "C"

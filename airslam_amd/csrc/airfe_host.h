@@ -11,7 +11,7 @@
 //   airfe_geom.hip    F-RANSAC, PnP, stereo points, track pose, frame optimisation, stereo lines
 //   airfe_bowdb.hip   the BoW vector, the keyframe database and its map tables, the relocalisation and loop detection composites (airfe_bowdb.h: the database
 //                     struct and the *_queue functions the next two files share with it)
-//   airfe_bowmap.hip  the database's map-point id table, the covisibility build and the map-point triangulation
+//   airfe_bowmap.hip  the database's map-point id table, the covisibility build, the map-point triangulation and the map-point merge
 //   airfe_junction.hip  the junction connections, the database's junction tables, relocalisation's junction term and its composites
 //   airfe_debug.hip   the kernel-level test hooks (include/airfe_debug.h): HookStage, the one stream-ordered holder they stage, wait and read back through
 #pragma once

@@ -4,6 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct MergeTables;      // merge_core.h
+struct MergeLoop;
+
 namespace airfe {
 
 enum Epi {
@@ -615,6 +618,18 @@ struct FillPointsArgs {
 void launch_fill_points(const FillPointsArgs& a, hipStream_t st);
 // triangulate_core.h's triangulate_point_host, compiled in the kernels' translation unit (no contraction); cami: tr_cam's
 int triangulate_point_core(const double* cami, const double* Twc, const float* xy, int n, int min_observers, double* xyz);
+
+// The map-point merge of loop closure (map_refiner.cc:338-372, :409-459, :603-713; kernels_merge.hip, merge_core.h; contract: include/airfe.h)
+struct MergeWork {
+  int *parent = nullptr, *flags = nullptr, *src = nullptr, *best = nullptr, *root = nullptr;      // [max_points] x 5
+  int* staged = nullptr;                                                     // [max_frames][cap]: the id an adopting row takes, -1: none
+  int max_frames = 0;
+  int32_t *map = nullptr, *info = nullptr;                                   // the caller's [max_points], [8]: info is ZERO on entry
+};
+// steps 1 - 7 from loop detection's outputs; size <= 4096, Q <= 4096, mcap <= 1024
+void launch_merge_loop(const ::MergeTables& t, const ::MergeLoop& l, const MergeWork& w, hipStream_t st);
+// steps 4 - 7 on the pair list [P][2]
+void launch_merge_pairs(const ::MergeTables& t, const int32_t* pairs, int P, const MergeWork& w, hipStream_t st);
 
 // Relocalisation's junction term (frame.cc:581-629, map_user.cc:285-331; kernels_junction.hip, junction_core.h; contract: include/airfe.h)
 struct JunctionConnectArgs {

@@ -694,8 +694,8 @@ int airfe_bowdb_query_stored_batch_dev(airfe_bowdb* db, const int32_t* d_qframe,
  * Return codes: no map state; poses never set (airfe_bowdb_set_poses); Q * K above cfg.max_batch; mcap > 1024; more than 4096 frames in the database;
  * K outside 1 .. 5; Q > 4096.  A caller with a large map runs the stored query and airfe_bowdb_group_dev over all frames first (both are cheap) and hands
  * the composite only the frames that kept a group, in chunks of max_batch / K: d_qframe is an arbitrary list for that reason.
- * OUT OF SCOPE (the caller's, as in the reference): the "find more matches" search of :322-438, TriangulateMappoint, the mappoint merge, the pose graph,
- * junction sentences. */
+ * OUT OF SCOPE (the caller's, as in the reference): the "find more matches" search of :322-438, the pose graph, junction sentences.  (TriangulateMappoint
+ * and the mappoint merge are the blocks "Map-point triangulation" and "Map-point merge" below.) */
 typedef struct airfe_loop_cfg {
   float ratio;            /* 0.5f */
   int min_words;          /* 8 */
@@ -787,6 +787,59 @@ int airfe_bowdb_triangulate_points_dev(airfe_bowdb* db, const double* cam, int m
 int airfe_bowdb_triangulate_points(airfe_bowdb* db, const double* cam, int min_observers, double* xyz, int32_t* status, int32_t* nobs, int* n_ok);
 int airfe_bowdb_fill_points_dev(airfe_bowdb* db, const double* d_xyz, const int32_t* d_status, int only_missing, int32_t* d_written, void* stream);
 int airfe_triangulate_point(const double* cam, const double* Twc, const float* xy, int n, double* xyz, int* status);
+
+/* ---- Map-point merge: the tail of MapRefiner::RelativatePoseEstimation (src/map_refiner.cc:338-372, :409-459) and MapRefiner::MergeMappoints /
+ * MergeMappointGroup (:603-713), on the device ------------------------------------------------------------------------------------------------------
+ * What turns a detected loop into a changed map: from airfe_loop_detect_batch_dev's outputs and the id and point tables to MERGED tables, on one stream,
+ * nothing copied to the host, nothing allocated.  Afterwards airfe_bowdb_triangulate_points_dev + _fill_points_dev(only_missing) and
+ * airfe_bowdb_build_covisibility_dev bring positions and graph in line (api.BowDatabase.loop_close_dev queues all of it).
+ * airfe_bowdb_attach_merge (needs airfe_bowdb_attach_point_ids; a second attach is a return code) allocates 24 bytes per point (parent, flags, src, best,
+ * root, the host form's map) and 4 bytes per feature row (the adoption staging); every call initialises the per-point arrays, so its cost grows with
+ * max_points like the covisibility build's.
+ * THE STATEMENT (airslam_amd/csrc/merge_core.h; valid(f, i), size, n[f] and max_points as in the covisibility build; an id is VALID iff it is in
+ * [0, max_points); the point table is xyz[f][i]).  An id m is TRIANGULATED iff some valid row holding m has a non-NaN x; src(m) = the smallest key
+ * f * cap + i of such a row.  Every gate reads the id table and the point table AS THEY WERE BEFORE THE CALL.
+ *   (1) live entries.  For query q with d_stage[q] == 0, fq = d_qframe[q], b_f = d_loop[q] and list entry e < min(d_nmatch[q], mcap), (qi, ci) = d_idx[q][e]:
+ *       dead if fq or b_f is outside 0 .. size - 1, if qi >= n[fq] or ci >= n[b_f] or either is negative, or if B = point_id[b_f][ci] is not valid.
+ *       xyz[b_f][ci].x not NaN: live iff d_mask[q][e] != 0.  STATED DIFFERENCE: an outlier is dropped where the reference searches the inverted file
+ *       (find_more_matches_in_group).  xyz[b_f][ci].x NaN: live iff the epipolar test of :338-352 passes on p1 = feat[fq][qi].xy, p2 = feat[b_f][ci].xy, in
+ *       double, no fused multiply-adds, every 3 x 3 product element (a0 b0 + a1 b1) + a2 b2:  fxi = 1.0 / fx, fyi = 1.0 / fy,
+ *       Kit = [fxi 0 0; 0 fyi 0; -(cx fxi) -(cy fyi) 1] (K^-T in closed form), tx = [tlq]x, F = ((Kit tx) Rlq) K;  el_r = (F[r][0] x1 + F[r][1] y1) + F[r][2];
+ *       s = sqrt(el_0 el_0 + el_1 el_1);  er = ((x2 el_0 + y2 el_1) + el_2) / s;  passes iff er < 10 (the reference's signed comparison; a NaN er fails).
+ *       STATED DIFFERENCES: the loop frame's keypoint is row ci, not GetKeypointIdx; every feature row counts as having a word.
+ *   (2) adoption (:452-457).  A live entry whose point_id[fq][qi] is not valid: the row adopts B.  Several live entries adopting one row: the row takes the
+ *       SMALLEST such B and all those B are joined into one group.  The row's xyz = xyz[src(B)] if B is triangulated, else NaN.  STATED DIFFERENCE: the
+ *       reference inserts the point at the frame without AddObverser; here the id table IS the observer list.
+ *   (3) pairs.  A live entry whose A = point_id[fq][qi] is valid gives the pair (A, B).
+ *   (4) groups (:608-651) = the connected components over ids of the pairs and of (2)'s joins.  A group of one is untouched.
+ *   (5) best (:674-681) = the group's smallest triangulated id; if none is triangulated, its smallest id.
+ *   (6) relabel (:683-712), on the table.  Group G, best b, frame f, R = the valid rows of f whose id after adoption is in G.  Some row of R holds b: the rows
+ *       holding b stay, every other row of R becomes id -1 with NaN xyz (its map point was erased; the reference leaves a bad pointer there).  Otherwise,
+ *       with m* the smallest id in R and i* the first row of f holding m*: row i* gets id b and xyz[src(b)] (NaN if b is not triangulated), every other row
+ *       of R becomes -1 / NaN.  Not touched: rows >= n[f], frames >= size, rows of ids in no group.
+ *   (7) outputs, every entry written.  d_map i32 [max_points]: b for a member of a group, else the id itself.  d_info i32 [8]: live entries, entries dropped
+ *       as outliers, entries dropped by the epipolar test, rows adopted (whatever (6) then makes of them), groups, ids removed (the sum of the group sizes
+ *       minus the groups), rows relabelled to a best, rows cleared.
+ * No output byte depends on the order of the queries or of a list's entries, or on the order in which an atomic landed (the kernels' atomics decide minima,
+ * flag bits, counts and a union-find forest of which only each id's root, the smallest id of its component, is read); two calls on the same tables give the
+ * same bytes.  Three statements that agree byte for byte: merge_build_host / merge_pairs_host (merge_core.h), the kernels (kernels_merge.hip) and
+ * tests/merge_ref.py (whose epipolar gate is numpy's inv(K^T) tx R K: a decision, equal wherever er is not within rounding of 10).
+ *   _merge_points_dev       steps (4) - (7) on an explicit pair list d_pairs i32 [P][2], the reference's merged_mappoints.  A pair with an id that is not valid
+ *                           is ignored and counted: d_info = pairs taken, pairs ignored, 0, 0, then as above.  d_pairs may be NULL when P is 0.
+ *   _merge_points           the same from host buffers (map [max_points], info [8]) on the context's stream, then a synchronisation.
+ *   _loop_merge_batch_dev   steps (1) - (7) straight from the buffers airfe_loop_detect_batch_dev wrote (cam: HOST f64 [4] = fx, fy, cx, cy; d_mask u8
+ *                           [Q][mcap], d_idx i32 [Q][mcap][2]); the per-query arrays may be NULL when Q is 0.
+ * The _dev forms are asynchronous on `stream`, without host synchronisation or allocation; they CHANGE the id table and the point table in place: a
+ * covisibility build, triangulation, relocalisation or loop detection on ANOTHER stream must have completed.
+ * Return codes (nothing is changed then): no merge attached; more than 4096 frames in the database; Q > 4096; mcap > 1024; a NULL argument; fx or fy zero
+ * or non-finite.
+ * OUT OF SCOPE: find_more_matches_in_group and the inverted file; MergeMaplines; the pose graph; GlobalBA; track ids (SetTrackId). */
+int airfe_bowdb_attach_merge(airfe_bowdb* db);
+int airfe_bowdb_merge_points_dev(airfe_bowdb* db, const int32_t* d_pairs, int P, int32_t* d_map, int32_t* d_info, void* stream);
+int airfe_bowdb_merge_points(airfe_bowdb* db, const int32_t* pairs, int P, int32_t* map, int32_t* info);
+int airfe_bowdb_loop_merge_batch_dev(airfe_bowdb* db, const double* cam, const int32_t* d_qframe, int Q, const int* d_stage, const int32_t* d_loop,
+                                     const double* d_Rlq, const double* d_tlq, const uint8_t* d_mask, const int32_t* d_idx, int mcap, const int* d_nmatch,
+                                     int32_t* d_map, int32_t* d_info, void* stream);
 
 /* ---- Junction term: junction_frame_scores * (1 + rate) of MapUser::Relocalization (src/map_user.cc:285-331), on the device ---------------------------
  * The number per stored frame that airfe_bowdb_group_dev / airfe_relocalize_batch_dev add to a group's score through d_extra [Q][N].  d_extra[q][deputy] is
