@@ -82,6 +82,12 @@ class DebugLgBlockArgs(C.Structure):
                 + [("Np", C.c_int)] + [(n, C.c_void_p) for n in ("q", "k", "vt")] + [("rows_past", C.c_int * 5)])
 
 
+class DebugWgPrimsArgs(C.Structure):
+    """airfe_debug_wg_prims_args (include/airfe_debug.h)"""
+    _fields_ = [("v", C.c_void_p), ("keep", C.c_void_p), ("n", C.c_int), ("threads", C.c_int), ("keys", C.c_void_p), ("P", C.c_int), ("key_bytes", C.c_int),
+                ("scan", C.c_void_p), ("pos", C.c_void_p), ("totals", C.c_void_p), ("wave", C.c_void_p), ("sorted", C.c_void_p)]
+
+
 class DebugConvArgs(C.Structure):
     """airfe_debug_conv_args (include/airfe_debug.h)"""
     _fields_ = ([(n, C.c_void_p) for n in ("x", "img", "w1a", "b1a", "w", "b")] + [(n, C.c_int) for n in ("cin", "cout", "B", "H", "W", "pool", "out_pad", "relu", "wgs")]
@@ -325,6 +331,7 @@ SIGNATURES = {
     "airfe_debug_trace_buffer": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "airfe_debug_trace_slots": (C.c_int, [C.c_void_p]),
     "airfe_debug_conv_order": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
+    "airfe_debug_wg_prims": (C.c_int, [C.c_void_p, C.POINTER(DebugWgPrimsArgs)]),
     "airfe_debug_trace_slot": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
     "airfe_debug_trace_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "airfe_debug_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,

@@ -326,6 +326,21 @@ class Context:
         self._chk(self._l.airfe_debug_plnet_s1_last(self._h, la.ctypes.data, sc.ctypes.data, cap, C.byref(m2)), "airfe_debug_plnet_s1_last")
         return la[:m2.value].copy(), sc[:m2.value].copy()
 
+    def debug_wg_prims(self, v, keep, keys, threads: int):
+        """csrc/wg_prims.h alone in one workgroup of `threads` threads: v int32 [n], keep 0 / 1 [n], keys uint32 / uint64 [P] ->
+        dict(scan [n], pos [n], totals [5] = scan total, kept, block_sum, block_max, block_min, wave [threads / 64, 3] = sum, max, min, sorted [P])."""
+        v = np.ascontiguousarray(v, dtype=np.int32)
+        keep = np.ascontiguousarray(keep, dtype=np.uint8)
+        keys = np.ascontiguousarray(keys)
+        assert keys.dtype in (np.uint32, np.uint64) and keep.shape == v.shape
+        out = {"scan": np.empty_like(v), "pos": np.empty_like(v), "totals": np.empty((5,), np.int32), "wave": np.empty((threads // 64, 3), np.int32),
+               "sorted": np.empty_like(keys)}
+        a = _lib.DebugWgPrimsArgs(v.ctypes.data, keep.ctypes.data, v.size, threads, keys.ctypes.data, keys.size, keys.dtype.itemsize, out["scan"].ctypes.data,
+                                  out["pos"].ctypes.data,
+                                  out["totals"].ctypes.data, out["wave"].ctypes.data, out["sorted"].ctypes.data)
+        self._chk(self._l.airfe_debug_wg_prims(self._h, C.byref(a)), "airfe_debug_wg_prims")
+        return out
+
     def match_superglue(self, f0: np.ndarray, f1: np.ndarray):
         """f0/f1: [n, 259] rows (score, normalised x, y, desc) -> (indices0, indices1, mscores0, mscores1)."""
         f0 = np.ascontiguousarray(f0, dtype=np.float32)

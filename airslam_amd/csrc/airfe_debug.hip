@@ -1,7 +1,9 @@
 // airfe — the kernel-level test hooks of libairfe.so (include/airfe_debug.h): host tensors -> one production launcher or line-path step -> host tensors.  Every hook has one
 // shape: argument checks, staging through a HookStage, the launches, the wait, read-backs through the HookStage.
 #include "airfe_host.h"
+#include "wg_prims.h"
 
+#include <limits.h>
 #include <memory>
 
 // One hook call's device work, bound to the context, the hook's name and the context's stream: every buffer the hook makes, every fill, upload and read-back, and the wait.
@@ -112,6 +114,46 @@ static void dbg_back2(const std::vector<uint16_t>& v, size_t n, int prec, float*
 }
 static void dbg_gemm_dispatch(const airfe_ctx* c, GemmArgs& g, int gr_wgs) {      // the context's dispatch thresholds, as run_linear hands them on
   g.small_max = c->gemm_small_max; g.g8_min = c->gemm8_min; g.gr_min = c->gemmr_min; g.gr_wgs = gr_wgs > 0 ? gr_wgs : c->gemmr_wgs;
+}
+
+// wg_prims.h on host arrays (airfe_debug_wg_prims): one workgroup, rounds of THREADS with a running base as in the production loops
+template <int THREADS, class K>
+__global__ __launch_bounds__(THREADS) void wg_prims_kernel(const int* v, const uint8_t* keep, int n, const K* keys, int P, int* scan, int* pos, int* totals, int* wave,
+                                                           K* sorted) {
+  __shared__ int wsum[THREADS / 64];
+  __shared__ K key[32768 / sizeof(K)];
+  const int t = threadIdx.x;
+  const int x0 = t < n ? v[t] : 0;
+  const int ws = wave_sum(x0), wx = wave_max(x0), wn = wave_min(x0);
+  if ((t & 63) == 0) { wave[3 * (t >> 6)] = ws; wave[3 * (t >> 6) + 1] = wx; wave[3 * (t >> 6) + 2] = wn; }
+  int sbase = 0, cbase = 0, s = 0, mx = INT_MIN, mn = INT_MAX;
+  for (int i0 = 0; i0 < n; i0 += THREADS) {                    // (uniform)
+    const int i = i0 + t;
+    const int x = i < n ? v[i] : 0;
+    int stot, ctot;
+    const int ex = sbase + block_excl_scan<THREADS>(x, wsum, &stot);
+    const int p = cbase + block_compact<THREADS>(i < n && keep[i], wsum, &ctot);
+    if (i < n) { scan[i] = ex; pos[i] = p; s += x; mx = max(mx, x); mn = min(mn, x); }
+    sbase += stot;
+    cbase += ctot;
+  }
+  s = block_sum<THREADS>(s, wsum);
+  mx = block_max<THREADS>(mx, wsum);
+  mn = block_min<THREADS>(mn, wsum);
+  if (t == 0) { totals[0] = sbase; totals[1] = cbase; totals[2] = s; totals[3] = mx; totals[4] = mn; }
+  for (int i = t; i < P; i += THREADS) key[i] = keys[i];
+  block_sort_asc<THREADS>(key, P);
+  for (int i = t; i < P; i += THREADS) sorted[i] = key[i];
+}
+template <int THREADS>
+static void launch_wg_prims(const airfe_debug_wg_prims_args* a, const int* v, const uint8_t* keep, const void* keys, int* out, void* sorted, hipStream_t st) {
+  int *scan = out, *pos = out + a->n, *totals = out + 2 * a->n, *wave = totals + 5;
+  if (a->key_bytes == 4)
+    hipLaunchKernelGGL((wg_prims_kernel<THREADS, unsigned>), dim3(1), dim3(THREADS), 0, st, v, keep, a->n, static_cast<const unsigned*>(keys), a->P, scan, pos, totals,
+                       wave, static_cast<unsigned*>(sorted));
+  else
+    hipLaunchKernelGGL((wg_prims_kernel<THREADS, unsigned long long>), dim3(1), dim3(THREADS), 0, st, v, keep, a->n, static_cast<const unsigned long long*>(keys), a->P,
+                       scan, pos, totals, wave, static_cast<unsigned long long*>(sorted));
 }
 
 extern "C" {
@@ -1174,6 +1216,34 @@ int airfe_debug_plnet_s1_last(airfe_ctx* c, float* lines_adjusted, float* scores
   HookStage s(c, "debug_plnet_s1_last");
   s.wait(HookStage::DEVICE_WIDE);              // the last entry may have run the line path on the second stream
   return dbg_s1_rows(s, c, lines_adjusted, scores_line, cap, m2);
+} AIRFE_CATCH(c)
+
+/* csrc/wg_prims.h alone on HOST arrays, in one workgroup */
+int airfe_debug_wg_prims(airfe_ctx* c, airfe_debug_wg_prims_args* a) try {
+  if (c && enter_device(c)) return 1;
+  if (!c || !a) return fail(c, "debug_wg_prims: bad argument");
+  const bool sizes = (a->threads == 64 || a->threads == 256 || a->threads == 1024) && a->n >= 0 && a->n <= (1 << 20) && (a->key_bytes == 4 || a->key_bytes == 8) &&
+                     a->P >= 0 && (a->P & (a->P - 1)) == 0 && (size_t)a->P * a->key_bytes <= 32768;
+  if (!sizes || !a->totals || !a->wave || (a->n && (!a->v || !a->keep || !a->scan || !a->pos)) || (a->P && (!a->keys || !a->sorted)))
+    return fail(c, "debug_wg_prims: bad argument");
+  HookStage s(c, "debug_wg_prims");
+  const size_t n = a->n, kb = (size_t)a->P * a->key_bytes, n_out = 2 * n + 5 + 3 * (a->threads / 64);
+  const int* v = s.up(a->v, n);
+  const uint8_t* keep = s.up(a->keep, n);
+  const uint8_t* keys = s.up(static_cast<const uint8_t*>(a->keys), kb);
+  int* out = s.fresh<int>(n_out, 0xFF);                           // scan | pos | totals | wave
+  uint8_t* sorted = s.fresh<uint8_t>(kb, 0xFF);
+  if (s.status()) return 1;
+  if (a->threads == 64) launch_wg_prims<64>(a, v, keep, keys, out, sorted, s.stream());
+  else if (a->threads == 256) launch_wg_prims<256>(a, v, keep, keys, out, sorted, s.stream());
+  else launch_wg_prims<1024>(a, v, keep, keys, out, sorted, s.stream());
+  s.wait(HookStage::OWN_TEXT);
+  s.get(a->scan, out, n * 4);
+  s.get(a->pos, out + n, n * 4);
+  s.get(a->totals, out + 2 * n, 5 * 4);
+  s.get(a->wave, out + 2 * n + 5, (size_t)3 * (a->threads / 64) * 4);
+  s.get(a->sorted, sorted, kb);
+  return s.status();
 } AIRFE_CATCH(c)
 
 }  // extern "C"

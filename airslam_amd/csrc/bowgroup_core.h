@@ -13,11 +13,7 @@
 
 #include <vector>
 
-#if defined(__HIPCC__)
-#define BG_HD __host__ __device__ inline
-#else
-#define BG_HD inline
-#endif
+#include "core_common.h"
 
 #define BG_MAX_CAND 4096        // candidates per query the kernel holds in LDS
 #define BG_MODE_RELOC 0
@@ -29,7 +25,7 @@
 #define BG_TOP 5                // CoviFrameScoreNum
 
 // slot of frame f in the ascending list, or -1
-BG_HD int bg_find(const int32_t* frame, int n, int f) {
+AIRFE_HD int bg_find(const int32_t* frame, int n, int f) {
   int lo = 0, hi = n;
   while (lo < hi) {
     const int mid = (lo + hi) >> 1;
@@ -39,14 +35,14 @@ BG_HD int bg_find(const int32_t* frame, int n, int f) {
 }
 
 // the covisibility row of frame f: entries [*e0, *e1)
-BG_HD void bg_row(const int32_t* row_ptr, int rows, int f, int* e0, int* e1) {
+AIRFE_HD void bg_row(const int32_t* row_ptr, int rows, int f, int* e0, int* e1) {
   if (f < 0 || f >= rows) { *e0 = *e1 = 0; return; }
   *e0 = row_ptr[f];
   *e1 = row_ptr[f + 1];
 }
 
 // map_user.cc:183-206 for candidate slot i: the group's score and its deputy's slot
-BG_HD void bg_candidate(const int32_t* frame, const double* score, int n, const int32_t* row_ptr, const int32_t* nbr, const int32_t* weight, int rows, int i,
+AIRFE_HD void bg_candidate(const int32_t* frame, const double* score, int n, const int32_t* row_ptr, const int32_t* nbr, const int32_t* weight, int rows, int i,
                         double* gscore, int* deputy) {
   double s = 0.0 + score[i], ds = score[i];       // group_score starts at 0 (map_user.h:24): a score of -0 enters as +0
   int d = i, e0, e1;
@@ -65,7 +61,7 @@ BG_HD void bg_candidate(const int32_t* frame, const double* score, int n, const 
 
 // map_user.cc:208-216 over the whole list, in list order: group_of[d] = the slot of the candidate whose group is stored under deputy slot d (-1: none).
 // Returns best_group_score.  Sequential by contract: a later candidate replaces a stored group only with a strictly larger score.
-BG_HD double bg_replace(const double* gscore, const int* deputy, int n, int* group_of) {
+AIRFE_HD double bg_replace(const double* gscore, const int* deputy, int n, int* group_of) {
   double best = -1.0;
   for (int i = 0; i < n; ++i) {
     const int d = deputy[i];
@@ -80,13 +76,13 @@ BG_HD double bg_replace(const double* gscore, const int* deputy, int n, int* gro
 }
 
 // is (s, p) ranked behind (ps, pp)?  Ranking: score descending, ties to the lower position.
-BG_HD bool bg_behind(double s, int p, double ps, int pp) { return s < ps || (s == ps && p > pp); }
+AIRFE_HD bool bg_behind(double s, int p, double ps, int pp) { return s < ps || (s == ps && p > pp); }
 // is (s, p) ranked before (bs, bp)?  bp < 0: there is no (bs, bp) yet
-BG_HD bool bg_before(double s, int p, double bs, int bp) { return bp < 0 || s > bs || (s == bs && p < bp); }
+AIRFE_HD bool bg_before(double s, int p, double bs, int bp) { return bp < 0 || s > bs || (s == bs && p < bp); }
 
 // map_user.cc:224-240 for the group candidate slot i stored: its members are the candidate and its qualifying neighbours (a std::set: the own entry
 // counts once); more than 5 members: the five largest scores in descending order, otherwise every score in ascending frame index; from +0.
-BG_HD double bg_resum(const int32_t* frame, const double* score, int n, const int32_t* row_ptr, const int32_t* nbr, const int32_t* weight, int rows, int i) {
+AIRFE_HD double bg_resum(const int32_t* frame, const double* score, int n, const int32_t* row_ptr, const int32_t* nbr, const int32_t* weight, int rows, int i) {
   const int f = frame[i];
   const double si = score[i];
   int e0, e1, members = 1;
@@ -130,7 +126,7 @@ BG_HD double bg_resum(const int32_t* frame, const double* score, int n, const in
 }
 
 // map_refiner.cc:177-191: is the deputy farther from the query than max_dist?
-BG_HD bool bg_far(const double* qpos, const double* p, double max_dist) {
+AIRFE_HD bool bg_far(const double* qpos, const double* p, double max_dist) {
   const double dx = qpos[0] - p[0], dy = qpos[1] - p[1], dz = qpos[2] - p[2];
   return sqrt((dx * dx + dy * dy) + dz * dz) > max_dist;
 }

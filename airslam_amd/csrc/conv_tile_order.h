@@ -17,9 +17,9 @@
 #pragma once
 
 #if defined(__HIPCC__)
-#define AIRFE_CTO_HD __host__ __device__ __forceinline__
+#define AIRFE_CTO_FN __host__ __device__ __forceinline__
 #else
-#define AIRFE_CTO_HD inline
+#define AIRFE_CTO_FN inline
 #endif
 
 namespace airfe {
@@ -36,8 +36,8 @@ struct ConvTileOrder {
   int sh_bw = 0, sh_blk = 0;                  // log2 bw, log2 (bw * bh)
 };
 
-AIRFE_CTO_HD bool conv_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
-AIRFE_CTO_HD int conv_log2(int v) {
+AIRFE_CTO_FN bool conv_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+AIRFE_CTO_FN int conv_log2(int v) {
   int s = 0;
   while ((1 << (s + 1)) <= v) ++s;
   return s;
@@ -46,7 +46,7 @@ AIRFE_CTO_HD int conv_log2(int v) {
 // The plan of one launch.  order 0: raster.  tile_w x tile_h: the tile in pixels (the block is grown toward a square of pixels).
 // Blocked needs grid % 8 == 0 and passes a power of two that divides grid / 8; everything else keeps the raster walk,
 // one launch per pass (the caller loops pass0 over `conv_tile_launches`).
-AIRFE_CTO_HD ConvTileOrder conv_tile_order(int order, int grid, int tiles_x, int tiles_y, int images, int passes, int tile_w, int tile_h) {
+AIRFE_CTO_FN ConvTileOrder conv_tile_order(int order, int grid, int tiles_x, int tiles_y, int images, int passes, int tile_w, int tile_h) {
   ConvTileOrder o;
   o.tiles_x = tiles_x;
   o.per_img = tiles_x * tiles_y;
@@ -77,11 +77,11 @@ AIRFE_CTO_HD ConvTileOrder conv_tile_order(int order, int grid, int tiles_x, int
   return o;
 }
 // the launches a layer of `passes` cout passes takes under plan o (the caller steps o.pass0 through them)
-AIRFE_CTO_HD int conv_tile_launches(const ConvTileOrder& o, int passes) { return o.chunk ? 1 : passes; }
+AIRFE_CTO_FN int conv_tile_launches(const ConvTileOrder& o, int passes) { return o.chunk ? 1 : passes; }
 
 // workgroup wg of `grid`: its first tile item, the step from one iteration to the next, and its pass.  The walk is
 //   for (tile = first; tile < o.ntiles; tile += step)
-AIRFE_CTO_HD void conv_tile_first(const ConvTileOrder& o, int wg, int grid, int& first, int& step, int& pass) {
+AIRFE_CTO_FN void conv_tile_first(const ConvTileOrder& o, int wg, int grid, int& first, int& step, int& pass) {
   if (o.chunk) {
     const int x = wg & (CONV_XCDS - 1), s = wg >> 3;
     first = x * o.chunk + (s >> o.sh_pass);
@@ -96,7 +96,7 @@ AIRFE_CTO_HD void conv_tile_first(const ConvTileOrder& o, int wg, int grid, int&
 
 // tile item -> (image, tile row, tile column).  Two forms, chosen by the plan (sh_img >= 0: shifts): a kernel at its register limit compiles one
 // instantiation per form (conv128r_kernel), the others branch (wave-uniform)
-AIRFE_CTO_HD void conv_tile_decode_shift(const ConvTileOrder& o, int tile, int& b, int& ty, int& tx) {
+AIRFE_CTO_FN void conv_tile_decode_shift(const ConvTileOrder& o, int tile, int& b, int& ty, int& tx) {
   b = tile >> o.sh_img;
   const int rem = tile & (o.per_img - 1);
   const int blk = rem >> o.sh_blk, w = rem & ((1 << o.sh_blk) - 1);
@@ -104,19 +104,19 @@ AIRFE_CTO_HD void conv_tile_decode_shift(const ConvTileOrder& o, int tile, int& 
   ty = ((blk >> sh_bx) << sh_bh) + (w >> o.sh_bw);
   tx = ((blk & ((1 << sh_bx) - 1)) << o.sh_bw) + (w & ((1 << o.sh_bw) - 1));
 }
-AIRFE_CTO_HD void conv_tile_decode_div(const ConvTileOrder& o, int tile, int& b, int& ty, int& tx) {
+AIRFE_CTO_FN void conv_tile_decode_div(const ConvTileOrder& o, int tile, int& b, int& ty, int& tx) {
   b = tile / o.per_img;
   const int rem = tile - b * o.per_img;
   ty = rem / o.tiles_x;
   tx = rem - ty * o.tiles_x;
 }
-AIRFE_CTO_HD void conv_tile_decode(const ConvTileOrder& o, int tile, int& b, int& ty, int& tx) {
+AIRFE_CTO_FN void conv_tile_decode(const ConvTileOrder& o, int tile, int& b, int& ty, int& tx) {
   if (o.sh_img >= 0) conv_tile_decode_shift(o, tile, b, ty, tx);
   else conv_tile_decode_div(o, tile, b, ty, tx);
 }
 
 // (workgroup, iteration) -> (pass, image, tile row, tile column); false: the workgroup has no tile in that iteration
-AIRFE_CTO_HD bool conv_tile_map(const ConvTileOrder& o, int wg, int i, int grid, int& pass, int& b, int& ty, int& tx) {
+AIRFE_CTO_FN bool conv_tile_map(const ConvTileOrder& o, int wg, int i, int grid, int& pass, int& b, int& ty, int& tx) {
   int first, step;
   conv_tile_first(o, wg, grid, first, step, pass);
   const long long tile = (long long)first + (long long)i * step;

@@ -14,22 +14,16 @@
 #include <algorithm>
 #include <vector>
 
-#if defined(__HIPCC__)
-#define CV_HD __host__ __device__ inline
-#else
-#define CV_HD inline
-#endif
+#include "core_common.h"
 
 #define CV_MAX_FRAMES 4096           // frames the build handles: one row's weights are an LDS histogram of this many int32
 #define CV_MAX_POINTS (1 << 24)      // map points an id table can be attached for: 8 bytes of work memory per point
 #define CV_SCAN_TILE 2048            // points per workgroup of the segment-start scan
 
-// the stored feature count of a frame as every reader clamps it
-CV_HD int cv_rows(int n, int cap) { return n < 0 ? 0 : (n > cap ? cap : n); }
 
 // what row i of a frame holds for the build: its id, or -1 (a row past the count is not an id and is never read as one; an id outside
 // [0, max_points) is ignored).  *ignored: 1 iff the row is inside the count and its id is neither -1 nor in range.
-CV_HD int cv_row_id(const int32_t* frame_ids, int i, int n, int max_points, int* ignored) {
+AIRFE_HD int cv_row_id(const int32_t* frame_ids, int i, int n, int max_points, int* ignored) {
   *ignored = 0;
   if (i >= n) return -1;
   const int id = frame_ids[i];
@@ -39,12 +33,12 @@ CV_HD int cv_row_id(const int32_t* frame_ids, int i, int n, int max_points, int*
 }
 
 // the work table's entry of a row: -1 without a point, otherwise the id and whether the row is the FIRST of its frame that holds it
-CV_HD int cv_pack(int id, bool first) { return id < 0 ? -1 : id * 2 + (first ? 1 : 0); }
-CV_HD int cv_id(int packed) { return packed < 0 ? -1 : packed >> 1; }
-CV_HD bool cv_first(int packed) { return packed >= 0 && (packed & 1); }
+AIRFE_HD int cv_pack(int id, bool first) { return id < 0 ? -1 : id * 2 + (first ? 1 : 0); }
+AIRFE_HD int cv_id(int packed) { return packed < 0 ? -1 : packed >> 1; }
+AIRFE_HD bool cv_first(int packed) { return packed >= 0 && (packed & 1); }
 
 // is row i the first of rows 0 .. i that holds ids[i]?  (ids: the frame's cv_row_id values)
-CV_HD bool cv_first_occurrence(const int* ids, int i) {
+AIRFE_HD bool cv_first_occurrence(const int* ids, int i) {
   const int v = ids[i];
   if (v < 0) return false;
   for (int j = 0; j < i; ++j)
@@ -53,7 +47,7 @@ CV_HD bool cv_first_occurrence(const int* ids, int i) {
 }
 
 // info i32 [4]: status (0 ok, 1 overflow), entries needed, valid (frame, row) entries, ids ignored as out of range
-CV_HD void cv_info(int32_t* info, long long needed, int max_edges, int valid, int ignored) {
+AIRFE_HD void cv_info(int32_t* info, long long needed, int max_edges, int valid, int ignored) {
   info[0] = needed > max_edges ? 1 : 0;
   info[1] = (int32_t)needed;
   info[2] = valid;
@@ -68,7 +62,7 @@ inline void covis_build_host(const int32_t* point_id, const int* n, int size, in
   std::vector<int> count((size_t)max_points + 1, 0);
   int valid = 0, ignored = 0;
   for (int f = 0; f < size; ++f) {
-    const int nf = cv_rows(n[f], cap);
+    const int nf = clamp_count(n[f], cap);
     for (int i = 0; i < cap; ++i) {
       int ig;
       ids[i] = cv_row_id(point_id + (size_t)f * cap, i, nf, max_points, &ig);

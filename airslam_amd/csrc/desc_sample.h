@@ -6,6 +6,7 @@
 #include <cfloat>
 
 #include "common.h"
+#include "wg_prims.h"
 
 namespace airfe {
 

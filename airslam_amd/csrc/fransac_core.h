@@ -8,11 +8,7 @@
 #include <stdint.h>
 #include <math.h>
 
-#if defined(__HIPCC__) || defined(__HIP__)
-#define FR_HD __host__ __device__ inline
-#else
-#define FR_HD inline
-#endif
+#include "core_common.h"
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
@@ -24,27 +20,27 @@
 #define FR_MIN_RANSAC 15       // 9..14 matches: LMedS
 #define FR_THRESH2 400.0f      // 20 px, squared
 
-FR_HD uint64_t fr_splitmix64(uint64_t z) {
+AIRFE_HD uint64_t fr_splitmix64(uint64_t z) {
   z += 0x9E3779B97F4A7C15ULL;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
   return z ^ (z >> 31);
 }
 // index of slot `slot` (0..6) of draw `attempt` of sample `s` among n matches
-FR_HD int fr_draw(int s, int attempt, int slot, int n) {
+AIRFE_HD int fr_draw(int s, int attempt, int slot, int n) {
   const uint64_t h = fr_splitmix64(FR_SEED ^ (((uint64_t)s << 32) | ((uint64_t)attempt << 8) | (uint64_t)slot));
   return (int)(((h >> 32) * (uint64_t)n) >> 32);
 }
 
 // OpenCV's collinearity form: |dx2*dy1 - dy2*dx1| <= FLT_EPSILON * (|dx1| + |dy1| + |dx2| + |dy2|)
-FR_HD bool fr_collinear(double xi, double yi, double xj, double yj, double xk, double yk) {
+AIRFE_HD bool fr_collinear(double xi, double yi, double xj, double yj, double xk, double yk) {
   const double dx1 = xj - xi, dy1 = yj - yi, dx2 = xk - xi, dy2 = yk - yi;
   return fabs(dx2 * dy1 - dy2 * dx1) <= 1.1920928955078125e-07 * (fabs(dx1) + fabs(dy1) + fabs(dx2) + fabs(dy2));
 }
 
 // Draws sample s: X[k] = (x0, y0, x1, y1) of its 7 matches (xy: [n][4], truncated coordinates).  false: every attempt was degenerate.
 template <typename T>
-FR_HD bool fr_sample(const T* xy, int n, int s, double X[7][4]) {
+AIRFE_HD bool fr_sample(const T* xy, int n, int s, double X[7][4]) {
   for (int att = 0; att < FR_MAX_ATTEMPTS; ++att) {
     int id[7];
 #pragma unroll
@@ -72,11 +68,11 @@ FR_HD bool fr_sample(const T* xy, int n, int s, double X[7][4]) {
   return false;
 }
 
-FR_HD double fr_det3(const double* m) {
+AIRFE_HD double fr_det3(const double* m) {
   return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
 }
 // det of the matrix whose column j is Y's where bit j of `mask` is set, X's otherwise
-FR_HD double fr_det3_mix(const double* X, const double* Y, int mask) {
+AIRFE_HD double fr_det3_mix(const double* X, const double* Y, int mask) {
   double m[9];
 #pragma unroll
   for (int i = 0; i < 9; ++i) m[i] = (mask >> (i % 3)) & 1 ? Y[i] : X[i];
@@ -84,7 +80,7 @@ FR_HD double fr_det3_mix(const double* X, const double* Y, int mask) {
 }
 
 // The 7-point solver: F[r][9] (row-major, x1^T F x0 = 0) for its 1..3 real roots, in root order; returns the number of models (0: degenerate).
-FR_HD int fr_solve7(const double X[7][4], double F[3][9]) {
+AIRFE_HD int fr_solve7(const double X[7][4], double F[3][9]) {
   double A[7][9];
   double mx = 0.0;
 #pragma unroll
@@ -199,7 +195,7 @@ FR_HD int fr_solve7(const double X[7][4], double F[3][9]) {
 }
 
 // the larger of the two squared point-to-epipolar-line distances, in double, rounded to float; NaN counts as +inf
-FR_HD float fr_error(const double* f, double x0, double y0, double x1, double y1) {
+AIRFE_HD float fr_error(const double* f, double x0, double y0, double x1, double y1) {
   const double a = f[0] * x0 + f[1] * y0 + f[2], b = f[3] * x0 + f[4] * y0 + f[5], c = f[6] * x0 + f[7] * y0 + f[8];
   const double d = x1 * a + y1 * b + c;
   const double ap = f[0] * x1 + f[3] * y1 + f[6], bp = f[1] * x1 + f[4] * y1 + f[7];
@@ -210,7 +206,7 @@ FR_HD float fr_error(const double* f, double x0, double y0, double x1, double y1
 }
 
 // RANSACUpdateNumIters(0.99, (n - good) / n, 7, 1000), with (1 - ep)^7 as repeated products
-FR_HD int fr_update_niters(int n, int good) {
+AIRFE_HD int fr_update_niters(int n, int good) {
   const double ep = (double)(n - good) / (double)n;
   const double num = 1.0 - 0.99;
   const double q = 1.0 - ep, q2 = q * q, q4 = q2 * q2;
@@ -221,7 +217,7 @@ FR_HD int fr_update_niters(int n, int good) {
 }
 
 // LMedS inlier bound from the smallest median: sigma = max(2.5 * 1.4826 * (1 + 5 / (n - 7)) * sqrt(median), 0.001); err <= (float)sigma^2
-FR_HD float fr_lmeds_thresh(int n, float median) {
+AIRFE_HD float fr_lmeds_thresh(int n, float median) {
   double sigma = 2.5 * 1.4826 * (1.0 + 5.0 / (double)(n - 7)) * sqrt((double)median);
   sigma = sigma > 0.001 ? sigma : 0.001;
   return (float)(sigma * sigma);

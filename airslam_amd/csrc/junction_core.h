@@ -1,6 +1,6 @@
 // airfe — relocalisation's junction term: Frame::FindJunctionConnections (src/frame.cc:581-629) and the counts of MapUser::Relocalization
 // (src/map_user.cc:285-331) on plain arrays.  Contract: include/airfe.h ("Junction term").  One statement for the host and the device: the kernels
-// (kernels_junction.hip) call the JN_HD routines below from their lanes, the *_host routines at the end call them in loops; tests/junction_ref.py restates
+// (kernels_junction.hip) call the AIRFE_HD routines below from their lanes, the *_host routines at the end call them in loops; tests/junction_ref.py restates
 // the reference literally (dense H x W map, std::set, inverted file, match_matrix, four nested loops).
 //   pixel(i)      ((int)((double)jx + 0.5), (int)((double)jy + 0.5)) of junction row i = (score, jx, jy, ...); outside [0, W) x [0, H): owns no cell
 //   owner(r, c)   the HIGHEST index i with pixel(i) = (c, r)  (the reference writes its map in index order)
@@ -19,11 +19,7 @@
 #include <algorithm>
 #include <vector>
 
-#if defined(__HIPCC__)
-#define JN_HD __host__ __device__ inline
-#else
-#define JN_HD inline
-#endif
+#include "core_common.h"
 
 #define JN_MAX_JUNCTIONS 1024        // junctions per frame (= BOW_MAX_FEATURES: the BoW kernels' limit)
 #define JN_MAX_EDGES 4096            // distinct directed edges per frame (ecap <= this): the products of the term fit int32
@@ -34,10 +30,9 @@
 #define JN_UNSET 1                   // a stored frame without junction state
 #define JN_OVERFLOW 2                // more than ecap distinct edges (or more than 1024 junctions): no edges, a term of 0
 
-JN_HD int jn_count(int n, int cap) { return n < 0 ? 0 : (n > cap ? cap : n); }
 
 // int(v + 0.5) as the reference computes it (a double sum, truncated towards zero); false where that conversion is undefined
-JN_HD bool jn_cell(double v, int* out) {
+AIRFE_HD bool jn_cell(double v, int* out) {
   const double t = v + 0.5;
   if (!(t > -2147483648.0 && t < 2147483648.0)) return false;       // NaN, infinities and everything outside int
   *out = (int)t;
@@ -45,7 +40,7 @@ JN_HD bool jn_cell(double v, int* out) {
 }
 
 // frame.cc:588-590 for one junction row; *x = JN_NO_PIXEL where the junction owns no cell
-JN_HD void jn_pixel(const float* row, int W, int H, int* x, int* y) {
+AIRFE_HD void jn_pixel(const float* row, int W, int H, int* x, int* y) {
   int px = 0, py = 0;
   if (jn_cell((double)row[1], &px) && jn_cell((double)row[2], &py) && px >= 0 && px < W && py >= 0 && py < H) { *x = px; *y = py; return; }
   *x = JN_NO_PIXEL;
@@ -54,7 +49,7 @@ JN_HD void jn_pixel(const float* row, int W, int H, int* x, int* y) {
 
 // frame.cc:594-617 over the junctions' pixels instead of the dense map: the row-major scan with a strict < keeps the first cell of the smallest distance,
 // i.e. the smallest (d, r, c); a cell shared by several junctions belongs to the highest index
-JN_HD int jn_match(const int* px, const int* py, int nj, double ex, double ey) {
+AIRFE_HD int jn_match(const int* px, const int* py, int nj, double ex, double ey) {
   int xi = 0, yi = 0;
   if (!jn_cell(ex, &xi) || !jn_cell(ey, &yi)) return -1;
   int best = -1, bd = 2 * JN_WS + 1, br = 0, bc = 0;
@@ -69,14 +64,14 @@ JN_HD int jn_match(const int* px, const int* py, int nj, double ex, double ey) {
   return best;
 }
 
-JN_HD unsigned jn_edge_key(int a, int b) { return ((unsigned)a << 16) | (unsigned)b; }
-JN_HD unsigned long long jn_word_key(unsigned wa, unsigned wb) { return ((unsigned long long)wa << 32) | wb; }
+AIRFE_HD unsigned jn_edge_key(int a, int b) { return ((unsigned)a << 16) | (unsigned)b; }
+AIRFE_HD unsigned long long jn_word_key(unsigned wa, unsigned wb) { return ((unsigned long long)wa << 32) | wb; }
 // is (a, b) an edge between two junctions of the frame?  (an edge list handed in by a caller is read with this guard)
-JN_HD bool jn_edge_ok(int a, int b, int nj) { return a >= 0 && a < nj && b >= 0 && b < nj; }
+AIRFE_HD bool jn_edge_ok(int a, int b, int nj) { return a >= 0 && a < nj && b >= 0 && b < nj; }
 
 // position of `w` in an ascending table of n distinct entries, or -1
 template <class T>
-JN_HD int jn_find(const T* tab, int n, T w) {
+AIRFE_HD int jn_find(const T* tab, int n, T w) {
   int lo = 0, hi = n;
   while (lo < hi) {
     const int mid = (lo + hi) >> 1;
@@ -86,7 +81,7 @@ JN_HD int jn_find(const T* tab, int n, T w) {
 }
 
 // map_user.cc:329-331: one division, one add, one multiply (the kernel file is compiled with -ffp-contract=off)
-JN_HD double jn_extra(double score, int match_num, int line_match_num) {
+AIRFE_HD double jn_extra(double score, int match_num, int line_match_num) {
   const double rate = match_num > 0 ? (double)line_match_num / match_num : 0;
   return score * (1.0 + rate);
 }

@@ -10,39 +10,22 @@
 //   bowdb_topk_kernel     (query)  the project's own ranking: K best scores, ties to the lower frame index
 //   bowdb_gather_kernel / bowdb_best_kernel  the composite's glue around the context's LightGlue batch and the F-matrix RANSAC
 #include "common.h"
+#include "core_common.h"
 #include "kernels.h"
+#include "wg_prims.h"
 
 namespace airfe {
 
 namespace {
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// exclusive scan of one int per thread over a 256-thread workgroup; returns the thread's offset, *total = the sum
-__device__ int block_scan256(int v, int* buf, int* total) {
-  const int t = threadIdx.x;
-  buf[t] = v;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    const int x = t >= d ? buf[t - d] : 0;
-    __syncthreads();
-    buf[t] += x;
-    __syncthreads();
-  }
-  const int incl = buf[t];
-  *total = buf[255];
-  __syncthreads();
-  return incl - v;
-}
-
 __global__ __launch_bounds__(256) void bow_vector_kernel(BowVecArgs a) {
   __shared__ unsigned long long key[BOW_MAX_FEATURES];
   __shared__ double val[BOW_MAX_FEATURES];
   __shared__ unsigned sid[BOW_MAX_FEATURES];
-  __shared__ int scan[256];
+  __shared__ int scan[4];
   __shared__ double s_tot;
   const int b = blockIdx.x, t = threadIdx.x;
-  const int n = clampi(a.n[b], 0, a.cap);
+  const int n = clamp_count(a.n[b], a.cap);
   const unsigned* word = a.word + (size_t)b * a.cap;
   const int* node = a.node + (size_t)b * a.cap;
   int P = 64;
@@ -55,18 +38,7 @@ __global__ __launch_bounds__(256) void bow_vector_kernel(BowVecArgs a) {
     }
     key[i] = k;
   }
-  __syncthreads();
-  for (int k = 2; k <= P; k <<= 1)                           // bitonic sort, ascending (word, feature index); the keys are distinct
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = t; i < P; i += 256) {
-        const int l = i ^ j;
-        if (l > i) {
-          const unsigned long long x = key[i], y = key[l];
-          if ((x > y) == ((i & k) == 0)) { key[i] = y; key[l] = x; }
-        }
-      }
-      __syncthreads();
-    }
+  block_sort_asc<256>(key, P);                               // ascending (word, feature index); the keys are distinct
   // segment heads: thread t owns positions 4 t .. 4 t + 3
   int heads = 0;
   for (int p = 4 * t; p < 4 * t + 4 && p < P; ++p) {
@@ -74,7 +46,7 @@ __global__ __launch_bounds__(256) void bow_vector_kernel(BowVecArgs a) {
     if (k != ~0ull && (p == 0 || (unsigned)(key[p - 1] >> 32) != (unsigned)(k >> 32))) ++heads;
   }
   int nw = 0;
-  int slot = block_scan256(heads, scan, &nw);
+  int slot = block_excl_scan<256>(heads, scan, &nw);
   for (int p = 4 * t; p < 4 * t + 4 && p < P; ++p) {
     const unsigned long long k = key[p];
     if (k == ~0ull) break;
@@ -126,7 +98,7 @@ __global__ __launch_bounds__(256) void bowdb_query_kernel(BowQueryArgs a) {
   unsigned* qi = reinterpret_cast<unsigned*>(smem + BOW_MAX_FEATURES * 8);         // [BOW_MAX_FEATURES]
   unsigned short* tab = reinterpret_cast<unsigned short*>(smem + BOW_MAX_FEATURES * 12);   // [n_words] (TABLE)
   const int q = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int nq = clampi(a.q_nw[q], 0, a.qcap);
+  const int nq = clamp_count(a.q_nw[q], a.qcap);
   for (int i = t; i < nq; i += 256) {
     qv[i] = a.q_vals[(size_t)q * a.qcap + i];
     qi[i] = a.q_ids[(size_t)q * a.qcap + i];
@@ -143,7 +115,7 @@ __global__ __launch_bounds__(256) void bowdb_query_kernel(BowQueryArgs a) {
   }
   const int f0 = blockIdx.y * a.frames_per_wg, f1 = min(a.N, f0 + a.frames_per_wg);
   for (int f = f0 + wave; f < f1; f += 4) {
-    const int nf = clampi(a.db_nw[f], 0, a.cap);
+    const int nf = clamp_count(a.db_nw[f], a.cap);
     const unsigned* ids = a.db_ids + (size_t)f * a.cap;
     const double* vals = a.db_vals + (size_t)f * a.cap;
     int share = 0;
@@ -175,27 +147,16 @@ __global__ __launch_bounds__(256) void bowdb_query_kernel(BowQueryArgs a) {
 }
 
 __global__ __launch_bounds__(256) void bowdb_select_kernel(BowSelectArgs a) {
-  __shared__ int red[256];
-  __shared__ int s_thr;
+  __shared__ int red[4];
   const int q = blockIdx.x, t = threadIdx.x;
   const int* sh = a.sharing + (size_t)q * a.N;
   const double* sc = a.score + (size_t)q * a.N;
   int m = 0;
   for (int f = t; f < a.N; f += 256) m = max(m, sh[f]);
-  red[t] = m;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if (t < d) red[t] = max(red[t], red[t + d]);
-    __syncthreads();
-  }
-  if (t == 0) {
-    const int ms = red[0];                                    // over ALL frames, before the filters (map_user.cc:142-145, map_refiner.cc:104-107)
-    a.max_sharing[q] = ms;
-    const float prod = __fmul_rn((float)ms, a.ratio);         // static_cast<int>(max_sharing_words * 0.3f): a float product, truncated
-    s_thr = max((int)prod, a.min_words);
-  }
-  __syncthreads();
-  const int thr = s_thr;
+  const int ms = block_max<256>(m, red);                      // over ALL frames, before the filters (map_user.cc:142-145, map_refiner.cc:104-107)
+  if (t == 0) a.max_sharing[q] = ms;
+  const float prod = __fmul_rn((float)ms, a.ratio);           // static_cast<int>(max_sharing_words * 0.3f): a float product, truncated
+  const int thr = max((int)prod, a.min_words);
   const int limit = a.max_index ? a.max_index[q] : a.N;
   const unsigned* ex = a.exclude ? a.exclude + (size_t)q * a.exclude_words : nullptr;
   int base = 0;
@@ -209,7 +170,7 @@ __global__ __launch_bounds__(256) void bowdb_select_kernel(BowSelectArgs a) {
       if (keep && ex) keep = (f >> 5) >= a.exclude_words || !((ex[f >> 5] >> (f & 31)) & 1u);
     }
     int total = 0;
-    const int pos = base + block_scan256(keep ? 1 : 0, red, &total);
+    const int pos = base + block_compact<256>(keep, red, &total);
     if (keep && pos < a.ccap) {
       a.cand_frame[(size_t)q * a.ccap + pos] = f;
       a.cand_sharing[(size_t)q * a.ccap + pos] = s;
@@ -229,7 +190,7 @@ __global__ __launch_bounds__(64) void bowdb_topk_kernel(BowTopkArgs a) {
   __shared__ double s_ps;
   __shared__ int s_pp;
   const int q = blockIdx.x, lane = threadIdx.x;
-  const int n = clampi(a.ncand[q], 0, a.ccap);
+  const int n = clamp_count(a.ncand[q], a.ccap);
   const double* sc = a.cand_score + (size_t)q * a.ccap;
   const int* fr = a.cand_frame + (size_t)q * a.ccap;
   double ps = 0.0;
@@ -274,7 +235,7 @@ __global__ __launch_bounds__(256) void bowdb_gather_kernel(BowGatherArgs a) {
   const int p = blockIdx.x, q = p / a.K;
   const int cand = a.cand[p];
   const bool hole = cand < 0 || cand >= a.N;
-  const int n0 = hole ? 0 : clampi(a.qn[q], 0, a.cap), n1 = hole ? 0 : clampi(a.db_n[cand], 0, a.cap);
+  const int n0 = hole ? 0 : clamp_count(a.qn[q], a.cap), n1 = hole ? 0 : clamp_count(a.db_n[cand], a.cap);
   if (threadIdx.x == 0) { a.n0[p] = n0; a.n1[p] = n1; }
   if (hole) return;
   const float* s0 = a.qfeat + (size_t)q * a.cap * 259;
@@ -293,7 +254,7 @@ __global__ __launch_bounds__(256) void bowdb_best_kernel(BowBestArgs a) {
     int bk = -1, bn = 0;
     for (int k = 0; k < a.K; ++k) {
       const int cand = a.cand[q * a.K + k];
-      const int nm = cand < 0 || cand >= a.N ? 0 : clampi(a.nmatch_all[q * a.K + k], 0, a.mcap);
+      const int nm = cand < 0 || cand >= a.N ? 0 : clamp_count(a.nmatch_all[q * a.K + k], a.mcap);
       if (a.out_nmatch_all) a.out_nmatch_all[q * a.K + k] = nm;
       if (nm > bn) { bn = nm; bk = k; }
     }

@@ -12,24 +12,11 @@
 #include "bowgroup_core.h"
 #include "common.h"
 #include "kernels.h"
+#include "wg_prims.h"
 
 namespace airfe {
 
 namespace {
-
-// sum of one int per thread over the 256-thread workgroup (every thread gets it)
-__device__ int bg_block_sum(int v, int* buf) {
-  const int t = threadIdx.x;
-  buf[t] = v;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if (t < d) buf[t] += buf[t + d];
-    __syncthreads();
-  }
-  const int s = buf[0];
-  __syncthreads();
-  return s;
-}
 
 __global__ __launch_bounds__(256) void bowgroup_kernel(BowGroupArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -41,7 +28,7 @@ __global__ __launch_bounds__(256) void bowgroup_kernel(BowGroupArgs a) {
   int* deputy = frame + C;                                      // [C] per candidate: its deputy's slot
   int* group_of = deputy + C;                                   // [C] per deputy slot: the candidate whose group is stored (-1: none / dropped)
   __shared__ double rs[256];
-  __shared__ int rp[256], ri[256];
+  __shared__ int rp[256], ri[4];
   __shared__ double s_best;
   const int q = blockIdx.x, t = threadIdx.x;
   int32_t* out_frame = a.group_frame + (size_t)q * a.K;
@@ -92,7 +79,7 @@ __global__ __launch_bounds__(256) void bowgroup_kernel(BowGroupArgs a) {
     ++cnt;
   }
   rs[t] = mx;
-  const int stored = bg_block_sum(cnt, ri);                     // (its barriers order rs as well)
+  const int stored = block_sum<256>(cnt, ri);                   // (its first barrier orders rs as well)
   for (int d = 128; d > 0; d >>= 1) {
     if (t < d && rs[t] < rs[t + d]) rs[t] = rs[t + d];
     __syncthreads();
@@ -109,7 +96,7 @@ __global__ __launch_bounds__(256) void bowgroup_kernel(BowGroupArgs a) {
     if (extra && f >= 0 && f < a.n_extra) fin[d] += extra[f];
     ++cnt;
   }
-  const int left = bg_block_sum(cnt, ri);
+  const int left = block_sum<256>(cnt, ri);
   if (t == 0) { a.ngroups[q] = left; a.status[q] = BG_OK; }
   double ps = 0.0;
   int pp = -1;
@@ -138,9 +125,8 @@ __global__ __launch_bounds__(256) void bowgroup_kernel(BowGroupArgs a) {
 
 __global__ __launch_bounds__(256) void reloc_gather_kernel(RelocGatherArgs g) {
   __shared__ int wsum[4];
-  const int q = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
-  int m = g.nmatch[q];
-  m = m < 0 ? 0 : (m > g.mcap ? g.mcap : m);
+  const int q = blockIdx.x, t = threadIdx.x;
+  int m = clamp_count(g.nmatch[q], g.mcap);
   const int best = g.best[q];
   int pre = 0;                                                  // the gates of map_user.cc:139 / 158, :219, :377
   if (g.ncand[q] <= 0) pre = 1;
@@ -164,27 +150,21 @@ __global__ __launch_bounds__(256) void reloc_gather_kernel(RelocGatherArgs g) {
       if (qi >= 0 && qi < g.cap && ci >= 0 && ci < g.cap) {     // the matcher's indices are in range; this is memory safety only
         const double* p = g.xyz + ((size_t)best * g.cap + ci) * 3;
         px = p[0]; py = p[1]; pz = p[2];
-        valid = !isnan(px);
+        valid = !is_nan(px);
         const float* f = g.qfeat + ((size_t)q * g.cap + qi) * 259;
         u = f[1]; v = f[2];
       }
     }
-    const unsigned long long bal = __ballot(valid);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[w] = __popcll(bal);
-    __syncthreads();
-    int off = kept;
-    for (int k = 0; k < w; ++k) off += wsum[k];
+    int total;
+    const int s = kept + block_compact<256>(valid, wsum, &total);
     if (valid) {
-      const int s = off + before;
       obj[3 * s] = (float)px; obj[3 * s + 1] = (float)py; obj[3 * s + 2] = (float)pz;      // cv::Point3f
       img[2 * s] = u; img[2 * s + 1] = v;
       map[s] = j;
       X[3 * s] = px; X[3 * s + 1] = py; X[3 * s + 2] = pz;
       obs[3 * s] = (double)u; obs[3 * s + 1] = (double)v; obs[3 * s + 2] = -1.0;           // the query frame has no right image: every edge mono
     }
-    kept += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    __syncthreads();
+    kept += total;
   }
   if (t == 0) {
     if (!pre && g.refine && kept < g.min_inlier) pre = 4;       // map_user.cc:448, behind PnP: the pose stays PnP's

@@ -14,33 +14,17 @@
 #include "common.h"
 #include "covis_core.h"
 #include "kernels.h"
+#include "wg_prims.h"
 
 namespace airfe {
 
 namespace {
 
-// the exclusive prefix of v over the workgroup's 256 threads and the total; wsum: 4 ints of LDS, free again on return
-__device__ inline int block_scan(int v, int* wsum, int* total) {
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  int x = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const int y = __shfl_up(x, d);
-    if (lane >= d) x += y;
-  }
-  if (lane == 63) wsum[w] = x;
-  __syncthreads();
-  int off = 0;
-  for (int k = 0; k < w; ++k) off += wsum[k];
-  *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-  __syncthreads();
-  return off + x - v;
-}
-
 __global__ __launch_bounds__(256) void covis_mark_kernel(CovisArgs a) {
   __shared__ int ids[BOW_MAX_FEATURES];
   __shared__ int tot[2];
   const int f = blockIdx.x, t = threadIdx.x;
-  const int n = cv_rows(a.n[f], a.cap);
+  const int n = clamp_count(a.n[f], a.cap);
   const int32_t* row = a.point_id + (size_t)f * a.cap;
   if (t < 2) tot[t] = 0;
   int valid = 0, ignored = 0;
@@ -72,8 +56,7 @@ __global__ __launch_bounds__(256) void covis_tile_sum_kernel(CovisArgs a) {
     const size_t m = base + (size_t)k * 256 + t;
     if (m < (size_t)P) s += a.count[m];
   }
-  int total;
-  (void)block_scan(s, wsum, &total);
+  const int total = block_sum<256>(s, wsum);
   if (t == 0) a.tile[blockIdx.x] = total;
 }
 
@@ -85,7 +68,7 @@ __global__ __launch_bounds__(256) void covis_tile_scan_kernel(CovisArgs a, int t
     const int b = base + t;
     const int v = b < tiles ? a.tile[b] : 0;
     int total;
-    const int ex = block_scan(v, wsum, &total);
+    const int ex = block_excl_scan<256>(v, wsum, &total);
     if (b < tiles) a.tile[b] = carry + ex;
     carry += total;
   }
@@ -104,7 +87,7 @@ __global__ __launch_bounds__(256) void covis_start_kernel(CovisArgs a) {
     s += v[k];
   }
   int total;
-  int run = a.tile[blockIdx.x] + block_scan(s, wsum, &total);
+  int run = a.tile[blockIdx.x] + block_excl_scan<256>(s, wsum, &total);
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
     if (base + k < (size_t)P) {
@@ -150,8 +133,7 @@ __global__ __launch_bounds__(256) void covis_count_kernel(CovisArgs a) {
   covis_hist(a, f, hist);
   int c = 0;
   for (int g = t; g < a.size; g += 256) c += hist[g] > 0;
-  int total;
-  (void)block_scan(c, wsum, &total);
+  const int total = block_sum<256>(c, wsum);
   if (t == 0) a.rowcnt[f] = total;
 }
 
@@ -163,7 +145,7 @@ __global__ __launch_bounds__(256) void covis_rows_kernel(CovisArgs a) {
     const int f = base + t;
     const int v = f < a.size ? a.rowcnt[f] : 0;
     int total;
-    const int ex = block_scan(v, wsum, &total);
+    const int ex = block_excl_scan<256>(v, wsum, &total);
     if (f < a.size) a.row_ptr[f] = carry + ex;
     carry += total;
   }
@@ -184,24 +166,20 @@ __global__ __launch_bounds__(256) void covis_rows_kernel(CovisArgs a) {
 __global__ __launch_bounds__(256) void covis_emit_kernel(CovisArgs a) {
   __shared__ int hist[CV_MAX_FRAMES];
   __shared__ int wsum[4];
-  const int f = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int f = blockIdx.x, t = threadIdx.x;
   if (a.acc[2]) return;                                          // overflow: the graph stays empty (uniform)
   covis_hist(a, f, hist);
   int base = a.row_ptr[f];
   for (int g0 = 0; g0 < a.size; g0 += 256) {                     // (uniform)
     const int g = g0 + t;
     const int wt = g < a.size ? hist[g] : 0;
-    const unsigned long long bal = __ballot(wt > 0);
-    if (lane == 0) wsum[w] = __popcll(bal);
-    __syncthreads();
-    int pos = base + __popcll(bal & ((1ull << lane) - 1ull));
-    for (int k = 0; k < w; ++k) pos += wsum[k];
+    int total;
+    const int pos = base + block_compact<256>(wt > 0, wsum, &total);
     if (wt > 0 && pos < a.max_edges) {
       a.nbr[pos] = g;
       a.weight[pos] = wt;
     }
-    base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    __syncthreads();
+    base += total;
   }
 }
 

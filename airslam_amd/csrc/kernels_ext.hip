@@ -6,30 +6,9 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "wg_prims.h"
 
 namespace airfe {
-
-// block-wide exclusive scan of one unsigned per thread (1024 threads); returns exclusive prefix, *total = sum
-__device__ __forceinline__ unsigned block_excl_scan_1024(unsigned v, unsigned* wsum /*[16] LDS*/, unsigned* total) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  unsigned incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned t = __shfl_up(incl, o);
-    if (lane >= o) incl += t;
-  }
-  __syncthreads();            // protect wsum from the previous use
-  if (lane == 63) wsum[wv] = incl;
-  __syncthreads();
-  unsigned off = 0, tot = 0;
-  for (int w = 0; w < 16; ++w) {
-    const unsigned t = wsum[w];
-    if (w < wv) off += t;
-    tot += t;
-  }
-  *total = tot;
-  return off + incl - v;
-}
 
 // =============================================================================== wireframe_matcher
 // src/plnet.cpp:272-307 on the device.  keep = raster-ordered indices with iskeep > 0; unique (min,max) junction pairs
@@ -47,10 +26,8 @@ __global__ __launch_bounds__(256) void wf_count_kernel(const float* __restrict__
   const int per_wg = (n + WF_WGS - 1) / WF_WGS, lo = blockIdx.x * per_wg, hi = min(lo + per_wg, n);
   int cnt = 0;
   for (int i = lo + threadIdx.x; i < hi; i += 256) cnt += iskeep[i] > 0.f;
-  cnt = (int)wave_sum((float)cnt);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) wg_counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  cnt = block_sum<256>(cnt, wsum);
+  if (threadIdx.x == 0) wg_counts[blockIdx.x] = cnt;
 }
 
 __global__ __launch_bounds__(256) void wf_emit_kernel(const float* __restrict__ iskeep, int n, const int* __restrict__ counts,
@@ -957,7 +934,7 @@ __global__ __launch_bounds__(1024) void line_filter_kernel(const float* __restri
   unsigned cnt = 0;
   for (int pass = 0; pass < 2; ++pass) {
     unsigned off = 0, tot = 0;
-    if (pass == 1) off = block_excl_scan_1024(cnt, wsum, &tot);
+    if (pass == 1) off = block_excl_scan<1024>(cnt, wsum, &tot);
     for (int i = lo; i < hi; ++i) {
       const float s = sc[i];
       if (s < 0.5f) continue;
@@ -1038,7 +1015,7 @@ __global__ __launch_bounds__(1024) void line_filter_junc_kernel(const float* __r
   unsigned cnt = 0;
   for (int pass = 0; pass < 2; ++pass) {
     unsigned off = 0, tot = 0;
-    if (pass == 1) off = block_excl_scan_1024(cnt, wsum, &tot);
+    if (pass == 1) off = block_excl_scan<1024>(cnt, wsum, &tot);
     for (int i = lo; i < hi; ++i) {
       const float s = sc[i];
       if (s < 0.5f) continue;
@@ -1083,7 +1060,7 @@ __global__ __launch_bounds__(1024) void line_filter_junc_kernel(const float* __r
 #pragma unroll
   for (int k = 0; k < 8; ++k) jc += __builtin_popcount(w[k]);
   unsigned jtot = 0;
-  unsigned joff = block_excl_scan_1024(jc, wsum, &jtot);
+  unsigned joff = block_excl_scan<1024>(jc, wsum, &jtot);
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     unsigned m = w[k];
@@ -1159,10 +1136,8 @@ __global__ __launch_bounds__(256) void junction_count_kernel(const unsigned char
   int cnt = 0;
   const int lo = blockIdx.x * per_wg + threadIdx.x * per, hi = min(min(lo + per, (blockIdx.x + 1) * per_wg), N);
   for (int i0 = lo; i0 < hi; i0 += JS_PT) cnt += __builtin_popcount(js_mask16(jmap, i0, min(hi, N), R, border));
-  cnt = (int)wave_sum((float)cnt);                                   // < 2^24: exact in fp32
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) wg_counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  cnt = block_sum<256>(cnt, wsum);
+  if (threadIdx.x == 0) wg_counts[blockIdx.x] = cnt;
 }
 
 __global__ __launch_bounds__(256) void junction_emit_kernel(const unsigned char* __restrict__ jmap, const float* __restrict__ heat, int R, int border,
@@ -1182,17 +1157,8 @@ __global__ __launch_bounds__(256) void junction_emit_kernel(const unsigned char*
   const int lo = blockIdx.x * per_wg + threadIdx.x * per, hi = min(min(lo + per, (blockIdx.x + 1) * per_wg), N);
   int cnt = 0;
   for (int i0 = lo; i0 < hi; i0 += JS_PT) cnt += __builtin_popcount(js_mask16(jmap, i0, min(hi, N), R, border));
-  // exclusive prefix over the 256 threads: within the wave by shuffles, then over the 4 waves
-  int incl = cnt;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(incl, o);
-    if ((int)(threadIdx.x & 63) >= o) incl += t;
-  }
-  if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
-  __syncthreads();
-  int off = base + incl - cnt;
-  for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) off += wsum[w];
+  int total;
+  int off = base + block_excl_scan<256>(cnt, wsum, &total);
   for (int i0 = lo; i0 < hi; i0 += JS_PT) {
     unsigned m = js_mask16(jmap, i0, min(hi, N), R, border);
     while (m) {
@@ -1830,29 +1796,18 @@ __global__ __launch_bounds__(256) void pl_assign_kernel(PlAssignArgs a) {
 
 // exclusive scan of counts[L] -> row_ptr[L+1] per frame (L is a few hundred: one workgroup per frame, serial per 256-chunk carry)
 __global__ __launch_bounds__(256) void pl_scan_kernel(PlAssignArgs a) {
-  __shared__ int buf[256];
-  __shared__ int carry;
+  __shared__ int wsum[4];
   const int b = blockIdx.x;
   const int L = min(a.nlines[b], a.capL);
   const int* counts = a.counts + (size_t)b * a.capL;
   int* row_ptr = a.row_ptr + (size_t)b * (a.capL + 1);
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
+  int carry = 0;                                                // (the same value in every thread)
   for (int i0 = 0; i0 < L; i0 += 256) {
     const int i = i0 + threadIdx.x;
-    const int v = i < L ? counts[i] : 0;
-    buf[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-      const int t = threadIdx.x >= o ? buf[threadIdx.x - o] : 0;
-      __syncthreads();
-      buf[threadIdx.x] += t;
-      __syncthreads();
-    }
-    if (i < L) row_ptr[i] = carry + buf[threadIdx.x] - v;
-    __syncthreads();
-    if (threadIdx.x == 255) carry += buf[255];
-    __syncthreads();
+    int total;
+    const int ex = block_excl_scan<256>(i < L ? counts[i] : 0, wsum, &total);
+    if (i < L) row_ptr[i] = carry + ex;
+    carry += total;
   }
   if (threadIdx.x == 0) {
     row_ptr[L] = carry;

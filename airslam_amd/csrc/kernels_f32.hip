@@ -4,6 +4,7 @@
 // deliberately plain (no LDS tiling, fragments straight from L1 / L2): the mode exists to pin the 2-byte kernels and the oracle
 // against each other at 1e-5, not to be fast (it measures ~25x slower than the fp16 path).
 #include "common.h"
+#include "wg_prims.h"
 #include "kernels.h"
 
 namespace airfe {

@@ -9,6 +9,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "fransac_core.h"
+#include "wg_prims.h"
 
 namespace airfe {
 
@@ -34,8 +35,7 @@ __device__ void load_points(const FransacArgs& a, int b, int n, float* xy) {
 }
 
 __device__ __forceinline__ int pair_n(const FransacArgs& a, int b) {
-  const int n = a.nmatch[b];
-  return n < 0 ? 0 : (n > a.mcap ? a.mcap : n);
+  return clamp_count(a.nmatch[b], a.mcap);
 }
 
 __global__ __launch_bounds__(FR_CHUNK) void fransac_models_kernel(FransacArgs a, int chunk0) {
@@ -94,20 +94,9 @@ __global__ __launch_bounds__(FR_CHUNK) void fransac_models_kernel(FransacArgs a,
   }
 }
 
-// block-wide min of an int (1024 threads)
-__device__ int block_min(int v, int* red) {
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int r = red[0];
-  for (int i = 1; i < (int)(blockDim.x >> 6); ++i) r = min(r, red[i]);
-  return r;
-}
-
 __global__ __launch_bounds__(1024) void fransac_scan_kernel(FransacArgs a, int final_pass) {
   __shared__ int red[16], wmax[16], bcast[2];
-  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int b = blockIdx.x, t = threadIdx.x;
   int* st = a.state + 4 * b;
   const int n = pair_n(a, b);
   if (n < 9) {
@@ -127,12 +116,12 @@ __global__ __launch_bounds__(1024) void fransac_scan_kernel(FransacArgs a, int f
         const unsigned u = (unsigned)sc[3 * t + r];
         if (u < 0x7F800000u) v = min(v, (int)u);
       }
-    const int mn = block_min(v, red);
+    const int mn = block_min<1024>(v, red);
     int pos = 0x7FFFFFFF;
     if (t < FR_LMEDS_ITERS && mn != 0x7FFFFFFF && v == mn)
       for (int r = 2; r >= 0; --r)
         if (sc[3 * t + r] == mn) pos = 3 * t + r;
-    const int sel = block_min(pos, red);
+    const int sel = block_min<1024>(pos, red);
     if (t == 0) st[0] = FR_LMEDS_ITERS, st[1] = 1, st[2] = mn == 0x7FFFFFFF ? -1 : sel;
     return;
   }
@@ -140,20 +129,10 @@ __global__ __launch_bounds__(1024) void fransac_scan_kernel(FransacArgs a, int f
   int v = -1;
   if (t < limit)
     for (int r = 0; r < 3; ++r) v = max(v, sc[3 * t + r]);
-  // exclusive prefix max E(t) = best count over the samples before t
-  int incl = v;
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(incl, o, 64);
-    if (lane >= o) incl = max(incl, u);
-  }
-  if (lane == 63) wmax[w] = incl;
-  __syncthreads();
-  int E = __shfl_up(incl, 1, 64);
-  if (lane == 0) E = -1;
-  for (int i = 0; i < w; ++i) E = max(E, wmax[i]);
+  const int E = block_excl_scan_max<1024>(v, -1, wmax);      // E(t) = best count over the samples before t
   const int nb = E > 6 ? fr_update_niters(n, E) : FR_RANSAC_ITERS;      // niters when sample t is reached
   const bool pred = t <= limit && t >= nb;
-  const int stop = block_min(pred ? t : 0x7FFFFFFF, red);
+  const int stop = block_min<1024>(pred ? t : 0x7FFFFFFF, red);
   if (stop == 0x7FFFFFFF) {                                   // first slice: still open; the bound for the next slice
     if (t == limit) st[0] = nb, st[1] = 0, st[2] = -1;
     return;
@@ -165,7 +144,7 @@ __global__ __launch_bounds__(1024) void fransac_scan_kernel(FransacArgs a, int f
   if (best > 6 && t < stop)
     for (int r = 2; r >= 0; --r)
       if (sc[3 * t + r] == best) pos = 3 * t + r;
-  const int sel = block_min(pos, red);
+  const int sel = block_min<1024>(pos, red);
   if (t == 0) st[0] = stop, st[1] = 1, st[2] = best > 6 ? sel : -1;
 }
 
@@ -226,19 +205,13 @@ __global__ __launch_bounds__(256) void fransac_compact_kernel(FransacArgs a) {
       sv = score[i];
       in = fr_error(f, xy[4 * i], xy[4 * i + 1], xy[4 * i + 2], xy[4 * i + 3]) <= thr;
     }
-    const unsigned long long bal = __ballot(in);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[w] = __popcll(bal);
-    __syncthreads();                                          // every element of this chunk is read before any is written
-    int off = kept;
-    for (int j = 0; j < w; ++j) off += wsum[j];
+    int total;                                                // in place: every element of this chunk is read before any is written, by the barrier
+    const int o = kept + block_compact<256>(in, wsum, &total);      // contract of wg_prims.h (rule 2)
     if (in) {
-      const int o = off + before;
       idx[2 * o] = id.x; idx[2 * o + 1] = id.y;
       score[o] = sv;
     }
-    kept += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    __syncthreads();
+    kept += total;
   }
   if (t == 0) a.nmatch[b] = kept;
 }

@@ -9,46 +9,13 @@
 #include "common.h"
 #include "kernels.h"
 #include "junction_core.h"
+#include "wg_prims.h"
 
 namespace airfe {
 
 namespace {
 
 #define JN_MERGE 8192                 // the connect kernel's merge buffer: the kept edges + the chunk's candidates
-
-// exclusive scan of one int per thread over a 256-thread workgroup; returns the thread's offset, *total = the sum
-__device__ int jn_scan256(int v, int* buf, int* total) {
-  const int t = threadIdx.x;
-  buf[t] = v;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    const int x = t >= d ? buf[t - d] : 0;
-    __syncthreads();
-    buf[t] += x;
-    __syncthreads();
-  }
-  const int incl = buf[t];
-  *total = buf[255];
-  __syncthreads();
-  return incl - v;
-}
-
-// ascending bitonic sort of key[0 .. P), P a power of two >= 256
-template <class T>
-__device__ void jn_sort(T* key, int P) {
-  const int t = threadIdx.x;
-  for (int k = 2; k <= P; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = t; i < P; i += 256) {
-        const int l = i ^ j;
-        if (l > i) {
-          const T x = key[i], y = key[l];
-          if ((x > y) == ((i & k) == 0)) { key[i] = y; key[l] = x; }
-        }
-      }
-      __syncthreads();
-    }
-}
 
 __device__ __forceinline__ int jn_pow2(int n) {
   int P = 256;
@@ -60,9 +27,9 @@ __global__ __launch_bounds__(256) void junction_connect_kernel(JunctionConnectAr
   __shared__ int px[JN_MAX_JUNCTIONS], py[JN_MAX_JUNCTIONS];
   __shared__ unsigned buf[JN_MERGE];
   __shared__ unsigned uniq[JN_MAX_EDGES];
-  __shared__ int scan[256];
+  __shared__ int scan[4];
   const int b = blockIdx.x, t = threadIdx.x;
-  const int nj = jn_count(a.njunc[b], a.capJ), nl = jn_count(a.nlines[b], a.capL);
+  const int nj = clamp_count(a.njunc[b], a.capJ), nl = clamp_count(a.nlines[b], a.capL);
   const float* junc = a.junc + (size_t)b * a.capJ * 259;
   const double* lines = a.lines + (size_t)b * a.capL * 4;
   int32_t* pair = a.line_pair ? a.line_pair + (size_t)b * a.capL * 2 : nullptr;
@@ -87,15 +54,14 @@ __global__ __launch_bounds__(256) void junction_connect_kernel(JunctionConnectAr
     if (over) continue;
     const int total = cnt + 2 * chunk, P = jn_pow2(total), per = P / 256;
     for (int i = total + t; i < P; i += 256) buf[i] = 0xFFFFFFFFu;
-    __syncthreads();
-    jn_sort(buf, P);
+    block_sort_asc<256>(buf, P);
     int heads = 0;                                            // thread t owns positions per t .. per t + per - 1
     for (int p = per * t; p < per * t + per; ++p) {
       const unsigned k = buf[p];
       if (k != 0xFFFFFFFFu && (p == 0 || buf[p - 1] != k)) ++heads;
     }
     int nu = 0;
-    int slot = jn_scan256(heads, scan, &nu);
+    int slot = block_excl_scan<256>(heads, scan, &nu);
     if (nu > a.ecap) { over = true; cnt = 0; continue; }      // (nu is the same in every thread)
     for (int p = per * t; p < per * t + per; ++p) {
       const unsigned k = buf[p];
@@ -122,11 +88,11 @@ __global__ __launch_bounds__(256) void junction_keys_kernel(JunctionKeysArgs a) 
   __shared__ int hp[JN_MAX_EDGES + 1];
   __shared__ unsigned wd[JN_MAX_JUNCTIONS];
   __shared__ int conn[JN_MAX_JUNCTIONS];
-  __shared__ int scan[256];
+  __shared__ int scan[4];
   const int b = blockIdx.x, t = threadIdx.x;
   const size_t f = (size_t)a.first + b;
   const bool bad = a.status_in && a.status_in[b] != JN_OK;
-  const int nj = jn_count(a.nj[b], a.cap), ne = bad ? 0 : jn_count(a.nedge[b], a.ecap);
+  const int nj = clamp_count(a.nj[b], a.cap), ne = bad ? 0 : clamp_count(a.nedge[b], a.ecap);
   const unsigned* word = a.word + (size_t)b * a.cap;
   const int32_t* edge = a.edge + (size_t)b * a.ecap * 2;
   if (a.out_word)
@@ -154,8 +120,7 @@ __global__ __launch_bounds__(256) void junction_keys_kernel(JunctionKeysArgs a) 
     }
     key[e] = k;
   }
-  __syncthreads();
-  jn_sort(key, PK);
+  block_sort_asc<256>(key, PK);
   {
     const int per = PK / 256;
     int heads = 0, valid = 0;
@@ -165,9 +130,9 @@ __global__ __launch_bounds__(256) void junction_keys_kernel(JunctionKeysArgs a) 
       ++valid;
       if (p == 0 || key[p - 1] != k) ++heads;
     }
-    int nu = 0, nv = 0;
-    int slot = jn_scan256(heads, scan, &nu);
-    (void)jn_scan256(valid, scan, &nv);
+    int nu = 0;
+    int slot = block_excl_scan<256>(heads, scan, &nu);
+    const int nv = block_sum<256>(valid, scan);
     for (int p = per * t; p < per * t + per; ++p) {
       const unsigned long long k = key[p];
       if (k == ~0ull) break;
@@ -184,8 +149,7 @@ __global__ __launch_bounds__(256) void junction_keys_kernel(JunctionKeysArgs a) 
   // the word table: (word, junction) keys sorted; the thread that owns a segment's head walks the segment
   const int PW = jn_pow2(nj);
   for (int i = t; i < PW; i += 256) key[i] = i < nj && wd[i] != JN_NO_WORD ? jn_word_key(wd[i], (unsigned)i) : ~0ull;
-  __syncthreads();
-  jn_sort(key, PW);
+  block_sort_asc<256>(key, PW);
   const int per = PW / 256;
   int heads = 0;
   for (int p = per * t; p < per * t + per; ++p) {
@@ -193,7 +157,7 @@ __global__ __launch_bounds__(256) void junction_keys_kernel(JunctionKeysArgs a) 
     if (k != ~0ull && (p == 0 || (unsigned)(key[p - 1] >> 32) != (unsigned)(k >> 32))) ++heads;
   }
   int nu = 0;
-  int slot = jn_scan256(heads, scan, &nu);
+  int slot = block_excl_scan<256>(heads, scan, &nu);
   for (int p = per * t; p < per * t + per; ++p) {
     const unsigned long long k = key[p];
     if (k == ~0ull) break;
@@ -209,11 +173,6 @@ __global__ __launch_bounds__(256) void junction_keys_kernel(JunctionKeysArgs a) 
   if (t == 0) a.nuw[f] = nu;
 }
 
-__device__ __forceinline__ int jn_wave_sum(int v) {
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void junction_term_kernel(JunctionTermArgs a) {
   __shared__ unsigned long long q_ukey[JN_MAX_EDGES];
   __shared__ int q_kcnt[JN_MAX_EDGES];
@@ -221,7 +180,7 @@ __global__ __launch_bounds__(256) void junction_term_kernel(JunctionTermArgs a) 
   __shared__ int q_wconn[JN_MAX_JUNCTIONS];
   const int q = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const bool q_ok = a.q_status[q] == JN_OK;
-  const int q_nuw = q_ok ? jn_count(a.q_nuw[q], a.cap) : 0, q_nuk = q_ok ? jn_count(a.q_nuk[q], a.ecap) : 0;
+  const int q_nuw = q_ok ? clamp_count(a.q_nuw[q], a.cap) : 0, q_nuk = q_ok ? clamp_count(a.q_nuk[q], a.ecap) : 0;
   for (int i = t; i < q_nuw; i += 256) {
     q_uword[i] = a.q_uword[(size_t)q * a.cap + i];
     q_wconn[i] = a.q_wconn[(size_t)q * a.cap + i];
@@ -236,7 +195,7 @@ __global__ __launch_bounds__(256) void junction_term_kernel(JunctionTermArgs a) 
     const bool ok = q_ok && a.f_status[f] == JN_OK;
     int mn = 0, lmn = 0;
     if (ok) {
-      const int nuw = jn_count(a.f_nuw[f], a.cap), nuk = jn_count(a.f_nuk[f], a.ecap);
+      const int nuw = clamp_count(a.f_nuw[f], a.cap), nuk = clamp_count(a.f_nuk[f], a.ecap);
       const unsigned* uw = a.f_uword + (size_t)f * a.cap;
       const int* wc = a.f_wcnt + (size_t)f * a.cap;
       for (int e = lane; e < nuw; e += 64) {
@@ -250,8 +209,8 @@ __global__ __launch_bounds__(256) void junction_term_kernel(JunctionTermArgs a) 
         if (s >= 0) lmn += q_kcnt[s] * kc[e];
       }
     }
-    mn = jn_wave_sum(mn);
-    lmn = jn_wave_sum(lmn);
+    mn = wave_sum(mn);
+    lmn = wave_sum(lmn);
     if (lane == 0) {
       const size_t o = (size_t)q * a.N + f;
       a.extra[o] = ok ? jn_extra(a.score[o], mn, lmn) : 0.0;

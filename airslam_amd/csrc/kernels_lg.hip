@@ -4,6 +4,7 @@
 #include <float.h>
 
 #include "common.h"
+#include "wg_prims.h"
 #include "kernels.h"
 
 namespace airfe {
@@ -351,8 +352,8 @@ __global__ __launch_bounds__(1024) void lg_filter_kernel(const int* __restrict__
                                                          const int* __restrict__ rowarg, const float* __restrict__ rowval,
                                                          const int* __restrict__ colarg, int32_t* __restrict__ idx,
                                                          float* __restrict__ score, int* __restrict__ nmatch) {
-  __shared__ unsigned wsum[16];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  __shared__ int wsum[16];
+  const int b = blockIdx.x, tid = threadIdx.x;
   const int n0 = lens[2 * b], n1 = lens[2 * b + 1];
   bool ok = false;
   int col = 0;
@@ -364,22 +365,14 @@ __global__ __launch_bounds__(1024) void lg_filter_kernel(const int* __restrict__
     e = expf_like_glibc(rowval[(size_t)b * Np + tid]);
     ok = (colarg[(size_t)b * Np + col] == tid) && (e > thr);
   }
-  const unsigned long long bal = __ballot(ok);
-  const unsigned before = __popcll(bal & ((1ull << lane) - 1ull));
-  if (lane == 0) wsum[wv] = __popcll(bal);
-  __syncthreads();
-  unsigned off = 0, tot = 0;
-  for (int w = 0; w < 16; ++w) {
-    if (w < wv) off += wsum[w];
-    tot += wsum[w];
-  }
-  const unsigned slot = off + before;
-  if (ok && slot < (unsigned)cap) {
+  int tot;
+  const int slot = block_compact<1024>(ok, wsum, &tot);
+  if (ok && slot < cap) {
     idx[((size_t)b * cap + slot) * 2] = tid;
     idx[((size_t)b * cap + slot) * 2 + 1] = col;
     score[(size_t)b * cap + slot] = e;
   }
-  if (tid == 0) nmatch[b] = min((int)tot, cap);
+  if (tid == 0) nmatch[b] = min(tot, cap);
 }
 
 void launch_lg_assign(const float* sim, const float* z, const int* lens, int B, int Np, int cap, float thr, float* rowlse,
@@ -641,9 +634,9 @@ __global__ __launch_bounds__(256, 2) void lg_sim_arg_kernel(const uint16_t* __re
 __global__ __launch_bounds__(1024) void lg_filter_fused_kernel(const int* __restrict__ lens, int Np, int nT, int cap, float thr, const float2* __restrict__ argpart,
                                                                int* __restrict__ rowarg, float* __restrict__ rowval, int* __restrict__ colarg,
                                                                int32_t* __restrict__ idx, float* __restrict__ score, int* __restrict__ nmatch) {
-  __shared__ unsigned wsum[16];
+  __shared__ int wsum[16];
   __shared__ int scol[1024];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int b = blockIdx.x, tid = threadIdx.x;
   const int n0 = lens[2 * b], n1 = lens[2 * b + 1];
   const int tr = (n0 + 63) >> 6, tc = (n1 + 63) >> 6;
   auto fold = [&](int side, int k, int ntile, float& best, int& bi) {
@@ -676,22 +669,14 @@ __global__ __launch_bounds__(1024) void lg_filter_fused_kernel(const int* __rest
   }
   __syncthreads();
   if (tid < n0 && n1 > 0) ok = (scol[col] == tid) && (e > thr);      // (col < n1 whenever n1 > 0; an empty second image has no matches: point_matcher.cc:53-55)
-  const unsigned long long bal = __ballot(ok);
-  const unsigned before = __popcll(bal & ((1ull << lane) - 1ull));
-  if (lane == 0) wsum[wv] = __popcll(bal);
-  __syncthreads();
-  unsigned off = 0, tot = 0;
-  for (int w = 0; w < 16; ++w) {
-    if (w < wv) off += wsum[w];
-    tot += wsum[w];
-  }
-  const unsigned slot = off + before;
-  if (ok && slot < (unsigned)cap) {
+  int tot;
+  const int slot = block_compact<1024>(ok, wsum, &tot);
+  if (ok && slot < cap) {
     idx[((size_t)b * cap + slot) * 2] = tid;
     idx[((size_t)b * cap + slot) * 2 + 1] = col;
     score[(size_t)b * cap + slot] = e;
   }
-  if (tid == 0) nmatch[b] = min((int)tot, cap);
+  if (tid == 0) nmatch[b] = min(tot, cap);
 }
 
 size_t lg_assign_part_floats(int B, int Np) { return (size_t)B * 2 * ((Np + 63) / 64) * Np * 2; }      // floats of ONE partial array (float2 per entry)

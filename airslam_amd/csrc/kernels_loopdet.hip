@@ -16,6 +16,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "loopdet_core.h"
+#include "wg_prims.h"
 
 namespace airfe {
 
@@ -32,7 +33,7 @@ __global__ __launch_bounds__(256) void loopdet_qvec_kernel(LoopQvecArgs a) {
   const int fq = a.qframe[q];
   const bool in = fq >= 0 && fq < a.N;
   int n = in ? a.db_nw[fq] : 0;
-  n = n < 0 ? 0 : (n > a.cap ? a.cap : n);
+  n = clamp_count(n, a.cap);
   if (t == 0) a.nw[q] = n;
   if (!in) return;
   const unsigned* si = a.db_ids + (size_t)fq * a.cap;
@@ -44,29 +45,17 @@ __global__ __launch_bounds__(256) void loopdet_qvec_kernel(LoopQvecArgs a) {
 }
 
 __global__ __launch_bounds__(256) void loopdet_select_kernel(LoopSelectArgs a) {
-  __shared__ int red[256];
   __shared__ int wsum[4];
-  __shared__ int s_thr;
-  const int q = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int q = blockIdx.x, t = threadIdx.x;
   const int fq = a.qframe[q];
   const int limit = (fq >= 0 && fq < a.N) ? fq : 0;             // the frames that exist for this query: 0 .. limit - 1
   int* sh = a.sharing + (size_t)q * a.N;
   const double* sc = a.score + (size_t)q * a.N;
   int m = 0;
   for (int f = t; f < limit; f += 256) m = max(m, sh[f]);
-  red[t] = m;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if (t < d) red[t] = max(red[t], red[t + d]);
-    __syncthreads();
-  }
-  if (t == 0) {
-    const int ms = red[0];                                      // over the PREFIX, before the filters (map_refiner.cc:104-107 on the database of :88-89)
-    a.max_sharing[q] = ms;
-    s_thr = ld_threshold(ms, a.ratio, a.min_words);
-  }
-  __syncthreads();
-  const int thr = s_thr;
+  const int ms = block_max<256>(m, wsum);                       // over the PREFIX, before the filters (map_refiner.cc:104-107 on the database of :88-89)
+  if (t == 0) a.max_sharing[q] = ms;
+  const int thr = ld_threshold(ms, a.ratio, a.min_words);
   int base = 0;
   for (int f0 = 0; f0 < limit; f0 += 256) {                     // (uniform)
     const int f = f0 + t;
@@ -76,18 +65,14 @@ __global__ __launch_bounds__(256) void loopdet_select_kernel(LoopSelectArgs a) {
       s = sh[f];
       keep = ld_candidate(s, thr, a.row_ptr != nullptr && ld_covisible(a.row_ptr, a.nbr, a.rows, fq, f));
     }
-    const unsigned long long bal = __ballot(keep);
-    if (lane == 0) wsum[w] = __popcll(bal);
-    __syncthreads();
-    int pos = base + __popcll(bal & ((1ull << lane) - 1ull));
-    for (int k = 0; k < w; ++k) pos += wsum[k];
+    int total;
+    const int pos = base + block_compact<256>(keep, wsum, &total);
     if (keep && pos < a.ccap) {
       a.cand_frame[(size_t)q * a.ccap + pos] = f;
       a.cand_sharing[(size_t)q * a.ccap + pos] = s;
       a.cand_score[(size_t)q * a.ccap + pos] = sc[f];
     }
-    base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    __syncthreads();
+    base += total;
   }
   if (a.zero_tail)                                              // the caller's dense counts: a frame that does not exist shares nothing
     for (int f = limit + t; f < a.N; f += 256) sh[f] = 0;
@@ -109,7 +94,7 @@ __global__ __launch_bounds__(256) void loopdet_state_kernel(LoopStateArgs a) {
   const int fq = a.qframe[q];
   const bool in = fq >= 0 && fq < a.N;
   int n = in ? a.db_n[fq] : 0;
-  n = n < 0 ? 0 : (n > a.cap ? a.cap : n);
+  n = clamp_count(n, a.cap);
   if (t == 0) {
     a.qn[q] = n;
     a.max_dist[q] = in ? a.odom[fq] * a.distance_rate : 0.0;
@@ -124,9 +109,9 @@ __global__ __launch_bounds__(256) void loopdet_state_kernel(LoopStateArgs a) {
 
 __global__ __launch_bounds__(256) void loopdet_gather_kernel(LoopGatherArgs g) {
   __shared__ int wsum[4];
-  const int q = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int q = blockIdx.x, t = threadIdx.x;
   int m = g.nmatch[q];
-  m = m < 0 ? 0 : (m > g.mcap ? g.mcap : m);
+  m = clamp_count(m, g.mcap);
   const int best = g.best[q];
   const int fq = g.qframe[q];
   int pre = ld_stage_before(g.ncand[q], g.gstatus[q], g.ngroups[q], best, g.N, m, g.min_matches);
@@ -146,18 +131,14 @@ __global__ __launch_bounds__(256) void loopdet_gather_kernel(LoopGatherArgs g) {
       if (qi >= 0 && qi < g.cap && ci >= 0 && ci < g.cap)       // the matcher's indices are in range; this is memory safety only
         valid = ld_constraint(g.xyz + ((size_t)best * g.cap + ci) * 3, g.feat + ((size_t)fq * g.cap + qi) * 259, g.u_right[(size_t)fq * g.cap + qi], px, po);
     }
-    const unsigned long long bal = __ballot(valid);
-    if (lane == 0) wsum[w] = __popcll(bal);
-    __syncthreads();
-    int s = kept + __popcll(bal & ((1ull << lane) - 1ull));
-    for (int k = 0; k < w; ++k) s += wsum[k];
+    int total;
+    const int s = kept + block_compact<256>(valid, wsum, &total);
     if (valid) {
       map[s] = j;
       X[3 * s] = px[0]; X[3 * s + 1] = px[1]; X[3 * s + 2] = px[2];
       obs[3 * s] = po[0]; obs[3 * s + 1] = po[1]; obs[3 * s + 2] = po[2];
     }
-    kept += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    __syncthreads();
+    kept += total;
   }
   if (t == 0) {
     g.n[q] = kept;

@@ -19,6 +19,7 @@
 #include "common.h"
 #include "merge_core.h"
 #include "kernels.h"
+#include "wg_prims.h"
 
 namespace airfe {
 
@@ -51,12 +52,6 @@ __device__ inline void mg_link(int* parent, int u, int v) {
 
 __device__ inline void mg_mark(int* flags, int m) { (void)__hip_atomic_fetch_or(flags + m, MG_TOUCHED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// one integer atomic per wave: the lanes with `yes` counted into *at
-__device__ inline void mg_count(bool yes, int32_t* at) {
-  const unsigned long long bal = __ballot(yes);
-  if (bal && (threadIdx.x & 63) == 0) atomicAdd(at, (int)__popcll(bal));
-}
-
 __global__ __launch_bounds__(256) void merge_init_kernel(MergeWork w, int max_points, size_t rows) {
   const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (g < (size_t)max_points) {
@@ -73,12 +68,12 @@ __global__ __launch_bounds__(256) void merge_gate_kernel(MergeTables t, MergeLoo
   const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
   const int q = (int)(g / l.mcap), e = (int)(g % l.mcap);
   int kind = MG_DEAD, A = -1, B = -1, row = -1;
-  if (q < l.Q && l.stage[q] == 0 && e < mg_entries(l.nmatch[q], l.mcap)) kind = mg_entry(t, l, q, e, &A, &B, &row);
+  if (q < l.Q && l.stage[q] == 0 && e < clamp_count(l.nmatch[q], l.mcap)) kind = mg_entry(t, l, q, e, &A, &B, &row);
   if (PHASE == 0) {
     if (kind == MG_ADOPT) atomicMin(reinterpret_cast<unsigned*>(w.staged) + row, (unsigned)B);      // -1 is the largest unsigned: the smallest B wins
-    mg_count(kind == MG_PAIR || kind == MG_ADOPT, w.info + MG_I_LIVE);
-    mg_count(kind == MG_OUTLIER, w.info + MG_I_OUTLIER);
-    mg_count(kind == MG_EPIPOLAR, w.info + MG_I_EPIPOLAR);
+    wave_count_add(kind == MG_PAIR || kind == MG_ADOPT, w.info + MG_I_LIVE);
+    wave_count_add(kind == MG_OUTLIER, w.info + MG_I_OUTLIER);
+    wave_count_add(kind == MG_EPIPOLAR, w.info + MG_I_EPIPOLAR);
   } else {
     if (kind == MG_ADOPT) A = w.staged[row];                       // (in range: a B of the launch before)
     if (kind == MG_PAIR || kind == MG_ADOPT) {
@@ -103,16 +98,16 @@ __global__ __launch_bounds__(256) void merge_pairs_kernel(const int32_t* pairs, 
     mg_mark(w.flags, A);
     mg_mark(w.flags, B);
   }
-  mg_count(ok, w.info + MG_I_LIVE);
-  mg_count(in && !ok, w.info + MG_I_OUTLIER);
+  wave_count_add(ok, w.info + MG_I_LIVE);
+  wave_count_add(in && !ok, w.info + MG_I_OUTLIER);
 }
 
 __global__ __launch_bounds__(256) void merge_src_kernel(MergeTables t, MergeWork w) {
   const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
   const int f = (int)(g / t.cap), i = (int)(g % t.cap);
-  if (f >= t.size || i >= cv_rows(t.n[f], t.cap)) return;
+  if (f >= t.size || i >= clamp_count(t.n[f], t.cap)) return;
   const int m = t.point_id[g];
-  if (!mg_valid_id(m, t.max_points) || !(w.flags[m] & MG_TOUCHED) || mg_isnan(t.xyz[3 * g])) return;
+  if (!mg_valid_id(m, t.max_points) || !(w.flags[m] & MG_TOUCHED) || is_nan(t.xyz[3 * g])) return;
   atomicMin(w.src + m, (int)g);
 }
 
@@ -130,7 +125,7 @@ __global__ __launch_bounds__(256) void merge_flatten_kernel(MergeWork w, int max
       removed = true;
     }
   }
-  mg_count(removed, w.info + MG_I_REMOVED);
+  wave_count_add(removed, w.info + MG_I_REMOVED);
 }
 
 // the group of a marked id: its root when the component has another member, else -1
@@ -154,14 +149,14 @@ __global__ __launch_bounds__(256) void merge_map_kernel(MergeWork w, int max_poi
     w.map[m] = r >= 0 ? mg_best(w, r) : m;
     group = r == m;
   }
-  mg_count(group, w.info + MG_I_GROUPS);
+  wave_count_add(group, w.info + MG_I_GROUPS);
 }
 
 __global__ __launch_bounds__(256) void merge_relabel_kernel(MergeTables t, MergeWork w) {
   __shared__ int ids[BOW_MAX_FEATURES];
   __shared__ int grp[BOW_MAX_FEATURES];                            // the row's group; -1: in none; -2: in none, but the row adopts
   const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-  const int nf = cv_rows(t.n[f], t.cap);
+  const int nf = clamp_count(t.n[f], t.cap);
   const size_t base = (size_t)f * t.cap;
   for (int i = tid; i < t.cap; i += 256) {
     int id = -1, g = -1;
@@ -191,15 +186,15 @@ __global__ __launch_bounds__(256) void merge_relabel_kernel(MergeTables t, Merge
       if (what != MG_KEEP || adopting) {
         const int now = what == MG_CLEAR ? -1 : (what == MG_BEST ? mg_best(w, grp[i]) : id);
         const int from = now >= 0 ? w.src[now] : MG_NONE;
-        double x = mg_nan(), y = mg_nan(), z = mg_nan();
+        double x = quiet_nan(), y = quiet_nan(), z = quiet_nan();
         if (from != MG_NONE) { x = t.xyz[3 * (size_t)from]; y = t.xyz[3 * (size_t)from + 1]; z = t.xyz[3 * (size_t)from + 2]; }
         t.point_id[base + i] = now;
         t.xyz[3 * (base + i)] = x; t.xyz[3 * (base + i) + 1] = y; t.xyz[3 * (base + i) + 2] = z;
       }
     }
-    mg_count(adopting, w.info + MG_I_ADOPTED);
-    mg_count(what == MG_BEST, w.info + MG_I_RELABELLED);
-    mg_count(what == MG_CLEAR, w.info + MG_I_CLEARED);
+    wave_count_add(adopting, w.info + MG_I_ADOPTED);
+    wave_count_add(what == MG_BEST, w.info + MG_I_RELABELLED);
+    wave_count_add(what == MG_CLEAR, w.info + MG_I_CLEARED);
   }
 }
 

@@ -10,6 +10,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "pnp_core.h"
+#include "wg_prims.h"
 
 namespace airfe {
 
@@ -18,18 +19,13 @@ namespace {
 constexpr int PNP_SPB = 4;            // samples per models workgroup (5.2 KB of LDS each); one lane solves a sample serially, ~1.1 ms: that latency is the kernel's time
 constexpr int PNP_CHUNKS = (PNP_MAX_ITERS + PNP_SPB - 1) / PNP_SPB;
 
-__device__ __forceinline__ int prob_n(const PnpArgs& a, int b) {
-  const int n = a.n[b];
-  return n < 0 ? 0 : (n > a.ncap ? a.ncap : n);
-}
-
 __global__ __launch_bounds__(64) void pnp_models_kernel(PnpArgs a) {
   __shared__ double ws[PNP_SPB][PNP_WS];
   __shared__ int ids[PNP_SPB][5];
   __shared__ int ok[PNP_SPB];
   __shared__ double sK[4];
   const int b = blockIdx.y, t = threadIdx.x, s0 = blockIdx.x * PNP_SPB;
-  const int n = prob_n(a, b);
+  const int n = clamp_count(a.n[b], a.ncap);
   int* sc = a.scores + (size_t)b * PNP_MAX_ITERS;
   if (n < PNP_MIN_POINTS) {
     if (t < PNP_SPB && s0 + t < PNP_MAX_ITERS) sc[s0 + t] = -1;
@@ -96,7 +92,7 @@ __global__ __launch_bounds__(PNP_LM_LANES) void pnp_refine_kernel(PnpArgs a) {
   __shared__ uint8_t msk[PNP_MAX_POINTS];
   __shared__ int sh[2];
   const int b = blockIdx.x, t = threadIdx.x;
-  const int n = prob_n(a, b);
+  const int n = clamp_count(a.n[b], a.ncap);
   uint8_t* mask = a.mask + (size_t)b * a.mcap;
   for (int i = t; i < a.mcap; i += PNP_LM_LANES) mask[i] = 0;
   if (t == 0) {
@@ -147,9 +143,8 @@ __global__ __launch_bounds__(PNP_LM_LANES) void pnp_refine_kernel(PnpArgs a) {
 
 __global__ __launch_bounds__(256) void pnp_gather_kernel(PnpGatherArgs g) {
   __shared__ int wsum[4];
-  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
-  int m = g.ntrack[b];
-  m = m < 0 ? 0 : (m > g.mcap ? g.mcap : m);
+  const int b = blockIdx.x, t = threadIdx.x;
+  const int m = clamp_count(g.ntrack[b], g.mcap);
   const int32_t* tidx = g.tidx + (size_t)b * g.mcap * 2;
   float* obj = g.obj + (size_t)b * g.ncap * 3;
   float* img = g.img + (size_t)b * g.ncap * 2;
@@ -163,26 +158,20 @@ __global__ __launch_bounds__(256) void pnp_gather_kernel(PnpGatherArgs g) {
       const int r = tidx[2 * j], c = tidx[2 * j + 1];
       if (r >= 0 && r < g.capK && c >= 0 && c < g.cap) {        // the matcher's indices are in range; this is memory safety only
         const double* p = g.xyz + ((size_t)b * g.capK + r) * 3;
-        valid = !isnan(p[0]);
+        valid = !is_nan(p[0]);
         X = (float)p[0]; Y = (float)p[1]; Z = (float)p[2];
         const float* f = g.feat + ((size_t)b * g.cap + c) * 259;
         u = f[1]; v = f[2];
       }
     }
-    const unsigned long long bal = __ballot(valid);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[w] = __popcll(bal);
-    __syncthreads();
-    int off = kept;
-    for (int k = 0; k < w; ++k) off += wsum[k];
+    int total;
+    const int q = kept + block_compact<256>(valid, wsum, &total);
     if (valid) {
-      const int q = off + before;
       obj[3 * q] = X; obj[3 * q + 1] = Y; obj[3 * q + 2] = Z;
       img[2 * q] = u; img[2 * q + 1] = v;
       map[q] = j;
     }
-    kept += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    __syncthreads();
+    kept += total;
   }
   if (t == 0) g.n[b] = kept;
 }
@@ -192,7 +181,7 @@ __global__ __launch_bounds__(256) void pnp_stereo_kernel(StereoArgs s) {
   __shared__ int wgood[4];
   __shared__ double cam[8];
   const int b = blockIdx.x, t = threadIdx.x;
-  const int nl = min(max(s.nl[b], 0), s.cap), nr = min(max(s.nr[b], 0), s.cap), m = min(max(s.nmatch[b], 0), s.mcap);
+  const int nl = clamp_count(s.nl[b], s.cap), nr = clamp_count(s.nr[b], s.cap), m = clamp_count(s.nmatch[b], s.mcap);
   if (t == 0) {
     cam[0] = s.min_x_diff; cam[1] = s.max_x_diff; cam[2] = s.max_y_diff; cam[3] = s.bf;
     cam[4] = s.fx; cam[5] = s.fy; cam[6] = s.cx; cam[7] = s.cy;
@@ -213,9 +202,7 @@ __global__ __launch_bounds__(256) void pnp_stereo_kernel(StereoArgs s) {
       atomicMax(&last[l], j);                                  // a later list entry overwrites an earlier one (frame.cc:161-172)
     }
   }
-  for (int k = 32; k > 0; k >>= 1) good += __shfl_xor(good, k, 64);
-  if ((t & 63) == 0) wgood[t >> 6] = good;
-  __syncthreads();
+  good = block_sum<256>(good, wgood);                          // (its first barrier: every atomicMax on last[] is done)
   double* ur = s.u_right + (size_t)b * s.cap;
   double* dp = s.depth + (size_t)b * s.cap;
   double* xyz = s.xyz + (size_t)b * s.cap * 3;
@@ -228,10 +215,10 @@ __global__ __launch_bounds__(256) void pnp_stereo_kernel(StereoArgs s) {
       pnp_stereo_point(a[1], a[2], c[1], cam, q);
       ur[i] = q[0]; dp[i] = q[1]; xyz[3 * i] = q[2]; xyz[3 * i + 1] = q[3]; xyz[3 * i + 2] = q[4];
     } else {
-      ur[i] = -1.0; dp[i] = -1.0; xyz[3 * i] = xyz[3 * i + 1] = xyz[3 * i + 2] = __builtin_nan("");
+      ur[i] = -1.0; dp[i] = -1.0; xyz[3 * i] = xyz[3 * i + 1] = xyz[3 * i + 2] = quiet_nan();
     }
   }
-  if (t == 0) s.good[b] = wgood[0] + wgood[1] + wgood[2] + wgood[3];
+  if (t == 0) s.good[b] = good;
 }
 
 }  // namespace

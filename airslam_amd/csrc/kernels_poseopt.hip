@@ -10,6 +10,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "poseopt_core.h"
+#include "wg_prims.h"
 
 namespace airfe {
 
@@ -17,15 +18,13 @@ namespace {
 
 constexpr int PO_PART = 29;           // row stride of the partials in LDS (odd: lanes 0..27 read a row without conflicts, writes spread over the banks)
 
-__device__ __forceinline__ int po_clamp(int n, int cap) { return n < 0 ? 0 : (n > cap ? cap : n); }
-
 __global__ __launch_bounds__(PO_LANES) void poseopt_kernel(PoseoptArgs a) {
   __shared__ double cons[6 * PO_MAX_POINTS];
   __shared__ double part[PO_LANES * PO_PART];
   __shared__ double tot[28], S[PO_SIZE], hin[36];
   __shared__ uint8_t lvl[PO_MAX_POINTS];
   const int b = blockIdx.x, t = threadIdx.x;
-  const int n = po_clamp(a.n[b], a.ncap);
+  const int n = clamp_count(a.n[b], a.ncap);
   const double* gX = a.X + (size_t)b * a.ncap * 3;
   const double* gO = a.obs + (size_t)b * a.ncap * 3;
   for (int i = t; i < n; i += PO_LANES) {
@@ -84,8 +83,7 @@ __global__ __launch_bounds__(PO_LANES) void poseopt_kernel(PoseoptArgs a) {
       lvl[i] = o ? 1 : 0;
       out += o ? 1 : 0;
     }
-    for (int k = 32; k > 0; k >>= 1) out += __shfl_xor(out, k, 64);
-    outliers = out;
+    outliers = wave_sum(out);
     __syncthreads();
     if (n < PO_MIN_EDGES) break;
   }
@@ -100,7 +98,7 @@ __global__ __launch_bounds__(PO_LANES) void poseopt_kernel(PoseoptArgs a) {
   }
   __syncthreads();
   if (t < 16) a.Twc[16 * (size_t)b + t] = hin[t];
-  if (a.Rt && t < 12) a.Rt[12 * (size_t)b + t] = po_canon(S[PO_CUR + t]);
+  if (a.Rt && t < 12) a.Rt[12 * (size_t)b + t] = canon_nan(S[PO_CUR + t]);
   uint8_t* mask = a.inlier + (size_t)b * a.mcap;
   if (a.map) {
     const int* map = a.map + (size_t)b * a.ncap;
@@ -118,7 +116,7 @@ __global__ __launch_bounds__(PO_LANES) void poseopt_kernel(PoseoptArgs a) {
 
 __global__ __launch_bounds__(256) void poseopt_gather_kernel(PoseoptGatherArgs g) {
   const int b = blockIdx.x, t = threadIdx.x;
-  const int n = po_clamp(g.n[b], g.ncap);
+  const int n = clamp_count(g.n[b], g.ncap);
   const int* map = g.map + (size_t)b * g.ncap;
   const int32_t* tidx = g.tidx + (size_t)b * g.mcap * 2;
   double* X = g.X + (size_t)b * g.ncap * 3;

@@ -10,6 +10,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "wg_prims.h"
 #include "kernels.h"
 
 namespace airfe {
@@ -275,17 +276,8 @@ __global__ __launch_bounds__(256) void s0_j2l_grid_kernel(const float* __restric
     int v[J2L_CPT], tot = 0;
 #pragma unroll
     for (int q = 0; q < J2L_CPT; ++q) { v[q] = fill[t * J2L_CPT + q]; tot += v[q]; }
-    const int lane = t & 63, wv = t >> 6;
-    int incl = tot;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int u = __shfl_up(incl, o);
-      if (lane >= o) incl += u;
-    }
-    if (lane == 63) wtot[wv] = incl;
-    __syncthreads();
-    int off = incl - tot;
-    for (int w = 0; w < wv; ++w) off += wtot[w];
+    int all;
+    int off = block_excl_scan<256>(tot, wtot, &all);
 #pragma unroll
     for (int q = 0; q < J2L_CPT; ++q) { cs[t * J2L_CPT + q] = off; off += v[q]; fill[t * J2L_CPT + q] = 0; }
     if (t == 255) cs[J2L_CELLS] = off;
@@ -329,11 +321,8 @@ __global__ __launch_bounds__(256) void s0_j2l_grid_kernel(const float* __restric
   }
   // the kept proposals of this workgroup's run of 256 * J2L_PT: the count wf_count_kernel would take over the same run (launch_wireframe's first launch)
   if (wg_counts) {
-    kept = (int)wave_sum((float)kept);
-    __syncthreads();                    // (wtot's earlier readers)
-    if ((t & 63) == 0) wtot[t >> 6] = kept;
-    __syncthreads();
-    if (t == 0) wg_counts[(size_t)blockIdx.y * LINE_CNT_LD + 2 + blockIdx.x] = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    kept = block_sum<256>(kept, wtot);
+    if (t == 0) wg_counts[(size_t)blockIdx.y * LINE_CNT_LD + 2 + blockIdx.x] = kept;
   }
 }
 

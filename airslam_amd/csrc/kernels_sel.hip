@@ -4,6 +4,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "desc_sample.h"
+#include "wg_prims.h"
 
 namespace airfe {
 
@@ -141,19 +142,8 @@ __global__ __launch_bounds__(1024) void select_list_kernel(const u64* __restrict
       __syncthreads();
       const unsigned h0 = hist[2047 - 2 * tid], h1 = hist[2046 - 2 * tid];
       const unsigned v = h0 + h1;
-      unsigned incl = v;
-      const int lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-      }
-      if (lane == 63) wsum[wv] = incl;
-      __syncthreads();
-      unsigned woff = 0;
-      for (int w2 = 0; w2 < wv; ++w2) woff += wsum[w2];
-      incl += woff;
-      const unsigned excl = incl - v;
+      unsigned all;
+      const unsigned excl = block_excl_scan<1024>(v, wsum, &all), incl = excl + v;
       if (excl < remaining && remaining <= excl + h0) {
         s_prefix = prefix | ((u64)(2047 - 2 * tid) << sh);
         s_remaining = remaining - excl;
@@ -185,19 +175,8 @@ __global__ __launch_bounds__(1024) void select_list_kernel(const u64* __restrict
       }
     }
   }
-  __syncthreads();
+  block_sort_asc<1024>(sk, 1024);
   const int n = min((int)s_cnt, min(topk, 1024));
-  for (int k2 = 2; k2 <= 1024; k2 <<= 1) {
-    for (int j = k2 >> 1; j > 0; j >>= 1) {
-      const int p = tid ^ j;
-      if (p > tid) {
-        const u64 a = sk[tid], c = sk[p];
-        const bool up = (tid & k2) == 0;
-        if ((a > c) == up) { sk[tid] = c; sk[p] = a; }
-      }
-      __syncthreads();
-    }
-  }
   int bl = b;                                                          // image index within its destination
   if (ex.feat1 && b >= ex.Bs) { feat = ex.feat1; n_out = ex.n_out1; bl = b - ex.Bs; }
   int4 rows = make_int4(0, 0, 0, 0);

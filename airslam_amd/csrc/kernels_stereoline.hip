@@ -14,7 +14,7 @@ namespace {
 
 __global__ __launch_bounds__(256) void stereoline_kernel(StereoLineArgs a) {
   const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-  const int nl = sl_rows(a.nl[b], a.capL), nr = sl_rows(a.nr[b], a.capL);
+  const int nl = clamp_count(a.nl[b], a.capL), nr = clamp_count(a.nr[b], a.capL);
   const bool live = i < nl;
   int s = -1;
   if (live) {

@@ -14,6 +14,7 @@
 #include "common.h"
 #include "triangulate_core.h"
 #include "kernels.h"
+#include "wg_prims.h"
 
 namespace airfe {
 
@@ -72,17 +73,13 @@ __global__ __launch_bounds__(256) void tri_point_kernel(TriangulateArgs a) {
     a.nobs[m] = s1 - s0;
     tr_info_flags(st, fl);
   }
-  const int lane = threadIdx.x & 63;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int c = __popcll(__ballot(fl[k] != 0));
-    if (lane == 0 && c) atomicAdd(a.info + k, c);
-  }
+  for (int k = 0; k < 4; ++k) wave_count_add(fl[k] != 0, a.info + k);
 }
 
 __global__ __launch_bounds__(256) void fill_points_kernel(FillPointsArgs a) {
   const int f = blockIdx.x, t = threadIdx.x, lane = t & 63;
-  const int n = cv_rows(a.n[f], a.cap);
+  const int n = clamp_count(a.n[f], a.cap);
   const int32_t* ids = a.point_id + (size_t)f * a.cap;
   int w = 0;
   for (int i = t; i < n; i += 256) {
@@ -90,11 +87,11 @@ __global__ __launch_bounds__(256) void fill_points_kernel(FillPointsArgs a) {
     const int m = cv_row_id(ids, i, n, a.max_points, &ig);
     if (m < 0 || a.status[m] != TR_OK) continue;
     double* p = a.points + ((size_t)f * a.cap + i) * 3;
-    if (a.only_missing && !(p[0] != p[0])) continue;
+    if (a.only_missing && !is_nan(p[0])) continue;
     p[0] = a.xyz[(size_t)3 * m]; p[1] = a.xyz[(size_t)3 * m + 1]; p[2] = a.xyz[(size_t)3 * m + 2];
     ++w;
   }
-  for (int d = 32; d > 0; d >>= 1) w += __shfl_down(w, d);
+  w = wave_sum(w);                                                 // (a lane writes several rows: a count per lane, not a predicate)
   if (lane == 0 && w) atomicAdd(a.written, w);
 }
 

@@ -16,23 +16,19 @@
 
 #include <vector>
 
-#if defined(__HIPCC__)
-#define LD_HD __host__ __device__ inline
-#else
-#define LD_HD inline
-#endif
+#include "core_common.h"
 
 #define LD_MAX_QUERIES 4096     // stored queries per call
 #define LD_MAX_FRAMES 4096      // frames the composite handles (the grouping's candidate capacity, the odometry kernel's LDS)
 
 // |b - a| as :76 computes it
-LD_HD double ld_step(const double* a, const double* b) {
+AIRFE_HD double ld_step(const double* a, const double* b) {
   const double dx = b[0] - a[0], dy = b[1] - a[1], dz = b[2] - a[2];
   return sqrt((dx * dx + dy * dy) + dz * dz);
 }
 
 // odom[0] = +0, odom[f] = odom[f - 1] + step[f]: sequential, ascending f (step[f] = |pos[f] - pos[f - 1]|, step[0] unused)
-LD_HD void ld_prefix(const double* step, int n, double* odom) {
+AIRFE_HD void ld_prefix(const double* step, int n, double* odom) {
   double s = 0.0;
   for (int f = 0; f < n; ++f) {
     if (f > 0) s += step[f];
@@ -41,17 +37,17 @@ LD_HD void ld_prefix(const double* step, int n, double* odom) {
 }
 
 // std::max(static_cast<int>(max_sharing_words * 0.5f), 8) (:108): a float product, truncated
-LD_HD int ld_threshold(int max_sharing, float ratio, int min_words) {
+AIRFE_HD int ld_threshold(int max_sharing, float ratio, int min_words) {
   const float prod = (float)max_sharing * ratio;
   const int t = (int)prod;
   return t > min_words ? t : min_words;
 }
 
 // does frame f exist for the query fq?  fq outside 0 .. size - 1: nothing does
-LD_HD bool ld_exists(int f, int fq, int size) { return fq >= 0 && fq < size && f >= 0 && f < fq; }
+AIRFE_HD bool ld_exists(int f, int fq, int size) { return fq >= 0 && fq < size && f >= 0 && f < fq; }
 
 // is f a neighbour in row fq of the covisibility CSR, at ANY weight (covi_frames.count(fsw), :115)?  Rows ascend strictly in nbr.
-LD_HD bool ld_covisible(const int32_t* row_ptr, const int32_t* nbr, int rows, int fq, int f) {
+AIRFE_HD bool ld_covisible(const int32_t* row_ptr, const int32_t* nbr, int rows, int fq, int f) {
   if (fq < 0 || fq >= rows) return false;
   int lo = row_ptr[fq], hi = row_ptr[fq + 1];
   while (lo < hi) {
@@ -62,11 +58,11 @@ LD_HD bool ld_covisible(const int32_t* row_ptr, const int32_t* nbr, int rows, in
 }
 
 // the candidate predicate for a frame that exists (f < fq), :113-120; (a frame without a common word is absent from frame_sharing_words)
-LD_HD bool ld_candidate(int sharing, int thr, bool covisible) { return sharing > 0 && sharing >= thr && !covisible; }
+AIRFE_HD bool ld_candidate(int sharing, int thr, bool covisible) { return sharing > 0 && sharing >= thr && !covisible; }
 
 // the constraint of list entry (qi, ci): point = xyz[b][ci], feat_row = the query's row qi ([259]: score, x, y, ...), u_right = u_right[fq][qi].
 // Returns whether there is one; obs = (x, y, u), u > 0 iff stereo (the convention of "Frame optimisation")
-LD_HD bool ld_constraint(const double* point, const float* feat_row, double u_right, double* X, double* obs) {
+AIRFE_HD bool ld_constraint(const double* point, const float* feat_row, double u_right, double* X, double* obs) {
   if (isnan(point[0])) return false;
   X[0] = point[0]; X[1] = point[1]; X[2] = point[2];
   obs[0] = (double)feat_row[1];
@@ -76,28 +72,28 @@ LD_HD bool ld_constraint(const double* point, const float* feat_row, double u_ri
 }
 
 // the gates before the constraints: :101 / :122, :174, :232 (STRICTLY more than min_matches)
-LD_HD int ld_stage_before(int ncand, int gstatus, int ngroups, int best, int size, int nmatch, int min_matches) {
+AIRFE_HD int ld_stage_before(int ncand, int gstatus, int ngroups, int best, int size, int nmatch, int min_matches) {
   if (ncand <= 0) return 1;
   if (gstatus != 0 || ngroups <= 0) return 2;
   if (best < 0 || best >= size || nmatch <= min_matches) return 3;
   return 0;
 }
 // ... and behind them: :301, :308
-LD_HD int ld_stage(int before, int ncons, int min_points, int num, int min_inliers) {
+AIRFE_HD int ld_stage(int before, int ncons, int min_points, int num, int min_inliers) {
   if (before) return before;
   if (ncons < min_points) return 4;
   return num < min_inliers ? 5 : 0;
 }
 
 // Twl, Twq [16] row-major -> Rlq [9] row-major, tlq [3]
-LD_HD void ld_relative_pose(const double* Twl, const double* Twq, double* Rlq, double* tlq) {
+AIRFE_HD void ld_relative_pose(const double* Twl, const double* Twq, double* Rlq, double* tlq) {
   const double d0 = Twq[3] - Twl[3], d1 = Twq[7] - Twl[7], d2 = Twq[11] - Twl[11];
   for (int i = 0; i < 3; ++i) {
     for (int j = 0; j < 3; ++j) Rlq[3 * i + j] = (Twl[i] * Twq[j] + Twl[4 + i] * Twq[4 + j]) + Twl[8 + i] * Twq[8 + j];
     tlq[i] = (Twl[i] * d0 + Twl[4 + i] * d1) + Twl[8 + i] * d2;
   }
 }
-LD_HD void ld_no_relative_pose(double* Rlq, double* tlq) {
+AIRFE_HD void ld_no_relative_pose(double* Rlq, double* tlq) {
   for (int k = 0; k < 9; ++k) Rlq[k] = (k % 4 == 0) ? 1.0 : 0.0;
   tlq[0] = tlq[1] = tlq[2] = 0.0;
 }

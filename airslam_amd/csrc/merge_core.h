@@ -3,7 +3,7 @@
 // statement for the host and the device: the kernels (kernels_merge.hip) call the routines below from their lanes, merge_build_host / merge_pairs_host at
 // the end call them in loops; tests/merge_ref.py restates the same over dicts and sorted sets.  Doubles, every sum in the order written, no fused
 // multiply-adds (the translation units that include this header are compiled with -ffp-contract=off).
-//   valid(f, i), size, n[f], max_points   as in covis_core.h (cv_rows).  An id is VALID iff it is in [0, max_points).
+//   valid(f, i), size, n[f], max_points   as in covis_core.h (clamp_count).  An id is VALID iff it is in [0, max_points).
 //   triangulated(m)   some valid row holding m has a non-NaN x in the point table;  src(m) = the smallest key f * cap + i of such a row
 //   Every gate reads the id table and the point table AS THEY WERE BEFORE THE CALL.
 //   1 entries     query q with stage[q] == 0, fq = qframe[q], b_f = loop[q], list entry e < min(nmatch[q], mcap), (qi, ci) = idx[q][e]:
@@ -40,7 +40,6 @@
 
 #include "covis_core.h"
 
-#define MG_HD CV_HD
 #define MG_MAX_FRAMES CV_MAX_FRAMES  // frames a merge handles: the key f * cap + i is an int32 at 4096 frames x 1024 rows
 #define MG_MAX_QUERIES 4096
 #define MG_MAX_MATCHES 1024          // mcap
@@ -64,15 +63,10 @@ struct MergeLoop {
   double cam[4] = {0, 0, 0, 0};                                              // fx, fy, cx, cy
 };
 
-MG_HD bool mg_finite(double v) { return v - v == 0.0; }
-MG_HD bool mg_isnan(double v) { return v != v; }
-MG_HD double mg_nan() { return __builtin_nan(""); }
-MG_HD bool mg_valid_id(int id, int max_points) { return id >= 0 && id < max_points; }
-MG_HD bool mg_cam_ok(const double* cam) { return mg_finite(cam[0]) && mg_finite(cam[1]) && cam[0] != 0.0 && cam[1] != 0.0; }
-// the entries of query q that step 1 looks at
-MG_HD int mg_entries(int nmatch, int mcap) { return nmatch < 0 ? 0 : (nmatch > mcap ? mcap : nmatch); }
+AIRFE_HD bool mg_valid_id(int id, int max_points) { return id >= 0 && id < max_points; }
+AIRFE_HD bool mg_cam_ok(const double* cam) { return is_finite(cam[0]) && is_finite(cam[1]) && cam[0] != 0.0 && cam[1] != 0.0; }
 
-MG_HD void mg_mul3(const double* A, const double* B, double* C) {
+AIRFE_HD void mg_mul3(const double* A, const double* B, double* C) {
 #pragma unroll
   for (int r = 0; r < 3; ++r)
 #pragma unroll
@@ -80,7 +74,7 @@ MG_HD void mg_mul3(const double* A, const double* B, double* C) {
 }
 
 // F = ((K^-T * [tlq]x) * Rlq) * K, row-major
-MG_HD void mg_fundamental(const double* cam, const double* Rlq, const double* tlq, double* F) {
+AIRFE_HD void mg_fundamental(const double* cam, const double* Rlq, const double* tlq, double* F) {
   const double fxi = 1.0 / cam[0], fyi = 1.0 / cam[1];
   const double Kit[9] = {fxi, 0.0, 0.0, 0.0, fyi, 0.0, -(cam[2] * fxi), -(cam[3] * fyi), 1.0};
   const double tx[9] = {0.0, -tlq[2], tlq[1], tlq[2], 0.0, -tlq[0], -tlq[1], tlq[0], 0.0};
@@ -92,25 +86,25 @@ MG_HD void mg_fundamental(const double* cam, const double* Rlq, const double* tl
 }
 
 // check_epipolar (:342-352): p1 on the query frame, p2 on the loop frame
-MG_HD bool mg_epipolar(const double* F, double x1, double y1, double x2, double y2) {
+AIRFE_HD bool mg_epipolar(const double* F, double x1, double y1, double x2, double y2) {
   const double el0 = (F[0] * x1 + F[1] * y1) + F[2], el1 = (F[3] * x1 + F[4] * y1) + F[5], el2 = (F[6] * x1 + F[7] * y1) + F[8];
   const double s = sqrt(el0 * el0 + el1 * el1);
   const double er = ((x2 * el0 + y2 * el1) + el2) / s;
   return er < 10.0;
 }
 
-// step 1 for entry (q, e), e < mg_entries(nmatch[q], mcap) of a query with stage 0 -> MG_DEAD .. MG_ADOPT; for MG_PAIR *A and *B, for MG_ADOPT *B and
+// step 1 for entry (q, e), e < clamp_count(nmatch[q], mcap) of a query with stage 0 -> MG_DEAD .. MG_ADOPT; for MG_PAIR *A and *B, for MG_ADOPT *B and
 // *row = the adopting row's key
-MG_HD int mg_entry(const MergeTables& t, const MergeLoop& l, int q, int e, int* A, int* B, int* row) {
+AIRFE_HD int mg_entry(const MergeTables& t, const MergeLoop& l, int q, int e, int* A, int* B, int* row) {
   const int fq = l.qframe[q], bf = l.loop[q];
   if (fq < 0 || fq >= t.size || bf < 0 || bf >= t.size) return MG_DEAD;
   const size_t at = (size_t)q * l.mcap + e;
   const int qi = l.idx[2 * at], ci = l.idx[2 * at + 1];
-  if (qi < 0 || ci < 0 || qi >= cv_rows(t.n[fq], t.cap) || ci >= cv_rows(t.n[bf], t.cap)) return MG_DEAD;
+  if (qi < 0 || ci < 0 || qi >= clamp_count(t.n[fq], t.cap) || ci >= clamp_count(t.n[bf], t.cap)) return MG_DEAD;
   const size_t rq = (size_t)fq * t.cap + qi, rl = (size_t)bf * t.cap + ci;
   const int b = t.point_id[rl];
   if (!mg_valid_id(b, t.max_points)) return MG_DEAD;
-  if (!mg_isnan(t.xyz[3 * rl])) {
+  if (!is_nan(t.xyz[3 * rl])) {
     if (l.mask[at] == 0) return MG_OUTLIER;
   } else {
     double F[9];
@@ -130,14 +124,14 @@ MG_HD int mg_entry(const MergeTables& t, const MergeLoop& l, int q, int e, int* 
 }
 
 // what row i of a frame holds after adoption: its own valid id; else the id staged for it (-1: none); -1 past the count
-MG_HD int mg_row_id(int own, int staged, int i, int n, int max_points) {
+AIRFE_HD int mg_row_id(int own, int staged, int i, int n, int max_points) {
   if (i >= n) return -1;
   if (mg_valid_id(own, max_points)) return own;
   return mg_valid_id(staged, max_points) ? staged : -1;
 }
 
 // step 6 for row i of a frame: ids = the rows' mg_row_id, grp = the group of each (its smallest id; -1: in no group), b = the best of grp[i]
-MG_HD int mg_row_decision(const int* ids, const int* grp, int rows, int i, int b) {
+AIRFE_HD int mg_row_decision(const int* ids, const int* grp, int rows, int i, int b) {
   const int g = grp[i];
   if (g < 0) return MG_KEEP;
   bool hasb = false;
@@ -173,15 +167,15 @@ inline void merge_apply_host(const MergeTables& t, const std::vector<std::pair<i
   int adopted = 0;
   if (!staged.empty())
     for (int f = 0; f < t.size; ++f)
-      for (int i = 0, nf = cv_rows(t.n[f], t.cap); i < nf; ++i) {
+      for (int i = 0, nf = clamp_count(t.n[f], t.cap); i < nf; ++i) {
         const size_t r = (size_t)f * t.cap + i;
         if (!mg_valid_id(t.point_id[r], P) && mg_valid_id(staged[r], P)) { touched[staged[r]] = 1; ++adopted; }
       }
   for (int f = 0; f < t.size; ++f)
-    for (int i = 0, nf = cv_rows(t.n[f], t.cap); i < nf; ++i) {
+    for (int i = 0, nf = clamp_count(t.n[f], t.cap); i < nf; ++i) {
       const size_t r = (size_t)f * t.cap + i;
       const int m = t.point_id[r];
-      if (mg_valid_id(m, P) && touched[m] && !mg_isnan(t.xyz[3 * r]) && src[m] == MG_NONE) src[m] = (int)r;      // ascending keys: the first is the smallest
+      if (mg_valid_id(m, P) && touched[m] && !is_nan(t.xyz[3 * r]) && src[m] == MG_NONE) src[m] = (int)r;      // ascending keys: the first is the smallest
     }
   int groups = 0, removed = 0;
   for (int m = 0; m < P; ++m) {
@@ -200,7 +194,7 @@ inline void merge_apply_host(const MergeTables& t, const std::vector<std::pair<i
   int relabelled = 0, cleared = 0;
   std::vector<int> ids(t.cap), grp(t.cap), what(t.cap);
   for (int f = 0; f < t.size; ++f) {
-    const int nf = cv_rows(t.n[f], t.cap);
+    const int nf = clamp_count(t.n[f], t.cap);
     bool any = false;
     for (int i = 0; i < nf; ++i) {
       const size_t r = (size_t)f * t.cap + i;
@@ -218,7 +212,7 @@ inline void merge_apply_host(const MergeTables& t, const std::vector<std::pair<i
       const int id = what[i] == MG_CLEAR ? -1 : (what[i] == MG_BEST ? map[ids[i]] : ids[i]);
       const int from = id >= 0 ? src[id] : MG_NONE;
       t.point_id[r] = id;
-      for (int k = 0; k < 3; ++k) t.xyz[3 * r + k] = from != MG_NONE ? t.xyz[3 * (size_t)from + k] : mg_nan();
+      for (int k = 0; k < 3; ++k) t.xyz[3 * r + k] = from != MG_NONE ? t.xyz[3 * (size_t)from + k] : quiet_nan();
       relabelled += what[i] == MG_BEST;
       cleared += what[i] == MG_CLEAR;
     }
@@ -246,7 +240,7 @@ inline void merge_build_host(const MergeTables& t, const MergeLoop& l, int max_f
   int count[5] = {0, 0, 0, 0, 0};
   for (int q = 0; q < l.Q; ++q) {
     if (l.stage[q] != 0) continue;
-    for (int e = 0, ne = mg_entries(l.nmatch[q], l.mcap); e < ne; ++e) {
+    for (int e = 0, ne = clamp_count(l.nmatch[q], l.mcap); e < ne; ++e) {
       int A = -1, B = -1, row = -1;
       const int kind = mg_entry(t, l, q, e, &A, &B, &row);
       ++count[kind];

@@ -7,7 +7,7 @@
 #ifndef AIRFE_PNP_CORE_H_
 #define AIRFE_PNP_CORE_H_
 
-#include "fransac_core.h"   // fr_splitmix64, FR_HD
+#include "fransac_core.h"   // fr_splitmix64, AIRFE_HD
 
 #if defined(__clang__)
 #pragma clang fp contract(off)
@@ -48,12 +48,12 @@
 #define PW_SS 647    // [9] cross-covariance of the alignment
 #define PNP_WS 656
 
-FR_HD int pnp_draw(int s, int attempt, int slot, int n) {
+AIRFE_HD int pnp_draw(int s, int attempt, int slot, int n) {
   const uint64_t h = fr_splitmix64(PNP_SEED ^ (((uint64_t)s << 32) | ((uint64_t)attempt << 8) | (uint64_t)slot));
   return (int)(((h >> 32) * (uint64_t)n) >> 32);
 }
 // sample s: id[0..4] = five distinct indices of n; false after 64 attempts with a repeat
-FR_HD bool pnp_sample(int n, int s, int* id) {
+AIRFE_HD bool pnp_sample(int n, int s, int* id) {
   for (int att = 0; att < PNP_MAX_ATTEMPTS; ++att) {
     bool ok = true;
     for (int k = 0; k < 5; ++k) {
@@ -66,7 +66,7 @@ FR_HD bool pnp_sample(int n, int s, int* id) {
 }
 
 // ---- cyclic Jacobi on a symmetric n x n matrix A (row-major, both triangles), eigenvectors in the columns of V --------------------------------
-FR_HD void pnp_jacobi_cs(double app, double aqq, double apq, double* c, double* s, double* t) {
+AIRFE_HD void pnp_jacobi_cs(double app, double aqq, double apq, double* c, double* s, double* t) {
   const double th = (aqq - app) / (2.0 * apq);
   const double tt = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
   *c = 1.0 / sqrt(tt * tt + 1.0);
@@ -74,7 +74,7 @@ FR_HD void pnp_jacobi_cs(double app, double aqq, double apq, double* c, double* 
   *t = tt;
 }
 // the part of rotation (p, q) that row k owns: no row reads what another row writes, so rows may run in any order (or in parallel)
-FR_HD void pnp_jacobi_row(double* A, double* V, int n, int k, int p, int q, double c, double s, double t, double apq) {
+AIRFE_HD void pnp_jacobi_row(double* A, double* V, int n, int k, int p, int q, double c, double s, double t, double apq) {
   if (k == p) {
     A[p * n + p] = A[p * n + p] - t * apq;
     A[p * n + q] = 0.0;
@@ -92,7 +92,7 @@ FR_HD void pnp_jacobi_row(double* A, double* V, int n, int k, int p, int q, doub
   V[k * n + q] = s * vkp + c * vkq;
 }
 // stopping rule, checked before each sweep: sum of squared off-diagonal entries (p < q, row-major order) <= 1e-30 * sum of squared diagonal entries
-FR_HD bool pnp_jacobi_converged(const double* A, int n) {
+AIRFE_HD bool pnp_jacobi_converged(const double* A, int n) {
   double off = 0.0, dia = 0.0;
   for (int p = 0; p < n; ++p) {
     dia = dia + A[p * n + p] * A[p * n + p];
@@ -100,7 +100,7 @@ FR_HD bool pnp_jacobi_converged(const double* A, int n) {
   }
   return off <= 1e-30 * dia;
 }
-FR_HD void pnp_jacobi(double* A, double* V, int n) {
+AIRFE_HD void pnp_jacobi(double* A, double* V, int n) {
   for (int i = 0; i < n * n; ++i) V[i] = (i % (n + 1)) == 0 ? 1.0 : 0.0;
   for (int sw = 0; sw < PNP_JACOBI_SWEEPS; ++sw) {
     if (pnp_jacobi_converged(A, n)) break;
@@ -115,7 +115,7 @@ FR_HD void pnp_jacobi(double* A, double* V, int n) {
   }
 }
 // rank r (0 = smallest) of eigenvalue i among the diagonal of A: ties go to the lower index
-FR_HD int pnp_rank(const double* A, int n, int i) {
+AIRFE_HD int pnp_rank(const double* A, int n, int i) {
   int r = 0;
   const double di = A[i * n + i];
   for (int j = 0; j < n; ++j) {
@@ -127,7 +127,7 @@ FR_HD int pnp_rank(const double* A, int n, int i) {
 
 // ---- least squares: the rows x cols matrix A (row-major, stride cols) and rhs b through the normal equations, Gaussian elimination with partial
 // pivoting (first largest |pivot|); a pivot that is not > 0 in magnitude: false
-FR_HD bool pnp_gauss(double* N, int m, double* x) {   // N: [m][m + 1] augmented
+AIRFE_HD bool pnp_gauss(double* N, int m, double* x) {   // N: [m][m + 1] augmented
   for (int k = 0; k < m; ++k) {
     int p = k;
     double best = fabs(N[k * (m + 1) + k]);
@@ -148,7 +148,7 @@ FR_HD bool pnp_gauss(double* N, int m, double* x) {   // N: [m][m + 1] augmented
   }
   return true;
 }
-FR_HD bool pnp_lsq(const double* A, const double* b, int rows, int cols, double* N, double* x) {
+AIRFE_HD bool pnp_lsq(const double* A, const double* b, int rows, int cols, double* N, double* x) {
   for (int r = 0; r < cols; ++r) {
     for (int c = 0; c < cols; ++c) {
       double s = 0.0;
@@ -164,7 +164,7 @@ FR_HD bool pnp_lsq(const double* A, const double* b, int rows, int cols, double*
 
 // ---- projection ------------------------------------------------------------------------------------------------------------------------------
 // Xc = R X + t in double, 1/z (1 where z == 0, as cvProjectPoints2), u = x / z * fx + cx
-FR_HD void pnp_project(const double* Rt, double X, double Y, double Z, const double* K, double* u, double* v) {
+AIRFE_HD void pnp_project(const double* Rt, double X, double Y, double Z, const double* K, double* u, double* v) {
   const double xc = Rt[0] * X + Rt[1] * Y + Rt[2] * Z + Rt[9];
   const double yc = Rt[3] * X + Rt[4] * Y + Rt[5] * Z + Rt[10];
   const double zc = Rt[6] * X + Rt[7] * Y + Rt[8] * Z + Rt[11];
@@ -173,7 +173,7 @@ FR_HD void pnp_project(const double* Rt, double X, double Y, double Z, const dou
   *v = yc * iz * K[1] + K[3];
 }
 // the inlier test's error: the projection rounded to float, err = dx^2 + dy^2 in float
-FR_HD float pnp_error(const double* Rt, float X, float Y, float Z, float u, float v, const double* K) {
+AIRFE_HD float pnp_error(const double* Rt, float X, float Y, float Z, float u, float v, const double* K) {
   double pu, pv;
   pnp_project(Rt, (double)X, (double)Y, (double)Z, K, &pu, &pv);
   const float dx = u - (float)pu, dy = v - (float)pv;
@@ -182,13 +182,13 @@ FR_HD float pnp_error(const double* Rt, float X, float Y, float Z, float u, floa
 
 // ---- EPnP on the five points in ws[PW_PW], ws[PW_UV] -----------------------------------------------------------------------------------------
 // rows a, b of control-point pair j (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)
-FR_HD int pnp_pair_a(int j) { return j < 3 ? 0 : (j < 5 ? 1 : 2); }
-FR_HD int pnp_pair_b(int j) { return j < 3 ? j + 1 : (j < 5 ? j - 1 : 3); }
+AIRFE_HD int pnp_pair_a(int j) { return j < 3 ? 0 : (j < 5 ? 1 : 2); }
+AIRFE_HD int pnp_pair_b(int j) { return j < 3 ? j + 1 : (j < 5 ? j - 1 : 3); }
 
 
 // R, t of ws[PW_SOL] from ws[PW_BETA]: control points in the camera frame (sign: z of the first point >= 0), Horn's quaternion alignment of the
 // object points onto them.  Returns the summed reprojection distance over the five points (NaN when anything is not finite).
-FR_HD double pnp_compute_rt(double* ws, const double* K) {
+AIRFE_HD double pnp_compute_rt(double* ws, const double* K) {
   double* ccs = ws + PW_CCS;
   double* pcs = ws + PW_PCS;
   const double* pw = ws + PW_PW;
@@ -249,7 +249,7 @@ FR_HD double pnp_compute_rt(double* ws, const double* K) {
 }
 
 // EPnP (Lepetit, Moreno-Noguer & Fua 2009) on the five points of ws[PW_PW] / ws[PW_UV]; the model (R row-major, t) in ws[PW_BEST]; false: no model
-FR_HD bool pnp_epnp(double* ws, const double* K) {
+AIRFE_HD bool pnp_epnp(double* ws, const double* K) {
   const double* pw = ws + PW_PW;
   double* cw = ws + PW_CW;
   double* al = ws + PW_AL;
@@ -376,7 +376,7 @@ FR_HD bool pnp_epnp(double* ws, const double* K) {
 }
 
 // sample s of a problem of n points: draw, gather, solve.  id [5] ints; ws [PNP_WS].  false: no model
-FR_HD bool pnp_solve_sample(const float* obj, const float* img, int n, int s, const double* K, int* id, double* ws) {
+AIRFE_HD bool pnp_solve_sample(const float* obj, const float* img, int n, int s, const double* K, int* id, double* ws) {
   if (!pnp_sample(n, s, id)) return false;
   for (int k = 0; k < 5; ++k) {
     const int i = id[k];
@@ -388,7 +388,7 @@ FR_HD bool pnp_solve_sample(const float* obj, const float* img, int n, int s, co
 
 // ---- the sequential rule ------------------------------------------------------------------------------------------------------------------------
 // RANSACUpdateNumIters(0.99, (n - good) / n, 5, maxIters), (1 - ep)^5 as repeated products
-FR_HD int pnp_update_niters(int n, int good, int max_iters) {
+AIRFE_HD int pnp_update_niters(int n, int good, int max_iters) {
   const double ep = (double)(n - good) / (double)n;
   const double num = 1.0 - 0.99;
   const double q = 1.0 - ep, q2 = q * q, q4 = q2 * q2;
@@ -398,7 +398,7 @@ FR_HD int pnp_update_niters(int n, int good, int max_iters) {
   return (ld >= 0.0 || -ln >= (double)max_iters * (-ld)) ? max_iters : (int)rint(ln / ld);
 }
 // scores [100]: inliers per sample (-1: no model).  The selected sample (-1: none); *best = its inlier count
-FR_HD int pnp_select(const int* scores, int n, int* best) {
+AIRFE_HD int pnp_select(const int* scores, int n, int* best) {
   int niters = PNP_MAX_ITERS, bc = 0, win = -1;
   for (int s = 0; s < niters && s < PNP_MAX_ITERS; ++s) {
     const int c = scores[s];
@@ -414,7 +414,7 @@ FR_HD int pnp_select(const int* scores, int n, int* best) {
 // ---- Levenberg-Marquardt refinement --------------------------------------------------------------------------------------------------------
 // parameters: the update (w, tau) maps R, t to Cay(w) R, t + tau with Cay(w) = I + 2 / (1 + w.w) ([w]x + [w]x^2) (rational: no sqrt, no trig)
 // per point: o[0..20] = J^T J (upper triangle, row-major), o[21..26] = J^T r, o[27] = r^T r; J [12] = the two rows of the Jacobian
-FR_HD void pnp_lm_point(const double* Rt, double X, double Y, double Z, double u, double v, const double* K, double* J, double* o) {
+AIRFE_HD void pnp_lm_point(const double* Rt, double X, double Y, double Z, double u, double v, const double* K, double* J, double* o) {
   const double p0 = Rt[0] * X + Rt[1] * Y + Rt[2] * Z, p1 = Rt[3] * X + Rt[4] * Y + Rt[5] * Z, p2 = Rt[6] * X + Rt[7] * Y + Rt[8] * Z;
   const double xc = p0 + Rt[9], yc = p1 + Rt[10], zc = p2 + Rt[11];
   if (zc == 0.0) {
@@ -443,22 +443,22 @@ FR_HD void pnp_lm_point(const double* Rt, double X, double Y, double Z, double u
 #define PL_AUG 60    // [6][7] damped normal equations, then Cay(w) [9]
 #define PL_SIZE 102
 
-FR_HD void pnp_lm_start(double* S, const double* Rt, const double* tot) {
+AIRFE_HD void pnp_lm_start(double* S, const double* Rt, const double* tot) {
   for (int k = 0; k < 12; ++k) S[PL_CUR + k] = Rt[k];
   for (int k = 0; k < 28; ++k) S[PL_ACC + k] = tot[k];
   S[PL_LAM] = 1e-3;
   S[PL_STOP] = (isfinite(tot[27]) && tot[27] > 0.0) ? 0.0 : 1.0;
 }
 // Cay(w) = I + 2 / (1 + w.w) ([w]x + [w]x^2), row-major in C [9] (shared with poseopt_core.h)
-FR_HD void pnp_cayley(double w0, double w1, double w2, double* C) {
+AIRFE_HD void pnp_cayley(double w0, double w1, double w2, double* C) {
   const double nn = (w0 * w0 + w1 * w1) + w2 * w2, k = 2.0 / (1.0 + nn);
   C[0] = 1.0 + k * (w0 * w0 - nn); C[1] = k * (-w2 + w0 * w1);      C[2] = k * (w1 + w0 * w2);
   C[3] = k * (w2 + w1 * w0);       C[4] = 1.0 + k * (w1 * w1 - nn); C[5] = k * (-w0 + w1 * w2);
   C[6] = k * (-w1 + w2 * w0);      C[7] = k * (w0 + w2 * w1);       C[8] = 1.0 + k * (w2 * w2 - nn);
 }
-FR_HD int pnp_uidx(int r, int c) { return r * 6 - (r * (r - 1)) / 2 + (c - r); }
+AIRFE_HD int pnp_uidx(int r, int c) { return r * 6 - (r * (r - 1)) / 2 + (c - r); }
 // (A + lambda diag(A)) delta = -g; the trial pose.  A singular system stops the refinement.
-FR_HD void pnp_lm_propose(double* S) {
+AIRFE_HD void pnp_lm_propose(double* S) {
   double* N = S + PL_AUG;
   const double lam = S[PL_LAM];
   for (int r = 0; r < 6; ++r) {
@@ -478,7 +478,7 @@ FR_HD void pnp_lm_propose(double* S) {
   for (int r = 0; r < 3; ++r) S[PL_TRY + 9 + r] = R[9 + r] + d[3 + r];
 }
 // a trial with a smaller cost is taken (lambda / 10; stop when max |delta| < FLT_EPSILON), otherwise lambda * 10
-FR_HD void pnp_lm_judge(double* S, const double* tot) {
+AIRFE_HD void pnp_lm_judge(double* S, const double* tot) {
   if (tot[27] < S[PL_ACC + 27]) {
     for (int k = 0; k < 12; ++k) S[PL_CUR + k] = S[PL_TRY + k];
     for (int k = 0; k < 28; ++k) S[PL_ACC + k] = tot[k];
@@ -491,7 +491,7 @@ FR_HD void pnp_lm_judge(double* S, const double* tot) {
   }
 }
 // Twc (16, row-major) of SolvePnPWithCV: Rwc = Rcw^T, twc = Rwc (-tcw)
-FR_HD void pnp_twc(const double* Rt, double* T) {
+AIRFE_HD void pnp_twc(const double* Rt, double* T) {
   for (int r = 0; r < 3; ++r) {
     for (int c = 0; c < 3; ++c) T[4 * r + c] = Rt[3 * c + r];
     T[4 * r + 3] = (Rt[r] * (-Rt[9]) + Rt[3 + r] * (-Rt[10])) + Rt[6 + r] * (-Rt[11]);
@@ -499,7 +499,7 @@ FR_HD void pnp_twc(const double* Rt, double* T) {
   }
   T[15] = 1.0;
 }
-FR_HD bool pnp_finite12(const double* Rt) {
+AIRFE_HD bool pnp_finite12(const double* Rt) {
   bool f = true;
   for (int k = 0; k < 12; ++k) f = f && isfinite(Rt[k]);
   return f;
@@ -507,14 +507,14 @@ FR_HD bool pnp_finite12(const double* Rt) {
 
 // ---- stereo back-projection (Frame::AddRightFeatures, src/frame.cc:141-172; Camera::BackProjectStereo, src/camera.cc:275-280) ------------------
 // cam [8] = min_x_diff, max_x_diff, max_y_diff, bf, fx, fy, cx, cy
-FR_HD bool pnp_stereo_good(float xl, float yl, float xr, float yr, const double* cam) {
+AIRFE_HD bool pnp_stereo_good(float xl, float yl, float xr, float yr, const double* cam) {
   const double dx = (double)fabsf(xl - xr), dy = (double)fabsf(yl - yr);
   if (!(dx > cam[0] && dx < cam[1] && dy <= cam[2])) return false;
   const double par = (double)(xl - xr);
   return par < cam[1] && par > cam[0];
 }
 // o = u_right, depth (bf / the float parallax), X, Y, Z (bf / the double difference x - u_right)
-FR_HD void pnp_stereo_point(float xl, float yl, float xr, const double* cam, double* o) {
+AIRFE_HD void pnp_stereo_point(float xl, float yl, float xr, const double* cam, double* o) {
   const double par = (double)(xl - xr);
   o[0] = (double)xr;
   o[1] = cam[3] / par;

@@ -8,7 +8,7 @@
 #ifndef AIRFE_POSEOPT_CORE_H_
 #define AIRFE_POSEOPT_CORE_H_
 
-#include "pnp_core.h"   // pnp_gauss, pnp_cayley, pnp_uidx, FR_HD
+#include "pnp_core.h"   // pnp_gauss, pnp_cayley, pnp_uidx, AIRFE_HD
 
 #if defined(__clang__)
 #pragma clang fp contract(off)
@@ -51,7 +51,7 @@
 #define PO_SIZE 168
 
 // Rcw = Rcb Rwb^T, tcw = tcb - Rcw twb (VIPose::Update's last lines) from wb [12] into cw [12]
-FR_HD void po_camera(const double* S, const double* wb, double* cw) {
+AIRFE_HD void po_camera(const double* S, const double* wb, double* cw) {
   const double* Rcb = S + PO_RCB;
   for (int r = 0; r < 3; ++r)
     for (int c = 0; c < 3; ++c) cw[3 * r + c] = (Rcb[3 * r] * wb[3 * c] + Rcb[3 * r + 1] * wb[3 * c + 1]) + Rcb[3 * r + 2] * wb[3 * c + 2];
@@ -59,7 +59,7 @@ FR_HD void po_camera(const double* S, const double* wb, double* cw) {
 }
 
 // Twc0 [16] row-major, Tcb [12] (Rcb row-major, tcb) or NULL = identity, cam [5], thr [2]
-FR_HD void po_init(double* S, const double* Twc0, const double* Tcb, const double* cam, const double* thr) {
+AIRFE_HD void po_init(double* S, const double* Twc0, const double* Tcb, const double* cam, const double* thr) {
   for (int k = 0; k < 9; ++k) S[PO_RCB + k] = Tcb ? Tcb[k] : ((k % 4) == 0 ? 1.0 : 0.0);
   for (int k = 0; k < 3; ++k) S[PO_TCB + k] = Tcb ? Tcb[9 + k] : 0.0;
   const double* Rcb = S + PO_RCB;
@@ -74,14 +74,14 @@ FR_HD void po_init(double* S, const double* Twc0, const double* Tcb, const doubl
   }
 }
 // every round starts from the start pose (g2o_optimization.cc:727)
-FR_HD void po_round_start(double* S) {
+AIRFE_HD void po_round_start(double* S) {
   for (int k = 0; k < 12; ++k) S[PO_WB + k] = S[PO_WB0 + k];
   po_camera(S, S + PO_WB, S + PO_CUR);
   S[PO_STOP] = 0.0;
 }
 
 // the error of constraint i at the pose Rt (Rcw, tcw): e [3] (e[2] = 0 for a mono edge), Xc [3], 1/z; returns chi2 = e.e; *stereo = u_right > 0
-FR_HD double po_error(const double* Rt, const double* S, const double* cons, int i, double* e, double* Xc, double* izp, bool* stereo) {
+AIRFE_HD double po_error(const double* Rt, const double* S, const double* cons, int i, double* e, double* Xc, double* izp, bool* stereo) {
   const double X = PO_C(cons, 0, i), Y = PO_C(cons, 1, i), Z = PO_C(cons, 2, i);
   const double x = PO_C(cons, 3, i), y = PO_C(cons, 4, i), ur = PO_C(cons, 5, i);
   const double xc = Rt[0] * X + Rt[1] * Y + Rt[2] * Z + Rt[9];
@@ -99,26 +99,26 @@ FR_HD double po_error(const double* Rt, const double* S, const double* cons, int
   *stereo = st;
   return (e0 * e0 + e1 * e1) + e2 * e2;
 }
-FR_HD double po_chi2(const double* Rt, const double* S, const double* cons, int i, bool* stereo) {
+AIRFE_HD double po_chi2(const double* Rt, const double* S, const double* cons, int i, bool* stereo) {
   double e[3], Xc[3], iz;
   return po_error(Rt, S, cons, i, e, Xc, &iz, stereo);
 }
 // g2o's RobustKernelHuber: rho and its derivative w
-FR_HD double po_huber(double chi2, double delta, double* w) {
+AIRFE_HD double po_huber(double chi2, double delta, double* w) {
   if (chi2 <= delta * delta) { *w = 1.0; return chi2; }
   const double s = sqrt(chi2);
   *w = delta / s;
   return 2.0 * s * delta - delta * delta;
 }
 // the robust chi of constraint i alone (a trial's cost)
-FR_HD double po_edge_chi(const double* Rt, const double* S, const double* cons, int i) {
+AIRFE_HD double po_edge_chi(const double* Rt, const double* S, const double* cons, int i) {
   bool st;
   double w;
   const double chi2 = po_chi2(Rt, S, cons, i, &st);
   return po_huber(chi2, S[PO_DEL + (st ? 1 : 0)], &w);
 }
 // acc [28] += w J^T J (21), w J^T e (6), rho of constraint i at the pose Rt.  J = P Rcb [ -[Xb]x | I ] (3 x 6; the third row is zero for a mono edge)
-FR_HD void po_edge_full(const double* Rt, const double* S, const double* cons, int i, double* acc) {
+AIRFE_HD void po_edge_full(const double* Rt, const double* S, const double* cons, int i, double* acc) {
   double e[3], Xc[3], iz, w;
   bool st;
   const double chi2 = po_error(Rt, S, cons, i, e, Xc, &iz, &st);
@@ -165,7 +165,7 @@ FR_HD void po_edge_full(const double* Rt, const double* S, const double* cons, i
   acc[27] = acc[27] + rho;
 }
 // the 64 partials p[l * stride] added in lane order
-FR_HD double po_sum_lanes(const double* p, int stride) {
+AIRFE_HD double po_sum_lanes(const double* p, int stride) {
   double s = 0.0;
   for (int l = 0; l < PO_LANES; ++l) s = s + p[l * stride];
   return s;
@@ -173,7 +173,7 @@ FR_HD double po_sum_lanes(const double* p, int stride) {
 
 // ---- g2o's OptimizationAlgorithmLevenberg::solve, one iteration split at its cost evaluations ------------------------------------------------------
 // tot [28]: the sums at the current pose
-FR_HD void po_iter_begin(double* S, const double* tot, int it) {
+AIRFE_HD void po_iter_begin(double* S, const double* tot, int it) {
   for (int k = 0; k < 28; ++k) S[PO_ACC + k] = tot[k];
   if (it == 0) {
     double mx = 0.0;
@@ -188,7 +188,7 @@ FR_HD void po_iter_begin(double* S, const double* tot, int it) {
   S[PO_NEXT] = 0.0;
 }
 // (H + lambda I) dx = b; the trial pose Rwb Cay(dr / 2), twb + Rwb dt.  A failed solve leaves dx = 0 and PO_OK = 0.
-FR_HD void po_propose(double* S) {
+AIRFE_HD void po_propose(double* S) {
   double* N = S + PO_AUG;
   const double lam = S[PO_LAM];
   for (int r = 0; r < 6; ++r) {
@@ -214,7 +214,7 @@ FR_HD void po_propose(double* S) {
   po_camera(S, T, S + PO_TRY);
 }
 // the trial's verdict.  chi_new: the robust chi at the trial pose
-FR_HD void po_judge(double* S, double chi_new) {
+AIRFE_HD void po_judge(double* S, double chi_new) {
   if (S[PO_OK] == 0.0) chi_new = INFINITY;
   const double lam = S[PO_LAM];
   const double* d = S + PO_DX;
@@ -246,20 +246,18 @@ FR_HD void po_judge(double* S, double chi_new) {
   }
 }
 // outlier (level 1) iff the chi2, rounded to float, exceeds the threshold
-FR_HD bool po_outlier(const double* Rt, const double* S, const double* cons, int i) {
+AIRFE_HD bool po_outlier(const double* Rt, const double* S, const double* cons, int i) {
   bool st;
   const double chi2 = po_chi2(Rt, S, cons, i, &st);
   return (double)(float)chi2 > S[PO_THR + (st ? 1 : 0)];
 }
-FR_HD bool po_finite12(const double* p) {
+AIRFE_HD bool po_finite12(const double* p) {
   bool f = true;
   for (int k = 0; k < 12; ++k) f = f && isfinite(p[k]);
   return f;
 }
-// an output NaN is the canonical quiet NaN (payload and sign of a computed NaN differ between processors)
-FR_HD double po_canon(double v) { return v != v ? __builtin_nan("") : v; }
 // Twc = Twb Tbc (16, row-major) of the current pose
-FR_HD void po_twc(const double* S, double* T) {
+AIRFE_HD void po_twc(const double* S, double* T) {
   const double* W = S + PO_WB;
   const double* Rcb = S + PO_RCB;
   for (int r = 0; r < 3; ++r) {
@@ -271,7 +269,7 @@ FR_HD void po_twc(const double* S, double* T) {
 }
 
 // ---- the tracking composite's seed (map_builder.cc:310-314): the PnP pose, or the last tracked pose when it jumps > 1 m or has too few inliers ------
-FR_HD bool po_use_last(const double* Tpnp, int pnp_count, double lx, double ly, double lz, int lost_num_match) {
+AIRFE_HD bool po_use_last(const double* Tpnp, int pnp_count, double lx, double ly, double lz, int lost_num_match) {
   const double dx = Tpnp[3] - lx, dy = Tpnp[7] - ly, dz = Tpnp[11] - lz;
   return sqrt((dx * dx + dy * dy) + dz * dz) > 1.0 || pnp_count < lost_num_match;
 }
@@ -334,7 +332,7 @@ inline int poseopt_solve_host(const double* X, const double* obs, int n, const d
     po_round_start(S);
   }
   if (Rt)
-    for (int k = 0; k < 12; ++k) Rt[k] = po_canon(S[PO_CUR + k]);
+    for (int k = 0; k < 12; ++k) Rt[k] = canon_nan(S[PO_CUR + k]);
   for (int i = 0; i < n; ++i) inlier[i] = (good && !lvl[i]) ? 1 : 0;
   *num = good ? n - outliers : 0;
   return rounds;

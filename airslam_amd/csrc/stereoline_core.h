@@ -10,11 +10,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define SL_HD __host__ __device__ inline
-#else
-#define SL_HD inline
-#endif
+#include "core_common.h"
 
 // The reference's gate is |atan(dy / dx)| < 0.175; an atan evaluated by two libms is two functions.  atan is monotone, so the gate is |dy / dx| < t with
 // t the smallest double whose atan is >= 0.175: 0x1.6a1aa2e1bef6fp-3 (= tan(0.175) rounded; tests/test_stereoline_cpu.py finds it again by bisection on
@@ -31,21 +27,19 @@ enum {
   SL_SHORT = 5                        // triangulated, |p2 - p1| < 0.01 (:317): endpoints set, no Pluecker line
 };
 
-// the frame's line count as every reader clamps it
-SL_HD int sl_rows(int n, int cap) { return n < 0 ? 0 : (n > cap ? cap : n); }
 
 // frame.cc:186 — `> 0` is the reference's: a match to right line 0 is dropped.  r >= nr (a stale index) is invalid and never indexes memory.
-SL_HD bool sl_right_valid(int r, int nr) { return r > 0 && r < nr; }
+AIRFE_HD bool sl_right_valid(int r, int nr) { return r > 0 && r < nr; }
 
 // line_processor.cc:210-211 / :215-216.  dx == 0: dy / dx = +-inf, not below the gate (atan = +-pi/2); dx == dy == 0: NaN, already horizontal by |dy| <= 3.
-SL_HD bool sl_horizontal(double dx, double dy) { return fabs(dy) <= 3.0 || fabs(dy / dx) < SL_TAN_GATE; }
+AIRFE_HD bool sl_horizontal(double dx, double dy) { return fabs(dy) <= 3.0 || fabs(dy / dx) < SL_TAN_GATE; }
 
-SL_HD void sl_nan(double* v, int n) {
-  for (int k = 0; k < n; ++k) v[k] = __builtin_nan("");
+AIRFE_HD void sl_nan(double* v, int n) {
+  for (int k = 0; k < n; ++k) v[k] = quiet_nan();
 }
 
 // Camera::BackProjectStereo on (x, y, x_right): ((x - cx) fx_inv, (y - cy) fy_inv, 1) * (bf / (x - x_right))
-SL_HD void sl_back_project(double x, double y, double x_right, double bf, double fx_inv, double fy_inv, double cx, double cy, double* p) {
+AIRFE_HD void sl_back_project(double x, double y, double x_right, double bf, double fx_inv, double fy_inv, double cx, double cy, double* p) {
   const double d = bf / (x - x_right);
   p[0] = ((x - cx) * fx_inv) * d;
   p[1] = ((y - cy) * fy_inv) * d;
@@ -53,7 +47,7 @@ SL_HD void sl_back_project(double x, double y, double x_right, double bf, double
 }
 
 // Rwc p + twc, Twc row-major [16]: each row ((r0 x + r1 y) + r2 z) + t.  Twc == nullptr: p stays as it is, nothing is multiplied.
-SL_HD void sl_to_world(const double* Twc, double* p) {
+AIRFE_HD void sl_to_world(const double* Twc, double* p) {
   if (!Twc) return;
   const double x = p[0], y = p[1], z = p[2];
   for (int r = 0; r < 3; ++r) p[r] = ((Twc[4 * r] * x + Twc[4 * r + 1] * y) + Twc[4 * r + 2] * z) + Twc[4 * r + 3];
@@ -61,7 +55,7 @@ SL_HD void sl_to_world(const double* Twc, double* p) {
 
 // ComputeLine3DFromEndpoints with g2o::Line3D::fromCartesian written out (the formula here is the contract): l = p2 - p1, d = l / |l|,
 // p = p1 - d (d . p1), w = p x (p + d); plucker = (w, d).  false (and NaN) when |l| < 0.01.
-SL_HD bool sl_plucker(const double* e, double* plucker) {
+AIRFE_HD bool sl_plucker(const double* e, double* plucker) {
   const double lx = e[3] - e[0], ly = e[4] - e[1], lz = e[5] - e[2];
   const double n = sqrt((lx * lx + ly * ly) + lz * lz);
   if (n < SL_MIN_LENGTH) {
@@ -81,7 +75,7 @@ SL_HD bool sl_plucker(const double* e, double* plucker) {
 
 // One left line with its selected right line.  cam [8] = min_x_diff, max_x_diff, max_y_diff (unused), bf, fx, fy, cx, cy.  endpoints [6] and
 // plucker [6] are always written (NaN where the status says they are not set).  Returns the status.
-SL_HD int sl_line(const double* cam, const double* left, const double* right, bool valid, const double* Twc, double* endpoints, double* plucker) {
+AIRFE_HD int sl_line(const double* cam, const double* left, const double* right, bool valid, const double* Twc, double* endpoints, double* plucker) {
   sl_nan(endpoints, 6);
   sl_nan(plucker, 6);
   if (!valid) return SL_NO_RIGHT;
@@ -106,7 +100,7 @@ SL_HD int sl_line(const double* cam, const double* left, const double* right, bo
 }
 
 // Line i of a frame: selection (frame.cc:185-191), then sl_line.  sel [4], *flag, *status, endpoints [6], plucker [6] are this line's slots.
-SL_HD int sl_frame_line(const double* cam, const double* lines_left, const double* lines_right, int nr, const int32_t* matches, const double* Twc, int i,
+AIRFE_HD int sl_frame_line(const double* cam, const double* lines_left, const double* lines_right, int nr, const int32_t* matches, const double* Twc, int i,
                         double* sel, uint8_t* flag, int32_t* status, double* endpoints, double* plucker) {
   const int r = matches[i];
   const bool valid = sl_right_valid(r, nr);

@@ -3,7 +3,7 @@
 // and the device: the kernels (kernels_triangulate.hip) call the routines below from their lanes, triangulate_build_host at the end calls them in loops;
 // tests/triangulate_ref.py restates the same in plain Python floats.  Doubles, every sum sequential in the order written, no fused multiply-adds (the
 // translation units that include this header are compiled with -ffp-contract=off).
-//   observers     valid(f, i) as in covis_core.h (cv_rows, cv_row_id).  The observation of point m in frame f is the FIRST row i of f with valid(f, i)
+//   observers     valid(f, i) as in covis_core.h (clamp_count, cv_row_id).  The observation of point m in frame f is the FIRST row i of f with valid(f, i)
 //                 and id m (cv_first_occurrence).  STATED DIFFERENCE: the reference keeps the last AddObverser per frame.  Observers are taken in
 //                 ascending frame index (the reference's std::map order); nobs[m] is their number.
 //   per observer  fxi = 1.0 / fx, fyi = 1.0 / fy (Camera::BackProjectMono, camera.cc:268-273); R, c = rotation and translation of the frame's stored Twc
@@ -33,19 +33,16 @@
 
 #include "covis_core.h"
 
-#define TR_HD CV_HD
 #define TR_MAX_FRAMES CV_MAX_FRAMES  // frames a triangulation handles: (frame, row) packs as f * cap + i into an int32 at 4096 frames x 1024 rows
 #define TR_RANK_TOL 1e-5             // kRankLossTolerance (map.cc:406)
 #define TR_TINY 2.2250738585072014e-308   // std::numeric_limits<double>::min(): makeHouseholder's threshold on the tail's squared norm
 
 enum { TR_NONE = -1, TR_OK = 0, TR_FEW = 1, TR_RANK = 2, TR_BAD = 3 };
 
-TR_HD bool tr_finite(double v) { return v - v == 0.0; }
-TR_HD double tr_nan() { return __builtin_nan(""); }
 
 // cam = fx, fy, cx, cy -> cami = fxi, fyi, cx, cy; false when fx or fy is zero or not finite
-TR_HD bool tr_cam(const double* cam, double* cami) {
-  if (!tr_finite(cam[0]) || !tr_finite(cam[1]) || cam[0] == 0.0 || cam[1] == 0.0) return false;
+AIRFE_HD bool tr_cam(const double* cam, double* cami) {
+  if (!is_finite(cam[0]) || !is_finite(cam[1]) || cam[0] == 0.0 || cam[1] == 0.0) return false;
   cami[0] = 1.0 / cam[0]; cami[1] = 1.0 / cam[1]; cami[2] = cam[2]; cami[3] = cam[3];
   return true;
 }
@@ -55,7 +52,7 @@ struct TrAcc {
   int bad;
 };
 
-TR_HD void tr_acc_init(TrAcc* a) {
+AIRFE_HD void tr_acc_init(TrAcc* a) {
 #pragma unroll
   for (int k = 0; k < 9; ++k) a->M[k] = 0.0;
 #pragma unroll
@@ -64,18 +61,18 @@ TR_HD void tr_acc_init(TrAcc* a) {
 }
 
 // one observer: keypoint (x, y) of a frame whose stored pose is T (Twc, row-major 4 x 4; row 3 is not read)
-TR_HD void tr_acc_add(TrAcc* a, const double* cami, float x, float y, const double* T) {
+AIRFE_HD void tr_acc_add(TrAcc* a, const double* cami, float x, float y, const double* T) {
   const double b0 = ((double)x - cami[2]) * cami[0], b1 = ((double)y - cami[3]) * cami[1], b2 = 1.0;
   double v[3], c[3], w[3];
-  bool ok = tr_finite((double)x) && tr_finite((double)y);
+  bool ok = is_finite((double)x) && is_finite((double)y);
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
-    ok = ok && tr_finite(T[4 * r]) && tr_finite(T[4 * r + 1]) && tr_finite(T[4 * r + 2]) && tr_finite(T[4 * r + 3]);
+    ok = ok && is_finite(T[4 * r]) && is_finite(T[4 * r + 1]) && is_finite(T[4 * r + 2]) && is_finite(T[4 * r + 3]);
     v[r] = (T[4 * r] * b0 + T[4 * r + 1] * b1) + T[4 * r + 2] * b2;
     c[r] = T[4 * r + 3];
   }
   const double s = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
-  ok = ok && tr_finite(s) && s != 0.0;
+  ok = ok && is_finite(s) && s != 0.0;
   const double inv = 1.0 / s;
   const double d = (v[0] * c[0] + v[1] * c[1]) + v[2] * c[2];
 #pragma unroll
@@ -92,7 +89,7 @@ TR_HD void tr_acc_add(TrAcc* a, const double* cami, float x, float y, const doub
 
 // A (row-major 3 x 3), rhs -> the rank by the 1e-5 rule; x only with rank 3; rdiag [3] = R's diagonal (or nullptr).  Every index below is a constant:
 // the arrays live in registers on the device.
-TR_HD int tr_qr_solve(const double* A, const double* rhs, double* x, double* rdiag) {
+AIRFE_HD int tr_qr_solve(const double* A, const double* rhs, double* x, double* rdiag) {
   double a[9], c[3];
   int perm[3] = {0, 1, 2};
 #pragma unroll
@@ -189,8 +186,8 @@ TR_HD int tr_qr_solve(const double* A, const double* rhs, double* x, double* rdi
 }
 
 // the accumulators of nobs observers -> the status; xyz [3] = the point, or NaN
-TR_HD int tr_finish(const TrAcc* a, int nobs, int min_observers, double* xyz) {
-  xyz[0] = xyz[1] = xyz[2] = tr_nan();
+AIRFE_HD int tr_finish(const TrAcc* a, int nobs, int min_observers, double* xyz) {
+  xyz[0] = xyz[1] = xyz[2] = quiet_nan();
   if (nobs <= 0) return TR_NONE;
   if (nobs < (min_observers > 2 ? min_observers : 2)) return TR_FEW;
   if (a->bad) return TR_BAD;
@@ -202,20 +199,20 @@ TR_HD int tr_finish(const TrAcc* a, int nobs, int min_observers, double* xyz) {
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
       A[3 * r + q] = (r == q ? n : 0.0) - a->M[3 * r + q];
-      ok = ok && tr_finite(A[3 * r + q]);
+      ok = ok && is_finite(A[3 * r + q]);
     }
     rhs[r] = a->C[r] - a->g[r];
-    ok = ok && tr_finite(rhs[r]);
+    ok = ok && is_finite(rhs[r]);
   }
   if (!ok) return TR_BAD;
   if (tr_qr_solve(A, rhs, x, nullptr) < 3) return TR_RANK;
-  if (!(tr_finite(x[0]) && tr_finite(x[1]) && tr_finite(x[2]))) return TR_BAD;
+  if (!(is_finite(x[0]) && is_finite(x[1]) && is_finite(x[2]))) return TR_BAD;
   xyz[0] = x[0]; xyz[1] = x[1]; xyz[2] = x[2];
   return TR_OK;
 }
 
 // info i32 [4]: points ok, points observed (status != -1), points of status 2, points of status 3
-TR_HD void tr_info_flags(int status, int* f) {
+AIRFE_HD void tr_info_flags(int status, int* f) {
   f[0] = status == TR_OK; f[1] = status != TR_NONE; f[2] = status == TR_RANK; f[3] = status == TR_BAD;
 }
 
@@ -238,7 +235,7 @@ inline void triangulate_build_host(const float* feat, int feat_dim, const int* n
     nobs[m] = 0;
   }
   for (int f = 0; f < size; ++f) {                                  // ascending frame index = observer order
-    const int nf = cv_rows(n[f], cap);
+    const int nf = clamp_count(n[f], cap);
     for (int i = 0; i < cap; ++i) {
       int ig;
       ids[i] = cv_row_id(point_id + (size_t)f * cap, i, nf, max_points, &ig);

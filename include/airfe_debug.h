@@ -370,6 +370,18 @@ int airfe_debug_trace_buffer(airfe_ctx* ctx, int slot, void* host, size_t bytes)
 int airfe_debug_trace_slots(airfe_ctx* ctx);
 int airfe_debug_trace_slot(airfe_ctx* ctx, int i, char* name, int name_cap, unsigned* off, unsigned* units, unsigned* unit_words);
 int airfe_debug_trace_read(airfe_ctx* ctx, void* stream, unsigned long long* digests, unsigned long long* table);
+/* ---- the kernels' workgroup primitives (csrc/wg_prims.h) alone, in ONE workgroup of `threads` (64, 256 or 1024) threads (tests/test_gpu_wg_prims.py).  The workgroup
+ * walks v [n] and keep [n] (0 / 1) in rounds of `threads` with a running base, as the production loops do: scan [n] = the exclusive prefix sum of v, pos [n] = the kept
+ * entries before each entry; totals [5] = sum of v by the scan, kept entries, then block_sum / block_max / block_min of v (INT32_MIN / INT32_MAX when n = 0); wave
+ * [threads / 64][3] = wave_sum / wave_max / wave_min of the first round's values, 0 past n.  keys [P] (key_bytes 4 or 8, unsigned; P = 0 or a power of two with
+ * P * key_bytes <= 32768) come back ascending in sorted [P]. */
+typedef struct airfe_debug_wg_prims_args {
+  const int32_t* v; const uint8_t* keep; int n, threads;
+  const void* keys; int P, key_bytes;
+  int32_t *scan, *pos, *totals, *wave;       /* out */
+  void* sorted;                              /* out */
+} airfe_debug_wg_prims_args;
+int airfe_debug_wg_prims(airfe_ctx* ctx, airfe_debug_wg_prims_args* a);
 
 #ifdef __cplusplus
 }

@@ -94,6 +94,22 @@ def test_wave_and_workgroup_tails(size):
     db.close()
 
 
+@pytest.mark.parametrize("tiles", [257, 513])
+def test_more_scan_tiles_than_one_round_of_the_tile_scan(tiles):
+    """max_points of 257 / 513 segment-start tiles (2048 points each): the one workgroup that turns the tile sums into tile offsets walks them in rounds of
+    256 with a running base, and its last round ends one tile into a wave.  Ids in the first tile, on both sides of the round's border and in the last tile."""
+    P = tiles * 2048 - 1
+    frames, cap = 6, 16
+    marks = np.array([0, 1, 2047, 2048, 255 * 2048 + 7, 256 * 2048 - 1, 256 * 2048, 256 * 2048 + 1, P // 2, P - 2048, P - 2, P - 1, P, -1], np.int64)
+    ids = marks[np.random.default_rng(tiles).integers(0, len(marks), size=(frames, cap))].astype(np.int32)
+    n = np.full(frames, cap, np.int32)
+    want = cr.build(ids, n, frames, frames, P)
+    db = _db(ids, n, frames, frames, P, want[3][1])
+    got = _build(db, want[3][1])
+    assert want[3][1] > frames and _same(got, want), (tiles, got[3], want[3])
+    db.close()
+
+
 def test_one_point_seen_by_300_frames():
     """a segment longer than a wave and than a workgroup: every frame's only row holds point 5, so every row is 300 entries of weight 1"""
     frames, cap = 300, 8

@@ -16,6 +16,7 @@ from planted import features, planted_pair
 
 pytestmark = pytest.mark.gpu
 CAP = 400
+PLANTED = (380, 360)         # keypoints of query 0 and of every revisit: about half of the smaller count come back as matches
 CAM = np.array(po.CAM_EUROC)
 THR = np.array(po.THR_EUROC)
 K = 5
@@ -170,6 +171,31 @@ def test_stored_query_equals_incremental_growth():
     db.close()
 
 
+def test_stored_query_over_more_frames_than_one_round_of_the_prefix_walk():
+    """514 stored frames of 16 .. 20 words out of 24 (any two share about 13, so most of a prefix passes the threshold): the select kernel walks the prefix
+    0 .. fq - 1 in rounds of 256 with a running base.  fq = 257 and 513 end one frame into a wave, 256 and 512 on a round's border; 300 inside the second."""
+    rng = np.random.default_rng(514)
+    N = 514
+    vecs = []
+    for f in range(N):
+        w = sorted(int(x) * 37 + 5 for x in rng.choice(24, size=int(rng.integers(16, 21)), replace=False))
+        vecs.append(br.frame_to_bow(w, rng.uniform(0.1, 1.0, len(w))))
+    csr = bc.csr(N, {f: sorted((int(g), int(rng.integers(1, 40))) for g in rng.choice(N, size=6, replace=False)) for f in range(N)})
+    covis = lr.covisible_sets(csr[0], csr[1], N)
+    db = _vector_db(vecs, csr, N)
+    qf = [256, 257, 300, 512, 513]
+    for excl in (False, True):
+        want = lr.stored_queries(vecs, qf, 0.5, 8, covis if excl else None)
+        got = _stored(db, qf, N, excl)
+        for q in range(len(qf)):
+            assert _key(got, q, N) == _want_key(want[q], N, N), (excl, qf[q])
+        assert len(want[1]["cands"]) > 128 and len(want[4]["cands"]) > 256          # the kept entries of a later round land behind a base above a round
+    small = _stored(db, qf, 200, True)                                              # ccap inside the first round: the later rounds write nothing
+    for q in range(len(qf)):
+        assert _key(small, q, 200) == _want_key(want[q], 200, N), qf[q]
+    db.close()
+
+
 # ---- the tables -------------------------------------------------------------------------------------------------------------------------------------
 def _loop_buffers(Q):
     import torch
@@ -265,7 +291,7 @@ def _scene(share=0.7):
         poses[f] = _T(pr.rotation(rng.normal(size=3), rng.uniform(0.0, 20.0)), (25.0 * f, rng.uniform(-1, 1), rng.uniform(-1, 1)))
     rel, kinds = [], []
     for j in range(Q):
-        a, b = planted_pair(380 - 20 * j, 360, 70 + 10 * j)
+        a, b = planted_pair(PLANTED[0] - 20 * j, PLANTED[1], 70 + 10 * j)
         fq, f = 8 + j, 2 * j + 1
         dbf[fq, :len(a)], dn[fq] = a, len(a)
         dbf[f], dn[f] = 0, len(b)
@@ -421,6 +447,24 @@ def test_composite_equals_the_steps_done_by_hand():
     for q in (0, 3):
         one = _composite(db, qf[q:q + 1])
         assert _qkey(one, 0) == _qkey(got, q), q
+    db.close()
+
+
+def test_composite_with_lists_longer_than_one_round_of_the_gather(monkeypatch):
+    """The scene at capacity 640 with 620 .. 560 x 600 keypoints: the loop frames' lists hold close to 300 entries, so loopdet_gather_kernel walks them in two
+    rounds of 256 with a running base and its last round ends inside a wave.  (Three rounds would need more than 512 entries: the planted recipe gives at most
+    half of max_keypoints <= 1024.)"""
+    import sys
+    me = sys.modules[__name__]
+    monkeypatch.setattr(me, "CAP", 640)
+    monkeypatch.setattr(me, "PLANTED", (620, 600))
+    monkeypatch.setattr(me, "_S", {})
+    s = _scene()
+    db = _scene_db(s)
+    got = _composite(db, s["qframes"])
+    _assert_equal(got, _by_hand(db, s, s["qframes"]), s["Q"], "long lists")
+    print("nmatch", got["nmatch"].tolist(), "ncons", got["ncons"].tolist())
+    assert (got["nmatch"] > 256).all() and (got["nmatch"] % 64 != 0).all() and got["stage"].tolist() == [0] * 4 and (got["ncons"] > 128).all()
     db.close()
 
 

@@ -13,6 +13,7 @@ from planted import features, planted_pair
 
 pytestmark = pytest.mark.gpu
 CAP = 400
+PLANTED = (380, 360)         # keypoints of query 0 and of every revisit: about half of the smaller count come back as matches
 CAM = np.array(po.CAM_EUROC)
 THR = np.array(po.THR_EUROC)
 MIN_INLIER = 20
@@ -158,7 +159,7 @@ def _scene():
         xyz[f, :k] = rng.uniform(-5, 5, (k, 3)) + (0, 0, 8)
     motions, kinds = [], []
     for q in range(Q):
-        a, b = planted_pair(380 - 20 * q, 360, 70 + 10 * q)
+        a, b = planted_pair(PLANTED[0] - 20 * q, PLANTED[1], 70 + 10 * q)
         qf[q, :len(a)], qn[q] = a, len(a)
         f = 2 * q + 1
         dbf[f], dn[f] = 0, len(b)
@@ -325,6 +326,24 @@ def test_composite_equals_the_steps_done_by_hand(refine):
     for q in (0, 3):
         one = _composite(db, s["qf"][q:q + 1], s["qn"][q:q + 1], refine)
         assert _key(one, 0) == _key(got, q), q
+    db.close()
+
+
+def test_composite_with_lists_longer_than_one_round_of_the_gather(monkeypatch):
+    """The scene at capacity 640 with 620 .. 560 x 600 keypoints: the winners' lists hold close to 300 entries, so reloc_gather_kernel walks them in two rounds
+    of 256 with a running base and its last round ends inside a wave.  (Three rounds would need more than 512 entries: the planted recipe gives at most half of
+    max_keypoints <= 1024.)"""
+    import sys
+    me = sys.modules[__name__]
+    monkeypatch.setattr(me, "CAP", 640)
+    monkeypatch.setattr(me, "PLANTED", (620, 600))
+    monkeypatch.setattr(me, "_S", {})
+    s = _scene()
+    db = _scene_db()
+    got = _composite(db, s["qf"], s["qn"], True)
+    _assert_equal(got, _by_hand(db, s["qf"], s["qn"], s["xyz"], True), s["Q"], "long lists")
+    print("nmatch", got["nmatch"].tolist(), "pnp", got["pnp_count"].tolist())
+    assert (got["nmatch"] > 256).all() and (got["nmatch"] % 64 != 0).all() and got["stage"].tolist() == [0] * 4 and (got["pnp_count"] > 128).all()
     db.close()
 
 

@@ -26,7 +26,7 @@ int main() {
   auto n = block<int>(frames);
   for (int r = 0; r < frames * cap; ++r) {
     ids[r] = -1;
-    xyz[3 * r] = xyz[3 * r + 1] = xyz[3 * r + 2] = mg_nan();
+    xyz[3 * r] = xyz[3 * r + 1] = xyz[3 * r + 2] = quiet_nan();
     feat[3 * r] = 0.f; feat[3 * r + 1] = 20.f + 7.f * (r % 11); feat[3 * r + 2] = 15.f + 5.f * (r % 13);
   }
   const int counts[frames] = {8, 8, 5, 8, 0, 8};

@@ -51,7 +51,7 @@ extern "C" int host_pairs(int32_t* point_id, double* xyz, const float* feat, con
   for (int k = 0; k < 4; ++k) l.cam[k] = cam[k];
   int P = 0;
   for (int q = 0; q < Q; ++q)
-    for (int e = 0, ne = mg_entries(nmatch[q], mcap); e < ne && stage[q] == 0; ++e) {
+    for (int e = 0, ne = clamp_count(nmatch[q], mcap); e < ne && stage[q] == 0; ++e) {
       int A, B, row;
       if (mg_entry(t, l, q, e, &A, &B, &row) == MG_PAIR) { pairs[2 * P] = A; pairs[2 * P + 1] = B; ++P; }
     }

@@ -41,7 +41,7 @@ extern "C" int host_fill(const int* n, const int32_t* point_id, int size, int ca
                          double* points) {
   int written = 0;
   for (int f = 0; f < size; ++f) {
-    const int nf = cv_rows(n[f], cap);
+    const int nf = clamp_count(n[f], cap);
     for (int i = 0; i < nf; ++i) {
       int ig;
       const int m = cv_row_id(point_id + (size_t)f * cap, i, nf, max_points, &ig);
