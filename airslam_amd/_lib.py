@@ -108,6 +108,12 @@ class DebugLgAssignArgs(C.Structure):
                 + [(n, C.c_void_p) for n in ("pad", "z", "sim", "scores", "rowlse", "collse", "rowval", "rowarg", "colarg", "idx", "score", "nmatch")])
 
 
+class DebugSgFrontArgs(C.Structure):
+    """airfe_debug_sg_front_args (include/airfe_debug.h)"""
+    _fields_ = ([(n, C.c_int) for n in ("prec", "split", "B", "cap", "normalize")] + [(n, C.c_void_p) for n in ("f0", "f1", "n0", "n1")] + [("rows", C.c_int)]
+                + [(n, C.c_void_p) for n in ("lens", "x32", "xb", "h128", "hb")] + [("rows_past", C.c_int)])
+
+
 class DebugAttentionArgs(C.Structure):
     """airfe_debug_attn_args (include/airfe_debug.h)"""
     _fields_ = ([(n, C.c_int) for n in ("prec", "S", "H", "n", "cross")] + [(n, C.c_void_p) for n in ("q", "k", "v", "lens")]
@@ -319,6 +325,7 @@ SIGNATURES = {
     "airfe_debug_s0_decode": (C.c_int, [C.c_void_p, C.POINTER(DebugS0DecodeArgs)]),
     "airfe_debug_lg_prepare": (C.c_int, [C.c_void_p, C.POINTER(DebugLgPrepareArgs)]),
     "airfe_debug_lg_assign": (C.c_int, [C.c_void_p, C.POINTER(DebugLgAssignArgs)]),
+    "airfe_debug_sg_front": (C.c_int, [C.c_void_p, C.POINTER(DebugSgFrontArgs)]),
     "airfe_debug_plnet_stage0": (C.c_int, [C.c_void_p] + [C.c_void_p] * 10),
     "airfe_debug_plnet_s1": (C.c_int, [C.c_void_p, C.POINTER(Stage0), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "airfe_debug_plnet_s1_last": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),

@@ -459,6 +459,25 @@ class Context:
         out["rows_past"], out["Np"] = int(a.rows_past), self.np_rows
         return out
 
+    def debug_sg_front(self, f0, f1, n0, n1, prec, split, normalize=0):
+        """SuperGlue's front alone (include/airfe_debug.h, airfe_debug_sg_front): f0 / f1 [B, cap, 259] host rows (score, x, y, descriptor), n0 / n1 [B]; prec the
+        context's 2-byte type (1 under a fp32 context); split 1 = the keypoint encoder's large layers as GEMMs.  -> dict lens [2B], x32, xb [rows, 256] and, split,
+        h128 [rows, 128], hb [rows, 256] (rows = M rounded up to 128, M = 2 B Np), rows_past, Np, M."""
+        f0, f1 = np.ascontiguousarray(f0, np.float32), np.ascontiguousarray(f1, np.float32)
+        n0, n1 = np.ascontiguousarray(n0, np.int32), np.ascontiguousarray(n1, np.int32)
+        b, cap, ld = f0.shape
+        assert ld == FEAT and f1.shape == f0.shape and n0.shape == (b,) and n1.shape == (b,)
+        m = 2 * b * self.np_rows
+        rows = (m + 127) // 128 * 128
+        out = {"lens": np.empty((2 * b,), np.int32), "x32": np.empty((rows, 256), np.float32), "xb": np.empty((rows, 256), np.float32)}
+        if split:
+            out["h128"], out["hb"] = np.empty((rows, 128), np.float32), np.empty((rows, 256), np.float32)
+        a = _lib.DebugSgFrontArgs(prec=int(prec), split=int(split), B=b, cap=cap, normalize=int(normalize), f0=f0.ctypes.data, f1=f1.ctypes.data, n0=n0.ctypes.data,
+                                  n1=n1.ctypes.data, rows=rows, **{k: v.ctypes.data for k, v in out.items()})
+        self._chk(self._l.airfe_debug_sg_front(self._h, C.byref(a)), "airfe_debug_sg_front")
+        out["rows_past"], out["Np"], out["M"] = int(a.rows_past), self.np_rows, m
+        return out
+
     def debug_lg_assign(self, md, x32, lens, w, b, prec, form, cap=None, thr=0.1, pad=None):
         """rowdot256 + the assignment tail alone (include/airfe_debug.h, airfe_debug_lg_assign): md, x32 [2B, n, 256], lens [2B] (0 allowed), w [256], b; form 0 the
         similarity matrix + launch_lg_assign, 1 launch_lg_assign_fused.  -> dict z [2B, n], sim, scores [B, n, n], rowlse, collse, rowval, rowarg, colarg [B, n],

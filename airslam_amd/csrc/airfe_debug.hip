@@ -692,6 +692,51 @@ int airfe_debug_lg_assign(airfe_ctx* c, airfe_debug_lg_assign_args* a) try {
   return s.wait();
 } AIRFE_CATCH(c)
 
+/* ---- SuperGlue's front alone: sg_front_dev, the statement superglue_dev runs (include/airfe_debug.h; tests/test_gpu_sg_front.py) */
+int airfe_debug_sg_front(airfe_ctx* c, airfe_debug_sg_front_args* a) try {
+  AIRFE_ENTER(c);
+  if (!c->has_sg) return fail(c, "debug_sg_front: SuperGlue not loaded");
+  if (!a || !a->f0 || !a->f1 || !a->n0 || !a->n1 || !a->lens || !a->x32 || !a->xb || (a->split && (!a->h128 || !a->hb))) return fail(c, "debug_sg_front: null argument");
+  const int Np = c->Np, B = a->B, cap = a->cap, prec = a->prec, split = a->split;
+  if ((prec != 0 && prec != 1) || (split != 0 && split != 1) || B < 1 || B > c->Pmax || cap < 1 || cap > Np)
+    return fail(c, "debug_sg_front: bad argument (prec 0 / 1, split 0 / 1, 1 <= B <= max_batch, 1 <= cap <= Np)");
+  if (prec != (c->mprec == 2 ? 1 : c->mprec) || (split && c->mprec == 2))
+    return fail(c, "debug_sg_front: prec must be the context's matcher_precision (fp32 context: 1, the shadow's type, and the unsplit form only)");
+  for (int b = 0; b < B; ++b)
+    if (a->n0[b] < 0 || a->n0[b] > cap || a->n1[b] < 0 || a->n1[b] > cap) return fail(c, "debug_sg_front: every n0, n1 must lie in 0 .. cap");
+  const size_t M = (size_t)2 * B * Np, rows = (M + 127) / 128 * 128, R = c->arena_rows;
+  if (rows > R || (size_t)a->rows != rows) return fail(c, "debug_sg_front: rows must be 2 B Np rounded up to 128 and fit the arena");
+  HookStage s(c, "debug_sg_front");
+  const size_t fl = (size_t)B * cap * AIRFE_FEAT_DIM;
+  const float *d0 = s.up(a->f0, fl), *d1 = s.up(a->f1, fl);
+  const int *dn0 = s.up(a->n0, (size_t)B), *dn1 = s.up(a->n1, (size_t)B);
+  const DevSpan arena[5] = {{c->x32, R * 256 * 4}, {c->xb, R * 256 * 2}, {c->msg, R * 256 * 2}, {c->hb, R * 512 * 2}, {c->lens, (size_t)2 * c->Pmax * 4}};
+  for (const DevSpan& e : arena) s.fill(e.p, 0xFF, e.bytes);
+  if (s.status()) return 1;
+  s.step(sg_front_dev(c, d0, dn0, d1, dn1, B, cap, a->normalize, split != 0, s.stream()));
+  s.wait();
+  const std::vector<float> hx = s.get<float>(c->x32, R * 256);
+  const std::vector<uint16_t> hxb = s.get<uint16_t>(c->xb, R * 256), hh = s.get<uint16_t>(c->msg, split ? rows * 128 : 0), hhb = s.get<uint16_t>(c->hb, split ? rows * 256 : 0);
+  s.get(a->lens, c->lens, (size_t)2 * B * 4);
+  if (s.status()) return 1;
+  memcpy(a->x32, hx.data(), rows * 256 * 4);
+  dbg_back2(hxb, rows * 256, prec, a->xb);
+  if (split) { dbg_back2(hh, rows * 128, prec, a->h128); dbg_back2(hhb, rows * 256, prec, a->hb); }
+  int past = 0;
+  for (size_t r = rows; r < R; ++r) {
+    bool touched = false;
+    for (int k = 0; k < 256 && !touched; ++k) {
+      uint32_t u;
+      memcpy(&u, &hx[r * 256 + k], 4);
+      touched = (u != 0u && u != 0xFFFFFFFFu) || (hxb[r * 256 + k] != 0u && hxb[r * 256 + k] != 0xFFFFu);
+    }
+    past += touched;
+  }
+  a->rows_past = past;
+  for (const DevSpan& e : arena) s.fill(e.p, 0, e.bytes);          // the arena as alloc_matcher_arena left it
+  return s.wait();
+} AIRFE_CATCH(c)
+
 /* ---- the matchers' tails alone on HOST score matrices, staged into the arena */
 /* filter_matches (src/light_glue.cpp:214-266) alone on one HOST score matrix [n0][n1] */
 int airfe_debug_lg_filter(airfe_ctx* c, const float* scores, int n0, int n1, int32_t* idx, float* score, int cap, int* nmatch) try {

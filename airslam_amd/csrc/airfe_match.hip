@@ -84,9 +84,7 @@ static int lightglue_dev_f32(airfe_ctx* c, const float* f0, const int* n0, const
 // scores / 256^.5 split over both sides; the optimal-transport tail is the shared fp32 code
 static int superglue_dev_f32(airfe_ctx* c, const float* f0, const int* n0, const float* f1, const int* n1, int B, int cap, int normalize, hipStream_t st) {
   const int S = 2 * B, Np = c->Np, M = S * Np;
-  const KpNorm k = kp_norm(c, 0.7f);
-  reset_slack_rows(c, M, st);
-  launch_sg_prepare(1, f0, f1, n0, n1, AIRFE_FEAT_DIM, normalize, k.cx, k.cy, k.linv, c->sg_kenc, B, cap, Np, c->x32, c->xb, c->lens, nullptr, st);
+  if (sg_front_dev(c, f0, n0, f1, n1, B, cap, normalize, false, st)) return 1;
   int li = 0;
   for (const auto& l : c->f_sg) attn_block_f32(c, l, S, li++ & 1, false, st);
   lin_f32(c, M, st, c->f_sgfinal, c->x32, nullptr, c->m_md, 256, 0, 0, 0.25f);
@@ -262,6 +260,20 @@ void reset_slack_rows(airfe_ctx* c, int M, hipStream_t st) {
   launch_zero16(c->xb + (size_t)M * 256, (c->arena_rows - (size_t)M) * 256 * sizeof(uint16_t), st);
 }
 
+// SuperGlue's front for production and airfe_debug_sg_front: x = descriptor + keypoint encoder; split: its two large layers (98 of 108 kFLOP per keypoint) as MFMA GEMMs
+int sg_front_dev(airfe_ctx* c, const float* f0, const int* n0, const float* f1, const int* n1, int B, int cap, int normalize, bool split, hipStream_t st) {
+  const int Np = c->Np, M = 2 * B * Np, Mg = (M + 127) / 128 * 128;
+  const KpNorm k = kp_norm(c, 0.7f);
+  reset_slack_rows(c, M, st);
+  launch_sg_prepare(c->mprec == 2 ? 1 : c->mprec, f0, f1, n0, n1, AIRFE_FEAT_DIM, normalize, k.cx, k.cy, k.linv, c->sg_kenc, B, cap, Np, c->x32, c->xb, c->lens, split ? c->msg : nullptr, st);
+  if (split && Mg > M) {          // the surplus rows of the 128-row rounding: zero inputs, so that the residual add leaves x = b4-ish garbage, not a running sum
+    HIPCHK(c, hipMemsetAsync(c->msg + (size_t)M * 128, 0, (size_t)(Mg - M) * 128 * 2, st));
+    HIPCHK(c, hipMemsetAsync(c->x32 + (size_t)M * 256, 0, (size_t)(Mg - M) * 256 * 4, st));
+  }
+  if (split) RUN(run_linear(c, c->sg_k3, c->msg, 128, 128, nullptr, 0, Mg, EPI_STORE, ACT_RELU, c->hb, 256, st));
+  return split ? run_linear(c, c->sg_k4, c->hb, 256, 256, nullptr, 0, Mg, EPI_RESID, ACT_NONE, c->xb, 256, st, false, nullptr, c->x32) : 0;
+}
+
 // LightGlue forward on B pairs whose feature rows live on the device
 int lightglue_dev(airfe_ctx* c, const float* f0, const int* n0, const float* f1, const int* n1, int B, int cap, int ld,
                   int kp_off, int normalize, int32_t* d_idx, float* d_score, int mcap, int* d_nmatch, float* scores_out,
@@ -359,20 +371,7 @@ int superglue_dev(airfe_ctx* c, const float* f0, const int* n0, const float* f1,
   if (c->mprec == 2) return superglue_dev_f32(c, f0, n0, f1, n1, B, cap, normalize, st);
   const int S = 2 * B, Np = c->Np, M = S * Np;
   const int Mg = (M + 127) / 128 * 128;
-  const KpNorm k = kp_norm(c, 0.7f);
-  // keypoint encoder: from block_min tokens on, its two large layers (98 of 108 kFLOP per keypoint) run as MFMA GEMMs
-  const bool kenc_gemm = c->sg_kenc_gemm == 1 || (c->sg_kenc_gemm < 0 && Mg >= c->block_min);
-  reset_slack_rows(c, M, st);
-  launch_sg_prepare(c->mprec, f0, f1, n0, n1, AIRFE_FEAT_DIM, normalize, k.cx, k.cy, k.linv, c->sg_kenc, B, cap, Np, c->x32, c->xb,
-                    c->lens, kenc_gemm ? c->msg : nullptr, st);
-  if (kenc_gemm) {
-    if (Mg > M) {          // the surplus rows of the 128-row rounding: zero inputs, so that the residual add leaves x = b4-ish garbage, not a running sum
-      HIPCHK(c, hipMemsetAsync(c->msg + (size_t)M * 128, 0, (size_t)(Mg - M) * 128 * 2, st));
-      HIPCHK(c, hipMemsetAsync(c->x32 + (size_t)M * 256, 0, (size_t)(Mg - M) * 256 * 4, st));
-    }
-    RUN(run_linear(c, c->sg_k3, c->msg, 128, 128, nullptr, 0, Mg, EPI_STORE, ACT_RELU, c->hb, 256, st));
-    RUN(run_linear(c, c->sg_k4, c->hb, 256, 256, nullptr, 0, Mg, EPI_RESID, ACT_NONE, c->xb, 256, st, false, nullptr, c->x32));
-  }
+  RUN(sg_front_dev(c, f0, n0, f1, n1, B, cap, normalize, c->sg_kenc_gemm == 1 || (c->sg_kenc_gemm < 0 && Mg >= c->block_min), st));      // split from block_min tokens on
   const bool fused_block = c->fuse_lg_block == 1 || (c->fuse_lg_block < 0 && Mg >= c->block_min);
   int li = 0;      // names = ['self', 'cross'] * 9; every layer launches its own projections (no rotary), nothing is traced
   for (const AttnBlock& l : c->sg) RUN(attn_block_dev(c, l, S, li++ & 1, true, false, fused_block, nullptr, false, 0, nullptr, st));

@@ -1220,6 +1220,11 @@ struct SgPrepArgs {
 // SPLIT: only the three small layers (3 -> 32 -> 64 -> 128: 10 of the 108 kFLOP per keypoint) run here; the kernel writes the 128
 // hidden features (2-byte) and x = the descriptor, and the two large layers (128 -> 256 + ReLU, 256 -> 256 added to x) follow as MFMA
 // GEMMs (airfe_match.hip).  As scalar FMA loops all five layers took 0.29 ms per 51200 keypoints, latency-bound on LDS broadcast reads.
+// Padding rows (len <= n < Np of every sequence, all Np rows of an empty one) differ between the forms (tests/test_gpu_sg_front.py pins both):
+//   unsplit  x32 and xb are exactly zero.
+//   SPLIT    the kernel writes zeros to x32, xb and h128; the two GEMMs then turn every such row into the same constant: hb = relu(b3), x32 = W4 relu(b3) + b4, xb its
+//            rounding.  The surplus rows [M, Mg) of the 128-row rounding get that row too, from the zeros sg_front_dev's memsets leave: rewritten, not added to.
+// Nothing downstream reads a padding row into a valid one: attention masks keys by lens, the similarity and the transport read rows below lens only.
 template <class P, bool SPLIT>
 __global__ __launch_bounds__(256) void sg_prepare_kernel(SgPrepArgs a) {
   __shared__ float bufa[KE_LT][256], bufb[KE_LT][256];

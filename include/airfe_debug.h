@@ -217,6 +217,25 @@ typedef struct airfe_debug_lg_assign_args {
   int32_t* nmatch;                /* [B] */
 } airfe_debug_lg_assign_args;
 int airfe_debug_lg_assign(airfe_ctx* ctx, airfe_debug_lg_assign_args* a);
+/* SuperGlue's front alone (sg_front_dev, the statement superglue_dev runs: the slack-row reset, launch_sg_prepare and, split, the two memsets of the surplus rows and
+ * the two GEMMs of the keypoint encoder's large layers) on HOST feature rows (tests/test_gpu_sg_front.py, tests/sg_front_ref.py).  The normalisation constants are the
+ * context's own (cfg.image_width / image_height, scale 0.7).  EVERY row of x32, xb, msg and hb in the arena, and lens, is 0xFF bytes (NaN in every type) when the launches
+ * start, so a finite output was written by this call.  prec names the context's 2-byte type (matcher_precision) and is refused when it differs; under a fp32 context
+ * (matcher_precision 2) only the unsplit form exists and prec is 1, the fp16 shadow production asks for.  M = 2 B Np, rows = Mg = M rounded up to 128: the rows the
+ * GEMMs run over.  rows_past counts the arena rows at or beyond `rows` whose x32 or xb bytes are neither zero (what the slack-row reset leaves) nor the fill.  The
+ * arena is zero again when the hook returns. */
+typedef struct airfe_debug_sg_front_args {
+  int prec, split;                /* prec 0 = bf16, 1 = fp16; split 1 = the large layers as GEMMs */
+  int B, cap, normalize;          /* f0 / f1 [B][cap][259] rows (score, x, y, descriptor), 1 <= cap <= Np */
+  const float *f0, *f1;
+  const int *n0, *n1;             /* [B], each 0 .. cap */
+  int rows;                       /* Mg */
+  int* lens;                      /* [2 B] */
+  float *x32, *xb;                /* [rows][256]; xb widened to float */
+  float *h128, *hb;               /* split: [rows][128], [rows][256], widened; unused (may be NULL) otherwise */
+  int rows_past;
+} airfe_debug_sg_front_args;
+int airfe_debug_sg_front(airfe_ctx* ctx, airfe_debug_sg_front_args* a);
 /* ---- the index work behind the networks on hand-built maps (tests/test_gpu_detector_tail_pin.py, tests/detector_tail_ref.py): exact ties, plateaus, exact zeros, scores
  * equal to the threshold, peaks on the border lines — inputs the soft-max maps of real images never hold.  HOST tensors are staged into the context's own buffers and the
  * launchers production calls run in production's order with production's arguments; nothing here has a kernel of its own.  Each reports an activation-range overflow as the

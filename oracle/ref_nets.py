@@ -291,19 +291,22 @@ def sinkhorn_log(scores: torch.Tensor, alpha: torch.Tensor, iters: int):
     return c + u[:, None] + v[None, :] - norm
 
 
+def superglue_kenc(w: W, k, s) -> torch.Tensor:
+    """SuperGlue's keypoint encoder: k [N,2] normalised, s [N] -> [256,N] (tests/test_sg_front_ref_cpu.py holds the float64 reference of the front to it)"""
+    x = torch.cat([_t(k).t(), _t(s)[None]], 0)                     # [3,N]
+    for i in range(5):
+        x = _conv1d(w, f"kenc.encoder.{i}", x)
+        if i < 4:
+            x = torch.relu(x)
+    return x
+
+
 def superglue_forward(w: W, kpts0, sc0, desc0, kpts1, sc1, desc1, n_layers: int = 18, iters: int = 100):
     """kpts [N,2] normalised, sc [N], desc [N,256] (row-major per keypoint) -> scores [N0+1,N1+1]
     (binding A.5; consumed by decode at src/super_glue.cpp:447-453)."""
     with torch.no_grad():
-        def kenc(k, s):
-            x = torch.cat([_t(k).t(), _t(s)[None]], 0)                     # [3,N]
-            for i in range(5):
-                x = _conv1d(w, f"kenc.encoder.{i}", x)
-                if i < 4:
-                    x = torch.relu(x)
-            return x
-        d0 = _t(desc0).t() + kenc(kpts0, sc0)
-        d1 = _t(desc1).t() + kenc(kpts1, sc1)
+        d0 = _t(desc0).t() + superglue_kenc(w, kpts0, sc0)
+        d1 = _t(desc1).t() + superglue_kenc(w, kpts1, sc1)
         for i in range(n_layers):
             g = f"gnn.layers.{i}"
             if i % 2 == 1:

@@ -36,6 +36,24 @@ def test_library_exports_every_declared_symbol(libpath):
     assert set(names) == set(_lib.SIGNATURES), "ctypes binding and include/airfe.h disagree"
 
 
+def test_sg_front_hook_is_declared_exported_and_bound_field_by_field(libpath):
+    """airfe_debug_sg_front: in the hooks' header, exported, bound with its argument struct, and the ctypes struct has the header's fields in the header's order
+    with the header's types (int -> c_int, any pointer -> c_void_p)"""
+    from airslam_amd import _lib
+    assert "airfe_debug_sg_front" in _header_symbols("airfe_debug.h") and hasattr(C.CDLL(libpath), "airfe_debug_sg_front")
+    assert _lib.SIGNATURES["airfe_debug_sg_front"] == (C.c_int, [C.c_void_p, C.POINTER(_lib.DebugSgFrontArgs)])
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "airfe_debug.h")).read(), flags=re.S)
+    body = re.search(r"typedef struct airfe_debug_sg_front_args \{(.*?)\} airfe_debug_sg_front_args;", src, flags=re.S).group(1)
+    fields = []
+    for decl in body.split(";"):
+        m = re.match(r"\s*(const\s+)?(int|float)\s*(.*)", decl, flags=re.S)
+        if m:
+            for name in m.group(3).split(","):
+                name = name.strip()
+                fields.append((name.lstrip("* "), C.c_void_p if name.startswith("*") else C.c_int))
+    assert fields == list(_lib.DebugSgFrontArgs._fields_), fields
+
+
 def test_default_cfg_matches_reference_yaml(libpath):
     from airslam_amd import _lib
     c = _lib.Cfg()
@@ -96,7 +114,7 @@ def test_every_c_entry_catches_exceptions():
     for fname, catch, least in (("airfe.hip", "} AIRFE_CATCH(", 18), ("airfe_frame.hip", "} AIRFE_CATCH(", 12), ("airfe_assoc.hip", "} AIRFE_CATCH(", 4),
                                 ("airfe_match.hip", "} AIRFE_CATCH(", 6), ("airfe_geom.hip", "} AIRFE_CATCH(", 10), ("airfe_bowdb.hip", "} AIRFE_CATCH(", 27),
                                 ("airfe_bowmap.hip", "} AIRFE_CATCH(", 11), ("airfe_junction.hip", "} AIRFE_CATCH(", 9),
-                                ("airfe_debug.hip", "} AIRFE_CATCH(", 18), ("airfe_seq.hip", "} SEQ_CATCH(", 5)):
+                                ("airfe_debug.hip", "} AIRFE_CATCH(", 19), ("airfe_seq.hip", "} SEQ_CATCH(", 5)):
         src = open(os.path.join(ROOT, "airslam_amd", "csrc", fname)).read()
         body = src[src.index('extern "C" {'):]
         defs = re.findall(r"^int (airfe_[a-z0-9_]+)\([^;{]*?\)\s*(try)?\s*\{", body, flags=re.M | re.S)

@@ -49,4 +49,4 @@ def test_the_matcher_file_keeps_the_two_score_hooks():
     names = re.findall(r"^int (airfe_debug_[a-z0-9_]+)\(", _code("airfe_match.hip"), flags=re.M)
     assert sorted(names) == ["airfe_debug_lightglue_scores", "airfe_debug_superglue_scores"]
     moved = re.findall(r"^int (airfe_debug_[a-z0-9_]+)\(", _code("airfe_debug.hip"), flags=re.M)
-    assert {"airfe_debug_lg_filter", "airfe_debug_sg_decode", "airfe_debug_sg_sinkhorn"} <= set(moved)
+    assert {"airfe_debug_lg_filter", "airfe_debug_sg_decode", "airfe_debug_sg_sinkhorn", "airfe_debug_sg_front"} <= set(moved)

@@ -8,6 +8,7 @@ import re
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "airslam_amd", "csrc")
 PARENT_LINES = 6703          # airfe*.hip + airfe_host.h of the commit this split was made on (`git show <parent>:<file> | wc -l`, summed)
 WG_PRIMS_HOOK_LINES = 70     # + airfe_debug_wg_prims with its one-workgroup kernel (airfe_debug.hip), the one entry point added since: the tree stood at 6702 before it
+SG_FRONT_HOOK_LINES = 45     # + airfe_debug_sg_front (airfe_debug.hip); sg_front_dev, the statement it and both SuperGlue forwards call, took airfe_match.hip from 504 to 503 lines
 
 
 def _code(path):
@@ -47,4 +48,4 @@ def test_host_side_did_not_grow():
     for path in _sources() + [os.path.join(CSRC, "airfe_host.h")]:
         with open(path) as f:
             total += sum(1 for _ in f)
-    assert total <= PARENT_LINES + WG_PRIMS_HOOK_LINES, total
+    assert total <= PARENT_LINES + WG_PRIMS_HOOK_LINES + SG_FRONT_HOOK_LINES, total
